@@ -204,6 +204,26 @@ def parity_sample(dcp, sc, sizes, shard_begin, qlen, q_range, nsample=48):
     return {"pairs": n, "max_rel_err_vs_oracle": float("%.3g" % worst), "tolerance": 5e-5, "ok": bool(worst <= 5e-5)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, hits):
+    """--dump-outputs: the hit records (HIT_DTYPE, global profile indices) that the last timed step handed its caller,
+    sorted by (seq_idx, profile_idx), one .npy per field: indices as float64 (exact), log-likelihoods as float32.
+    The inputs are seeded, so two builds run with the same arguments can be compared file for file.  Above
+    DUMP_MAX_BYTES a fixed-seed sample of the records is written instead (never the case for one 65 536-record
+    hit buffer per rank)."""
+    order = np.lexsort((hits["profile_idx"], hits["seq_idx"]))
+    hits = hits[order]
+    max_records = DUMP_MAX_BYTES // (8 + 8 + 4 + 4)
+    if len(hits) > max_records:
+        hits = hits[np.sort(np.random.default_rng(0).choice(len(hits), max_records, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    for name, dtype in (("seq_idx", np.float64), ("profile_idx", np.float64),
+                        ("null_loglik", np.float32), ("alt_loglik", np.float32)):
+        np.save(os.path.join(out_dir, name + ".npy"), hits[name].astype(dtype))
+
+
 def profiler_preload():
     """A profiler's preloaded library (rocprofv3 and friends) initialises the GPU in THIS process before main()
     runs; starting rank children from such a process is the exec-after-HIP-init hop this pool forbids.  Returns
@@ -386,13 +406,15 @@ def stub_rank(args, rank, world):
     gather_s = [0.0]
     for i in range(args.warmup):
         step(i)
-    dist.barrier()
+    # gloo's monitored_barrier, never dist.barrier(): barrier() asks the accelerator runtime for the current device,
+    # which opens the GPU in every stub rank -- on a GPU box, 8 ranks would hold it for a run that never uses it
+    dist.monitored_barrier()
     gather_s[0] = 0.0
     t0 = time.perf_counter()
     for i in range(args.warmup, args.warmup + args.steps):
         step(i)
     mine_s = time.perf_counter() - t0
-    dist.barrier()
+    dist.monitored_barrier()
     tt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     bounds = [torch.zeros(2, dtype=torch.int64) for _ in range(world)]
@@ -409,7 +431,7 @@ def stub_rank(args, rank, world):
                           "shards": [[int(x) for x in t] for t in bounds], "hits_gathered": seen,
                           "multi_gpu": mg,
                           "self_launched": os.environ.get("DCP_BENCH_SELF_LAUNCHED") == "1"}))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -642,11 +664,15 @@ def main():
     ap.add_argument("--one-layout", action="store_true",
                     help="DCP_DB_ONE_LAYOUT: only the row-sweep tables resident, the query-lane kernels gather their tile "
                          "images from them (half the DB's footprint; not the default, not the headline line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the hit records the last timed step returned as DIR/<field>.npy")
     ap.add_argument("--stub-scan", action="store_true", help=argparse.SUPPRESS)  # launcher test on CPU (gloo)
     ap.add_argument("--stub-fail-rank", type=int, default=-1, help=argparse.SUPPRESS)
     ap.add_argument("--stub-sleep", type=float, default=0.0, help=argparse.SUPPRESS)  # seconds per stub step
     ap.add_argument("--launch-grace", type=float, default=20.0, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process only starts and reaps the N ranks
@@ -793,6 +819,7 @@ def main():
     cdist_state = {"comm": cdist, "kind": gather_kind}
 
     gather_s = [0.0]
+    last_gathered = [None]  # N > 1: the hit list the last step handed back (N = 1 reads the scanner's own after the leg)
 
     def step(i):
         sc.scan(True, False, 10.0, keep_scores=False, sync=False, q_range=(i * qstep, (i + 1) * qstep),
@@ -824,6 +851,7 @@ def main():
                 hits_seen.append({(int(r[0]), int(r[1]) + b) for r in rec})
             else:
                 hits_seen.append({(int(r["seq_idx"]), int(r["profile_idx"])) for r in h})
+        last_gathered[0] = h
         return h
 
     def fence():
@@ -842,6 +870,14 @@ def main():
     per_class, kernel_ms, redo_pairs, elapsed = timed.per_class, timed.kernel_ms, timed.redo_pairs, timed.elapsed
 
     cells_rank = float(sum(v["cells"] for v in per_class.values()))
+    if args.dump_outputs and rank == 0:
+        # before any later leg scans on this context and overwrites the hit buffer
+        if last_gathered[0] is not None:
+            last_hits = last_gathered[0]
+        else:
+            last_hits = sc.hits(cap)
+            last_hits["profile_idx"] += b  # shard-local -> global (b > 0 only under --as-rank)
+        dump_outputs(args.dump_outputs, last_hits)
 
     # ---- end-to-end leg (SURVEY 8d "kernel-only AND end-to-end"): nothing of a step is resident but the DB.
     # Each step hands its own host sequences to the boundary (dcp_gpu_seqs_upload: H2D, 2-bit packing, the

@@ -153,3 +153,43 @@ def test_a_rank_of_eight_counts_all_the_step_s_queries():
     assert roof["hbm"]["analytic_scratch_plane_bytes_per_launch"] == 24 * int(((ntiles - 1) // 2).sum()) * qstep * qlen
     assert roof["hbm"]["analytic_tile_image_bytes_per_launch"] == int(ntiles.sum()) * 8 * 1364 * 4 * ((qstep + 255) // 256)
     assert roof["traffic"] is None  # the committed counters are those of the one-GPU command
+
+
+def test_dump_outputs_writes_the_sorted_hit_fields(tmp_path):
+    """--dump-outputs: one float .npy per hit field, records in (seq_idx, profile_idx) order whatever order they came in."""
+    bench = load_bench()
+    hit = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
+                    ("null_loglik", np.float32), ("alt_loglik", np.float32)])
+    rec = np.zeros(4, hit)
+    rec["seq_idx"] = [7, 2, 7, 4000000000]
+    rec["profile_idx"] = [19999, 5, 3, 0]
+    rec["null_loglik"] = [-1.5, -2.5, -3.5, -4.5]
+    rec["alt_loglik"] = [1.25, 2.25, 3.25, 4.25]
+    bench.dump_outputs(str(tmp_path / "out"), rec)
+    got = {f: np.load(tmp_path / "out" / (f + ".npy")) for f in hit.names}
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(f + ".npy" for f in hit.names)
+    assert got["seq_idx"].dtype == np.float64 and got["profile_idx"].dtype == np.float64
+    assert got["null_loglik"].dtype == np.float32 and got["alt_loglik"].dtype == np.float32
+    assert got["seq_idx"].tolist() == [2, 7, 7, 4000000000]
+    assert got["profile_idx"].tolist() == [5, 3, 19999, 0]
+    assert got["null_loglik"].tolist() == [-2.5, -3.5, -1.5, -4.5]
+    assert got["alt_loglik"].tolist() == [2.25, 3.25, 1.25, 4.25]
+
+
+def test_dump_outputs_samples_above_the_size_cap(tmp_path, monkeypatch):
+    bench = load_bench()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 24 * 100)
+    rec = np.zeros(1000, np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
+                                   ("null_loglik", np.float32), ("alt_loglik", np.float32)]))
+    rec["seq_idx"] = np.arange(1000)[::-1]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), rec)
+    a, b = (np.load(tmp_path / d / "seq_idx.npy") for d in ("a", "b"))
+    assert len(a) == 100 and (np.diff(a) > 0).all() and np.array_equal(a, b)  # a fixed sample, still sorted
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 24 * 100 + 4 * 256
+
+
+def test_steps_below_one_are_refused():
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and "--steps" in r.stderr

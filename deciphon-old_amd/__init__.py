@@ -67,6 +67,10 @@ ABI_SYMBOLS = [
     "dcp_h3reader_error", "dcp_h3reader_close", "dcp_swissprot_null_lprobs", "dcp_profile_consensus",
     "dcp_db_write", "dcp_db_open", "dcp_db_close", "dcp_db_nprofiles", "dcp_db_entry_dist", "dcp_db_epsilon",
     "dcp_db_profile_sizes", "dcp_db_partitions", "dcp_db_read",
+    # the double build
+    "dcp_profile_new64", "dcp_profile_sample64", "dcp_profile_precision", "dcp_profile_epsilon64",
+    "dcp_profile_trans8_64", "dcp_profile_null_dist64", "dcp_profile_insert_dist64", "dcp_profile_match_dist64",
+    "dcp_xtrans64", "dcp_gpu_db_upload64", "dcp_gpu_db_precision", "dcp_gpu_set_lrt_threshold64", "dcp_gpu_fetch_scores64", "dcp_gpu_fetch_hits64",
 ]
 
 
@@ -97,6 +101,11 @@ class Hit(C.Structure):
                 ("null_loglik", C.c_float), ("alt_loglik", C.c_float)]
 
 
+class Hit64(C.Structure):
+    _fields_ = [("seq_idx", C.c_uint32), ("profile_idx", C.c_uint32),
+                ("null_loglik", C.c_double), ("alt_loglik", C.c_double)]
+
+
 class LaunchInfo(C.Structure):
     _fields_ = [("nodes_per_lane", C.c_int), ("waves_per_pair", C.c_int), ("nprofiles", C.c_uint),
                 ("ms", C.c_float), ("cells", C.c_uint64), ("algorithmic_bytes", C.c_uint64)]
@@ -105,6 +114,8 @@ class LaunchInfo(C.Structure):
 STEP_DTYPE = np.dtype([("state_id", np.uint16), ("seqlen", np.uint8), ("reserved", np.uint8)])
 HIT_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
                       ("null_loglik", np.float32), ("alt_loglik", np.float32)])
+HIT64_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
+                        ("null_loglik", np.float64), ("alt_loglik", np.float64)])
 
 
 def _load(path=None, hooks=False):
@@ -179,6 +190,20 @@ def _load(path=None, hooks=False):
         "dcp_db_read": (I, [P, U, U, P]),
         "dcp_gpu_scan_cells": (C.c_uint64, [P]),
         "dcp_gpu_scan_algorithmic_bytes": (C.c_uint64, [P]),
+        "dcp_profile_new64": (P, [C.c_char_p, U, I, C.c_double, P, P, P, C.c_char_p, C.POINTER(I)]),
+        "dcp_profile_sample64": (P, [C.c_char_p, U, U, I, C.c_double, C.POINTER(I)]),
+        "dcp_profile_precision": (I, [P]),
+        "dcp_profile_epsilon64": (C.c_double, [P]),
+        "dcp_profile_trans8_64": (P, [P]),
+        "dcp_profile_null_dist64": (P, [P]),
+        "dcp_profile_insert_dist64": (P, [P]),
+        "dcp_profile_match_dist64": (P, [P]),
+        "dcp_xtrans64": (I, [U, I, I, P]),
+        "dcp_gpu_db_upload64": (I, [P, P, U]),
+        "dcp_gpu_db_precision": (I, [P]),
+        "dcp_gpu_set_lrt_threshold64": (I, [P, C.c_double]),
+        "dcp_gpu_fetch_scores64": (I, [P, P, P]),
+        "dcp_gpu_fetch_hits64": (I, [P, P, U, C.POINTER(U)]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -207,6 +232,10 @@ def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
 class ProteinCfg:
     """struct protein_cfg {entry_dist, epsilon} (include/deciphon/model/protein_cfg.h)."""
 
@@ -215,6 +244,7 @@ class ProteinCfg:
             raise DcpError(RC_EINVAL, "epsilon out of [0, 1]")
         self.entry_dist = entry_dist
         self.epsilon = float(np.float32(epsilon))
+        self.epsilon64 = float(epsilon)  # what the double build takes (dcp_profile_sample64 / new64)
 
 
 PROTEIN_CFG_DEFAULT = ProteinCfg(ENTRY_DIST_OCCUPANCY, 0.01)  # protein_cfg.h:22-23
@@ -235,27 +265,39 @@ class ProteinProfile:
             lib.dcp_profile_del(h)
 
     @classmethod
-    def sample(cls, seed, core_size, cfg=PROTEIN_CFG_DEFAULT, accession="accession"):
-        """protein_profile_sample (src/model/protein_profile.c:259-304)."""
+    def sample(cls, seed, core_size, cfg=PROTEIN_CFG_DEFAULT, accession="accession", precision=32):
+        """protein_profile_sample (src/model/protein_profile.c:259-304).  precision=64: the reference's
+        IMM_DOUBLE_PRECISION build (dcp_profile_sample64), whose epsilon is cfg's value in double."""
         rc = C.c_int(0)
-        h = lib.dcp_profile_sample(accession.encode(), seed, core_size, cfg.entry_dist,
-                                   cfg.epsilon, C.byref(rc))
+        if precision == 64:
+            h = lib.dcp_profile_sample64(accession.encode(), seed, core_size, cfg.entry_dist,
+                                         cfg.epsilon64, C.byref(rc))
+        elif precision == 32:
+            h = lib.dcp_profile_sample(accession.encode(), seed, core_size, cfg.entry_dist,
+                                       cfg.epsilon, C.byref(rc))
+        else:
+            raise DcpError(RC_EINVAL, "precision is 32 or 64")
         if not h:
             raise DcpError(rc.value, "protein_profile_sample")
         return cls(h)
 
     @classmethod
     def from_params(cls, null_lprobs, match_lprobs, trans, cfg=PROTEIN_CFG_DEFAULT,
-                    accession="accession", consensus=None):
-        """protein_model_init/setup/add_node/add_trans + protein_profile_absorb."""
-        nl, ml, tr = _f32(null_lprobs), _f32(match_lprobs), _f32(trans)
+                    accession="accession", consensus=None, precision=32):
+        """protein_model_init/setup/add_node/add_trans + protein_profile_absorb.  precision=64: built in
+        double from double parameters (dcp_profile_new64)."""
+        if precision not in (32, 64):
+            raise DcpError(RC_EINVAL, "precision is 32 or 64")
+        cv = _f64 if precision == 64 else _f32
+        nl, ml, tr = cv(null_lprobs), cv(match_lprobs), cv(trans)
         M = ml.shape[0] if ml.ndim == 2 else 0
         if nl.shape != (20,) or ml.shape != (M, 20) or tr.shape != (M + 1, 7):
             raise DcpError(RC_EINVAL, "bad parameter shapes")
         rc = C.c_int(0)
         cons = consensus.encode() if consensus else None
-        h = lib.dcp_profile_new(accession.encode(), M, cfg.entry_dist, cfg.epsilon,
-                                nl.ctypes.data, ml.ctypes.data, tr.ctypes.data, cons, C.byref(rc))
+        new, eps = (lib.dcp_profile_new64, cfg.epsilon64) if precision == 64 else (lib.dcp_profile_new, cfg.epsilon)
+        h = new(accession.encode(), M, cfg.entry_dist, eps, nl.ctypes.data, ml.ctypes.data, tr.ctypes.data, cons,
+                C.byref(rc))
         if not h:
             raise DcpError(rc.value, "protein_model_setup")
         return cls(h)
@@ -263,6 +305,11 @@ class ProteinProfile:
     @property
     def core_size(self):
         return lib.dcp_profile_core_size(self._h)
+
+    @property
+    def precision(self):
+        """64 for a profile of the double build, else 32."""
+        return lib.dcp_profile_precision(self._h)
 
     def decode(self, frag, state_id):
         """protein_profile_decode (src/model/protein_profile.c:306-331): most likely codon of a
@@ -294,9 +341,24 @@ class ProteinProfile:
     def accession(self):
         return lib.dcp_profile_accession(self._h).decode()
 
-    def _view(self, ptr, shape):
+    def _view(self, ptr, shape, ctype=C.c_float):
         n = int(np.prod(shape))
-        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_float)), shape=(n,)).reshape(shape).copy()
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).reshape(shape).copy()
+
+    def parts64(self):
+        """The double build's scan-time parts (trans8 [8, M], null [129], insert [129], match [M, 129]) in
+        float64; RC_EINVAL for a float profile."""
+        if self.precision != 64:
+            raise DcpError(RC_EINVAL, "a float profile has no double parts")
+        M, d = self.core_size, C.c_double
+        return (self._view(lib.dcp_profile_trans8_64(self._h), (8, M), d),
+                self._view(lib.dcp_profile_null_dist64(self._h), (NDIST,), d),
+                self._view(lib.dcp_profile_insert_dist64(self._h), (NDIST,), d),
+                self._view(lib.dcp_profile_match_dist64(self._h), (M, NDIST), d))
+
+    @property
+    def epsilon64(self):
+        return lib.dcp_profile_epsilon64(self._h)
 
     @property
     def consensus(self):
@@ -435,6 +497,15 @@ def xtrans(seq_size, multi_hits=True, hmmer3_compat=False):
     return out
 
 
+def xtrans64(seq_size, multi_hits=True, hmmer3_compat=False):
+    """The same 13 special transitions in double (dcp_xtrans64)."""
+    out = np.zeros(NXTRANS, np.float64)
+    rc = lib.dcp_xtrans64(seq_size, int(multi_hits), int(hmmer3_compat), out.ctypes.data)
+    if rc:
+        raise DcpError(rc, "sequence cannot be empty")
+    return out
+
+
 def lrt(null_loglik, alt_loglik):
     """xmath_lrt_f32 (include/deciphon/core/xmath.h:32-35)."""
     return lib.dcp_lrt(float(null_loglik), float(alt_loglik))
@@ -496,11 +567,26 @@ class Scanner:
         return self._lib.dcp_gpu_stream(self._c)
 
     def upload_db(self, profiles, expand_on_host=False, one_layout=False):
-        """one_layout: DCP_DB_ONE_LAYOUT (include/dcp_gpu.h) -- no tile images, the query-lane kernels gather them."""
+        """one_layout: DCP_DB_ONE_LAYOUT (include/dcp_gpu.h) -- no tile images, the query-lane kernels gather them.
+        Profiles of the double build (precision=64) go to dcp_gpu_db_upload64: a double DB, scanned in double
+        (the flags do not apply to it).  A list mixing both precisions is refused."""
+        precs = {p.precision for p in profiles}
+        if len(precs) > 1:
+            raise DcpError(RC_EINVAL, "a DB holds profiles of one precision: this list mixes float and double")
         arr = (C.c_void_p * len(profiles))(*[p._h for p in profiles])
-        flags = (DB_EXPAND_ON_HOST if expand_on_host else 0) | (DB_ONE_LAYOUT if one_layout else 0)
-        self._check(self._lib.dcp_gpu_db_upload(self._c, arr, len(profiles), flags))
+        if precs == {64}:
+            if expand_on_host or one_layout:
+                raise DcpError(RC_EINVAL, "a double DB has one layout, expanded on the device")
+            self._check(self._lib.dcp_gpu_db_upload64(self._c, arr, len(profiles)))
+        else:
+            flags = (DB_EXPAND_ON_HOST if expand_on_host else 0) | (DB_ONE_LAYOUT if one_layout else 0)
+            self._check(self._lib.dcp_gpu_db_upload(self._c, arr, len(profiles), flags))
         self._profiles = list(profiles)
+
+    @property
+    def precision(self):
+        """32 or 64: the precision of the resident DB (0 without one)."""
+        return self._lib.dcp_gpu_db_precision(self._c)
 
     @property
     def one_layout(self):
@@ -552,6 +638,8 @@ class Scanner:
              sync=True, q_range=None, kernel=KERNEL_AUTO):
         prm = ScanParams(int(multi_hits), int(hmmer3_compat), float(lrt_threshold), int(keep_scores),
                          int(kernel))
+        # a double DB filters with the threshold in double (dcp_gpu_set_lrt_threshold64)
+        self._check(self._lib.dcp_gpu_set_lrt_threshold64(self._c, float(lrt_threshold)))
         if q_range is None:
             self._check(self._lib.dcp_gpu_scan(self._c, C.byref(prm)))
         else:
@@ -627,10 +715,12 @@ class Scanner:
         return self._lib.dcp_gpu_scan_algorithmic_bytes(self._c)
 
     def scores(self):
-        """(null[nseqs, nprofiles], alt[nseqs, nprofiles]) of the last scan."""
-        nl = np.zeros((self.nseqs, self.nprofiles), np.float32)
+        """(null[nseqs, nprofiles], alt[nseqs, nprofiles]) of the last scan: float64 after a scan of a double DB."""
+        f64 = self.precision == 64
+        nl = np.zeros((self.nseqs, self.nprofiles), np.float64 if f64 else np.float32)
         al = np.zeros_like(nl)
-        self._check(self._lib.dcp_gpu_fetch_scores(self._c, nl.ctypes.data, al.ctypes.data))
+        fetch = self._lib.dcp_gpu_fetch_scores64 if f64 else self._lib.dcp_gpu_fetch_scores
+        self._check(fetch(self._c, nl.ctypes.data, al.ctypes.data))
         return nl, al
 
     def trace_paths(self, hits, multi_hits=True, hmmer3_compat=False, null_model=False):
@@ -649,9 +739,12 @@ class Scanner:
         return [steps[off[i]:off[i + 1]].copy() for i in range(n)], alt
 
     def hits(self, cap=1 << 20):
-        buf = np.zeros(cap, HIT_DTYPE)
+        """Hit records of the last scan, sorted by (seq_idx, profile_idx): HIT64_DTYPE after a scan of a double DB."""
+        f64 = self.precision == 64
+        buf = np.zeros(cap, HIT64_DTYPE if f64 else HIT_DTYPE)
         n = C.c_uint(0)
-        rc = self._lib.dcp_gpu_fetch_hits(self._c, buf.ctypes.data, cap, C.byref(n))
+        fetch = self._lib.dcp_gpu_fetch_hits64 if f64 else self._lib.dcp_gpu_fetch_hits
+        rc = fetch(self._c, buf.ctypes.data, cap, C.byref(n))
         if rc == RC_ENOMEM and n.value > cap:
             return self.hits(n.value)
         self._check(rc)

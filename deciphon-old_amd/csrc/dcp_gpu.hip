@@ -6,6 +6,7 @@
 // imm_task_setup (src/server/scan_thread.c:51-55) and the per-pair body of
 // thread_run (src/server/scan_thread.c:99-123).  No CPU fallback exists.
 #include "dcp_kernels.h"
+#include "dcp_f64.h"
 
 #include <hip/hip_runtime.h>
 
@@ -210,6 +211,32 @@ struct dcp_gpu_ctx
     uint64_t seg_col_bytes = (uint64_t)6 << 30; // cap on one class's boundary columns (test hook: shrink it to reach the chunked path)
     unsigned n_launched = 0;
 
+    // The resident DB is float (dcp_gpu_db_upload) or double (dcp_gpu_db_upload64): 32 / 64, 0 while none is.
+    int precision = 0;
+    bool last_f64 = false; // the last scan ran on a double DB: its results are the f64 ones below
+    double lrt_threshold64 = std::numeric_limits<double>::quiet_NaN(); // NaN: the scan's float threshold
+    struct F64Db
+    {
+        std::vector<dcp_f64_prof> profs;   // by launch group (kF64Groups), then by caller index
+        unsigned group_first[5] = {0, 0, 0, 0, 0};
+        DevBuf<dcp_f64_prof> d_profs;
+        DevBuf<double> d_tab, d_trans, d_xe; // match tables, trans8 rows, insert + null tables
+        DevBuf<double> d_xt, d_null, d_alt, d_col;
+        DevBuf<dcp_hit64> d_hits;
+        DevBuf<unsigned> d_nhits;
+        unsigned hit_cap = 0;
+        bool have_scores = false;
+        void release()
+        {
+            profs.clear();
+            d_profs.release(), d_tab.release(), d_trans.release(), d_xe.release();
+            d_xt.release(), d_null.release(), d_alt.release(), d_col.release();
+            d_hits.release(), d_nhits.release();
+            hit_cap = 0;
+            have_scores = false;
+        }
+    } f64;
+
     int fail(int rc, char const *fmt, ...)
     {
         char buf[512];
@@ -385,9 +412,18 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
     int const expand_on_host = flags & DCP_DB_EXPAND_ON_HOST;
     if (!profiles || nprofiles == 0) return c->fail(DCP_EINVAL, "empty profile list");
     if (nprofiles > (1u << 20)) return c->fail(DCP_EINVAL, "too many profiles"); // MAX_NPROFILES limits.h:7
+    for (unsigned p = 0; p < nprofiles; ++p)
+        if (profiles[p] && dcp_profile_precision(profiles[p]) == 64)
+            return c->fail(DCP_EINVAL, "profile %u was built in double: upload it with dcp_gpu_db_upload64", p);
     HIP_TRY(c, hipSetDevice(c->device));
     c->scanned = false;
     c->redo_pending = false;
+    if (c->precision == 64) // one resident DB per context: the double one goes
+    {
+        c->f64.release();
+        c->nprof = 0;
+    }
+    c->precision = 0;
 
     // classify and order: by size class, then by caller index
     std::vector<int> cls(nprofiles);
@@ -799,6 +835,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
     }
     c->rs_ready = expand_on_host != 0 || c->one_layout;
     c->nprof = nprofiles;
+    c->precision = 32;
     return DCP_OK;
 }
 
@@ -820,9 +857,11 @@ static int ensure_rowsweep_layout(dcp_gpu_ctx *c)
 }
 
 int dcp_gpu_db_one_layout(dcp_gpu_ctx const *c) { return c && c->one_layout ? 1 : 0; }
+int dcp_gpu_db_precision(dcp_gpu_ctx const *c) { return c ? c->precision : 0; }
 uint64_t dcp_gpu_db_table_bytes(dcp_gpu_ctx const *c)
 {
     if (!c || c->nprof == 0) return 0;
+    if (c->precision == 64) return c->f64.d_tab.n * sizeof(double);
     // the lazily expanded row-sweep tables count once they are there
     bool const lazy_there = !c->one_layout && c->rs_ready && c->d_dists.p;
     return c->table_bytes + (lazy_there ? c->rs_floats * sizeof(float) : 0);
@@ -831,6 +870,7 @@ uint64_t dcp_gpu_db_table_bytes(dcp_gpu_ctx const *c)
 int dcp_gpu_db_fetch_match_table(dcp_gpu_ctx *c, unsigned p, float *out)
 {
     if (!c || !out || p >= c->nprof) return DCP_EINVAL;
+    if (c->precision == 64) return c->fail(DCP_EINVAL, "the resident DB is double: it has no float match tables");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure_rowsweep_layout(c)) return rc;
     for (dcp_prof_meta const &m : c->metas)
@@ -844,6 +884,127 @@ int dcp_gpu_db_fetch_match_table(dcp_gpu_ctx *c, unsigned p, float *out)
             return DCP_OK;
         }
     return DCP_EINVAL;
+}
+
+// ---------------------------------------------------------------------------
+// The double DB (dcp_gpu_db_upload64) and its scan: dcp_f64.hip
+// ---------------------------------------------------------------------------
+// Launch groups of an f64 DB: nodes per lane R of viterbi64_kernel<R>, and whether the profiles are swept in
+// column segments (more than 64 x 4 nodes: DCP_F64_SEG)
+static constexpr int kF64R[4] = {1, 2, 4, 4};
+static int f64_group(unsigned M) { return M <= 64u ? 0 : M <= 128u ? 1 : M <= (unsigned)DCP_F64_SEG ? 2 : 3; }
+
+int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned nprofiles)
+{
+    if (!c) return DCP_EINVAL;
+    if (!profiles || nprofiles == 0) return c->fail(DCP_EINVAL, "empty profile list");
+    if (nprofiles > (1u << 20)) return c->fail(DCP_EINVAL, "too many profiles");
+    for (unsigned p = 0; p < nprofiles; ++p)
+    {
+        if (!profiles[p]) return c->fail(DCP_EINVAL, "null profile %u", p);
+        if (dcp_profile_precision(profiles[p]) != 64)
+            return c->fail(DCP_EINVAL, "profile %u was built in float: dcp_gpu_db_upload64 takes double profiles only", p);
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // one resident DB per context: whatever was there goes, also if this upload fails half way
+    c->scanned = false;
+    c->redo_pending = false;
+    c->ring_check_pending = false;
+    c->precision = 0;
+    c->nprof = 0;
+    c->f64.release();
+    c->d_emis_match.release(), c->d_emis_tiles.release(), c->d_mp_in.release(), c->d_dists.release();
+    c->rs_tiles.clear();
+    c->rs_ready = false;
+    c->mp_in_ready = false;
+    c->one_layout = false;
+    c->table_bytes = 0;
+
+    std::vector<unsigned> order(nprofiles);
+    for (unsigned p = 0; p < nprofiles; ++p)
+        order[p] = p;
+    std::stable_sort(order.begin(), order.end(), [&](unsigned a, unsigned b) {
+        return f64_group(dcp_profile_core_size(profiles[a])) < f64_group(dcp_profile_core_size(profiles[b]));
+    });
+    auto &F = c->f64;
+    F.profs.assign(nprofiles, dcp_f64_prof{});
+    for (int g = 0; g < 5; ++g)
+        F.group_first[g] = 0;
+    uint64_t tab = 0, trans = 0, xe = 0;
+    for (unsigned i = 0; i < nprofiles; ++i)
+    {
+        unsigned const p = order[i], M = dcp_profile_core_size(profiles[p]);
+        int const g = f64_group(M);
+        unsigned const span = 64u * (unsigned)kF64R[g];
+        unsigned const nseg = (M + span - 1u) / span;
+        dcp_f64_prof &m = F.profs[i];
+        m.core_size = M;
+        m.nseg = nseg;
+        m.ldk = nseg * span;
+        m.pidx = p;
+        m.tab_off = tab;
+        m.trans_off = trans;
+        m.xe_off = xe;
+        tab += (uint64_t)DCP_NCODES * m.ldk; // ldk is a multiple of 64: every table starts 512-byte aligned
+        trans += 8ull * m.ldk;
+        xe += 2ull * DCP_NCODES;
+        F.group_first[g + 1] = i + 1;
+    }
+    for (int g = 1; g < 5; ++g) // empty groups start where the one before ends
+        F.group_first[g] = std::max(F.group_first[g], F.group_first[g - 1]);
+
+    // transitions padded with -inf; one expansion job per table column
+    std::vector<double> h_trans(trans, -std::numeric_limits<double>::infinity());
+    std::vector<double> h_dists;
+    std::vector<dcp_f64_expand_job> jobs, xe_jobs; // columns of the match tables; the insert / null tables
+    jobs.reserve(tab / DCP_NCODES);
+    xe_jobs.reserve(2ull * nprofiles);
+    for (dcp_f64_prof const &m : F.profs)
+    {
+        dcp_profile const *pf = profiles[m.pidx];
+        unsigned const M = m.core_size;
+        double const *t8 = dcp_profile_trans8_64(pf);
+        for (unsigned r = 0; r < 8; ++r)
+            std::memcpy(&h_trans[m.trans_off + (uint64_t)r * m.ldk], t8 + (size_t)r * M, sizeof(double) * M);
+        double const eps = dcp_profile_epsilon64(pf);
+        uint32_t const d0 = (uint32_t)(h_dists.size() / DCP_NDIST);
+        double const *md = dcp_profile_match_dist64(pf);
+        h_dists.insert(h_dists.end(), md, md + (size_t)M * DCP_NDIST);
+        h_dists.insert(h_dists.end(), dcp_profile_insert_dist64(pf), dcp_profile_insert_dist64(pf) + DCP_NDIST);
+        h_dists.insert(h_dists.end(), dcp_profile_null_dist64(pf), dcp_profile_null_dist64(pf) + DCP_NDIST);
+        for (unsigned k = 0; k < m.ldk; ++k)
+            jobs.push_back(dcp_f64_expand_job{m.tab_off + k, k < M ? d0 + k : ~0u, m.ldk, eps});
+        xe_jobs.push_back(dcp_f64_expand_job{m.xe_off, d0 + M, 1u, eps});
+        xe_jobs.push_back(dcp_f64_expand_job{m.xe_off + DCP_NCODES, d0 + M + 1u, 1u, eps});
+    }
+    if (jobs.size() >= (1ull << 30) || h_dists.size() / DCP_NDIST >= 0xffffffffull)
+        return c->fail(DCP_EINVAL, "profile DB too large");
+    HIP_TRY(c, F.d_profs.alloc(nprofiles));
+    HIP_TRY(c, F.d_tab.alloc(tab));
+    HIP_TRY(c, F.d_trans.alloc(trans));
+    HIP_TRY(c, F.d_xe.alloc(xe));
+    DevBuf<double> d_dists;
+    DevBuf<dcp_f64_expand_job> d_jobs, d_xe_jobs;
+    HIP_TRY(c, d_dists.alloc(h_dists.size()));
+    HIP_TRY(c, d_jobs.alloc(jobs.size()));
+    HIP_TRY(c, d_xe_jobs.alloc(xe_jobs.size()));
+    HIP_TRY(c, hipMemcpy(F.d_profs.p, F.profs.data(), nprofiles * sizeof(dcp_f64_prof), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(F.d_trans.p, h_trans.data(), trans * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_dists.p, h_dists.data(), h_dists.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(dcp_f64_expand_job), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(d_xe_jobs.p, xe_jobs.data(), xe_jobs.size() * sizeof(dcp_f64_expand_job), hipMemcpyHostToDevice));
+    // every column of the match tables (padding ones -inf), then the insert / null tables
+    dcp_f64_launch_expand(d_jobs.p, (unsigned)jobs.size(), d_dists.p, F.d_tab.p, c->stream);
+    dcp_f64_launch_expand(d_xe_jobs.p, (unsigned)xe_jobs.size(), d_dists.p, F.d_xe.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->core_sizes.assign(nprofiles, 0);
+    for (unsigned p = 0; p < nprofiles; ++p)
+        c->core_sizes[p] = dcp_profile_core_size(profiles[p]);
+    c->nprof = nprofiles;
+    c->precision = 64;
+    return DCP_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -985,6 +1146,13 @@ int dcp_gpu_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm)
     return dcp_gpu_scan_range(c, prm, 0, c->nseqs);
 }
 
+int dcp_gpu_set_lrt_threshold64(dcp_gpu_ctx *c, double lrt_threshold64)
+{
+    if (!c) return DCP_EINVAL;
+    c->lrt_threshold64 = lrt_threshold64;
+    return DCP_OK;
+}
+
 int dcp_gpu_set_hit_buffer(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void *nhits_dev)
 {
     if (!c) return DCP_EINVAL;
@@ -1000,6 +1168,7 @@ int dcp_gpu_hit_buffer(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsign
 {
     if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a double DB: its hits are struct dcp_hit64 (dcp_gpu_fetch_hits64)");
     *hits_dev = c->ext_hits ? (void *)c->ext_hits : (void *)c->d_hits.p;
     *nhits_dev = c->ext_hits ? (void *)c->ext_nhits : (void *)c->d_nhits.p;
     *cap = c->ext_hits ? c->ext_cap : c->hit_cap;
@@ -1191,6 +1360,115 @@ static void rowsweep_variant(dcp_gpu_ctx const *c, int R, int W, unsigned nchunk
     if (forced && g > 0) *pf = c->rs_force_pf;
 }
 
+// A scan of the resident double DB: viterbi64_kernel<R> per launch group (dcp_f64.hip), the LRT filter in its
+// epilogue, results in the f64 buffers.
+static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_begin, unsigned q_end)
+{
+    if (prm->kernel != 0 && prm->kernel != 1)
+        return c->fail(DCP_EINVAL, "a double DB is scanned by the f64 row sweep only (kernel 0 or 1, not %d)", prm->kernel);
+    if (c->xt_explicit)
+        return c->fail(DCP_EINVAL, "explicit special transitions are float: a double DB derives them from the lengths");
+    auto &F = c->f64;
+    c->scanned = false;
+    unsigned const nq = q_end - q_begin;
+    // protein_profile_setup in double, once per length
+    std::vector<double> xt((size_t)nq * DCP_F64_XSTRIDE, 0.0);
+    std::map<uint32_t, size_t> first_of_len;
+    uint32_t lmax = 0;
+    for (unsigned q = 0; q < nq; ++q)
+    {
+        uint32_t const L = c->seq_len[q_begin + q];
+        lmax = std::max(lmax, L);
+        auto it = first_of_len.find(L);
+        if (it != first_of_len.end())
+        {
+            std::memcpy(&xt[(size_t)q * DCP_F64_XSTRIDE], &xt[it->second * DCP_F64_XSTRIDE], sizeof(double) * DCP_NXTRANS);
+            continue;
+        }
+        if (int rc = dcp_xtrans64(L, prm->multi_hits, prm->hmmer3_compat, &xt[(size_t)q * DCP_F64_XSTRIDE]))
+            return c->fail(rc, "sequence cannot be empty");
+        first_of_len.emplace(L, q);
+    }
+    if (F.d_xt.n < xt.size()) HIP_TRY(c, F.d_xt.alloc(xt.size()));
+    HIP_TRY(c, hipMemcpyAsync(F.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+
+    size_t const npairs = (size_t)c->nseqs * c->nprof;
+    if (prm->keep_scores && F.d_null.n != npairs)
+    {
+        HIP_TRY(c, F.d_null.alloc(npairs));
+        HIP_TRY(c, F.d_alt.alloc(npairs));
+    }
+    F.have_scores = prm->keep_scores != 0;
+    unsigned const want_cap = (unsigned)std::min<size_t>(npairs, (size_t)1 << 22);
+    if (F.hit_cap < want_cap)
+    {
+        HIP_TRY(c, F.d_hits.alloc(want_cap));
+        F.hit_cap = want_cap;
+    }
+    if (!F.d_nhits.p) HIP_TRY(c, F.d_nhits.alloc(1));
+    // boundary columns of the segmented group: 5 doubles per row and wavefront, at most 1 GiB
+    uint64_t const col_stride = 5ull * ((uint64_t)lmax + 1u);
+    unsigned const nseg_prof = F.group_first[4] - F.group_first[3];
+    uint64_t seg_waves = 0;
+    if (nseg_prof)
+    {
+        seg_waves = std::min<uint64_t>((uint64_t)nseg_prof * nq, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / col_stride));
+        if (F.d_col.n < seg_waves * col_stride) HIP_TRY(c, F.d_col.alloc(seg_waves * col_stride));
+    }
+
+    dcp_f64_scan_args a{};
+    a.nprof_total = c->nprof;
+    a.tab = F.d_tab.p;
+    a.trans = F.d_trans.p;
+    a.xe = F.d_xe.p;
+    a.seq_words = c->d_seq_words.p;
+    a.seq_woff = c->d_seq_woff.p + q_begin;
+    a.seq_len = c->d_seq_len.p + q_begin;
+    a.xtrans = F.d_xt.p;
+    a.nq = nq;
+    a.q_base = q_begin;
+    a.out_null = F.have_scores ? F.d_null.p + (size_t)q_begin * c->nprof : nullptr;
+    a.out_alt = F.have_scores ? F.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
+    a.hits = F.d_hits.p;
+    a.nhits = F.d_nhits.p;
+    a.hit_cap = F.hit_cap;
+    uint64_t thr_bits; // this file is built with -fno-honor-nans: test the encoding for the NaN sentinel
+    std::memcpy(&thr_bits, &c->lrt_threshold64, sizeof thr_bits);
+    bool const thr_unset = (thr_bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+    a.lrt_threshold = thr_unset ? (double)prm->lrt_threshold : c->lrt_threshold64;
+    HIP_TRY(c, hipMemsetAsync(F.d_nhits.p, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    unsigned launches = 0;
+    for (int g = 0; g < 4; ++g)
+    {
+        unsigned const n = F.group_first[g + 1] - F.group_first[g];
+        if (n == 0) continue;
+        a.profs = F.d_profs.p + F.group_first[g];
+        a.nprof = n;
+        uint64_t const pairs = (uint64_t)n * nq;
+        // one wavefront per pair; the segmented group strides over its pairs with one boundary column per wavefront
+        uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(pairs, 1ull << 24); // 2^22 blocks of 256
+        a.col = g == 3 ? F.d_col.p : nullptr;
+        a.col_stride = g == 3 ? col_stride : 0;
+        if (dcp_f64_launch_scan(kF64R[g], &a, (unsigned)waves, c->stream))
+            return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
+        HIP_TRY(c, hipGetLastError());
+        ++launches;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->last_q0 = q_begin;
+    c->last_q1 = q_end;
+    c->last_launches = launches;
+    c->n_launched = 0; // no per-launch records (dcp_gpu_last_scan_launch_info) for the f64 kernel
+    c->last_kernel = 1;
+    c->last_kernel_variant = 1;
+    c->last_overlapped = false;
+    c->have_scores = false;
+    c->last_f64 = true;
+    c->scanned = true;
+    return DCP_OK;
+}
+
 int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_begin,
                        unsigned q_end)
 {
@@ -1199,6 +1477,8 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
     if (q_begin >= q_end || q_end > c->nseqs) return c->fail(DCP_EINVAL, "bad sequence range");
     HIP_TRY(c, hipSetDevice(c->device));
+    if (c->precision == 64) return scan64(c, prm, q_begin, q_end);
+    c->last_f64 = false;
     // One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST
     // scan.  A scan enqueued while the previous one still has unchecked redo lists first completes
     // that one (its overflow re-run included), so nothing of it is silently half done.
@@ -1838,6 +2118,8 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_
 int dcp_gpu_fetch_scores(dcp_gpu_ctx *c, float *null_out, float *alt_out)
 {
     if (!c) return DCP_EINVAL;
+    if (c->scanned && c->last_f64)
+        return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its scores with dcp_gpu_fetch_scores64");
     if (!c->scanned || !c->have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc;
@@ -1851,6 +2133,8 @@ int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsig
 {
     if (!c || !nhits) return DCP_EINVAL;
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
+    if (c->last_f64)
+        return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its hits with dcp_gpu_fetch_hits64");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc;
     unsigned n = 0;
@@ -1868,6 +2152,41 @@ int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsig
     return DCP_OK;
 }
 
+int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->scanned && !c->last_f64)
+        return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its scores with dcp_gpu_fetch_scores");
+    if (!c->scanned || !c->f64.have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc;
+    size_t const bytes = (size_t)c->nseqs * c->nprof * sizeof(double);
+    if (null_out) HIP_TRY(c, hipMemcpy(null_out, c->f64.d_null.p, bytes, hipMemcpyDeviceToHost));
+    if (alt_out) HIP_TRY(c, hipMemcpy(alt_out, c->f64.d_alt.p, bytes, hipMemcpyDeviceToHost));
+    return DCP_OK;
+}
+
+int dcp_gpu_fetch_hits64(dcp_gpu_ctx *c, struct dcp_hit64 *hits, unsigned cap, unsigned *nhits)
+{
+    if (!c || !nhits) return DCP_EINVAL;
+    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
+    if (!c->last_f64)
+        return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its hits with dcp_gpu_fetch_hits");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc;
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, c->f64.d_nhits.p, sizeof n, hipMemcpyDeviceToHost));
+    *nhits = n;
+    if (n > c->f64.hit_cap) return c->fail(DCP_ENOMEM, "device hit buffer overflow: %u > %u", n, c->f64.hit_cap);
+    if (n > cap || (n && !hits)) return DCP_ENOMEM;
+    if (n == 0) return DCP_OK;
+    HIP_TRY(c, hipMemcpy(hits, c->f64.d_hits.p, (size_t)n * sizeof(dcp_hit64), hipMemcpyDeviceToHost));
+    std::sort(hits, hits + n, [](dcp_hit64 const &x, dcp_hit64 const &y) {
+        return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
+    });
+    return DCP_OK;
+}
+
 
 // ---------------------------------------------------------------------------
 // Hits -> alt paths (device traceback)
@@ -1879,6 +2198,7 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
 {
     if (!c || !step_off || (nhits && !hits)) return DCP_EINVAL;
     if (c->nprof == 0 || c->nseqs == 0) return c->fail(DCP_EINVAL, "no DB / sequences resident");
+    if (c->precision == 64) return c->fail(DCP_EINVAL, "no traceback on a double DB");
     HIP_TRY(c, hipSetDevice(c->device));
     step_off[0] = 0;
     if (nhits == 0) return DCP_OK;

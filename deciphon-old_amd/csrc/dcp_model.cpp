@@ -161,6 +161,98 @@ void make_nuclt_dist(float const aa_lprobs[20], float out[DCP_NDIST])
             }
 }
 
+// ---- the double build (IMM_DOUBLE_PRECISION): imm's own log-domain arithmetic, no rounding to float -------------
+// imm_lprob_add: logaddexp with log1p, as imm computes it (the order of every sum below is imm's, so that the parts
+// are those of the reference's double build to the last bit where the C library's log / exp / log1p agree)
+double lp_add(double x, double y)
+{
+    if (x == y) return x + 0.69314718055994530942;
+    double const t = x - y;
+    if (t > 0) return x + std::log1p(std::exp(-t));
+    if (t <= 0) return y + std::log1p(std::exp(t));
+    return t; // NaN
+}
+
+// imm_lprob_normalize: subtract the chained sum
+void lp_normalize64(unsigned n, double *v)
+{
+    double s = kNegInf;
+    for (unsigned i = 0; i < n; ++i)
+        s = lp_add(s, v[i]);
+    for (unsigned i = 0; i < n; ++i)
+        v[i] -= s;
+}
+
+// setup_nuclt_dist in double (protein_model.c:342-408): codon lprobs from the amino lprobs split over synonyms,
+// normalised; base lprobs as imm's chained sums over the codon table in its published (TCAG) order; codon marginals
+// as chained sums over the matching codons.
+void make_nuclt_dist64(double const aa_lprobs[20], double out[DCP_NDIST])
+{
+    double by_letter[128];
+    for (double &v : by_letter)
+        v = kNegInf;
+    for (int i = 0; i < 20; ++i)
+    {
+        int const letter = kAminoSymbols[i];
+        by_letter[letter] = aa_lprobs[i] - std::log((double)g_codons.synonyms[letter]);
+    }
+    double codon_lp[64]; // a*16+b*4+c in ACGT ids
+    for (int i = 0; i < 64; ++i)
+        codon_lp[i] = by_letter[(int)g_codons.aa[i]];
+    lp_normalize64(64, codon_lp);
+    double base[4] = {kNegInf, kNegInf, kNegInf, kNegInf};
+    double const norm = std::log(3.0);
+    for (int i = 0; i < 64; ++i) // the genetic code's own codon order
+    {
+        int const a = kTcagToAcgt[i >> 4], b = kTcagToAcgt[(i >> 2) & 3], c = kTcagToAcgt[i & 3];
+        double const lp = codon_lp[a * 16 + b * 4 + c];
+        base[a] = lp_add(base[a], lp - norm);
+        base[b] = lp_add(base[b], lp - norm);
+        base[c] = lp_add(base[c], lp - norm);
+    }
+    for (int i = 0; i < 4; ++i)
+        out[i] = base[i];
+    for (int a = 0; a < 5; ++a)
+        for (int b = 0; b < 5; ++b)
+            for (int c = 0; c < 5; ++c)
+            {
+                double acc = kNegInf;
+                for (int i = (a == 4 ? 0 : a); i < (a == 4 ? 4 : a + 1); ++i)
+                    for (int j = (b == 4 ? 0 : b); j < (b == 4 ? 4 : b + 1); ++j)
+                        for (int k = (c == 4 ? 0 : c); k < (c == 4 ? 4 : c + 1); ++k)
+                            acc = lp_add(acc, codon_lp[i * 16 + j * 4 + k]);
+                out[4 + a * 25 + b * 5 + c] = acc;
+            }
+}
+
+// calculate_occupancy + setup_entry_trans in double (protein_model.c:258-283, 410-439)
+void entry_scores64(unsigned M, int entry_dist, double const *trans, double *entry)
+{
+    if (entry_dist == DCP_ENTRY_DIST_UNIFORM)
+    {
+        double const Mf = (double)M;
+        double const cost = std::log(2.0 / (Mf * (Mf + 1))) * Mf;
+        for (unsigned i = 0; i < M; ++i)
+            entry[i] = cost;
+        return;
+    }
+    enum { MM, MI, MD, IM, II, DM, DD };
+    std::vector<double> locc(M);
+    locc[0] = lp_add(trans[MI], trans[MM]);
+    for (unsigned i = 1; i < M; ++i)
+    {
+        double const *t = trans + 7 * (size_t)i;
+        double const v0 = locc[i - 1] + lp_add(t[MM], t[MI]);
+        double const v1 = std::log1p(-std::exp(locc[i - 1])) + t[DM];
+        locc[i] = lp_add(v0, v1);
+    }
+    double logZ = kNegInf;
+    for (unsigned i = 0; i < M; ++i)
+        logZ = lp_add(logZ, locc[i] + std::log((double)(M - i)));
+    for (unsigned i = 0; i < M; ++i)
+        entry[i] = locc[i] - logZ;
+}
+
 } // namespace
 
 struct dcp_profile
@@ -183,6 +275,14 @@ struct dcp_profile
     };
     mutable std::once_flag decode_once;
     mutable DecodeExp decode_exp[2]; // 0 null, 1 insert
+    // A profile of the double build (dcp_profile_new64 / dcp_profile_sample64) keeps its scan-time parts in double
+    // as well; the float parts above are then those values rounded once (what the float-only consumers read).
+    bool f64 = false;
+    double epsilon64 = 0;
+    std::vector<double> trans8_64;     // [8][M]
+    std::vector<double> match_dist64;  // [M][129]
+    std::vector<double> null_dist64;   // [129]
+    std::vector<double> insert_dist64; // [129]
 };
 
 // calculate_occupancy + setup_entry_trans (protein_model.c:258-283,410-439)
@@ -352,6 +452,154 @@ dcp_profile *dcp_profile_from_parts(char const *accession, unsigned core_size, i
         if (p->null_dist[i] != p->null_dist[i] || p->insert_dist[i] != p->insert_dist[i]) { delete p; return fail(DCP_EINVAL); }
     if (rc) *rc = DCP_OK;
     return p;
+}
+
+dcp_profile *dcp_profile_new64(char const *accession, unsigned core_size, int entry_dist, double epsilon,
+                               double const *null_lprobs, double const *match_lprobs, double const *trans,
+                               char const *consensus, int *rc)
+{
+    auto fail = [&](int code) -> dcp_profile * {
+        if (rc) *rc = code;
+        return nullptr;
+    };
+    if (core_size == 0 || core_size > DCP_CORE_SIZE_MAX) return fail(DCP_EINVAL);
+    if (!null_lprobs || !match_lprobs || !trans) return fail(DCP_EINVAL);
+    if (entry_dist != DCP_ENTRY_DIST_UNIFORM && entry_dist != DCP_ENTRY_DIST_OCCUPANCY)
+        return fail(DCP_EINVAL);
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(DCP_EINVAL);
+
+    dcp_profile *p = new (std::nothrow) dcp_profile();
+    if (!p) return fail(DCP_ENOMEM);
+    unsigned const M = core_size;
+    std::memset(p->accession, 0, sizeof p->accession);
+    if (accession) std::strncpy(p->accession, accession, sizeof p->accession - 1);
+    p->core_size = M;
+    p->entry_dist = entry_dist;
+    p->f64 = true;
+    p->epsilon64 = epsilon;
+    p->epsilon = (float)epsilon;
+    p->consensus.assign(M + 1, '\0');
+    bool ended = !consensus;
+    for (unsigned i = 0; i < M; ++i)
+    {
+        if (!ended && consensus[i] == '\0') ended = true;
+        p->consensus[i] = ended ? '-' : consensus[i];
+    }
+
+    // the same wiring as dcp_profile_new, every value in double
+    p->null_dist64.resize(DCP_NDIST);
+    p->insert_dist64.resize(DCP_NDIST);
+    make_nuclt_dist64(null_lprobs, p->null_dist64.data());
+    double const zeros[20] = {0};
+    make_nuclt_dist64(zeros, p->insert_dist64.data());
+    p->match_dist64.resize((size_t)M * DCP_NDIST);
+    for (unsigned k = 0; k < M; ++k)
+    {
+        double lodds[20];
+        for (int i = 0; i < 20; ++i)
+            lodds[i] = match_lprobs[k * 20 + i] - null_lprobs[i];
+        make_nuclt_dist64(lodds, &p->match_dist64[(size_t)k * DCP_NDIST]);
+    }
+    enum { MM, MI, MD, IM, II, DM, DD };
+    p->trans8_64.assign((size_t)8 * M, kNegInf);
+    double *t8 = p->trans8_64.data();
+    entry_scores64(M, entry_dist, trans, t8 + DCP_T_ENTRY * M);
+    for (unsigned i = 0; i + 1 < M; ++i)
+    {
+        double const *t = trans + 7 * (i + 1);
+        t8[DCP_T_MI * M + i] = t[MI];
+        t8[DCP_T_II * M + i] = t[II];
+        t8[DCP_T_MM * M + i + 1] = t[MM];
+        t8[DCP_T_IM * M + i + 1] = t[IM];
+        t8[DCP_T_MD * M + i + 1] = t[MD];
+        t8[DCP_T_DD * M + i + 1] = t[DD];
+        t8[DCP_T_DM * M + i + 1] = t[DM];
+    }
+    // the float parts: the double values rounded once
+    p->trans8.assign(p->trans8_64.begin(), p->trans8_64.end());
+    p->match_dist.assign(p->match_dist64.begin(), p->match_dist64.end());
+    for (int i = 0; i < DCP_NDIST; ++i)
+    {
+        p->null_dist[i] = (float)p->null_dist64[i];
+        p->insert_dist[i] = (float)p->insert_dist64[i];
+    }
+    if (rc) *rc = DCP_OK;
+    return p;
+}
+
+dcp_profile *dcp_profile_sample64(char const *accession, unsigned seed, unsigned core_size, int entry_dist,
+                                  double epsilon, int *rc)
+{
+    if (core_size < 2 || core_size > DCP_CORE_SIZE_MAX)
+    {
+        if (rc) *rc = DCP_EINVAL;
+        return nullptr;
+    }
+    // imm_lprob_sample + imm_lprob_normalize on doubles: the same random stream as dcp_profile_sample
+    Rnd rnd(seed);
+    unsigned const M = core_size;
+    auto sample = [&](unsigned n, double *out) {
+        for (unsigned i = 0; i < n; ++i)
+            out[i] = std::log(rnd.next());
+    };
+    double null_lp[20];
+    sample(20, null_lp);
+    lp_normalize64(20, null_lp);
+    std::vector<double> match((size_t)20 * M), trans((size_t)7 * (M + 1));
+    for (unsigned k = 0; k < M; ++k)
+    {
+        sample(20, &match[(size_t)20 * k]);
+        lp_normalize64(20, &match[(size_t)20 * k]);
+    }
+    for (unsigned i = 0; i <= M; ++i)
+    {
+        double *t = &trans[(size_t)7 * i];
+        sample(7, t);
+        if (i == 0) t[6] = kNegInf; // DD
+        if (i == M) t[2] = t[6] = kNegInf; // MD, DD
+        lp_normalize64(7, t);
+    }
+    return dcp_profile_new64(accession, M, entry_dist, epsilon, null_lp, match.data(), trans.data(), nullptr, rc);
+}
+
+int dcp_profile_precision(dcp_profile const *p) { return p && p->f64 ? 64 : 32; }
+double dcp_profile_epsilon64(dcp_profile const *p) { return p->f64 ? p->epsilon64 : (double)p->epsilon; }
+double const *dcp_profile_trans8_64(dcp_profile const *p) { return p->f64 ? p->trans8_64.data() : nullptr; }
+double const *dcp_profile_null_dist64(dcp_profile const *p) { return p->f64 ? p->null_dist64.data() : nullptr; }
+double const *dcp_profile_insert_dist64(dcp_profile const *p) { return p->f64 ? p->insert_dist64.data() : nullptr; }
+double const *dcp_profile_match_dist64(dcp_profile const *p) { return p->f64 ? p->match_dist64.data() : nullptr; }
+
+// protein_profile_setup in double (protein_profile.c:155-216)
+int dcp_xtrans64(unsigned seq_size, int multi_hits, int hmmer3_compat, double out[DCP_NXTRANS])
+{
+    if (seq_size == 0) return DCP_EINVAL;
+    double const L = (double)seq_size;
+    double q = 0.0, log_q = kNegInf;
+    if (multi_hits)
+    {
+        q = 0.5;
+        log_q = std::log(0.5);
+    }
+    double const lp = std::log(L) - std::log(L + 2 + q / (1 - q));
+    double const l1p = std::log(2 + q / (1 - q)) - std::log(L + 2 + q / (1 - q));
+    double const lr = std::log(L) - std::log(L + 1);
+    double NN = lp, CC = lp, JJ = lp;
+    double const NB = l1p, CT = l1p, JB = l1p, RR = lr, EJ = log_q, EC = std::log(1 - q);
+    if (hmmer3_compat) NN = CC = JJ = 0.0;
+    out[DCP_X_RR] = RR;
+    out[DCP_X_SB] = NB;
+    out[DCP_X_SN] = NN;
+    out[DCP_X_NN] = NN;
+    out[DCP_X_NB] = NB;
+    out[DCP_X_ET] = EC + CT;
+    out[DCP_X_EC] = EC + CC;
+    out[DCP_X_CC] = CC;
+    out[DCP_X_CT] = CT;
+    out[DCP_X_EB] = EJ + JB;
+    out[DCP_X_EJ] = EJ + JJ;
+    out[DCP_X_JJ] = JJ;
+    out[DCP_X_JB] = JB;
+    return DCP_OK;
 }
 
 void dcp_rnd_seed(uint64_t state[4], uint64_t seed)

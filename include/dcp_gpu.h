@@ -190,6 +190,27 @@ float const *dcp_profile_null_dist(dcp_profile const *);
 float const *dcp_profile_insert_dist(dcp_profile const *);
 float const *dcp_profile_match_dist(dcp_profile const *);
 
+/* ---- The double build (the reference's IMM_DOUBLE_PRECISION) ----------------------------------------------
+ * dcp_profile_new64 / dcp_profile_sample64: the same arguments as dcp_profile_new / dcp_profile_sample with
+ * lprobs, trans and epsilon in double.  The profile is built in double throughout -- imm's log-domain sums in its
+ * order, no rounding to float -- and keeps its scan-time parts in double: trans8 [8][core_size], null / insert
+ * dists [129], match dists [core_size][129].  Its float parts (dcp_profile_trans8 ...) hold the same values
+ * rounded once, for the float-only consumers (dcp_db_write, decode, product rows); dcp_gpu_db_upload refuses it,
+ * dcp_gpu_db_upload64 takes it. */
+dcp_profile *dcp_profile_new64(char const *accession, unsigned core_size, int entry_dist, double epsilon,
+                               double const *null_lprobs, double const *match_lprobs, double const *trans,
+                               char const *consensus, int *rc);
+dcp_profile *dcp_profile_sample64(char const *accession, unsigned seed, unsigned core_size, int entry_dist,
+                                  double epsilon, int *rc);
+/* 64 for a profile of the double build, 32 otherwise. */
+int dcp_profile_precision(dcp_profile const *);
+/* The double parts (same layouts as the float views below); NULL for a float profile. */
+double dcp_profile_epsilon64(dcp_profile const *);
+double const *dcp_profile_trans8_64(dcp_profile const *);
+double const *dcp_profile_null_dist64(dcp_profile const *);
+double const *dcp_profile_insert_dist64(dcp_profile const *);
+double const *dcp_profile_match_dist64(dcp_profile const *);
+
 /* Frame-state emission table of one nuclt_dist over all 1364 words (host).
  * out[code], code = {0,4,20,84,340}[len-1] + base-4 value of the word, first
  * base most significant. Same formula the device expansion kernel evaluates. */
@@ -201,6 +222,9 @@ void dcp_frame_table_host(float const dist[DCP_NDIST], float epsilon,
  * DCP_EINVAL for seq_size == 0 (:158). */
 int dcp_xtrans(unsigned seq_size, int multi_hits, int hmmer3_compat,
                float out[DCP_NXTRANS]);
+
+/* The same 13 values in double (protein_profile_setup of the double build). */
+int dcp_xtrans64(unsigned seq_size, int multi_hits, int hmmer3_compat, double out[DCP_NXTRANS]);
 
 /* xmath_lrt_f32 (xmath.h:32-35) */
 float dcp_lrt(float null_loglik, float alt_loglik);
@@ -247,6 +271,15 @@ void *dcp_gpu_stream(dcp_gpu_ctx *);
 #define DCP_DB_ONE_LAYOUT 2
 int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
                       unsigned nprofiles, int flags);
+/* Upload a DB of double-build profiles (dcp_profile_new64 / dcp_profile_sample64): their frame tables are
+ * expanded on the device in double, [1364][core_size padded to the kernel's columns] per profile -- one layout.
+ * DCP_EINVAL if any profile was built in float.  A context holds ONE resident DB, float or double: either upload
+ * replaces the other.  Scans of a double DB run the f64 kernel (dcp_scan_params.kernel 0 or 1; 2 and 3 are
+ * DCP_EINVAL) and leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64.  The float-only calls
+ * (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table, dcp_gpu_hit_buffer, explicit xtrans) return DCP_EINVAL on it. */
+int dcp_gpu_db_upload64(dcp_gpu_ctx *, dcp_profile *const *profiles, unsigned nprofiles);
+/* 32 or 64: the precision of the resident DB; 0 without one. */
+int dcp_gpu_db_precision(dcp_gpu_ctx const *);
 unsigned dcp_gpu_db_nprofiles(dcp_gpu_ctx const *);
 /* 1 when the resident DB holds one table layout (asked for or chosen). */
 int dcp_gpu_db_one_layout(dcp_gpu_ctx const *);
@@ -284,6 +317,10 @@ struct dcp_scan_params
                           * LDS: throughput path); 3 = query lane, two-stage blocks (even / odd tiles of a
                           * profile pipelined through an LDS ring: half the scratch traffic) */
 };
+/* The LRT threshold of the scans of a double DB, in double.  NaN -- the sentinel, and the default -- means
+ * "(double) dcp_scan_params.lrt_threshold".  (Not a field of dcp_scan_params: callers that initialise it
+ * positionally under -Wextra -Werror would stop compiling.)  Stays in force for the context's later scans. */
+int dcp_gpu_set_lrt_threshold64(dcp_gpu_ctx *, double lrt_threshold64);
 
 /* scan_thread.c:121-123 keeps a pair iff lrt is finite and >= threshold */
 struct dcp_hit
@@ -292,6 +329,15 @@ struct dcp_hit
     uint32_t profile_idx;
     float null_loglik;
     float alt_loglik;
+};
+
+/* The hit record of a scan of a double DB: same keep rule, evaluated in double */
+struct dcp_hit64
+{
+    uint32_t seq_idx;
+    uint32_t profile_idx;
+    double null_loglik;
+    double alt_loglik;
 };
 
 /* Enqueue the scan of all resident sequences against all resident profiles on
@@ -384,6 +430,10 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *, unsigned i,
 int dcp_gpu_fetch_scores(dcp_gpu_ctx *, float *null_out, float *alt_out);
 int dcp_gpu_fetch_hits(dcp_gpu_ctx *, struct dcp_hit *hits, unsigned cap,
                        unsigned *nhits);
+/* The same for a scan of a double DB, in double.  A float fetch after a double scan, or a double fetch after a
+ * float scan, is DCP_EINVAL (with a message): results are never rounded or widened on the way out. */
+int dcp_gpu_fetch_scores64(dcp_gpu_ctx *, double *null_out, double *alt_out);
+int dcp_gpu_fetch_hits64(dcp_gpu_ctx *, struct dcp_hit64 *hits, unsigned cap, unsigned *nhits);
 /* ------------------------------------------------------------------------ */
 /* Hits -> paths -> product rows                           */
 /* ------------------------------------------------------------------------ */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised differential run of every scan kernel on an MI355X (test infrastructure; uses the CPU oracle).
 
-    python3 tests/tools/fuzz_gpu.py [--seconds 420] [--seed 1] [--oracle-cells 6e7]
+    python3 tests/tools/fuzz_gpu.py [--seconds 420] [--seed 1] [--oracle-cells 6e7] [--precision 64]
 
 The parity tests in tests/test_gpu_parity.py fix their seeds and shapes.  This tool draws them: each round builds a
 small database whose core sizes cluster around the kernels' size-class, segment and tile boundaries, a batch of
@@ -18,6 +18,10 @@ are drawn with the same probability as the short ones) must equal the oracle's f
 tables, bit for bit.  The round's hits (and a few other pairs) are traced back twice -- forward pass by the row-sweep
 kernels, and by the trace kernel's own loop -- and must give the same steps and the scan's score.  The first difference prints the round's seed and shapes and exits 1; `--seed S --rounds 1`
 replays a round.  One line per round; no file of the reference is read.
+
+`--precision 64` runs rounds of the double build instead (one_round64): f64 profiles at the same EDGES, planted
+multi-copy queries, the automatic choice against the row sweep (the same bits), a sample of pairs against the
+oracle's f64 Viterbi within DESIGN §11's 1e-12 * max(1, |ref|).
 """
 import argparse
 import os
@@ -252,6 +256,101 @@ def one_round(dcp, oracle32, sc, hk, seed, oracle_cells, pool, big_every=0):
     return True, len(chosen)
 
 
+def one_round64(dcp, oracle64, sc, seed, oracle_cells, pool):
+    """A round of the double build (--precision 64): f64 profiles with core sizes from EDGES, queries of mixed
+    lengths with a few planted multi-copy ones (the segmented sweep's B(j) fixed point), a random flag combination.
+    KERNEL_AUTO and KERNEL_ROWSWEEP must give the same bits and hits; a sample of pairs bounded by oracle_cells must
+    be within 1e-12 * max(1, |ref|) of the oracle's f64 Viterbi (-inf exactly where it has -inf); the hit list must
+    be the LRT filter over the device's scores, in double."""
+    t0 = time.time()
+    rng = np.random.default_rng(seed)
+    nprof = int(rng.choice([1, 2, 3, 5, 8, 13]))
+    sizes = [int(rng.choice(EDGES[:EDGES.index(2049) + 1])) if rng.random() < 0.7 else int(rng.integers(1, 1200))
+             for _ in range(nprof)]
+    nq = int(rng.choice([1, 2, 5, 9, 21, 64, 65, 130]))
+    entry = int(rng.choice([ENTRY_DIST_UNIFORM, ENTRY_DIST_OCCUPANCY]))
+    eps = float(rng.choice([0.01, 0.05, 0.1]))
+    cfg = dcp.ProteinCfg(entry, float(np.float32(eps)))
+    # a profile whose delete transitions gain score (draw_params' flagged kind) only up to 256 nodes: a segmented one
+    # re-enters B on nearly every row of a multi-hit scan, and the fixed point then takes up to L passes (DESIGN §11)
+    params = [draw_params(rng, M) if M <= 256 else
+              (pfam_like_params(rng, M) if rng.random() < 0.7 else delete_heavy_params(rng, M)) for M in sizes]
+    profiles = [dcp.ProteinProfile.from_params(*prm, cfg, precision=64) for prm in params]
+    oprofs = [oracle64.new(*prm, entry, eps) for prm in params]
+    lens = rng.integers(1, int(rng.choice([12, 40, 150, 400, 1500])) + 1, nq)
+    if rng.random() < 0.2:
+        lens[int(rng.integers(0, nq))] = int(rng.integers(5000, 20000))
+    seqs = [rng.integers(0, 4, int(L), dtype=np.uint8) for L in lens]
+    for _ in range(int(rng.integers(0, 4))):  # k copies of a profile's planted core, back to back or spaced
+        p = int(rng.integers(0, nprof))
+        if sizes[p] > 1100:
+            continue
+        core = planted_query(rng, oprofs[p], sizes[p], flank=0)
+        parts = [rng.integers(0, 4, int(rng.integers(0, 40)), dtype=np.uint8)]
+        for i in range(int(rng.integers(1, 4))):
+            if i and rng.random() < 0.5:
+                parts.append(rng.integers(0, 4, int(rng.integers(20, 201)), dtype=np.uint8))
+            parts.append(core)
+        seqs[int(rng.integers(0, nq))] = np.concatenate(parts + [rng.integers(0, 4, 30, dtype=np.uint8)])
+    multi = bool(rng.random() < 0.7)
+    h3 = bool(rng.random() < 0.3)
+    shape = f"seed {seed} [f64]: {nprof} profiles {sizes} x {nq} queries (1..{max(len(s) for s in seqs)} nt) " \
+            f"multi={int(multi)} h3={int(h3)}"
+
+    sc.upload_db(profiles)
+    sc.upload_seqs(seqs)
+    results = {}
+    for name, k in (("auto", dcp.KERNEL_AUTO), ("rowsweep", dcp.KERNEL_ROWSWEEP)):
+        sc.scan(multi, h3, 10.0, kernel=k)
+        n, a = sc.scores()
+        results[name] = (n.copy(), a.copy(), sc.hits().copy())
+    rn, ra, rh = results["rowsweep"]
+    n, a, h = results["auto"]
+    if not (same_bits64(n, rn) and same_bits64(a, ra)) or not np.array_equal(h, rh):
+        print(f"MISMATCH auto vs rowsweep\n  {shape}", flush=True)
+        return False, 0
+
+    pairs = [(q, p) for q in range(nq) for p in range(nprof)]
+    chosen, cells = [], 0
+    for i in rng.permutation(len(pairs)):
+        q, p = pairs[i]
+        c = sizes[p] * len(seqs[q])
+        if chosen and cells + c > oracle_cells:
+            continue
+        chosen.append((q, p))
+        cells += c
+    by_prof = {}
+    for q, p in chosen:
+        by_prof.setdefault(p, []).append(q)
+
+    def score(item):
+        p, qs = item
+        _, on, oa = oracle64.scan([oprofs[p]], [bytes(seqs[q]) for q in qs], multi, h3, 10.0, 1, 1)
+        return p, qs, on[:, 0], oa[:, 0]
+
+    for p, qs, on, oa in pool.map(score, by_prof.items()):
+        for got, ref, what in ((rn[qs, p], on, "null"), (ra[qs, p], oa, "alt")):
+            inf = np.isinf(ref)
+            err = np.abs(got[~inf] - ref[~inf]) / np.maximum(1.0, np.abs(ref[~inf]))
+            if not (np.array_equal(np.isinf(got), inf) and np.array_equal(got[inf], ref[inf])) or err.max(initial=0) > 1e-12:
+                i = int(np.argmax(np.where(inf, 0, np.abs(got - ref))))
+                print(f"ORACLE MISMATCH ({what}, profile {p} M {sizes[p]}, query {qs[i]} len {len(seqs[qs[i]])}): "
+                      f"device {got[i]!r} oracle {ref[i]!r}\n  {shape}", flush=True)
+                return False, 0
+    lrt = -2 * (rn - ra)
+    want = [(int(q), int(p)) for q, p in zip(*np.nonzero(np.isfinite(lrt) & (lrt >= 10.0)))]
+    if want != list(zip(rh["seq_idx"].tolist(), rh["profile_idx"].tolist())):
+        print(f"HIT LIST != LRT FILTER ({len(rh)} vs {len(want)})\n  {shape}", flush=True)
+        return False, 0
+    print(f"ok  {shape}; 2 scans agree, {len(chosen)} pairs ({cells / 1e6:.1f} Mcell) == oracle, {len(rh)} hits, "
+          f"{time.time() - t0:.1f} s", flush=True)
+    return True, len(chosen)
+
+
+def same_bits64(a, b):
+    return np.array_equal(np.asarray(a, np.float64).view(np.uint64), np.asarray(b, np.float64).view(np.uint64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=420.0)
@@ -260,8 +359,12 @@ def main():
     ap.add_argument("--oracle-cells", type=float, default=6e7)
     ap.add_argument("--big-every", type=int, default=7, help="every N-th seed draws 513 .. 2311 queries against 1 .. 7 profiles (0: never)")
     ap.add_argument("--threads", type=int, default=min(16, os.cpu_count() or 1))
+    ap.add_argument("--precision", type=int, choices=(32, 64), default=32,
+                    help="64: rounds of the double build (f64 DB and kernel) against the oracle's f64 Viterbi")
     a = ap.parse_args()
     dcp = conftest.load_product()
+    if a.precision == 64:
+        return main64(a, dcp)
     oracle32 = conftest.Oracle(32)
     sc = dcp.Scanner(0)
     hk = dcp.Scanner(0, lib=dcp.load_testhooks())
@@ -277,6 +380,23 @@ def main():
     hk.close()
     print(f"{'PASS' if ok else 'FAIL'}: {rounds} rounds (seeds {a.seed} .. {a.seed + rounds - 1}), {pairs} pairs checked against the "
           f"oracle, {time.time() - t0:.0f} s", flush=True)
+    return 0 if ok else 1
+
+
+def main64(a, dcp):
+    oracle64 = conftest.Oracle(64)
+    sc = dcp.Scanner(0)
+    t0 = time.time()
+    rounds = pairs = 0
+    ok = True
+    with ThreadPoolExecutor(a.threads) as pool:
+        while ok and (a.rounds == 0 or rounds < a.rounds) and (a.rounds > 0 or time.time() - t0 < a.seconds):
+            ok, n = one_round64(dcp, oracle64, sc, a.seed + rounds, a.oracle_cells, pool)
+            rounds += 1
+            pairs += n
+    sc.close()
+    print(f"{'PASS' if ok else 'FAIL'}: {rounds} f64 rounds (seeds {a.seed} .. {a.seed + rounds - 1}), {pairs} pairs "
+          f"checked against the oracle's f64 Viterbi, {time.time() - t0:.0f} s", flush=True)
     return 0 if ok else 1
 
 

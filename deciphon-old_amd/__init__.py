@@ -733,9 +733,15 @@ class Scanner:
         cap = int(sum(2 * int(self._seq_lens[q]) + 2 * self._profiles[p].core_size + 16
                       for q, p in zip(h["seq_idx"], h["profile_idx"]))) if n else 0
         steps = np.zeros(max(cap, 1), STEP_DTYPE)
-        self._check(self._lib.dcp_gpu_trace_paths(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat),
-                                            int(null_model), steps.ctypes.data, cap, off.ctypes.data,
-                                            alt.ctypes.data))
+        rc = self._lib.dcp_gpu_trace_paths(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat),
+                                           int(null_model), steps.ctypes.data, cap, off.ctypes.data, alt.ctypes.data)
+        if rc == RC_ENOMEM and off[n] > cap:  # the estimate is short of a long multi-domain path: the true total
+            cap = int(off[n])
+            steps = np.zeros(cap, STEP_DTYPE)
+            rc = self._lib.dcp_gpu_trace_paths(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat),
+                                               int(null_model), steps.ctypes.data, cap, off.ctypes.data,
+                                               alt.ctypes.data)
+        self._check(rc)
         return [steps[off[i]:off[i + 1]].copy() for i in range(n)], alt
 
     def hits(self, cap=1 << 20):

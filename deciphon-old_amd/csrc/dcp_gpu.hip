@@ -2199,8 +2199,9 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     if (!c || !step_off || (nhits && !hits)) return DCP_EINVAL;
     if (c->nprof == 0 || c->nseqs == 0) return c->fail(DCP_EINVAL, "no DB / sequences resident");
     if (c->precision == 64) return c->fail(DCP_EINVAL, "no traceback on a double DB");
+    // step_off[nhits] stays 0 unless the paths are traced: a DCP_ENOMEM of a device allocation then reads as no shortfall
+    step_off[0] = step_off[nhits] = 0;
     HIP_TRY(c, hipSetDevice(c->device));
-    step_off[0] = 0;
     if (nhits == 0) return DCP_OK;
     for (unsigned h = 0; h < nhits; ++h)
         if (hits[h].seq_idx >= c->nseqs || hits[h].profile_idx >= c->nprof)
@@ -2215,7 +2216,9 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     // 5 of its 23 s there, profiles/r04/host_scan_probe.txt); it is kept as the tests' second implementation
     // (trace_mode) and for the null model's one-state path.
     bool const sweep_forward = !null_model && c->trace_mode != 1;
-    // per-hit work area and step capacity
+    // per-hit work area and step capacity.  2L + 2M + 16 steps is an estimate, not a bound: a multi-hit path crosses up
+    // to M + 1 silent states per domain.  The walk counts past its capacity, so a hit whose path is longer is traced
+    // once more at its exact count.
     std::vector<uint64_t> need(nhits);
     std::vector<uint32_t> cap(nhits), wld(nhits);
     std::vector<int> cls(nhits);
@@ -2234,167 +2237,175 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     }
     uint64_t const budget = c->trace_budget ? c->trace_budget : 1ull << 31; // floats (8 GiB) of work area per round of launches
     int rc = DCP_OK;
-    uint64_t total_steps = 0;
-    std::vector<dcp_step> host_steps;
-    for (unsigned h0 = 0; h0 < nhits;)
+    std::vector<std::vector<dcp_step>> got(nhits);
+    std::vector<unsigned> todo(nhits);
+    for (unsigned h = 0; h < nhits; ++h)
+        todo[h] = h;
+    for (int pass = 0; !todo.empty(); ++pass)
     {
-        unsigned h1 = h0;
-        uint64_t work = 0, scap = 0;
-        while (h1 < nhits && (h1 == h0 || work + need[h1] <= budget))
-            work += need[h1], scap += cap[h1], ++h1;
-        unsigned const n = h1 - h0;
-        // this round's hits in size-class order (the forward launches take contiguous pair lists); results go back
-        // to the caller's order on the host
-        std::vector<unsigned> ord(n);
-        for (unsigned i = 0; i < n; ++i)
-            ord[i] = h0 + i;
-        if (sweep_forward) std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return cls[x] < cls[y]; });
-        std::vector<uint64_t> woff(n);
-        std::vector<uint32_t> soff(n + 1, 0), ld(n);
-        std::vector<dcp_hit> shits(n);
-        std::vector<dcp_pair> pairs(n);
-        unsigned cfirst[kNumClasses + 1] = {0};
-        uint64_t acc = 0;
-        for (unsigned i = 0; i < n; ++i)
+        std::vector<unsigned> again; // hits whose paths exceeded their capacity
+        for (size_t t0 = 0; t0 < todo.size();)
         {
-            unsigned const h = ord[i];
-            woff[i] = acc;
-            acc += need[h];
-            soff[i + 1] = soff[i] + cap[h];
-            ld[i] = wld[h];
-            shits[i] = hits[h];
-            pairs[i] = dcp_pair{hits[h].seq_idx, c->slot_of_pidx[hits[h].profile_idx]}; // {q, slot}
-            cfirst[cls[h] + 1] = i + 1u;
-        }
-        for (int k = 1; k <= kNumClasses; ++k)
-            if (cfirst[k] < cfirst[k - 1]) cfirst[k] = cfirst[k - 1];
-        if (c->d_trace_work.n < work) HIP_TRY(c, c->d_trace_work.alloc(work));
-        DevBuf<float> d_alt;
-        DevBuf<uint64_t> d_woff;
-        DevBuf<uint32_t> d_soff, d_nsteps, d_ld, d_counts;
-        DevBuf<dcp_step> d_steps;
-        DevBuf<dcp_hit> d_hits;
-        DevBuf<dcp_pair> d_pairs;
-        HIP_TRY(c, d_alt.alloc(n));
-        HIP_TRY(c, d_woff.alloc(n));
-        HIP_TRY(c, d_soff.alloc(n + 1));
-        HIP_TRY(c, d_nsteps.alloc(n));
-        HIP_TRY(c, d_ld.alloc(n));
-        HIP_TRY(c, d_steps.alloc(scap));
-        HIP_TRY(c, d_hits.alloc(n));
-        HIP_TRY(c, hipMemcpy(d_woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_ld.p, ld.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-        HIP_TRY(c, hipMemcpy(d_hits.p, shits.data(), n * sizeof(dcp_hit), hipMemcpyHostToDevice));
-        if (sweep_forward)
-        {
-            unsigned counts[kNumClasses];
-            for (int k = 0; k < kNumClasses; ++k)
-                counts[k] = cfirst[k + 1] - cfirst[k];
-            HIP_TRY(c, d_pairs.alloc(n));
-            HIP_TRY(c, d_counts.alloc(kNumClasses));
-            HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_pair), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
-            dcp_scan_args fa{};
-            fa.profs = c->d_metas.p;
-            fa.emis_match = c->d_emis_match.p;
-            fa.emis_insert = c->d_emis_insert.p;
-            fa.emis_null = c->d_emis_null.p;
-            fa.trans8 = c->d_trans8.p;
-            fa.seq_words = c->d_seq_words.p;
-            fa.seq_woff = c->d_seq_woff.p;
-            fa.seq_len = c->d_seq_len.p;
-            fa.xtrans = c->d_xtrans.p;
-            fa.nprof_total = c->nprof;
-            fa.nprof = c->nprof;
-            fa.nseqs = c->nseqs;
-            fa.qchunk = 1u;
-            fa.nchunks = c->nseqs;
-            fa.trace_work = c->d_trace_work.p;
-            // the classes' launches side by side on their own streams, largest profiles first: a class's launch lasts as
-            // long as its longest hit and seldom fills the chip (one after the other they took 0.31 of a job's 0.40 s of
-            // traceback, profiles/r04/host_scan_probe_mixed_kernel_stats.csv)
-            for (int k = 0; k <= kNumClasses; ++k)
-                if (!c->ev_trace[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_trace[k], hipEventDisableTiming));
-            HIP_TRY(c, hipEventRecord(c->ev_trace[kNumClasses], c->stream));
-            for (int k = kNumClasses - 1; k >= 0; --k)
+            size_t t1 = t0;
+            uint64_t work = 0, scap = 0;
+            while (t1 < todo.size() &&
+                   (t1 == t0 || (work + need[todo[t1]] <= budget && scap + cap[todo[t1]] <= UINT32_MAX)))
+                work += need[todo[t1]], scap += cap[todo[t1]], ++t1;
+            unsigned const n = (unsigned)(t1 - t0);
+            // this round's hits in size-class order (the forward launches take contiguous pair lists); results go back
+            // to the caller's order on the host
+            std::vector<unsigned> ord(todo.begin() + t0, todo.begin() + t1);
+            if (sweep_forward) std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return cls[x] < cls[y]; });
+            std::vector<uint64_t> woff(n);
+            std::vector<uint32_t> soff(n + 1, 0), ld(n);
+            std::vector<dcp_hit> shits(n);
+            std::vector<dcp_pair> pairs(n);
+            unsigned cfirst[kNumClasses + 1] = {0};
+            uint64_t acc = 0;
+            for (unsigned i = 0; i < n; ++i)
             {
-                if (counts[k] == 0u) continue;
-                SizeClass const sc = kClasses[k];
-                hipStream_t const ls = c->class_stream[k];
-                HIP_TRY(c, hipStreamWaitEvent(ls, c->ev_trace[kNumClasses], 0));
-                fa.pairs = d_pairs.p + cfirst[k];
-                fa.npairs = d_counts.p + k;
-                fa.pair_cap = counts[k];
-                fa.trace_woff = d_woff.p + cfirst[k];
-                fa.trace_alt = d_alt.p + cfirst[k];
-                unsigned const tpb = dcp_rowsweep_tasks_per_block(sc.W);
-                unsigned const nb = ((counts[k] + tpb - 1u) / tpb + 7u) / 8u * 8u;
-                if (dcp_launch_trace_forward(sc.R, sc.W, &fa, nb, ls))
-                    return c->fail(DCP_EFAIL, "no traceback kernel for class R=%d W=%d", sc.R, sc.W);
-                HIP_TRY(c, hipEventRecord(c->ev_trace[k], ls));
-                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trace[k], 0));
+                unsigned const h = ord[i];
+                woff[i] = acc;
+                acc += need[h];
+                soff[i + 1] = soff[i] + cap[h];
+                ld[i] = wld[h];
+                shits[i] = hits[h];
+                pairs[i] = dcp_pair{hits[h].seq_idx, c->slot_of_pidx[hits[h].profile_idx]}; // {q, slot}
+                cfirst[cls[h] + 1] = i + 1u;
             }
+            for (int k = 1; k <= kNumClasses; ++k)
+                if (cfirst[k] < cfirst[k - 1]) cfirst[k] = cfirst[k - 1];
+            if (c->d_trace_work.n < work) HIP_TRY(c, c->d_trace_work.alloc(work));
+            DevBuf<float> d_alt;
+            DevBuf<uint64_t> d_woff;
+            DevBuf<uint32_t> d_soff, d_nsteps, d_ld, d_counts;
+            DevBuf<dcp_step> d_steps;
+            DevBuf<dcp_hit> d_hits;
+            DevBuf<dcp_pair> d_pairs;
+            HIP_TRY(c, d_alt.alloc(n));
+            HIP_TRY(c, d_woff.alloc(n));
+            HIP_TRY(c, d_soff.alloc(n + 1));
+            HIP_TRY(c, d_nsteps.alloc(n));
+            HIP_TRY(c, d_ld.alloc(n));
+            HIP_TRY(c, d_steps.alloc(scap));
+            HIP_TRY(c, d_hits.alloc(n));
+            HIP_TRY(c, hipMemcpy(d_woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_ld.p, ld.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_hits.p, shits.data(), n * sizeof(dcp_hit), hipMemcpyHostToDevice));
+            if (sweep_forward)
+            {
+                unsigned counts[kNumClasses];
+                for (int k = 0; k < kNumClasses; ++k)
+                    counts[k] = cfirst[k + 1] - cfirst[k];
+                HIP_TRY(c, d_pairs.alloc(n));
+                HIP_TRY(c, d_counts.alloc(kNumClasses));
+                HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_pair), hipMemcpyHostToDevice));
+                HIP_TRY(c, hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
+                dcp_scan_args fa{};
+                fa.profs = c->d_metas.p;
+                fa.emis_match = c->d_emis_match.p;
+                fa.emis_insert = c->d_emis_insert.p;
+                fa.emis_null = c->d_emis_null.p;
+                fa.trans8 = c->d_trans8.p;
+                fa.seq_words = c->d_seq_words.p;
+                fa.seq_woff = c->d_seq_woff.p;
+                fa.seq_len = c->d_seq_len.p;
+                fa.xtrans = c->d_xtrans.p;
+                fa.nprof_total = c->nprof;
+                fa.nprof = c->nprof;
+                fa.nseqs = c->nseqs;
+                fa.qchunk = 1u;
+                fa.nchunks = c->nseqs;
+                fa.trace_work = c->d_trace_work.p;
+                // the classes' launches side by side on their own streams, largest profiles first: a class's launch lasts as
+                // long as its longest hit and seldom fills the chip (one after the other they took 0.31 of a job's 0.40 s of
+                // traceback, profiles/r04/host_scan_probe_mixed_kernel_stats.csv)
+                for (int k = 0; k <= kNumClasses; ++k)
+                    if (!c->ev_trace[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_trace[k], hipEventDisableTiming));
+                HIP_TRY(c, hipEventRecord(c->ev_trace[kNumClasses], c->stream));
+                for (int k = kNumClasses - 1; k >= 0; --k)
+                {
+                    if (counts[k] == 0u) continue;
+                    SizeClass const sc = kClasses[k];
+                    hipStream_t const ls = c->class_stream[k];
+                    HIP_TRY(c, hipStreamWaitEvent(ls, c->ev_trace[kNumClasses], 0));
+                    fa.pairs = d_pairs.p + cfirst[k];
+                    fa.npairs = d_counts.p + k;
+                    fa.pair_cap = counts[k];
+                    fa.trace_woff = d_woff.p + cfirst[k];
+                    fa.trace_alt = d_alt.p + cfirst[k];
+                    unsigned const tpb = dcp_rowsweep_tasks_per_block(sc.W);
+                    unsigned const nb = ((counts[k] + tpb - 1u) / tpb + 7u) / 8u * 8u;
+                    if (dcp_launch_trace_forward(sc.R, sc.W, &fa, nb, ls))
+                        return c->fail(DCP_EFAIL, "no traceback kernel for class R=%d W=%d", sc.R, sc.W);
+                    HIP_TRY(c, hipEventRecord(c->ev_trace[k], ls));
+                    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trace[k], 0));
+                }
+                HIP_TRY(c, hipGetLastError());
+            }
+            dcp_trace_args ta{};
+            ta.profs = c->d_metas.p;
+            ta.slot_of_pidx = c->d_slot_of_pidx.p;
+            ta.emis_match = c->d_emis_match.p;
+            ta.emis_insert = c->d_emis_insert.p;
+            ta.emis_null = c->d_emis_null.p;
+            ta.trans8 = c->d_trans8.p;
+            ta.seq_words = c->d_seq_words.p;
+            ta.seq_woff = c->d_seq_woff.p;
+            ta.seq_len = c->d_seq_len.p;
+            ta.xtrans = c->d_xtrans.p;
+            ta.hits = d_hits.p;
+            ta.nhits = n;
+            ta.work = c->d_trace_work.p;
+            ta.work_off = d_woff.p;
+            ta.steps = d_steps.p;
+            ta.step_off = d_soff.p;
+            ta.nsteps = d_nsteps.p;
+            ta.alt_out = d_alt.p;
+            ta.null_model = null_model ? 1 : 0;
+            ta.skip_forward = sweep_forward ? 1 : 0;
+            ta.work_ld = d_ld.p;
+            dcp_launch_trace(&ta, n, c->stream);
             HIP_TRY(c, hipGetLastError());
-        }
-        dcp_trace_args ta{};
-        ta.profs = c->d_metas.p;
-        ta.slot_of_pidx = c->d_slot_of_pidx.p;
-        ta.emis_match = c->d_emis_match.p;
-        ta.emis_insert = c->d_emis_insert.p;
-        ta.emis_null = c->d_emis_null.p;
-        ta.trans8 = c->d_trans8.p;
-        ta.seq_words = c->d_seq_words.p;
-        ta.seq_woff = c->d_seq_woff.p;
-        ta.seq_len = c->d_seq_len.p;
-        ta.xtrans = c->d_xtrans.p;
-        ta.hits = d_hits.p;
-        ta.nhits = n;
-        ta.work = c->d_trace_work.p;
-        ta.work_off = d_woff.p;
-        ta.steps = d_steps.p;
-        ta.step_off = d_soff.p;
-        ta.nsteps = d_nsteps.p;
-        ta.alt_out = d_alt.p;
-        ta.null_model = null_model ? 1 : 0;
-        ta.skip_forward = sweep_forward ? 1 : 0;
-        ta.work_ld = d_ld.p;
-        dcp_launch_trace(&ta, n, c->stream);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::vector<uint32_t> ns(n);
-        std::vector<dcp_step> st(scap);
-        std::vector<float> alts(n);
-        HIP_TRY(c, hipMemcpy(ns.data(), d_nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(st.data(), d_steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
-        HIP_TRY(c, hipMemcpy(alts.data(), d_alt.p, n * sizeof(float), hipMemcpyDeviceToHost));
-        // back to the caller's order
-        std::vector<unsigned> at(n);
-        for (unsigned i = 0; i < n; ++i)
-            at[ord[i] - h0] = i;
-        for (unsigned j = 0; j < n; ++j)
-        {
-            unsigned const i = at[j], h = h0 + j;
-            if (alt_out) alt_out[h] = alts[i];
-            if (ns[i] == 0xffffffffu)
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            std::vector<uint32_t> ns(n);
+            std::vector<dcp_step> st(scap);
+            std::vector<float> alts(n);
+            HIP_TRY(c, hipMemcpy(ns.data(), d_nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(st.data(), d_steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(alts.data(), d_alt.p, n * sizeof(float), hipMemcpyDeviceToHost));
+            for (unsigned i = 0; i < n; ++i)
             {
-                rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite alt path", hits[h].seq_idx, hits[h].profile_idx);
-                ns[i] = 0;
+                unsigned const h = ord[i];
+                if (alt_out) alt_out[h] = alts[i];
+                if (ns[i] == DCP_TRACE_NO_PATH)
+                    rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite alt path", hits[h].seq_idx, hits[h].profile_idx);
+                else if (ns[i] == DCP_TRACE_TOO_LONG)
+                    rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
+                                 hits[h].profile_idx);
+                else if (ns[i] > cap[h] && pass == 0)
+                    cap[h] = ns[i], again.push_back(h);
+                else if (ns[i] > cap[h])
+                    rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
+                else
+                    got[h].assign(st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
             }
-            else if (ns[i] > cap[h])
-            {
-                rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
-                ns[i] = 0;
-            }
-            host_steps.insert(host_steps.end(), st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
-            total_steps += ns[i];
-            step_off[h + 1] = (uint32_t)total_steps;
+            t0 = t1;
         }
-        h0 = h1;
+        if (rc) return rc;
+        todo.swap(again);
     }
-    if (rc) return rc;
+    uint64_t total_steps = 0;
+    for (unsigned h = 0; h < nhits; ++h)
+    {
+        total_steps += got[h].size();
+        if (total_steps > UINT32_MAX) return c->fail(DCP_EFAIL, "the paths of %u hits exceed 2^32 - 1 steps", nhits);
+        step_off[h + 1] = (uint32_t)total_steps;
+    }
     if (total_steps > cap_steps || (total_steps && !steps_out)) return DCP_ENOMEM;
-    if (total_steps) std::memcpy(steps_out, host_steps.data(), total_steps * sizeof(dcp_step));
+    for (unsigned h = 0; h < nhits; ++h)
+        if (!got[h].empty()) std::memcpy(steps_out + step_off[h], got[h].data(), got[h].size() * sizeof(dcp_step));
     return DCP_OK;
 }
 

@@ -116,6 +116,12 @@ struct dcp_expand_tile
 };
 
 // ---- alt-path traceback for hits (viterbi_trace_kernel) ----------------------
+// what nsteps holds for a hit without a path: no finite path ends in T (R); or a path of more than 2^32 - 3 steps
+enum : uint32_t
+{
+    DCP_TRACE_NO_PATH = 0xffffffffu,
+    DCP_TRACE_TOO_LONG = 0xfffffffeu,
+};
 struct dcp_trace_args
 {
     dcp_prof_meta const *profs;
@@ -134,7 +140,7 @@ struct dcp_trace_args
     uint64_t const *work_off; // [nhits] float offset of each hit's work area
     dcp_step *steps;
     uint32_t const *step_off; // [nhits+1] capacity slices of steps[]
-    uint32_t *nsteps;         // [nhits] steps written; 0xffffffff = no path
+    uint32_t *nsteps;         // [nhits] steps of the path (written: up to the capacity), or DCP_TRACE_NO_PATH / _TOO_LONG
     float *alt_out;           // [nhits] log-likelihood recomputed by the trace
     int null_model;           // 0: alt model path (S..T); 1: null model path (R steps)
     int skip_forward;         // the work areas are filled (dcp_launch_trace_forward): walk back only

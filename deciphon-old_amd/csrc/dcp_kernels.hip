@@ -1531,7 +1531,7 @@ __global__ __launch_bounds__(64) void viterbi_trace_kernel(dcp_trace_args a)
             out[i] = out[m - 1 - i];
             out[m - 1 - i] = t;
         }
-        a.nsteps[h] = ok ? n : 0xffffffffu;
+        a.nsteps[h] = ok ? n : DCP_TRACE_NO_PATH;
         return;
     }
 
@@ -1618,16 +1618,18 @@ __global__ __launch_bounds__(64) void viterbi_trace_kernel(dcp_trace_args a)
     dcp_step *out = a.steps + a.step_off[h];
     unsigned const cap = a.step_off[h + 1] - a.step_off[h];
     unsigned n = 0;
-    bool ok = alt > ni;
+    bool ok = alt > ni, too_long = false;
     enum { ST_S = 1, ST_N, ST_B, ST_E, ST_J, ST_C, ST_T, ST_M, ST_I, ST_D };
     int st = ST_T;
     unsigned k = 0, j = L;
     auto push = [&](unsigned id, unsigned len) {
         if (n < cap) out[n] = dcp_step{(uint16_t)id, (uint8_t)len, 0};
-        ++n;
+        if (++n == DCP_TRACE_TOO_LONG) too_long = true, ok = false; // an error, never a wrap into the sentinels
     };
     unsigned const EXT = 3u << 14;
-    unsigned guard = 0, const_guard = 4u * (L + v.M) + 64u;
+    // a path has at most L emitting steps and, per domain (at most L of them), M + 1 silent core steps and B, E, J
+    uint64_t guard = 0;
+    uint64_t const const_guard = ((uint64_t)L + 1u) * (v.M + 4u) + 64u;
     while (ok && guard++ < const_guard)
     {
         if (st == ST_T)
@@ -1764,7 +1766,7 @@ __global__ __launch_bounds__(64) void viterbi_trace_kernel(dcp_trace_args a)
         out[i] = out[m - 1 - i];
         out[m - 1 - i] = t;
     }
-    a.nsteps[h] = ok ? n : 0xffffffffu;
+    a.nsteps[h] = ok ? n : too_long ? DCP_TRACE_TOO_LONG : DCP_TRACE_NO_PATH;
 }
 
 extern "C" void dcp_launch_trace(dcp_trace_args const *a, unsigned nhits, void *stream)

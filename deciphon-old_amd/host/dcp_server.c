@@ -488,12 +488,26 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
     if (!rc)
     {
         res->steps = malloc((size_t)cap * sizeof *res->steps);
-        res->soff = malloc(((size_t)nhits + 1) * sizeof *res->soff);
+        res->soff = calloc((size_t)nhits + 1, sizeof *res->soff);
         if (!res->steps || !res->soff) rc = fail(RC_ENOMEM, "alloc paths");
     }
     if (!rc && (drc = dcp_gpu_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
-                                          (unsigned)cap, res->soff, NULL)))
-        rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+                                          (unsigned)cap, res->soff, NULL)) == DCP_ENOMEM &&
+        res->soff[nhits] > cap)
+    {
+        /* 2L + 2M + 16 per hit is an estimate: multi-domain paths through long delete runs are longer.  Again at the
+         * true total, which the call left in soff[nhits] (a device allocation's DCP_ENOMEM leaves it 0: no retry). */
+        cap = res->soff[nhits];
+        struct dcp_step *more = realloc(res->steps, (size_t)cap * sizeof *res->steps);
+        if (!more) rc = fail(RC_ENOMEM, "alloc paths");
+        else
+        {
+            res->steps = more;
+            drc = dcp_gpu_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
+                                      (unsigned)cap, res->soff, NULL);
+        }
+    }
+    if (!rc && drc) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
     if (rc) batch_result_free(res);
     else
     {

@@ -313,6 +313,19 @@ static enum imm_rc viterbi_locked(struct imm_dp const *dp, struct imm_task *task
     uint32_t soff[2] = {0, 0};
     float traced = NAN;
     drc = dcp_gpu_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
+    if (drc == DCP_ENOMEM && soff[1] > cap)
+    {
+        /* a multi-domain path can be longer than the estimate: again at its true count */
+        cap = soff[1];
+        struct dcp_step *more = realloc(steps, (size_t)cap * sizeof *steps);
+        if (!more)
+        {
+            free(steps);
+            return IMM_FAILURE;
+        }
+        steps = more;
+        drc = dcp_gpu_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
+    }
     enum imm_rc out = IMM_FAILURE;
     if (!drc && !dcp_host_path_assign(&prod->path, steps, soff[1]))
     {

@@ -452,7 +452,11 @@ struct dcp_step
  * them. steps_out receives the paths back to back; step_off[nhits+1] their
  * offsets; alt_out (may be NULL) the log-likelihood the trace recomputed (equal
  * to the scan's). DCP_ENOMEM if cap_steps is too small (step_off[nhits] then
- * holds the needed total), DCP_EFAIL if a pair has no finite path.
+ * holds the needed total, more than cap_steps: call again with that much; a device allocation's
+ * DCP_ENOMEM leaves it 0), DCP_EFAIL if a pair has no finite path or one of more than 2^32 - 3 steps.
+ * A path has no bound of the form 2L + cM: in multi-hit mode each domain can cross M + 1 silent states, so a
+ * path has up to L emitting steps plus M + 4 per domain.  2L + 2M + 16 per hit is a first estimate only: the call
+ * traces a longer hit once more at its exact count.
  * Device work: the rows of every hit are swept once more by its size class's row-sweep kernel, which parks every
  * row's M, I, D, N, B, E, J, C in a work area (12 x 64 R W + 20 bytes per row; at most 8 GiB per round of launches,
  * kept by the context between calls), then one wavefront per hit walks back through it. */

@@ -1077,14 +1077,18 @@ ofloat orc_path_score(struct orc_profile const *p, int alt, unsigned char const 
 /* ======================================================================== */
 static inline ofloat omax(ofloat a, ofloat b) { return a > b ? a : b; }
 
-int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
-                  ofloat const *emis_match, ofloat const *emis_insert,
-                  ofloat const *emis_null, ofloat const *xt, unsigned char const *seq,
-                  unsigned L, ofloat *null_loglik, ofloat *alt_loglik)
+/* Every row of the recursion, for a traceback: M, I, D [L+1][M] and the special states [L+1]. */
+struct dp_rows
 {
-    if (L == 0) return ORC_EINVAL;
-    for (unsigned i = 0; i < L; ++i)
-        if (seq[i] > 3) return ORC_EINVAL;
+    ofloat *Mv, *Iv, *Dv;
+    ofloat *N, *B, *E, *J, *C, *R;
+};
+
+static int dp_tables_run(unsigned M, unsigned ldk, ofloat const *trans8,
+                         ofloat const *emis_match, ofloat const *emis_insert,
+                         ofloat const *emis_null, ofloat const *xt, unsigned char const *seq,
+                         unsigned L, ofloat *null_loglik, ofloat *alt_loglik, struct dp_rows const *keep)
+{
     ofloat const *ENT = trans8 + 0 * (size_t)ldk, *MM = trans8 + 1 * (size_t)ldk,
                  *IM = trans8 + 2 * (size_t)ldk, *DM = trans8 + 3 * (size_t)ldk,
                  *MD = trans8 + 4 * (size_t)ldk, *DD = trans8 + 5 * (size_t)ldk,
@@ -1099,6 +1103,11 @@ int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
     ofloat *Ir = malloc(sizeof(ofloat) * (size_t)M);
     ofloat *Dr = malloc(sizeof(ofloat) * (size_t)M);
     ofloat PN[6], PJ[6], PC[6], PR[6];
+    if (!PM || !QI || !Mr || !Ir || !Dr)
+    {
+        free(PM), free(QI), free(Mr), free(Ir), free(Dr);
+        return ORC_ENOMEM;
+    }
 
     /* row 0 */
     {
@@ -1112,6 +1121,13 @@ int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
         PJ[0] = NEG_INF;
         PC[0] = NEG_INF;
         PR[0] = 0; /* start lprob of R */
+        if (keep)
+        {
+            for (unsigned k = 0; k < M; ++k)
+                keep->Mv[k] = keep->Iv[k] = keep->Dv[k] = NEG_INF;
+            keep->N[0] = keep->E[0] = keep->J[0] = keep->C[0] = keep->R[0] = NEG_INF;
+            keep->B[0] = B;
+        }
     }
     ofloat E = NEG_INF, Cc = NEG_INF, Rr = NEG_INF;
     unsigned w = 0;
@@ -1169,11 +1185,327 @@ int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
         PJ[r] = omax(E + EJ, J + JJ);
         PC[r] = omax(E + EC, Cc + CC);
         PR[r] = Rr + RR;
+        if (keep)
+        {
+            size_t const o = (size_t)j * M;
+            memcpy(keep->Mv + o, Mr, sizeof(ofloat) * M);
+            memcpy(keep->Iv + o, Ir, sizeof(ofloat) * M);
+            memcpy(keep->Dv + o, Dr, sizeof(ofloat) * M);
+            keep->N[j] = N, keep->B[j] = B, keep->E[j] = E, keep->J[j] = J, keep->C[j] = Cc, keep->R[j] = Rr;
+        }
     }
     *null_loglik = Rr;
     *alt_loglik = omax(E + ET, Cc + CT);
     free(PM), free(QI), free(Mr), free(Ir), free(Dr);
     return ORC_OK;
+}
+
+static int check_seq(unsigned char const *seq, unsigned L)
+{
+    if (L == 0) return ORC_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return ORC_EINVAL;
+    return ORC_OK;
+}
+
+int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
+                  ofloat const *emis_match, ofloat const *emis_insert,
+                  ofloat const *emis_null, ofloat const *xt, unsigned char const *seq,
+                  unsigned L, ofloat *null_loglik, ofloat *alt_loglik)
+{
+    if (check_seq(seq, L)) return ORC_EINVAL;
+    return dp_tables_run(M, ldk, trans8, emis_match, emis_insert, emis_null, xt, seq, L, null_loglik,
+                         alt_loglik, NULL);
+}
+
+/* ---- traceback on given tables ----------------------------------------------------------------------
+ * The walk asks, at every step, which incoming edge of the current state gave its value, in the order
+ * viterbi_generic scans them: the CSR order of the transitions, i.e. the order build_models wires them
+ * (first maximum wins, strict >), and for an emitting state the shortest fragment first.  Incoming edges:
+ *   M_k: M_{k-1} -> M_k, I_{k-1} -> M_k, D_{k-1} -> M_k (setup_transitions), then B -> M_k (entry)
+ *   I_k: M_k -> I_k, I_k -> I_k          D_k: M_{k-1} -> D_k, D_{k-1} -> D_k
+ *   E: M_M -> E (wired with the nodes), M_1 .. M_{M-1} -> E, D_2 .. D_M -> E (exits)
+ *   B: S, N, E, J        N: S, N        J: E, J        C: E, C        T: E, C        R: start, R */
+enum { W_S = 1, W_N, W_B, W_E, W_J, W_C, W_T, W_M, W_I, W_D, W_R };
+
+struct walk
+{
+    unsigned M, ldk;
+    struct dp_rows rows;
+    ofloat const *ENT, *MM, *IM, *DM, *MD, *DD, *MI, *II;
+    ofloat const *em, *ei, *en, *xt;
+};
+
+static inline void first_max(ofloat v, int id, ofloat *best, int *arg)
+{
+    if (v > *best) *best = v, *arg = id;
+}
+
+/* the value an emitting state's fragment leaves from row r, and which predecessor gave it */
+static ofloat walk_pred(struct walk const *w, int st, unsigned k, unsigned r, int *arg)
+{
+    struct dp_rows const *v = &w->rows;
+    ofloat const *xt = w->xt;
+    ofloat best = NEG_INF;
+    int a = -1;
+    size_t const o = (size_t)r * w->M;
+    switch (st)
+    {
+    case W_M:
+        if (k)
+        {
+            first_max(v->Mv[o + k - 1] + w->MM[k], W_M, &best, &a);
+            first_max(v->Iv[o + k - 1] + w->IM[k], W_I, &best, &a);
+            first_max(v->Dv[o + k - 1] + w->DM[k], W_D, &best, &a);
+        }
+        first_max(v->B[r] + w->ENT[k], W_B, &best, &a);
+        break;
+    case W_I:
+        first_max(v->Mv[o + k] + w->MI[k], W_M, &best, &a);
+        first_max(v->Iv[o + k] + w->II[k], W_I, &best, &a);
+        break;
+    case W_N:
+        first_max((r == 0 ? 0 : NEG_INF) + xt[2], W_S, &best, &a);
+        first_max(v->N[r] + xt[3], W_N, &best, &a);
+        break;
+    case W_J:
+        first_max(v->E[r] + xt[10], W_E, &best, &a);
+        first_max(v->J[r] + xt[11], W_J, &best, &a);
+        break;
+    case W_C:
+        first_max(v->E[r] + xt[6], W_E, &best, &a);
+        first_max(v->C[r] + xt[7], W_C, &best, &a);
+        break;
+    default: /* W_R */
+        if (r == 0) first_max(0, W_S, &best, &a); /* the null model's start */
+        first_max(v->R[r] + xt[0], W_R, &best, &a);
+        break;
+    }
+    *arg = a;
+    return best;
+}
+
+static ofloat walk_emis(struct walk const *w, int st, unsigned k, unsigned code)
+{
+    if (st == W_M) return w->em[(size_t)code * w->ldk + k];
+    if (st == W_I) return w->ei[code];
+    return w->en[code];
+}
+
+static uint16_t walk_id(int st, unsigned k)
+{
+    switch (st)
+    {
+    case W_M: return (uint16_t)(ORC_MATCH_STATE | (k + 1));
+    case W_I: return (uint16_t)(ORC_INSERT_STATE | (k + 1));
+    case W_D: return (uint16_t)(ORC_DELETE_STATE | (k + 1));
+    case W_R: return (uint16_t)ORC_R_STATE;
+    default: return (uint16_t)(ORC_EXT_STATE | (unsigned)(st - W_S + 1));
+    }
+}
+
+/* Walks back from T (alt) or R(L) (null).  Writes up to *nsteps steps, sets *nsteps to the path's length;
+ * ORC_ENOMEM if that exceeds the capacity, ORC_EFAIL if no finite path ends there. */
+static int walk_back(struct walk const *w, unsigned char const *seq, unsigned L, int alt, uint16_t *path_state,
+                     uint8_t *path_len, unsigned *nsteps)
+{
+    struct dp_rows const *v = &w->rows;
+    ofloat const *xt = w->xt;
+    unsigned const cap = *nsteps;
+    uint64_t const bound = ((uint64_t)L + 1) * (w->M + 4) + 64;
+    uint64_t cnt = 0;
+    int st = alt ? W_T : W_R;
+    unsigned k = 0, j = L;
+    int ok = 1;
+    while (ok && cnt < bound)
+    {
+        if (cnt < cap)
+        {
+            path_state[cnt] = walk_id(st, k);
+            path_len[cnt] = 0;
+        }
+        ++cnt;
+        if (st == W_S) break;
+        ofloat best = NEG_INF;
+        int a = -1;
+        unsigned ak = k;
+        size_t const o = (size_t)j * w->M;
+        switch (st)
+        {
+        case W_T:
+            first_max(v->E[j] + xt[5], W_E, &best, &a);
+            first_max(v->C[j] + xt[8], W_C, &best, &a);
+            break;
+        case W_B:
+            first_max((j == 0 ? 0 : NEG_INF) + xt[1], W_S, &best, &a);
+            first_max(v->N[j] + xt[4], W_N, &best, &a);
+            first_max(v->E[j] + xt[9], W_E, &best, &a);
+            first_max(v->J[j] + xt[12], W_J, &best, &a);
+            break;
+        case W_E:
+            first_max(v->Mv[o + w->M - 1] + 0, W_M, &best, &a), ak = w->M - 1;
+            for (unsigned kk = 0; kk + 1 < w->M; ++kk)
+                if (v->Mv[o + kk] + 0 > best) best = v->Mv[o + kk] + 0, a = W_M, ak = kk;
+            for (unsigned kk = 1; kk < w->M; ++kk)
+                if (v->Dv[o + kk] + 0 > best) best = v->Dv[o + kk] + 0, a = W_D, ak = kk;
+            break;
+        case W_D:
+            if (k == 0) break;
+            first_max(v->Mv[o + k - 1] + w->MD[k], W_M, &best, &a);
+            first_max(v->Dv[o + k - 1] + w->DD[k], W_D, &best, &a);
+            ak = k - 1;
+            break;
+        default: /* emitting: the fragment first (shortest wins ties), then the predecessor it left */
+        {
+            unsigned const maxl = j < 5 ? j : 5;
+            unsigned bl = 0;
+            for (unsigned l = 1; l <= maxl; ++l)
+            {
+                int unused;
+                unsigned const code = orc_word_code(seq + j - l, l);
+                ofloat sc = walk_pred(w, st, k, j - l, &unused) + walk_emis(w, st, k, code);
+                if (sc > best) best = sc, bl = l;
+            }
+            if (!bl) break;
+            if (cnt - 1 < cap) path_len[cnt - 1] = (uint8_t)bl;
+            j -= bl;
+            walk_pred(w, st, k, j, &a);
+            /* M_k's chain predecessors are node k-1's; the self loops and N/J/C keep k */
+            if (st == W_M && a != W_B) ak = k - 1;
+            break;
+        }
+        }
+        if (a < 0) ok = 0;
+        st = a, k = ak;
+    }
+    if (!ok || st != W_S || j != 0)
+    {
+        *nsteps = 0;
+        return ORC_EFAIL;
+    }
+    if (!alt) --cnt; /* the null model's start is R itself: no S step */
+    if (cnt > UINT32_MAX - 1)
+    {
+        *nsteps = 0;
+        return ORC_EFAIL;
+    }
+    unsigned const m = cnt < cap ? (unsigned)cnt : cap;
+    for (unsigned i = 0; i < m / 2; ++i)
+    {
+        uint16_t ts = path_state[i];
+        path_state[i] = path_state[m - 1 - i];
+        path_state[m - 1 - i] = ts;
+        uint8_t tl = path_len[i];
+        path_len[i] = path_len[m - 1 - i];
+        path_len[m - 1 - i] = tl;
+    }
+    *nsteps = (unsigned)cnt;
+    return cnt > cap ? ORC_ENOMEM : ORC_OK;
+}
+
+int orc_dp_tables_path(unsigned M, unsigned ldk, ofloat const *trans8,
+                       ofloat const *emis_match, ofloat const *emis_insert,
+                       ofloat const *emis_null, ofloat const *xt, unsigned char const *seq,
+                       unsigned L, ofloat *null_loglik, ofloat *alt_loglik,
+                       uint16_t *alt_state, uint8_t *alt_len, unsigned *alt_nsteps,
+                       uint16_t *null_state, uint8_t *null_len, unsigned *null_nsteps)
+{
+    if (check_seq(seq, L) || M == 0 || ldk < M) return ORC_EINVAL;
+    size_t const cells = ((size_t)L + 1) * M, rows = (size_t)L + 1;
+    struct walk w = {.M = M, .ldk = ldk, .em = emis_match, .ei = emis_insert, .en = emis_null, .xt = xt};
+    w.ENT = trans8, w.MM = trans8 + (size_t)ldk, w.IM = trans8 + 2 * (size_t)ldk, w.DM = trans8 + 3 * (size_t)ldk;
+    w.MD = trans8 + 4 * (size_t)ldk, w.DD = trans8 + 5 * (size_t)ldk, w.MI = trans8 + 6 * (size_t)ldk;
+    w.II = trans8 + 7 * (size_t)ldk;
+    ofloat *mem = malloc(sizeof(ofloat) * (3 * cells + 6 * rows));
+    if (!mem) return *alt_nsteps = *null_nsteps = 0, ORC_ENOMEM; /* no counts: nothing to retry with */
+    struct dp_rows *v = &w.rows;
+    v->Mv = mem, v->Iv = mem + cells, v->Dv = mem + 2 * cells;
+    v->N = mem + 3 * cells, v->B = v->N + rows, v->E = v->B + rows, v->J = v->E + rows, v->C = v->J + rows;
+    v->R = v->C + rows;
+    if (dp_tables_run(M, ldk, trans8, emis_match, emis_insert, emis_null, xt, seq, L, null_loglik, alt_loglik, v))
+    {
+        free(mem);
+        *alt_nsteps = *null_nsteps = 0;
+        return ORC_ENOMEM;
+    }
+    /* no finite path: none (as viterbi_generic leaves it) */
+    int rc_alt = ORC_OK, rc_null = ORC_OK;
+    if (*alt_loglik > NEG_INF) rc_alt = walk_back(&w, seq, L, 1, alt_state, alt_len, alt_nsteps);
+    else *alt_nsteps = 0;
+    if (*null_loglik > NEG_INF) rc_null = walk_back(&w, seq, L, 0, null_state, null_len, null_nsteps);
+    else *null_nsteps = 0;
+    free(mem);
+    if (rc_alt == ORC_EFAIL || rc_null == ORC_EFAIL) return ORC_EFAIL;
+    return rc_alt ? rc_alt : rc_null;
+}
+
+ofloat orc_path_score_tables(unsigned M, unsigned ldk, ofloat const *trans8,
+                             ofloat const *emis_match, ofloat const *emis_insert,
+                             ofloat const *emis_null, ofloat const *xt, unsigned char const *seq,
+                             unsigned L, int alt, uint16_t const *path_state,
+                             uint8_t const *path_len, unsigned nsteps)
+{
+    ofloat const *ENT = trans8, *MM = trans8 + (size_t)ldk, *IM = trans8 + 2 * (size_t)ldk,
+                 *DM = trans8 + 3 * (size_t)ldk, *MD = trans8 + 4 * (size_t)ldk, *DD = trans8 + 5 * (size_t)ldk,
+                 *MI = trans8 + 6 * (size_t)ldk, *II = trans8 + 7 * (size_t)ldk;
+    ofloat score = 0;
+    unsigned pos = 0, pkind = 0, pk = 0;
+    for (unsigned i = 0; i < nsteps; ++i)
+    {
+        unsigned const id = path_state[i], kind = id >> 14, k = (id & 0x3fffu) - 1u, len = path_len[i];
+        unsigned const x = id & 0x3fffu; /* special state: 0 R, 1 S, 2 N, 3 B, 4 E, 5 J, 6 C, 7 T */
+        if (kind < 3 ? (x == 0 || x > M) : x > 7) return (ofloat)NAN;
+        int const emitting = kind < 2 || (kind == 3 && (x == 0 || x == 2 || x == 5 || x == 6));
+        if (emitting ? (len < 1 || len > 5) : len != 0) return (ofloat)NAN;
+        if (pos + len > L) return (ofloat)NAN;
+        if (!alt && !(kind == 3 && x == 0)) return (ofloat)NAN;
+        if (alt && kind == 3 && x == 0) return (ofloat)NAN;
+        ofloat t = (ofloat)NAN; /* the transition from the previous step; NaN: no such edge */
+        if (i == 0)
+            t = (kind == 3 && x == (alt ? 1u : 0u)) ? 0 : (ofloat)NAN; /* the start state, start lprob 0 */
+        else if (kind == 0)
+        {
+            if (pkind == 3 && pk == 3) t = ENT[k];
+            else if (k > 0 && pk == k)
+                t = pkind == 0 ? MM[k] : pkind == 1 ? IM[k] : pkind == 2 ? DM[k] : (ofloat)NAN;
+        }
+        else if (kind == 1)
+        {
+            if (pk == k + 1) t = pkind == 0 ? MI[k] : pkind == 1 ? II[k] : (ofloat)NAN;
+        }
+        else if (kind == 2)
+        {
+            if (k > 0 && pk == k) t = pkind == 0 ? MD[k] : pkind == 2 ? DD[k] : (ofloat)NAN;
+        }
+        else
+        {
+            unsigned const from = pkind == 3 ? pk : 100u; /* a core state only precedes E */
+            switch (x)
+            {
+            case 0: t = from == 0 ? xt[0] : (ofloat)NAN; break;
+            case 2: t = from == 1 ? xt[2] : from == 2 ? xt[3] : (ofloat)NAN; break;
+            case 3:
+                t = from == 1 ? xt[1] : from == 2 ? xt[4] : from == 4 ? xt[9] : from == 5 ? xt[12] : (ofloat)NAN;
+                break;
+            case 4: t = pkind == 0 || (pkind == 2 && pk >= 2) ? 0 : (ofloat)NAN; break;
+            case 5: t = from == 4 ? xt[10] : from == 5 ? xt[11] : (ofloat)NAN; break;
+            case 6: t = from == 4 ? xt[6] : from == 6 ? xt[7] : (ofloat)NAN; break;
+            case 7: t = from == 4 ? xt[5] : from == 6 ? xt[8] : (ofloat)NAN; break;
+            default: break;
+            }
+        }
+        if (t != t) return (ofloat)NAN;
+        if (i > 0) score = score + t;
+        if (len)
+        {
+            unsigned const code = orc_word_code(seq + pos, len);
+            score = score + (kind == 0 ? emis_match[(size_t)code * ldk + k] : kind == 1 ? emis_insert[code] : emis_null[code]);
+        }
+        pos += len;
+        pkind = kind, pk = x;
+    }
+    if (!nsteps || pos != L || pkind != 3 || pk != (alt ? 7u : 0u)) return (ofloat)NAN;
+    return score;
 }
 
 int orc_viterbi_fast(struct orc_profile const *p, unsigned char const *seq,

@@ -174,6 +174,30 @@ int orc_dp_tables(unsigned M, unsigned ldk, ofloat const *trans8,
                   unsigned char const *seq, unsigned L, ofloat *null_loglik,
                   ofloat *alt_loglik);
 
+/* orc_dp_tables' recursion with every row kept, then the Viterbi paths walked back through them: the alt
+ * path (S ... T) and the null path (R steps), ties broken as orc_viterbi breaks them (first maximum in the
+ * order the model wires its transitions, the shortest fragment first).  On input *alt_nsteps and
+ * *null_nsteps are the capacities; on output the paths' lengths.  ORC_ENOMEM if either capacity is too
+ * small (the lengths are then the true counts) or, with both lengths 0, if the work area could not be
+ * allocated; ORC_EFAIL if the walk finds no path; no finite score: an empty path.
+ * Memory: 3 (L+1) M values. */
+int orc_dp_tables_path(unsigned M, unsigned ldk, ofloat const *trans8,
+                       ofloat const *emis_match, ofloat const *emis_insert,
+                       ofloat const *emis_null, ofloat const *xtrans,
+                       unsigned char const *seq, unsigned L, ofloat *null_loglik,
+                       ofloat *alt_loglik, uint16_t *alt_state, uint8_t *alt_len,
+                       unsigned *alt_nsteps, uint16_t *null_state, uint8_t *null_len,
+                       unsigned *null_nsteps);
+
+/* Score of a given path on given tables, in the DP's own float order ((pred + trans) + emis): O(steps).
+ * alt = 1: a path S ... T; 0: R steps.  NaN if it is not a path of the graph or does not cover seq. */
+ofloat orc_path_score_tables(unsigned M, unsigned ldk, ofloat const *trans8,
+                             ofloat const *emis_match, ofloat const *emis_insert,
+                             ofloat const *emis_null, ofloat const *xtrans,
+                             unsigned char const *seq, unsigned L, int alt,
+                             uint16_t const *path_state, uint8_t const *path_len,
+                             unsigned nsteps);
+
 /* xmath_lrt (xmath.h:32-43) */
 ofloat orc_lrt(ofloat null_loglik, ofloat alt_loglik);
 

@@ -613,6 +613,117 @@ static void scan_run_batched(void)
     fclose(fp);
 }
 
+/* A profile of 1 000 nodes whose nodes 11 .. 990 are crossed by deletes (MM/MI/MD 0.5/0.01/0.49, DM/DD 0.001/0.999):
+ * a query of k planted copies of nodes 1 .. 10 and 991 .. 1000 is a k-domain hit with a run of 980 deletes per
+ * domain, a path longer than the 2L + 2M + 16 steps its capacity is first sized at.  The step counts are the CPU
+ * oracle's on the same profile (tests/test_trace_oracle.py pins them there too). */
+enum { GAP_M = 1000 };
+static unsigned const kGapCopies[2] = {3, 8}, kGapSteps[2] = {3016, 8036};
+
+static void gapped_profile(struct protein_profile *prof, struct imm_nuclt_code const *code, char domain[61])
+{
+    protein_profile_init(prof, "PFGAP", &imm_amino_iupac, code, PROTEIN_CFG_DEFAULT);
+    static char const amino[] = "ACDEFGHIKLMNPQRSTVWY";
+    imm_float null[20], *match = malloc(sizeof(imm_float) * 20 * GAP_M), *trans = malloc(sizeof(imm_float) * 7 * (GAP_M + 1));
+    for (int a = 0; a < 20; ++a)
+        null[a] = logf(1.0f / 20);
+    unsigned n = 0;
+    for (unsigned k = 0; k < GAP_M; ++k)
+    {
+        char fav = k % 3 == 0 ? 'W' : 'M';
+        for (int a = 0; a < 20; ++a)
+            match[20 * k + a] = logf(amino[a] == fav ? 0.81f : 0.01f);
+        if (k < 10 || k >= GAP_M - 10) memcpy(domain + 3 * n++, fav == 'W' ? "TGG" : "ATG", 3);
+    }
+    domain[3 * n] = '\0';
+    for (unsigned i = 0; i <= GAP_M; ++i)
+    {
+        imm_float *t = trans + 7 * i; /* MM MI MD IM II DM DD */
+        t[0] = logf(0.95f), t[1] = logf(0.025f), t[2] = logf(0.025f), t[3] = logf(0.6f), t[4] = logf(0.4f);
+        t[5] = logf(0.6f), t[6] = logf(0.4f);
+        if (i >= 10 && i < GAP_M - 10) t[0] = logf(0.5f), t[1] = logf(0.01f), t[2] = logf(0.49f);
+        if (i >= 11 && i < GAP_M - 10) t[5] = logf(0.001f), t[6] = logf(0.999f);
+        if (i == 0) t[6] = -INFINITY, t[5] = 0.0f;
+        if (i == GAP_M) t[2] = -INFINITY, t[6] = -INFINITY, t[0] = logf(0.975f), t[5] = 0.0f;
+    }
+    CHECK(protein_profile_from_params(prof, GAP_M, null, match, trans) == RC_OK);
+    free(match);
+    free(trans);
+}
+
+/* imm_dp_viterbi returns the whole path of such a hit, and scan_run_local writes its product row */
+static void long_multi_domain_paths(void)
+{
+    struct imm_nuclt const *nuclt = imm_super(&imm_dna_iupac);
+    struct imm_nuclt_code code;
+    imm_nuclt_code_init(&code, nuclt);
+    struct protein_profile prof;
+    char domain[61];
+    gapped_profile(&prof, &code, domain);
+    char text[2][8 * 66 + 7];
+    struct scan_seq seqs[2];
+    for (unsigned i = 0; i < 2; ++i)
+    {
+        text[i][0] = '\0';
+        for (unsigned c = 0; c < kGapCopies[i]; ++c)
+            strcat(strcat(text[i], "ACGTAC"), domain);
+        strcat(text[i], "GATTAC");
+        seqs[i] = (struct scan_seq){2000 + i, text[i]};
+
+        struct imm_seq seq = imm_seq(imm_str(text[i]), prof.super.code->abc);
+        CHECK(protein_profile_setup(&prof, imm_seq_size(&seq), true, false) == RC_OK);
+        struct imm_dp const *dp = profile_alt_dp(&prof.super);
+        struct imm_task *task = imm_task_new(dp);
+        struct imm_prod prod = imm_prod();
+        CHECK(imm_task_setup(task, &seq) == IMM_OK);
+        CHECK(imm_dp_viterbi(dp, task, &prod) == IMM_OK);
+        CHECK(imm_path_nsteps(&prod.path) == kGapSteps[i]);
+        CHECK(imm_path_nsteps(&prod.path) > 2 * imm_seq_size(&seq) + 2 * GAP_M + 16);
+        CHECK(imm_path_step(&prod.path, 0)->state_id == PROTEIN_S_STATE);
+        CHECK(imm_path_step(&prod.path, kGapSteps[i] - 1)->state_id == PROTEIN_T_STATE);
+        imm_task_del(task);
+        imm_prod_del(&prod);
+    }
+
+    char path[64];
+    snprintf(path, sizeof path, "/tmp/dcp_test_gap_XXXXXX");
+    int fd = mkstemp(path);
+    CHECK(fd >= 0);
+    FILE *fp = fdopen(fd, "wb");
+    struct protein_db_writer db = {0};
+    CHECK(protein_db_writer_open(&db, fp, &imm_amino_iupac, nuclt, PROTEIN_CFG_DEFAULT) == RC_OK);
+    CHECK(protein_db_writer_pack_profile(&db, &prof) == RC_OK);
+    CHECK(db_writer_close((struct db_writer *)&db, true) == RC_OK);
+    CHECK(fclose(fp) == 0);
+    profile_del(&prof.super);
+
+    FILE *out = tmpfile();
+    CHECK(out != NULL);
+    CHECK(scan_run_local(path, seqs, 2, 1, true, false, 10.0, 9, 2, out) == RC_OK);
+    char *got = slurp(out);
+    fclose(out);
+    remove(path);
+    char *lines[8];
+    unsigned const n = split_lines(got + strlen(prod_header()), lines, 8);
+    CHECK(n == 2);
+    for (unsigned i = 0; i < n && i < 2; ++i)
+    {
+        /* one row per query; its last column holds one ';'-separated match per step */
+        char want[32];
+        snprintf(want, sizeof want, "9\t%u\tPFGAP\t", 2000 + i);
+        CHECK(strstr(lines[i], want) == lines[i]);
+        char const *col = lines[i];
+        for (unsigned f = 0; f < 8 && col; ++f)
+            col = strchr(col, '\t'), col = col ? col + 1 : NULL;
+        CHECK(col != NULL);
+        unsigned steps = col && *col ? 1 : 0;
+        for (char const *c = col; c && *c && *c != '\n'; ++c)
+            steps += *c == ';';
+        CHECK(steps == kGapSteps[i]);
+    }
+    free(got);
+}
+
 /* The reference calls imm_dp_viterbi from every thread of an OpenMP team (scan.c:239-249, through its own
  * thread_run): callers that share the library's single-pair context must be serialised, not race. */
 static void concurrent_viterbi(void)
@@ -764,6 +875,7 @@ int main(void)
     passes_sized_by_symbols();
     resident_reuse();
     remove(g_db_path);
+    long_multi_domain_paths();
     one_process_per_gpu();
     concurrent_viterbi();
     CHECK(xmath_partition_size(20000, 8, 7) == 2500);

@@ -16,6 +16,8 @@ ENTRY_DIST_UNIFORM = 1
 ENTRY_DIST_OCCUPANCY = 2
 NCODES = 1364
 
+ORC_EFAIL, ORC_ENOMEM = 2, 5
+
 R_STATE, S_STATE, N_STATE, B_STATE, E_STATE, J_STATE, C_STATE, T_STATE = (
     (3 << 14) | i for i in range(8))
 
@@ -56,10 +58,15 @@ class Profile:
         cap = 2 * len(seq) + 3 * self.core_size + 16
         n = C.c_uint(cap)
         if want_path:
-            st = np.zeros(cap, np.uint16)
-            ln = np.zeros(cap, np.uint8)
-            rc = o.lib.orc_viterbi(self.h, int(alt), seq, len(seq), C.byref(ll),
-                                   st.ctypes.data, ln.ctypes.data, C.byref(n))
+            while True:
+                st = np.zeros(max(cap, 1), np.uint16)
+                ln = np.zeros(max(cap, 1), np.uint8)
+                rc = o.lib.orc_viterbi(self.h, int(alt), seq, len(seq), C.byref(ll),
+                                       st.ctypes.data, ln.ctypes.data, C.byref(n))
+                if rc != ORC_ENOMEM or n.value <= cap:
+                    break
+                cap = n.value  # a multi-domain path can be longer than the estimate: again at the true count
+                n = C.c_uint(cap)
             return rc, ll.value, list(zip(st[:n.value].tolist(), ln[:n.value].tolist()))
         rc = o.lib.orc_viterbi(self.h, int(alt), seq, len(seq), C.byref(ll), None, None, C.byref(n))
         return rc, ll.value, None
@@ -136,6 +143,11 @@ class Oracle:
         lib.orc_viterbi_fast.argtypes = [C.c_void_p, C.c_char_p, C.c_uint, C.POINTER(fl), C.POINTER(fl)]
         lib.orc_dp_tables.argtypes = [C.c_uint, C.c_uint] + [C.c_void_p] * 5 + [
             C.c_char_p, C.c_uint, C.POINTER(fl), C.POINTER(fl)]
+        lib.orc_dp_tables_path.argtypes = [C.c_uint, C.c_uint] + [C.c_void_p] * 5 + [
+            C.c_char_p, C.c_uint, C.POINTER(fl), C.POINTER(fl)] + [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint)] * 2
+        lib.orc_path_score_tables.restype = fl
+        lib.orc_path_score_tables.argtypes = [C.c_uint, C.c_uint] + [C.c_void_p] * 5 + [
+            C.c_char_p, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_uint]
         lib.orc_profile_decode.restype = fl
         lib.orc_profile_decode.argtypes = [C.c_void_p, C.c_char_p, C.c_uint, C.c_uint, C.c_char_p]
         lib.orc_path_score.restype = fl
@@ -207,6 +219,47 @@ class Oracle:
                                     en.ctypes.data, xt.ctypes.data, seq, len(seq),
                                     C.byref(nl), C.byref(al))
         return rc, nl.value, al.value
+
+    def _tables(self, t8, em, ei, en, xt, M):
+        t8, em = np.ascontiguousarray(t8, self.np), np.ascontiguousarray(em, self.np)
+        ldk = t8.shape[1]
+        assert em.shape == (NCODES, ldk) and (M or ldk) <= ldk
+        return (M or ldk, ldk, t8, em, np.ascontiguousarray(ei, self.np), np.ascontiguousarray(en, self.np),
+                np.ascontiguousarray(xt, self.np))
+
+    def dp_tables_path(self, t8, em, ei, en, xt, seq: bytes, M=None):
+        """orc_dp_tables_path on given tables (trans8 [8, ldk], emis_match [1364, ldk]; M <= ldk nodes, default
+        ldk): (null, alt, alt_path, null_path), each path a pair of arrays (state ids uint16, lengths uint8).
+        Capacities start at the usual estimates and are retried at the true count."""
+        M, ldk, t8, em, ei, en, xt = self._tables(t8, em, ei, en, xt, M)
+        L = len(seq)
+        caps = [2 * L + 2 * M + 16, L + 1]
+        while True:
+            bufs = [(np.zeros(c, np.uint16), np.zeros(c, np.uint8), C.c_uint(c)) for c in caps]
+            nl, al = self.fl(), self.fl()
+            rc = self.lib.orc_dp_tables_path(M, ldk, t8.ctypes.data, em.ctypes.data, ei.ctypes.data,
+                                             en.ctypes.data, xt.ctypes.data, seq, L, C.byref(nl), C.byref(al),
+                                             *[a for st, ln, n in bufs for a in (st.ctypes.data, ln.ctypes.data,
+                                                                                 C.byref(n))])
+            if rc != ORC_ENOMEM:
+                break
+            more = [max(c, n.value) for c, (_, _, n) in zip(caps, bufs)]
+            if more == caps:  # not a capacity shortfall: the work area could not be allocated
+                raise MemoryError(f"orc_dp_tables_path: no memory for {3 * (L + 1) * M} values")
+            caps = more
+        if rc:
+            raise ValueError(f"orc_dp_tables_path: rc {rc}")
+        (ast, aln, an), (nst, nln, nn) = bufs
+        return nl.value, al.value, (ast[:an.value], aln[:an.value]), (nst[:nn.value], nln[:nn.value])
+
+    def path_score_tables(self, t8, em, ei, en, xt, seq: bytes, states, lens, alt=True, M=None):
+        """orc_path_score_tables: a given path's score on given tables, in the DP's float order; NaN if not a path"""
+        M, ldk, t8, em, ei, en, xt = self._tables(t8, em, ei, en, xt, M)
+        st = np.ascontiguousarray(states, np.uint16)
+        ln = np.ascontiguousarray(lens, np.uint8)
+        return self.lib.orc_path_score_tables(M, ldk, t8.ctypes.data, em.ctypes.data, ei.ctypes.data,
+                                              en.ctypes.data, xt.ctypes.data, seq, len(seq), int(alt),
+                                              st.ctypes.data, ln.ctypes.data, len(st))
 
     def scan(self, profiles, seqs, multi_hits=True, hmmer3_compat=False, lrt_thr=10.0,
              nthreads=1, mode=0):

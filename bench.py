@@ -16,6 +16,11 @@ uniform-ACGT 1 000-nt queries (seed 0x5E9+q), multi_hits, lrt threshold 10.  A s
 the scan path over one batch of 1 000*N distinct queries against the whole (sharded) DB, inputs
 resident in HBM; 10 steps at N=1 are the full 10 000-query config.  With N ranks the DB is sharded
 by cells and the hits are all-gathered over RCCL each step (weak scaling: per-GPU pairs fixed).
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the steps, writes
+--dump-outputs and prints its JSON line.  --full adds the legs that measure or check something beside it, each
+with runs of its own after the timed steps: end to end (`e2e`), small batches, the two CPU baselines and the
+in-run parity sample against the CPU oracle.
 """
 import argparse
 import importlib.util
@@ -643,7 +648,11 @@ def main():
     ap.add_argument("--nprof", type=int, default=0, help="override profile count (debug)")
     ap.add_argument("--qstep", type=int, default=0, help="override queries per step per GPU (debug)")
     ap.add_argument("--qlen", type=int, default=0, help="override query length (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the end-to-end and small-batch legs, the CPU baselines and "
+                         "the parity sample against the CPU oracle (a plain run prints the headline line alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baselines and the parity sample")
     ap.add_argument("--kernel", default="auto", choices=["auto", "rowsweep", "qlane", "qlane2"],
                     help="dcp_scan_params.kernel (auto = the library's cost model)")
     ap.add_argument("--hit-gather", default="c", choices=["c", "torch"],
@@ -656,8 +665,8 @@ def main():
     ap.add_argument("--planted", action="store_true",
                     help="planted-hit variant: 1 %% of the queries carry a real hit (exercises hits / gather)")
     ap.add_argument("--e2e-steps", type=int, default=-1,
-                    help="steps of the end-to-end leg (each step uploads its own sequences, scans, fetches the hits "
-                         "to the host); default min(steps, 5), 0 = skip")
+                    help="--full: steps of the end-to-end leg (each step uploads its own sequences, scans, fetches "
+                         "the hits to the host); default min(steps, 5), 0 = skip")
     ap.add_argument("--as-rank", default="", metavar="R/N",
                     help="one-GPU rehearsal of an N-GPU run's rank R: this GPU holds shard R of N of the DB and scans the "
                          "N x larger query step an N-GPU run uses (value = this one rank's rate; --gpus 1 only)")
@@ -673,6 +682,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.e2e_steps > 0 and not args.full:
+        ap.error("--e2e-steps sizes the end-to-end leg, which only --full runs")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: this process only starts and reaps the N ranks
@@ -763,12 +774,16 @@ def main():
         sc.upload_seqs_flat(queries.reshape(-1), off)
     else:
         sc.upload_seqs(queries)
-    # the end-to-end leg re-uploads the batches of the first timed steps from these host copies
-    n_e2e = (min(args.steps, 5) if args.e2e_steps < 0 else min(args.e2e_steps, args.steps)) if not args.dense else 0
+    # --full only: the end-to-end leg re-uploads the batches of the first timed steps from these host copies
+    n_e2e = ((min(args.steps, 5) if args.e2e_steps < 0 else min(args.e2e_steps, args.steps))
+             if args.full and not args.dense else 0)
     e2e_batches = [queries[i * qstep:(i + 1) * qstep] for i in range(args.warmup, args.warmup + n_e2e)]
     if qlen:
         e2e_batches = [np.ascontiguousarray(x) for x in e2e_batches]
-    small_src = queries[:min(64, qstep)].copy() if qlen else list(queries[:min(64, qstep)])  # the small-batch leg's queries
+    small_leg = args.full and world == 1 and not force_dist and not args.dense and args.kernel == "auto"
+    small_src = None
+    if small_leg:  # the small-batch leg's queries
+        small_src = queries[:min(64, qstep)].copy() if qlen else list(queries[:min(64, qstep)])
     del queries
 
     cap = 1 << 16
@@ -879,7 +894,7 @@ def main():
             last_hits["profile_idx"] += b  # shard-local -> global (b > 0 only under --as-rank)
         dump_outputs(args.dump_outputs, last_hits)
 
-    # ---- end-to-end leg (SURVEY 8d "kernel-only AND end-to-end"): nothing of a step is resident but the DB.
+    # ---- end-to-end leg (--full; SURVEY 8d "kernel-only AND end-to-end"): nothing of a step is resident but the DB.
     # Each step hands its own host sequences to the boundary (dcp_gpu_seqs_upload: H2D, 2-bit packing, the
     # 13 length-dependent transitions per query), scans them against the whole shard, and brings the hit
     # list back to the host (N = 1: D2H of the records; N > 1: the RCCL gather, which ends on the host).
@@ -921,11 +936,11 @@ def main():
                        "scan of the whole resident DB shard -> hit records on the host"
                        + (" through the hit gather" if (world > 1 or force_dist) else " (D2H)")
                        + "; the batches are those of the first timed steps of the resident leg"}
-    # ---- small batches (N = 1 only): what the reference's own loop sees -- it scans ONE sequence at a time
+    # ---- small batches (--full, N = 1 only): what the reference's own loop sees -- it scans ONE sequence at a time
     # (src/server/scan.c:227-258) -- and batches of 8 and 64: upload + scan of the whole DB + hits on the host per
     # batch, automatic kernel choice (the row sweep at these sizes), median of three; outside every timed region
     small = None
-    if world == 1 and not force_dist and not args.dense and not args.stub_scan and args.kernel == "auto":
+    if small_leg:
         small = small_batches_leg(sc, dcp, small_src, qlen, float(sizes[b:e].sum()),
                                   lambda: hit_words[:min(cap, int(hit_count.item()))].cpu().numpy())
     multi_gpu = None
@@ -984,7 +999,7 @@ def main():
             # DCP_BENCH_FORCE_DIST only)
             "env_dcp": {k: v for k, v in sorted(os.environ.items()) if k.startswith("DCP_")},
         }
-        if world == 1 and not args.no_cpu_baseline and qlen:
+        if args.full and world == 1 and not args.no_cpu_baseline and qlen:
             native = build_native_oracle()
             out["cpu_baseline"] = cpu_baseline(dcp, sizes, args.workload, qlen, lib=native)
             out["cpu_baseline_optimised"] = cpu_baseline(dcp, sizes, args.workload, qlen, budget_s=8.0, mode=2, lib=native)

@@ -8,7 +8,7 @@
 # profiles/rNN/.  The program after `--` is python3 itself (no env/bash hop under the profiler).
 set -e -o pipefail
 TAG=${1:?tag}; shift
-ARGS=${*:---steps 1 --warmup 0 --no-cpu-baseline}
+ARGS=${*:---full --steps 1 --warmup 0 --no-cpu-baseline}
 ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"

@@ -10,13 +10,13 @@ TAG=${1:?tag}; PART=${2:?driver|lines|pmc|c5full}
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 line() { # name, bench args...
   local name=$1; shift
-  timeout -k 10 ${LINE_TIMEOUT:-300} python3 bench.py "$@" 2> $OUT/$name.err | tail -1 > $OUT/$name.json
+  timeout -k 10 ${LINE_TIMEOUT:-300} python3 bench.py --full "$@" 2> $OUT/$name.err | tail -1 > $OUT/$name.json
   python3 -c "import json,sys; d=json.load(open('$OUT/$name.json')); print('$name', d['value'], d['unit'], 'ms/step', d['ms_per_step'])" || { echo "$name FAILED"; tail -5 $OUT/$name.err; }
 }
 case $PART in
 driver)
   line c3_driver_command_bench --steps 20 --warmup 5
-  PASSES=stats PASS_TIMEOUT=500 bash profiles/collect_pmc.sh $TAG/driver_rocprof --steps 20 --warmup 5
+  PASSES=stats PASS_TIMEOUT=500 bash profiles/collect_pmc.sh $TAG/driver_rocprof --full --steps 20 --warmup 5
   ;;
 lines)
   line c3_rowsweep_bench --kernel rowsweep --steps 3 --warmup 1 --no-cpu-baseline
@@ -35,7 +35,7 @@ pmc)
   # the headline's literal 10 000-query batch, the HBM counter passes of the driver's workload
   # (FETCH_SIZE / WRITE_SIZE in separate runs; folded by pmc_summary.py), and the row sweep's per-class counters
   line c3_bench_10000q --qstep 10000 --steps 2 --warmup 1 --no-cpu-baseline --e2e-steps 0
-  PASSES="fetch write" PASS_TIMEOUT=300 bash profiles/collect_pmc.sh $TAG/pmc_qlane2 --steps 5 --warmup 1 --no-cpu-baseline --e2e-steps 0
+  PASSES="fetch write" PASS_TIMEOUT=300 bash profiles/collect_pmc.sh $TAG/pmc_qlane2 --full --steps 5 --warmup 1 --no-cpu-baseline --e2e-steps 0
   timeout -k 10 400 python3 profiles/latency_probe.py c5 > $OUT/latency_probe_c5_db.txt 2>&1; grep "^auto" $OUT/latency_probe_c5_db.txt
   ;;
 c5full)

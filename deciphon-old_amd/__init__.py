@@ -71,7 +71,7 @@ ABI_SYMBOLS = [
     "dcp_profile_new64", "dcp_profile_sample64", "dcp_profile_precision", "dcp_profile_epsilon64",
     "dcp_profile_trans8_64", "dcp_profile_null_dist64", "dcp_profile_insert_dist64", "dcp_profile_match_dist64",
     "dcp_xtrans64", "dcp_gpu_db_upload64", "dcp_gpu_db_precision", "dcp_gpu_set_lrt_threshold64", "dcp_gpu_fetch_scores64", "dcp_gpu_fetch_hits64",
-    "dcp_gpu_db_fetch_match_table64", "dcp_gpu_db_fetch_insert_null64",
+    "dcp_gpu_db_fetch_match_table64", "dcp_gpu_db_fetch_insert_null64", "dcp_gpu_trace_paths64",
 ]
 
 
@@ -207,6 +207,7 @@ def _load(path=None, hooks=False):
         "dcp_gpu_fetch_hits64": (I, [P, P, U, C.POINTER(U)]),
         "dcp_gpu_db_fetch_match_table64": (I, [P, U, P]),
         "dcp_gpu_db_fetch_insert_null64": (I, [P, U, P, P]),
+        "dcp_gpu_trace_paths64": (I, [P, P, U, I, I, I, P, U, P, P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -751,22 +752,24 @@ class Scanner:
 
     def trace_paths(self, hits, multi_hits=True, hmmer3_compat=False, null_model=False):
         """Viterbi paths (alt model, or null model if null_model) of the given hit records, computed
-        on the device: a list of STEP_DTYPE arrays, plus the log-likelihoods the trace recomputed."""
-        h = np.ascontiguousarray(hits, HIT_DTYPE)
+        on the device: a list of STEP_DTYPE arrays, plus the log-likelihoods the trace recomputed.
+        On a double DB the records are HIT64_DTYPE and the log-likelihoods float64 (dcp_gpu_trace_paths64)."""
+        f64 = self.precision == 64
+        h = np.ascontiguousarray(hits, HIT64_DTYPE if f64 else HIT_DTYPE)
+        trace = self._lib.dcp_gpu_trace_paths64 if f64 else self._lib.dcp_gpu_trace_paths
         n = len(h)
         off = np.zeros(n + 1, np.uint32)
-        alt = np.zeros(n, np.float32)
+        alt = np.zeros(n, np.float64 if f64 else np.float32)
         cap = int(sum(2 * int(self._seq_lens[q]) + 2 * self._profiles[p].core_size + 16
                       for q, p in zip(h["seq_idx"], h["profile_idx"]))) if n else 0
         steps = np.zeros(max(cap, 1), STEP_DTYPE)
-        rc = self._lib.dcp_gpu_trace_paths(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat),
-                                           int(null_model), steps.ctypes.data, cap, off.ctypes.data, alt.ctypes.data)
+        rc = trace(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat), int(null_model),
+                   steps.ctypes.data, cap, off.ctypes.data, alt.ctypes.data)
         if rc == RC_ENOMEM and off[n] > cap:  # the estimate is short of a long multi-domain path: the true total
             cap = int(off[n])
             steps = np.zeros(cap, STEP_DTYPE)
-            rc = self._lib.dcp_gpu_trace_paths(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat),
-                                               int(null_model), steps.ctypes.data, cap, off.ctypes.data,
-                                               alt.ctypes.data)
+            rc = trace(self._c, h.ctypes.data, n, int(multi_hits), int(hmmer3_compat), int(null_model),
+                       steps.ctypes.data, cap, off.ctypes.data, alt.ctypes.data)
         self._check(rc)
         return [steps[off[i]:off[i + 1]].copy() for i in range(n)], alt
 

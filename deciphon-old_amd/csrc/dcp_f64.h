@@ -64,7 +64,57 @@ void dcp_f64_launch_expand(dcp_f64_expand_job const *jobs, unsigned njobs, doubl
 int dcp_f64_launch_scan(int R, dcp_f64_scan_args const *a, unsigned nwaves, void *stream);
 
 #ifdef __cplusplus
-}
+} // extern "C"
+
+// ---- the traceback of the double build -------------------------------------------------------------------------
+// One traced pair: its sequence (absolute index) and its entry of the launch's profs[].
+struct dcp_f64_pair
+{
+    uint32_t q;
+    uint32_t prof;
+};
+
+// The forward pass (viterbi64_kernel<R, TRACE>): the scan's fields, except that seq_woff / seq_len are not offset
+// (pairs name absolute queries), xtrans holds one row per pair of the list, and no score, hit or hit count is
+// written.  Pair i writes M, I, D of every row j = 0 .. L and column k < ldk as three [L + 1][ldk] double matrices
+// at trace_work + trace_woff[i], then N, B, E, J, C as five [L + 1] vectors; its alt score goes to trace_alt[i].
+struct dcp_f64_trace_args : dcp_f64_scan_args
+{
+    dcp_f64_pair const *pairs;
+    unsigned npairs;
+    double *trace_work;
+    uint64_t const *trace_woff;
+    double *trace_alt;
+};
+
+// The walk back (trace64_kernel): one wavefront per hit of the round, lane 0 walking on the work area the forward
+// pass filled; for the null model lane 0 runs the one-state R recursion into the work area itself.
+struct dcp_f64_walk_args
+{
+    dcp_f64_prof const *profs;
+    dcp_f64_pair const *pairs; // [nhits]
+    unsigned nhits;
+    double const *tab, *trans, *xe;
+    uint32_t const *seq_words, *seq_woff, *seq_len;
+    double const *xtrans;      // [nhits][DCP_F64_XSTRIDE]
+    double *work;
+    uint64_t const *work_off;  // [nhits] doubles
+    struct dcp_step *steps;
+    uint32_t const *step_off;  // [nhits + 1]
+    uint32_t *nsteps;          // [nhits]: steps of the path (written up to the capacity), or a sentinel below
+    double *alt_out;           // [nhits]: the score the walk starts from
+    int null_model;
+};
+
+enum : uint32_t
+{
+    DCP_F64_TRACE_NO_PATH = 0xffffffffu, // DCP_TRACE_NO_PATH / DCP_TRACE_TOO_LONG of dcp_kernels.h
+    DCP_F64_TRACE_TOO_LONG = 0xfffffffeu,
+};
+
+// R = 1, 2 or 4; nwaves wavefronts stride over the a->npairs pairs (one boundary column each where a->col is set)
+int dcp_f64_launch_trace_forward(int R, dcp_f64_trace_args const *a, unsigned nwaves, void *stream);
+void dcp_f64_launch_walk(dcp_f64_walk_args const *a, void *stream);
 #endif
 
 #endif

@@ -7,6 +7,9 @@
 //                       256 nodes over all rows, one after the other; what row j of the next segment needs from
 //                       this one (M, I, D of its last node, E so far) goes through a per-wavefront column in global
 //                       memory, as viterbi_segment_kernel's does.
+//  viterbi64_kernel<R, true>  the traceback's forward pass: the same sweep over a list of pairs, every row's M, I, D
+//                       and N, B, E, J, C written to the pair's work area instead of a score (dcp_f64_trace_args).
+//  trace64_kernel       the walk back from T(L) to S(0) on that work area, one wavefront per hit.
 //
 // Arithmetic contract: the recursion of the CPU oracle's double build, operation by operation --
 // every candidate is (predecessor + transition) or (predecessor + emission) formed once in IEEE double, combined
@@ -159,6 +162,9 @@ struct Seg64
     uint32_t const *words;
     double *col;     // the pair's boundary column (segmented sweep), 5 doubles per row: m, i, d, e, B
     bool first_seg, last_seg, multi, first_pass;
+    // TRACE: this lane's first column of the M matrix (row 0), the matrices' and vectors' lengths, N of row 0
+    double *wm, *wspec;
+    uint64_t wmat, wrows;
 };
 
 template <int R> __device__ __forceinline__ void chain_rest(double const (&a)[R], double (&d)[R], double const (&dd)[R])
@@ -168,7 +174,7 @@ template <int R> __device__ __forceinline__ void chain_rest(double const (&a)[R]
         d[r] = fmax(a[r], d[r - 1] + dd[r]);
 }
 
-template <int R, int PH>
+template <int R, int PH, bool TRACE>
 __device__ __forceinline__ void row64(State64<R> &s, Trans64<R> const &t, X64 const &x, Seg64 const &g, unsigned j,
                                       unsigned lane, bool &changed)
 {
@@ -279,23 +285,58 @@ __device__ __forceinline__ void row64(State64<R> &s, Trans64<R> const &t, X64 co
 
     if (g.multi && !g.last_seg && lane == 63u)
         cj[0] = m[R - 1], cj[1] = ins[R - 1], cj[2] = d[R - 1], cj[3] = E;
+
+    // the traceback's work area: this segment's columns; the specials only where they are final (the last segment:
+    // its E(j) is over the whole profile, its B(j) the one this pass used, and J, C follow from that E)
+    if constexpr (TRACE)
+    {
+        double *const w = g.wm + (uint64_t)j * g.ldk;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            w[r] = m[r], w[g.wmat + r] = ins[r], w[2u * g.wmat + r] = d[r];
+        if (g.last_seg && lane == 0u)
+        {
+            double *const sp = g.wspec + j;
+            sp[0] = N, sp[g.wrows] = B, sp[2u * g.wrows] = E, sp[3u * g.wrows] = J, sp[4u * g.wrows] = Cc;
+        }
+    }
 }
 
-template <int R>
-__global__ __launch_bounds__(256) void viterbi64_kernel(dcp_f64_scan_args a)
+template <bool TRACE> struct Args64
+{
+    using T = dcp_f64_scan_args;
+};
+template <> struct Args64<true>
+{
+    using T = dcp_f64_trace_args;
+};
+
+// TRACE: the traceback's forward pass (dcp_f64_trace_args): pair i of the list writes every row to its work area
+// and its alt score to trace_alt[i]; every fixed-point pass rewrites all rows, so the last one leaves the exact
+// recursion there.  The scan's instantiations (TRACE = false) are the code they were before it existed.
+template <int R, bool TRACE = false>
+__global__ __launch_bounds__(256) void viterbi64_kernel(typename Args64<TRACE>::T a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
     uint64_t const nw = a.nwaves;
     if (gw >= nw) return; // the grid's last block may hold wavefronts past nwaves: they have no boundary column
-    uint64_t const npairs = (uint64_t)a.nprof * a.nq;
+    uint64_t npairs;
+    if constexpr (TRACE) npairs = a.npairs;
+    else npairs = (uint64_t)a.nprof * a.nq;
     double *const col = a.col ? a.col + gw * a.col_stride : nullptr;
     for (uint64_t pair = gw; pair < npairs; pair += nw)
     {
-        unsigned const pi = (unsigned)(pair / a.nq), q = (unsigned)(pair % a.nq);
+        unsigned pi, q;
+        if constexpr (TRACE)
+        {
+            dcp_f64_pair const pp = a.pairs[pair];
+            pi = pp.prof, q = pp.q;
+        }
+        else pi = (unsigned)(pair / a.nq), q = (unsigned)(pair % a.nq);
         dcp_f64_prof const pr = a.profs[pi];
         unsigned const L = a.seq_len[q];
-        double const *xt = a.xtrans + (size_t)q * DCP_F64_XSTRIDE;
+        double const *xt = a.xtrans + (size_t)(TRACE ? pair : q) * DCP_F64_XSTRIDE;
         X64 const x{xt[DCP_X_RR], xt[DCP_X_SB], xt[DCP_X_SN], xt[DCP_X_NN], xt[DCP_X_NB], xt[DCP_X_ET], xt[DCP_X_EC],
                     xt[DCP_X_CC], xt[DCP_X_CT], xt[DCP_X_EB], xt[DCP_X_EJ], xt[DCP_X_JJ], xt[DCP_X_JB]};
         Seg64 g;
@@ -344,13 +385,27 @@ __global__ __launch_bounds__(256) void viterbi64_kernel(dcp_f64_scan_args a)
 #pragma unroll
                 for (int r = 0; r < R; ++r)
                     s.P[0][r] = B0 + t.ent[r];
+                if constexpr (TRACE) // row 0: M, I, D, N, E, J, C are -inf, B = S + SB
+                {
+                    double *const work = a.trace_work + a.trace_woff[pair];
+                    g.wrows = (uint64_t)L + 1u;
+                    g.wmat = g.wrows * pr.ldk;
+                    g.wm = work + c0;
+                    g.wspec = work + 3u * g.wmat;
+#pragma unroll
+                    for (int r = 0; r < R; ++r)
+                        g.wm[r] = ninf(), g.wm[g.wmat + r] = ninf(), g.wm[2u * g.wmat + r] = ninf();
+                    if (g.last_seg && lane == 0u)
+                        g.wspec[0] = ninf(), g.wspec[g.wrows] = B0, g.wspec[2u * g.wrows] = ninf(),
+                        g.wspec[3u * g.wrows] = ninf(), g.wspec[4u * g.wrows] = ninf();
+                }
                 s.PN[0] = 0.0 + x.SN;
                 s.PR[0] = 0.0;
                 s.E = s.Cc = s.Rr = ninf();
                 s.w = 0u;
                 unsigned j = 1u;
 #define DCP_ROW64(PH)                                                                                                  \
-    row64<R, PH>(s, t, x, g, j, lane, changed);                                                                        \
+    row64<R, PH, TRACE>(s, t, x, g, j, lane, changed);                                                                        \
     if (j == L) break;                                                                                                 \
     ++j;
                 for (;;)
@@ -366,6 +421,11 @@ __global__ __launch_bounds__(256) void viterbi64_kernel(dcp_f64_scan_args a)
                 alt_ll = fmax(s.E + x.ET, s.Cc + x.CT);
             }
             if (!changed) break;
+        }
+        if constexpr (TRACE)
+        {
+            if (lane == 0u) a.trace_alt[pair] = alt_ll;
+            continue;
         }
         if (lane == 0u)
         {
@@ -383,6 +443,328 @@ __global__ __launch_bounds__(256) void viterbi64_kernel(dcp_f64_scan_args a)
             }
         }
     }
+}
+
+// ---- the walk back ----------------------------------------------------------------------------------------------
+// viterbi_trace_kernel's walk (dcp_kernels.hip), restated on double values and the f64 DB's layout: lane 0 walks
+// from T(L) to S(0) re-deriving each arg-max from the stored rows -- first maximum wins, candidates in the order
+// the reference wires the transitions (protein_model.c:460-500, :322-340), which is also the oracle's.  Each
+// candidate is the sum the forward pass formed (predecessor + transition, then + emission), so a recomputed maximum
+// is the stored value to the bit.
+struct View64
+{
+    double const *Mv, *Iv, *Dv;      // [L + 1][ld]
+    double const *N, *B, *E, *J, *C; // [L + 1]
+    double const *ent, *mm, *im, *dm, *md, *dd, *mi, *ii;
+    double const *eM, *eI, *eN;
+    double const *xt;
+    uint32_t const *words;
+    uint64_t ld; // the DB's columns of the profile: row length of its tables and of the work matrices
+    unsigned M, L;
+};
+
+__device__ __forceinline__ unsigned code64(unsigned w, unsigned l) // word of the last l bases of window w
+{
+    constexpr unsigned off[5] = {0u, 4u, 20u, 84u, 340u};
+    return off[l - 1u] + (w & ((1u << (2u * l)) - 1u));
+}
+
+__device__ __forceinline__ unsigned window64(uint32_t const *words, unsigned j) // the (up to) 5 bases before row j
+{
+    unsigned w = 0;
+    for (unsigned p = j > 5u ? j - 5u : 0u; p < j; ++p)
+        w = (w << 2) | ((words[p >> 4] >> ((p & 15u) * 2u)) & 3u);
+    return w & 1023u;
+}
+
+// P_k(jj): best predecessor of M_k leaving row jj; *arg: 0 = M_{k-1}, 1 = I_{k-1}, 2 = D_{k-1}, 3 = B
+__device__ double walk_P(View64 const &v, uint64_t jj, unsigned k, int *arg)
+{
+    double best = ninf();
+    int a = -1;
+    if (k > 0)
+    {
+        uint64_t const o = jj * v.ld + k - 1u;
+        double const c0 = v.Mv[o] + v.mm[k], c1 = v.Iv[o] + v.im[k], c2 = v.Dv[o] + v.dm[k];
+        if (c0 > best) best = c0, a = 0;
+        if (c1 > best) best = c1, a = 1;
+        if (c2 > best) best = c2, a = 2;
+    }
+    double const cb = v.B[jj] + v.ent[k];
+    if (cb > best) best = cb, a = 3;
+    if (arg) *arg = a;
+    return best;
+}
+
+// Q_k(jj): best predecessor of I_k; *arg: 0 = M_k, 1 = I_k
+__device__ double walk_Q(View64 const &v, uint64_t jj, unsigned k, int *arg)
+{
+    uint64_t const o = jj * v.ld + k;
+    double best = ninf();
+    int a = -1;
+    double const c0 = v.Mv[o] + v.mi[k], c1 = v.Iv[o] + v.ii[k];
+    if (c0 > best) best = c0, a = 0;
+    if (c1 > best) best = c1, a = 1;
+    if (arg) *arg = a;
+    return best;
+}
+
+// predecessor maxima of the special emitting states; *arg: 0 = first source, 1 = self loop
+__device__ double walk_PN(View64 const &v, uint64_t jj, int *arg)
+{
+    double best = ninf();
+    int a = -1;
+    double const c0 = (jj == 0 ? 0.0 : ninf()) + v.xt[DCP_X_SN], c1 = v.N[jj] + v.xt[DCP_X_NN];
+    if (c0 > best) best = c0, a = 0;
+    if (c1 > best) best = c1, a = 1;
+    if (arg) *arg = a;
+    return best;
+}
+__device__ double walk_PJ(View64 const &v, uint64_t jj, int *arg)
+{
+    double best = ninf();
+    int a = -1;
+    double const c0 = v.E[jj] + v.xt[DCP_X_EJ], c1 = v.J[jj] + v.xt[DCP_X_JJ];
+    if (c0 > best) best = c0, a = 0;
+    if (c1 > best) best = c1, a = 1;
+    if (arg) *arg = a;
+    return best;
+}
+__device__ double walk_PC(View64 const &v, uint64_t jj, int *arg)
+{
+    double best = ninf();
+    int a = -1;
+    double const c0 = v.E[jj] + v.xt[DCP_X_EC], c1 = v.C[jj] + v.xt[DCP_X_CC];
+    if (c0 > best) best = c0, a = 0;
+    if (c1 > best) best = c1, a = 1;
+    if (arg) *arg = a;
+    return best;
+}
+
+__global__ __launch_bounds__(64) void trace64_kernel(dcp_f64_walk_args a)
+{
+    unsigned const h = blockIdx.x;
+    if (h >= a.nhits || threadIdx.x != 0u) return; // lane 0 walks; the wavefront is one per hit
+    dcp_f64_pair const pp = a.pairs[h];
+    dcp_f64_prof const pr = a.profs[pp.prof];
+    unsigned const q = pp.q;
+    View64 v;
+    v.ld = pr.ldk;
+    v.M = pr.core_size;
+    v.L = a.seq_len[q];
+    v.words = a.seq_words + a.seq_woff[q];
+    v.xt = a.xtrans + (uint64_t)h * DCP_F64_XSTRIDE;
+    double const *tb = a.trans + pr.trans_off;
+    v.ent = tb + DCP_T_ENTRY * v.ld, v.mm = tb + DCP_T_MM * v.ld, v.im = tb + DCP_T_IM * v.ld;
+    v.dm = tb + DCP_T_DM * v.ld, v.md = tb + DCP_T_MD * v.ld, v.dd = tb + DCP_T_DD * v.ld;
+    v.mi = tb + DCP_T_MI * v.ld, v.ii = tb + DCP_T_II * v.ld;
+    v.eM = a.tab + pr.tab_off;
+    v.eI = a.xe + pr.xe_off;
+    v.eN = v.eI + DCP_NCODES;
+    unsigned const L = v.L;
+    uint64_t const rows = (uint64_t)L + 1u, mat = rows * v.ld;
+    double *const work = a.work + a.work_off[h];
+    v.Mv = work, v.Iv = work + mat, v.Dv = work + 2u * mat;
+    v.N = work + 3u * mat, v.B = v.N + rows, v.E = v.B + rows, v.J = v.E + rows, v.C = v.J + rows;
+    dcp_step *const out = a.steps + a.step_off[h];
+    unsigned const cap = a.step_off[h + 1] - a.step_off[h];
+    double const ni = ninf();
+
+    // ---- null model (one state R, protein_model.c:223-225, 316-320): its recursion here, then its walk
+    if (a.null_model)
+    {
+        double *const Rv = work; // [L + 1]
+        Rv[0] = ni;
+        auto PR = [&](unsigned jj) { return jj == 0 ? 0.0 : Rv[jj] + v.xt[DCP_X_RR]; };
+        for (unsigned j = 1; j <= L; ++j)
+        {
+            unsigned const w = window64(v.words, j);
+            double r = ni;
+            for (unsigned l = 1; l <= (j < 5u ? j : 5u); ++l)
+                r = fmax(r, PR(j - l) + v.eN[code64(w, l)]);
+            Rv[j] = r;
+        }
+        a.alt_out[h] = Rv[L];
+        unsigned n = 0, j = L;
+        bool ok = Rv[L] > ni;
+        while (ok && j > 0)
+        {
+            unsigned const w = window64(v.words, j);
+            double best = ni;
+            unsigned bl = 0;
+            for (unsigned l = 1; l <= (j < 5u ? j : 5u); ++l)
+            {
+                double const sc = PR(j - l) + v.eN[code64(w, l)];
+                if (sc > best) best = sc, bl = l;
+            }
+            if (bl == 0) { ok = false; break; }
+            if (n < cap) out[n] = dcp_step{(uint16_t)(3u << 14), (uint8_t)bl, 0};
+            ++n;
+            j -= bl;
+        }
+        unsigned const m = n < cap ? n : cap;
+        for (unsigned i = 0; i < m / 2; ++i)
+        {
+            dcp_step const t = out[i];
+            out[i] = out[m - 1 - i];
+            out[m - 1 - i] = t;
+        }
+        a.nsteps[h] = ok ? n : DCP_F64_TRACE_NO_PATH;
+        return;
+    }
+
+    double const alt = fmax(v.E[L] + v.xt[DCP_X_ET], v.C[L] + v.xt[DCP_X_CT]);
+    a.alt_out[h] = alt;
+    unsigned n = 0;
+    bool ok = alt > ni, too_long = false;
+    enum { ST_S = 1, ST_N, ST_B, ST_E, ST_J, ST_C, ST_T, ST_M, ST_I, ST_D };
+    int st = ST_T;
+    unsigned k = 0, j = L;
+    auto push = [&](unsigned id, unsigned len) {
+        if (n < cap) out[n] = dcp_step{(uint16_t)id, (uint8_t)len, 0};
+        if (++n == DCP_F64_TRACE_TOO_LONG) too_long = true, ok = false; // an error, never a wrap into the sentinels
+    };
+    unsigned const EXT = 3u << 14;
+    // a path has at most L emitting steps and, per domain (at most L of them), M + 1 silent core steps and B, E, J
+    uint64_t guard = 0;
+    uint64_t const max_steps = ((uint64_t)L + 1u) * (v.M + 4u) + 64u;
+    while (ok && guard++ < max_steps)
+    {
+        if (st == ST_T)
+        {
+            push(EXT | 7u, 0);
+            double const c0 = v.E[j] + v.xt[DCP_X_ET], c1 = v.C[j] + v.xt[DCP_X_CT];
+            st = !(c1 > c0) ? ST_E : ST_C; // E -> T was wired first
+        }
+        else if (st == ST_E)
+        {
+            push(EXT | 4u, 0);
+            // M_M, M_1 .. M_{M-1}, D_2 .. D_M (1-based): protein_model.c:494, :441-458
+            double best = ni;
+            int bs = -1;
+            unsigned bk = 0;
+            double const *Mj = v.Mv + (uint64_t)j * v.ld, *Dj = v.Dv + (uint64_t)j * v.ld;
+            double c = Mj[v.M - 1] + 0.0;
+            if (c > best) best = c, bs = ST_M, bk = v.M - 1;
+            for (unsigned kk = 0; kk + 1 < v.M; ++kk)
+            {
+                c = Mj[kk] + 0.0;
+                if (c > best) best = c, bs = ST_M, bk = kk;
+            }
+            for (unsigned kk = 1; kk < v.M; ++kk)
+            {
+                c = Dj[kk] + 0.0;
+                if (c > best) best = c, bs = ST_D, bk = kk;
+            }
+            if (bs < 0) ok = false;
+            st = bs, k = bk;
+        }
+        else if (st == ST_M || st == ST_I || st == ST_N || st == ST_J || st == ST_C)
+        {
+            unsigned const w = window64(v.words, j);
+            unsigned const maxl = j < 5u ? j : 5u;
+            double best = ni;
+            unsigned bl = 0;
+            for (unsigned l = 1; l <= maxl; ++l)
+            {
+                unsigned const c = code64(w, l);
+                double sc;
+                if (st == ST_M) sc = walk_P(v, j - l, k, nullptr) + v.eM[(uint64_t)c * v.ld + k];
+                else if (st == ST_I) sc = walk_Q(v, j - l, k, nullptr) + v.eI[c];
+                else if (st == ST_N) sc = walk_PN(v, j - l, nullptr) + v.eN[c];
+                else if (st == ST_J) sc = walk_PJ(v, j - l, nullptr) + v.eN[c];
+                else sc = walk_PC(v, j - l, nullptr) + v.eN[c];
+                if (sc > best) best = sc, bl = l;
+            }
+            if (bl == 0) { ok = false; break; }
+            int arg = -1;
+            if (st == ST_M)
+            {
+                push(k + 1u, bl);
+                walk_P(v, j - bl, k, &arg);
+                j -= bl;
+                if (arg == 0) st = ST_M, k = k - 1;
+                else if (arg == 1) st = ST_I, k = k - 1;
+                else if (arg == 2) st = ST_D, k = k - 1;
+                else if (arg == 3) st = ST_B;
+                else ok = false;
+            }
+            else if (st == ST_I)
+            {
+                push((1u << 14) | (k + 1u), bl);
+                walk_Q(v, j - bl, k, &arg);
+                j -= bl;
+                if (arg == 0) st = ST_M;
+                else if (arg == 1) st = ST_I;
+                else ok = false;
+            }
+            else if (st == ST_N)
+            {
+                push(EXT | 2u, bl);
+                walk_PN(v, j - bl, &arg);
+                j -= bl;
+                st = arg == 0 ? ST_S : ST_N;
+                if (arg < 0) ok = false;
+            }
+            else if (st == ST_J)
+            {
+                push(EXT | 5u, bl);
+                walk_PJ(v, j - bl, &arg);
+                j -= bl;
+                st = arg == 0 ? ST_E : ST_J;
+                if (arg < 0) ok = false;
+            }
+            else
+            {
+                push(EXT | 6u, bl);
+                walk_PC(v, j - bl, &arg);
+                j -= bl;
+                st = arg == 0 ? ST_E : ST_C;
+                if (arg < 0) ok = false;
+            }
+        }
+        else if (st == ST_D)
+        {
+            push((2u << 14) | (k + 1u), 0);
+            if (k == 0) { ok = false; break; }
+            uint64_t const o = (uint64_t)j * v.ld + k - 1u;
+            double const c0 = v.Mv[o] + v.md[k], c1 = v.Dv[o] + v.dd[k];
+            st = !(c1 > c0) ? ST_M : ST_D; // M_{k-1} -> D_k was wired first
+            k = k - 1;
+        }
+        else if (st == ST_B)
+        {
+            push(EXT | 3u, 0);
+            // S -> B, N -> B, E -> B, J -> B (protein_model.c:324-337)
+            double best = ni;
+            int bs = -1;
+            double c = (j == 0 ? 0.0 : ni) + v.xt[DCP_X_SB];
+            if (c > best) best = c, bs = ST_S;
+            c = v.N[j] + v.xt[DCP_X_NB];
+            if (c > best) best = c, bs = ST_N;
+            c = v.E[j] + v.xt[DCP_X_EB];
+            if (c > best) best = c, bs = ST_E;
+            c = v.J[j] + v.xt[DCP_X_JB];
+            if (c > best) best = c, bs = ST_J;
+            if (bs < 0) ok = false;
+            st = bs;
+        }
+        else // ST_S
+        {
+            push(EXT | 1u, 0);
+            if (j != 0) ok = false;
+            break;
+        }
+    }
+    if (st != ST_S) ok = false;
+    unsigned const m = n < cap ? n : cap;
+    for (unsigned i = 0; i < m / 2; ++i)
+    {
+        dcp_step const t = out[i];
+        out[i] = out[m - 1 - i];
+        out[m - 1 - i] = t;
+    }
+    a.nsteps[h] = ok ? n : too_long ? DCP_F64_TRACE_TOO_LONG : DCP_F64_TRACE_NO_PATH;
 }
 
 } // namespace
@@ -409,4 +791,26 @@ extern "C" int dcp_f64_launch_scan(int R, dcp_f64_scan_args const *a, unsigned n
     case 4: hipLaunchKernelGGL(viterbi64_kernel<4>, dim3(blocks), dim3(256), 0, st, b); return 0;
     default: return 1;
     }
+}
+
+int dcp_f64_launch_trace_forward(int R, dcp_f64_trace_args const *a, unsigned nwaves, void *stream)
+{
+    unsigned const blocks = (unsigned)(((uint64_t)nwaves + 3u) / 4u);
+    if (blocks == 0) return 0;
+    hipStream_t const st = (hipStream_t)stream;
+    dcp_f64_trace_args b = *a;
+    b.nwaves = nwaves;
+    switch (R)
+    {
+    case 1: hipLaunchKernelGGL((viterbi64_kernel<1, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
+    case 2: hipLaunchKernelGGL((viterbi64_kernel<2, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
+    case 4: hipLaunchKernelGGL((viterbi64_kernel<4, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
+    default: return 1;
+    }
+}
+
+void dcp_f64_launch_walk(dcp_f64_walk_args const *a, void *stream)
+{
+    if (a->nhits == 0) return;
+    hipLaunchKernelGGL(trace64_kernel, dim3(a->nhits), dim3(64), 0, (hipStream_t)stream, *a);
 }

@@ -200,9 +200,10 @@ struct dcp_gpu_ctx
     int launched_class[kMaxLaunches] = {0};
     bool launched_redo[kMaxLaunches] = {false}; // the exact kernel behind a segmented sweep: its cells are counted there
     // segmented sweep of the multi-wavefront classes (grid mode): per-class scratch columns and redo lists
-    DevBuf<float> d_trace_work;   // the traceback's work areas (kept between calls, grows to the largest round)
+    DevBuf<float> d_trace_work;   // the traceback's work areas (kept between calls, grows to the largest round): floats, or
+                                  // the double traceback's values in the same bytes (one work area per context)
     int trace_mode = 0;            // test hook: 1 = the trace kernel's own forward loop instead of the row sweep's
-    uint64_t trace_budget = 0;     // test hook: floats of work area per round of launches (0 = 2^31)
+    uint64_t trace_budget = 0;     // test hook: 4-byte units of work area per round of launches (0 = 2^31: 8 GiB)
     DevBuf<float> d_seg_scratch;
     DevBuf<dcp_pair> d_seg_redo;
     DevBuf<unsigned> d_seg_redo_n; // [DCP_MAX_CLASSES]
@@ -2443,6 +2444,219 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
                 if (ns[i] == DCP_TRACE_NO_PATH)
                     rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite alt path", hits[h].seq_idx, hits[h].profile_idx);
                 else if (ns[i] == DCP_TRACE_TOO_LONG)
+                    rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
+                                 hits[h].profile_idx);
+                else if (ns[i] > cap[h] && pass == 0)
+                    cap[h] = ns[i], again.push_back(h);
+                else if (ns[i] > cap[h])
+                    rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
+                else
+                    got[h].assign(st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
+            }
+            t0 = t1;
+        }
+        if (rc) return rc;
+        todo.swap(again);
+    }
+    uint64_t total_steps = 0;
+    for (unsigned h = 0; h < nhits; ++h)
+    {
+        total_steps += got[h].size();
+        if (total_steps > UINT32_MAX) return c->fail(DCP_EFAIL, "the paths of %u hits exceed 2^32 - 1 steps", nhits);
+        step_off[h + 1] = (uint32_t)total_steps;
+    }
+    if (total_steps > cap_steps || (total_steps && !steps_out)) return DCP_ENOMEM;
+    for (unsigned h = 0; h < nhits; ++h)
+        if (!got[h].empty()) std::memcpy(steps_out + step_off[h], got[h].data(), got[h].size() * sizeof(dcp_step));
+    return DCP_OK;
+}
+
+// The double DB's traceback: dcp_gpu_trace_paths' contract on dcp_hit64 records.  Forward pass: viterbi64_kernel<R,
+// TRACE> of each launch group over the round's pair list, every row written to the hit's work area in double
+// (3 [L + 1][ldk] matrices + 5 [L + 1] vectors); then one wavefront per hit walks back (trace64_kernel).  The null
+// model's one-state path needs no forward launch: the walk's lane 0 runs that recursion in the work area itself.
+int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned nhits,
+                          int multi_hits, int hmmer3_compat, int null_model,
+                          struct dcp_step *steps_out, unsigned cap_steps, uint32_t *step_off,
+                          double *alt_out)
+{
+    if (!c || !step_off || (nhits && !hits)) return DCP_EINVAL;
+    if (c->nprof == 0 || c->nseqs == 0) return c->fail(DCP_EINVAL, "no DB / sequences resident");
+    if (c->precision != 64)
+        return c->fail(DCP_EINVAL, "dcp_gpu_trace_paths64 traces on a double DB: trace a float DB's hits with dcp_gpu_trace_paths");
+    // step_off[nhits] stays 0 unless the paths are traced: a DCP_ENOMEM of a device allocation then reads as no shortfall
+    step_off[0] = step_off[nhits] = 0;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (nhits == 0) return DCP_OK;
+    for (unsigned h = 0; h < nhits; ++h)
+        if (hits[h].seq_idx >= c->nseqs || hits[h].profile_idx >= c->nprof)
+            return c->fail(DCP_EINVAL, "hit %u is outside the resident batch / DB", h);
+    auto &F = c->f64;
+    // entry of F.profs (group-sorted) of each caller's profile index
+    std::vector<uint32_t> slot(c->nprof);
+    for (unsigned i = 0; i < (unsigned)F.profs.size(); ++i)
+        slot[F.profs[i].pidx] = i;
+    auto group_of = [&](unsigned s) {
+        int g = 0;
+        while (g < 3 && s >= F.group_first[g + 1])
+            ++g;
+        return g;
+    };
+    // per-hit work area (doubles) and step capacity: 2L + 2M + 16 is an estimate, not a bound; the walk counts past its
+    // capacity, so a hit whose path is longer is traced once more at its exact count
+    std::vector<uint64_t> need(nhits);
+    std::vector<uint32_t> cap(nhits);
+    std::vector<int> grp(nhits);
+    for (unsigned h = 0; h < nhits; ++h)
+    {
+        dcp_f64_prof const &m = F.profs[slot[hits[h].profile_idx]];
+        uint64_t const L = c->seq_len[hits[h].seq_idx];
+        grp[h] = group_of(slot[hits[h].profile_idx]);
+        need[h] = null_model ? L + 1 : 3ull * (L + 1) * m.ldk + 5ull * (L + 1);
+        cap[h] = (uint32_t)(2 * L + 2ull * m.core_size + 16);
+    }
+    // the budget of dcp_gpu_trace_paths in bytes (its test hook counts 4-byte units); the work area is the same buffer
+    uint64_t const budget = (c->trace_budget ? c->trace_budget : 1ull << 31) * sizeof(float) / sizeof(double);
+    std::map<uint32_t, std::vector<double>> xt_of_len; // protein_profile_setup in double, as scan64 does
+    int rc = DCP_OK;
+    std::vector<std::vector<dcp_step>> got(nhits);
+    std::vector<unsigned> todo(nhits);
+    for (unsigned h = 0; h < nhits; ++h)
+        todo[h] = h;
+    for (int pass = 0; !todo.empty(); ++pass)
+    {
+        std::vector<unsigned> again; // hits whose paths exceeded their capacity
+        for (size_t t0 = 0; t0 < todo.size();)
+        {
+            size_t t1 = t0;
+            uint64_t work = 0, scap = 0;
+            while (t1 < todo.size() &&
+                   (t1 == t0 || (work + need[todo[t1]] <= budget && scap + cap[todo[t1]] <= UINT32_MAX)))
+                work += need[todo[t1]], scap += cap[todo[t1]], ++t1;
+            unsigned const n = (unsigned)(t1 - t0);
+            // this round's hits by launch group (each forward launch takes a contiguous pair list); results go back to
+            // the caller's order on the host
+            std::vector<unsigned> ord(todo.begin() + t0, todo.begin() + t1);
+            std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return grp[x] < grp[y]; });
+            std::vector<uint64_t> woff(n);
+            std::vector<uint32_t> soff(n + 1, 0);
+            std::vector<dcp_f64_pair> pairs(n);
+            std::vector<double> xt((size_t)n * DCP_F64_XSTRIDE, 0.0);
+            unsigned gfirst[5] = {0, 0, 0, 0, 0};
+            uint32_t seg_lmax = 0;
+            uint64_t acc = 0;
+            for (unsigned i = 0; i < n; ++i)
+            {
+                unsigned const h = ord[i];
+                uint32_t const L = c->seq_len[hits[h].seq_idx];
+                woff[i] = acc;
+                acc += need[h];
+                soff[i + 1] = soff[i] + cap[h];
+                pairs[i] = dcp_f64_pair{hits[h].seq_idx, slot[hits[h].profile_idx]};
+                auto it = xt_of_len.find(L);
+                if (it == xt_of_len.end())
+                {
+                    std::vector<double> x(DCP_NXTRANS);
+                    if (int e = dcp_xtrans64(L, multi_hits, hmmer3_compat, x.data())) return c->fail(e, "sequence cannot be empty");
+                    it = xt_of_len.emplace(L, std::move(x)).first;
+                }
+                std::memcpy(&xt[(size_t)i * DCP_F64_XSTRIDE], it->second.data(), sizeof(double) * DCP_NXTRANS);
+                gfirst[grp[h] + 1] = i + 1u;
+                if (grp[h] == 3) seg_lmax = std::max(seg_lmax, L);
+            }
+            for (int g = 1; g < 5; ++g)
+                if (gfirst[g] < gfirst[g - 1]) gfirst[g] = gfirst[g - 1];
+            size_t const work_floats = (size_t)(work * (sizeof(double) / sizeof(float)));
+            if (c->d_trace_work.n < work_floats) HIP_TRY(c, c->d_trace_work.alloc(work_floats));
+            double *const d_work = reinterpret_cast<double *>(c->d_trace_work.p);
+            DevBuf<double> d_alt, d_xt;
+            DevBuf<uint64_t> d_woff;
+            DevBuf<uint32_t> d_soff, d_nsteps;
+            DevBuf<dcp_step> d_steps;
+            DevBuf<dcp_f64_pair> d_pairs;
+            HIP_TRY(c, d_alt.alloc(n));
+            HIP_TRY(c, d_xt.alloc(xt.size()));
+            HIP_TRY(c, d_woff.alloc(n));
+            HIP_TRY(c, d_soff.alloc(n + 1));
+            HIP_TRY(c, d_nsteps.alloc(n));
+            HIP_TRY(c, d_steps.alloc(scap));
+            HIP_TRY(c, d_pairs.alloc(n));
+            HIP_TRY(c, hipMemcpy(d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_f64_pair), hipMemcpyHostToDevice));
+            if (!null_model)
+            {
+                // boundary columns of the segmented group: 5 doubles per row and wavefront, at most 1 GiB (scan64's)
+                uint64_t const col_stride = 5ull * ((uint64_t)seg_lmax + 1u);
+                uint64_t const nseg_pairs = gfirst[4] - gfirst[3];
+                uint64_t const seg_waves =
+                    nseg_pairs ? std::min<uint64_t>(nseg_pairs, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / col_stride)) : 0;
+                if (seg_waves && F.d_col.n < seg_waves * col_stride) HIP_TRY(c, F.d_col.alloc(seg_waves * col_stride));
+                dcp_f64_trace_args fa{};
+                fa.profs = F.d_profs.p;
+                fa.nprof_total = c->nprof;
+                fa.tab = F.d_tab.p;
+                fa.trans = F.d_trans.p;
+                fa.xe = F.d_xe.p;
+                fa.seq_words = c->d_seq_words.p;
+                fa.seq_woff = c->d_seq_woff.p;
+                fa.seq_len = c->d_seq_len.p;
+                fa.trace_work = d_work;
+                // one launch per non-empty group on the context stream, one wavefront per pair (the segmented group
+                // strides over its pairs with one boundary column per wavefront)
+                for (int g = 0; g < 4; ++g)
+                {
+                    unsigned const cnt = gfirst[g + 1] - gfirst[g];
+                    if (cnt == 0) continue;
+                    fa.pairs = d_pairs.p + gfirst[g];
+                    fa.npairs = cnt;
+                    fa.xtrans = d_xt.p + (size_t)gfirst[g] * DCP_F64_XSTRIDE;
+                    fa.trace_woff = d_woff.p + gfirst[g];
+                    fa.trace_alt = d_alt.p + gfirst[g];
+                    fa.col = g == 3 ? F.d_col.p : nullptr;
+                    fa.col_stride = g == 3 ? col_stride : 0;
+                    uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(cnt, 1ull << 24);
+                    if (dcp_f64_launch_trace_forward(kF64R[g], &fa, (unsigned)waves, c->stream))
+                        return c->fail(DCP_EFAIL, "no f64 traceback kernel for %d nodes per lane", kF64R[g]);
+                }
+                HIP_TRY(c, hipGetLastError());
+            }
+            dcp_f64_walk_args wa{};
+            wa.profs = F.d_profs.p;
+            wa.pairs = d_pairs.p;
+            wa.nhits = n;
+            wa.tab = F.d_tab.p;
+            wa.trans = F.d_trans.p;
+            wa.xe = F.d_xe.p;
+            wa.seq_words = c->d_seq_words.p;
+            wa.seq_woff = c->d_seq_woff.p;
+            wa.seq_len = c->d_seq_len.p;
+            wa.xtrans = d_xt.p;
+            wa.work = d_work;
+            wa.work_off = d_woff.p;
+            wa.steps = d_steps.p;
+            wa.step_off = d_soff.p;
+            wa.nsteps = d_nsteps.p;
+            wa.alt_out = d_alt.p;
+            wa.null_model = null_model ? 1 : 0;
+            dcp_f64_launch_walk(&wa, c->stream);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            std::vector<uint32_t> ns(n);
+            std::vector<dcp_step> st(scap);
+            std::vector<double> alts(n);
+            HIP_TRY(c, hipMemcpy(ns.data(), d_nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(st.data(), d_steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(alts.data(), d_alt.p, n * sizeof(double), hipMemcpyDeviceToHost));
+            for (unsigned i = 0; i < n; ++i)
+            {
+                unsigned const h = ord[i];
+                if (alt_out) alt_out[h] = alts[i];
+                if (ns[i] == DCP_F64_TRACE_NO_PATH)
+                    rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite %s path", hits[h].seq_idx,
+                                 hits[h].profile_idx, null_model ? "null" : "alt");
+                else if (ns[i] == DCP_F64_TRACE_TOO_LONG)
                     rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
                                  hits[h].profile_idx);
                 else if (ns[i] > cap[h] && pass == 0)

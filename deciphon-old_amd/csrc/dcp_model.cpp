@@ -283,6 +283,9 @@ struct dcp_profile
     std::vector<double> match_dist64;  // [M][129]
     std::vector<double> null_dist64;   // [129]
     std::vector<double> insert_dist64; // [129]
+    // dcp_profile_decode's exp() cache of null_dist64 / insert_dist64 (the double build decodes with those)
+    mutable std::once_flag decode_once64;
+    mutable DecodeExp decode_exp64[2]; // 0 null, 1 insert
 };
 
 // calculate_occupancy + setup_entry_trans (protein_model.c:258-283,410-439)
@@ -877,7 +880,9 @@ char dcp_gc_decode(uint8_t const codon[3])
 
 // protein_profile_decode (src/model/protein_profile.c:306-331): the distribution is the
 // insert dist for I states, the node's match dist for M states, the null dist otherwise;
-// imm_frame_cond_decode = arg-max over the 64 codons of p(fragment, codon).
+// imm_frame_cond_decode = arg-max over the 64 codons of p(fragment, codon).  A profile of the double build decodes
+// with its double parts and epsilon, as the reference's IMM_DOUBLE_PRECISION build does: its float parts are those
+// rounded once, and a near-tie of two codons can fall either way after that rounding.
 int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, unsigned state_id,
                        uint8_t codon[3])
 {
@@ -885,21 +890,13 @@ int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, 
     for (unsigned i = 0; i < len; ++i)
         if (frag[i] > 3) return DCP_EINVAL;
     unsigned const msb = state_id & (3u << 14);
-    float const *dist;
-    if (msb == (1u << 14))
-        dist = p->insert_dist;
-    else if (msb == 0)
-    {
-        unsigned k = (state_id & 0x3FFFu) - 1u; // protein_state_idx
-        if (k >= p->core_size) return DCP_EINVAL;
-        dist = &p->match_dist[(size_t)k * DCP_NDIST];
-    }
-    else if (state_id == ((3u << 14) | 1u) || state_id == ((3u << 14) | 3u) ||
-             state_id == ((3u << 14) | 4u) || state_id == ((3u << 14) | 7u) || msb == (2u << 14))
+    unsigned const k = (state_id & 0x3FFFu) - 1u; // protein_state_idx of an M state
+    if (msb == 0 && k >= p->core_size) return DCP_EINVAL;
+    if (state_id == ((3u << 14) | 1u) || state_id == ((3u << 14) | 3u) || state_id == ((3u << 14) | 4u) ||
+        state_id == ((3u << 14) | 7u) || msb == (2u << 14))
         return DCP_EINVAL; // mute states emit nothing: assert(!protein_state_is_mute) :310
-    else
-        dist = p->null_dist;
-    auto const fill = [](float const *d, dcp_profile::DecodeExp &x) {
+    int const which = msb == (1u << 14) ? 1 : msb == 0 ? 2 : 0; // the null, the insert or the node's match dist
+    auto const fill = [](auto const *d, dcp_profile::DecodeExp &x) {
         for (int i = 0; i < 4; ++i)
             x.b[i] = std::exp((double)d[i]);
         for (int a = 0; a < 4; ++a)
@@ -909,15 +906,31 @@ int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, 
     };
     dcp_profile::DecodeExp own;
     dcp_profile::DecodeExp const *x = &own;
-    if (dist == p->null_dist || dist == p->insert_dist)
+    double e;
+    if (p->f64)
     {
-        std::call_once(p->decode_once, [&]() { fill(p->null_dist, p->decode_exp[0]), fill(p->insert_dist, p->decode_exp[1]); });
-        x = &p->decode_exp[dist == p->insert_dist];
+        if (which == 2) fill(&p->match_dist64[(size_t)k * DCP_NDIST], own);
+        else
+        {
+            std::call_once(p->decode_once64, [&]() {
+                fill(p->null_dist64.data(), p->decode_exp64[0]), fill(p->insert_dist64.data(), p->decode_exp64[1]);
+            });
+            x = &p->decode_exp64[which];
+        }
+        e = p->epsilon64;
     }
     else
-        fill(dist, own);
+    {
+        if (which == 2) fill(&p->match_dist[(size_t)k * DCP_NDIST], own);
+        else
+        {
+            std::call_once(p->decode_once, [&]() { fill(p->null_dist, p->decode_exp[0]), fill(p->insert_dist, p->decode_exp[1]); });
+            x = &p->decode_exp[which];
+        }
+        e = (double)p->epsilon;
+    }
     double const *b = x->b;
-    double const e = (double)p->epsilon, f = 1.0 - e;
+    double const f = 1.0 - e;
     double best = -1.0;
     codon[0] = codon[1] = codon[2] = 4;
     for (int a = 0; a < 4; ++a)

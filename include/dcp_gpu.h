@@ -275,8 +275,9 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
  * expanded on the device in double, [1364][core_size padded to the kernel's columns] per profile -- one layout.
  * DCP_EINVAL if any profile was built in float.  A context holds ONE resident DB, float or double: either upload
  * replaces the other.  Scans of a double DB run the f64 kernel (dcp_scan_params.kernel 0 or 1; 2 and 3 are
- * DCP_EINVAL) and leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64.  The float-only calls
- * (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table, dcp_gpu_hit_buffer, explicit xtrans) return DCP_EINVAL on it. */
+ * DCP_EINVAL) and leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
+ * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table,
+ * dcp_gpu_hit_buffer, explicit xtrans) return DCP_EINVAL on it. */
 int dcp_gpu_db_upload64(dcp_gpu_ctx *, dcp_profile *const *profiles, unsigned nprofiles);
 /* 32 or 64: the precision of the resident DB; 0 without one. */
 int dcp_gpu_db_precision(dcp_gpu_ctx const *);
@@ -383,7 +384,8 @@ int dcp_gpu_test_set_seg_col_bytes(dcp_gpu_ctx *, unsigned long long bytes);
 /* Same build only.  own_forward != 0: dcp_gpu_trace_paths fills the hits' work areas with the trace kernel's own
  * one-wavefront forward loop (rounds 1-3) instead of the row-sweep kernels' -- the tests' second implementation of
  * the same rows; budget_floats != 0: floats of work area per round of launches (default 2^31), so that a handful of
- * hits already takes several rounds. */
+ * hits already takes several rounds.  dcp_gpu_trace_paths64 takes budget_floats as 4-byte units of its double work
+ * area and ignores own_forward (the double build has one forward pass). */
 int dcp_gpu_test_set_trace_mode(dcp_gpu_ctx *, int own_forward, unsigned long long budget_floats);
 /* Same build only.  Forces the grid-mode row-sweep kernel variant -- leading emission rows a block stages in
  * LDS (0, 20 or 84) and, in `block_waves`: bits 0..7 wavefronts per block (0: the default), bits 8..15 KiB of
@@ -476,6 +478,16 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *, struct dcp_hit const *hits, unsigned nhit
                         int multi_hits, int hmmer3_compat, int null_model,
                         struct dcp_step *steps_out, unsigned cap_steps, uint32_t *step_off,
                         float *alt_out);
+/* dcp_gpu_trace_paths on a double DB (dcp_gpu_db_upload64), word for word, with dcp_hit64 records and double
+ * log-likelihoods: the paths of the double build's recursion on the DB's own tables, special transitions
+ * dcp_xtrans64 of each hit's length and the flags.  DCP_EINVAL on a float DB.
+ * Device work: viterbi64_kernel's forward pass per launch group over the round's pairs parks every row's M, I, D
+ * (24 bytes per column of the DB's padded width) and N, B, E, J, C (40 bytes) in the context's traceback work area,
+ * at most 8 GiB per round of launches; one wavefront per hit walks back through it. */
+int dcp_gpu_trace_paths64(dcp_gpu_ctx *, struct dcp_hit64 const *hits, unsigned nhits,
+                          int multi_hits, int hmmer3_compat, int null_model,
+                          struct dcp_step *steps_out, unsigned cap_steps, uint32_t *step_off,
+                          double *alt_out);
 
 /* protein_state_name (src/model/protein_state.c:5-39): "M12", "I3", "N"... */
 unsigned dcp_state_name(unsigned state_id, char name[8]);

@@ -83,7 +83,7 @@ def same_bits(a, b):
     return np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
-@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True), (False, True)])
 def test_dp_bit_exact_small(dcp, oracle32, scanner, multi, h3, kern):
     rng = np.random.default_rng(1)
     specs = [(1, 2, ENTRY_DIST_UNIFORM, 0.1), (2, 2, ENTRY_DIST_OCCUPANCY, 0.01),
@@ -886,7 +886,7 @@ def test_qlane_at_block_scale(dcp, oracle32, scanner):
                     ("auto", dcp.KERNEL_AUTO)):
         scanner.scan(True, False, 10.0, kernel=k)
         out[name] = scanner.scores() + (scanner.hits(),)
-    for name in ("qlane", "auto"):
+    for name in ("qlane", "qlane2", "auto"):
         assert same_bits(out[name][0], out["rowsweep"][0])
         assert same_bits(out[name][1], out["rowsweep"][1])
         assert np.array_equal(out[name][2], out["rowsweep"][2])

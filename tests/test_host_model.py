@@ -72,7 +72,7 @@ def test_from_params_matches_oracle(dcp, oracle32):
 
 
 @pytest.mark.parametrize("L", [1, 2, 5, 32, 300, 1000, 1053, 10000])
-@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True), (False, True)])
 def test_xtrans_matches_oracle(dcp, oracle32, L, multi, h3):
     op = oracle32.sample(1, 2)
     assert op.setup(L, multi, h3) == 0

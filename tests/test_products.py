@@ -120,7 +120,7 @@ def test_trace_reference_golden(dcp):
 
 
 @gpu
-@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True), (False, True)])
 def test_trace_matches_oracle_paths(dcp, oracle32, multi, h3):
     import test_gpu_parity as tp
 
@@ -168,7 +168,7 @@ def test_trace_matches_oracle_paths(dcp, oracle32, multi, h3):
 
 
 @gpu
-@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True)])
+@pytest.mark.parametrize("multi,h3", [(True, False), (False, False), (True, True), (False, True)])
 def test_trace_forward_by_the_row_sweep_equals_the_trace_kernels_own(dcp, oracle32, multi, h3):
     """dcp_gpu_trace_paths fills the hits' work areas with the row-sweep kernel of each profile's size class (round 4:
     viterbi_rowsweep_kernel<R, W, 0, false, TRACE>, the scan's own rows) and walks back through them; the trace kernel's

@@ -94,6 +94,7 @@ class ScanParams(C.Structure):
 
 
 KERNEL_AUTO, KERNEL_ROWSWEEP, KERNEL_QLANE, KERNEL_QLANE2 = 0, 1, 2, 3
+KERNEL_QLANE64 = 4  # double DBs only: the f64 query-lane kernel
 DB_EXPAND_ON_HOST, DB_ONE_LAYOUT = 1, 2  # dcp_gpu_db_upload flags (include/dcp_gpu.h)
 
 
@@ -652,6 +653,10 @@ class Scanner:
 
     def scan(self, multi_hits=True, hmmer3_compat=False, lrt_threshold=10.0, keep_scores=True,
              sync=True, q_range=None, kernel=KERNEL_AUTO):
+        """Scan the resident sequences (or q_range of them) against the resident DB.  kernel: KERNEL_AUTO, or one of
+        KERNEL_ROWSWEEP (either DB), KERNEL_QLANE / KERNEL_QLANE2 (float DB), KERNEL_QLANE64 (double DB: the f64
+        query-lane kernel, the row sweep's bits at several times its rate from a few hundred queries on; on a
+        double DB KERNEL_AUTO is the row sweep).  A kernel that does not fit the DB's precision is RC_EINVAL."""
         prm = ScanParams(int(multi_hits), int(hmmer3_compat), float(lrt_threshold), int(keep_scores),
                          int(kernel))
         # a double DB filters with the threshold in double (dcp_gpu_set_lrt_threshold64)
@@ -719,7 +724,8 @@ class Scanner:
 
     @property
     def last_scan_kernel(self):
-        """KERNEL_ROWSWEEP / KERNEL_QLANE / KERNEL_QLANE2: what the last scan ran with."""
+        """KERNEL_ROWSWEEP / KERNEL_QLANE / KERNEL_QLANE2 / KERNEL_QLANE64: what the last scan ran with
+        (KERNEL_ROWSWEEP after a query-lane scan whose redo list overflowed and was repeated)."""
         return self._lib.dcp_gpu_last_scan_kernel(self._c)
 
     @property

@@ -1,5 +1,6 @@
-// dcp_f64.h -- the double build's device side (dcp_f64.hip): the resident f64 DB's frame-table expansion and the
-// f64 row-sweep kernel, as dcp_gpu.hip drives them.  Internal; the public C-ABI is include/dcp_gpu.h.
+// dcp_f64.h -- the double build's device side: the resident f64 DB's frame-table expansion, the f64 row-sweep
+// kernel and the traceback (dcp_f64.hip) and the f64 query-lane kernel (dcp_f64_qlane.hip), as dcp_gpu.hip drives
+// them.  Internal; the public C-ABI is include/dcp_gpu.h.
 #ifndef DCP_F64_H
 #define DCP_F64_H
 
@@ -15,6 +16,8 @@ enum
 {
     DCP_F64_XSTRIDE = 16, // doubles per sequence in the f64 xtrans array (DCP_X_* order)
     DCP_F64_SEG = 256,    // nodes of one column segment of the wide-profile sweep (64 lanes x 4)
+    DCP_F64_QL_KT = 4,    // nodes of one tile of the query-lane kernel (dcp_f64_qlane.hip)
+    DCP_F64_QL_LANES = 256, // queries (threads) of one of its blocks
 };
 
 // One resident profile of an f64 DB.  Offsets in doubles.
@@ -111,6 +114,45 @@ enum : uint32_t
     DCP_F64_TRACE_NO_PATH = 0xffffffffu, // DCP_TRACE_NO_PATH / DCP_TRACE_TOO_LONG of dcp_kernels.h
     DCP_F64_TRACE_TOO_LONG = 0xfffffffeu,
 };
+
+// The pair-list scan (viterbi64_kernel<R, false, true>): the scan's fields with profs the whole resident DB; pair i of
+// pairs[0 .. min(*npairs_dev, pair_cap)) names a query relative to the scan's first one and an entry of profs[], and
+// is scored, filtered and stored exactly as the grid mode does.  The count is read on the device: the list is the
+// query-lane kernel's redo list, filled by the launch before.
+struct dcp_f64_pairs_args : dcp_f64_scan_args
+{
+    dcp_f64_pair const *pairs;
+    unsigned const *npairs_dev;
+    unsigned pair_cap;
+};
+int dcp_f64_launch_scan_pairs(int R, dcp_f64_pairs_args const *a, unsigned nwaves, void *stream);
+
+// The query-lane kernel (dcp_f64_qlane.hip): a persistent grid of blocks of DCP_F64_QL_LANES queries pulling
+// (profile, query block) tasks from *task_counter; task i is profile order[i / nqb] against queries
+// qorder[256 (i % nqb) ..] (relative to the scan's first query, ascending length).
+struct dcp_f64_qlane_args
+{
+    dcp_f64_prof const *profs; // the whole resident DB
+    uint32_t const *order;     // [nprof] entries of profs, largest core size first
+    unsigned nprof_total;
+    double const *tab, *trans, *xe;
+    uint32_t const *seq_words, *seq_woff, *seq_len; // relative to the scan's first query
+    double const *xtrans;                           // [nq][DCP_F64_XSTRIDE]
+    uint32_t const *qorder;                         // [nq]
+    unsigned nq, q_base, nqb, ntasks;
+    double *out_null, *out_alt;
+    struct dcp_hit64 *hits;
+    unsigned *nhits;
+    unsigned hit_cap;
+    double lrt_threshold;
+    double *planes;        // plane_stride doubles per block of the grid: [row 0 .. lmax][3][DCP_F64_QL_LANES]
+    uint64_t plane_stride;
+    unsigned *task_counter;
+    dcp_f64_pair *redo;    // one list per launch group of the DB, group g at redo_first[g], redo_cap[g] long
+    unsigned redo_first[4], redo_cap[4];
+    unsigned *redo_n;      // [4] pairs appended (counts on past the capacity), [1] overflow flag
+};
+void dcp_f64_launch_qlane(dcp_f64_qlane_args const *a, unsigned nblocks, void *stream);
 
 // R = 1, 2 or 4; nwaves wavefronts stride over the a->npairs pairs (one boundary column each where a->col is set)
 int dcp_f64_launch_trace_forward(int R, dcp_f64_trace_args const *a, unsigned nwaves, void *stream);

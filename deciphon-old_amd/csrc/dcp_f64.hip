@@ -9,6 +9,8 @@
 //                       memory, as viterbi_segment_kernel's does.
 //  viterbi64_kernel<R, true>  the traceback's forward pass: the same sweep over a list of pairs, every row's M, I, D
 //                       and N, B, E, J, C written to the pair's work area instead of a score (dcp_f64_trace_args).
+//  viterbi64_kernel<R, false, true>  the same sweep over a pair list that was filled on the device: the redo list
+//                       of the query-lane kernel (dcp_f64_qlane.hip), scores and hits written as the grid mode's.
 //  trace64_kernel       the walk back from T(L) to S(0) on that work area, one wavefront per hit.
 //
 // Arithmetic contract: the recursion of the CPU oracle's double build, operation by operation --
@@ -302,20 +304,27 @@ __device__ __forceinline__ void row64(State64<R> &s, Trans64<R> const &t, X64 co
     }
 }
 
-template <bool TRACE> struct Args64
+template <bool TRACE, bool PAIRS = false> struct Args64
 {
     using T = dcp_f64_scan_args;
 };
-template <> struct Args64<true>
+template <> struct Args64<true, false>
 {
     using T = dcp_f64_trace_args;
+};
+template <> struct Args64<false, true>
+{
+    using T = dcp_f64_pairs_args;
 };
 
 // TRACE: the traceback's forward pass (dcp_f64_trace_args): pair i of the list writes every row to its work area
 // and its alt score to trace_alt[i]; every fixed-point pass rewrites all rows, so the last one leaves the exact
-// recursion there.  The scan's instantiations (TRACE = false) are the code they were before it existed.
-template <int R, bool TRACE = false>
-__global__ __launch_bounds__(256) void viterbi64_kernel(typename Args64<TRACE>::T a)
+// recursion there.  PAIRS: a scan of a pair list whose length is read on the device (dcp_f64_pairs_args) -- the
+// query-lane kernel's redo list: scores, filter and hits as the grid mode's, the special transitions those of the
+// pair's QUERY, boundary columns per wavefront as in the other modes.  The grid mode's instantiations (neither)
+// are the code they were before the other two existed.
+template <int R, bool TRACE = false, bool PAIRS = false>
+__global__ __launch_bounds__(256) void viterbi64_kernel(typename Args64<TRACE, PAIRS>::T a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -323,12 +332,17 @@ __global__ __launch_bounds__(256) void viterbi64_kernel(typename Args64<TRACE>::
     if (gw >= nw) return; // the grid's last block may hold wavefronts past nwaves: they have no boundary column
     uint64_t npairs;
     if constexpr (TRACE) npairs = a.npairs;
+    else if constexpr (PAIRS)
+    {
+        unsigned const n = *a.npairs_dev; // counts on past the capacity when the list overflowed
+        npairs = n < a.pair_cap ? n : a.pair_cap;
+    }
     else npairs = (uint64_t)a.nprof * a.nq;
     double *const col = a.col ? a.col + gw * a.col_stride : nullptr;
     for (uint64_t pair = gw; pair < npairs; pair += nw)
     {
         unsigned pi, q;
-        if constexpr (TRACE)
+        if constexpr (TRACE || PAIRS)
         {
             dcp_f64_pair const pp = a.pairs[pair];
             pi = pp.prof, q = pp.q;
@@ -789,6 +803,22 @@ extern "C" int dcp_f64_launch_scan(int R, dcp_f64_scan_args const *a, unsigned n
     case 1: hipLaunchKernelGGL(viterbi64_kernel<1>, dim3(blocks), dim3(256), 0, st, b); return 0;
     case 2: hipLaunchKernelGGL(viterbi64_kernel<2>, dim3(blocks), dim3(256), 0, st, b); return 0;
     case 4: hipLaunchKernelGGL(viterbi64_kernel<4>, dim3(blocks), dim3(256), 0, st, b); return 0;
+    default: return 1;
+    }
+}
+
+int dcp_f64_launch_scan_pairs(int R, dcp_f64_pairs_args const *a, unsigned nwaves, void *stream)
+{
+    unsigned const blocks = (unsigned)(((uint64_t)nwaves + 3u) / 4u);
+    if (blocks == 0) return 0;
+    hipStream_t const st = (hipStream_t)stream;
+    dcp_f64_pairs_args b = *a;
+    b.nwaves = nwaves;
+    switch (R)
+    {
+    case 1: hipLaunchKernelGGL((viterbi64_kernel<1, false, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
+    case 2: hipLaunchKernelGGL((viterbi64_kernel<2, false, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
+    case 4: hipLaunchKernelGGL((viterbi64_kernel<4, false, true>), dim3(blocks), dim3(256), 0, st, b); return 0;
     default: return 1;
     }
 }

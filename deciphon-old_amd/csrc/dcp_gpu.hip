@@ -227,12 +227,23 @@ struct dcp_gpu_ctx
         DevBuf<unsigned> d_nhits;
         unsigned hit_cap = 0;
         bool have_scores = false;
+        // the query-lane kernel (dcp_f64_qlane.hip): profiles by falling core size, the scan's queries by rising
+        // length, the resident blocks' boundary planes, the task counter, the redo lists of the four launch groups
+        // and their counters ([4] pairs, [1] overflow flag); kept between scans
+        DevBuf<uint32_t> d_order, d_qorder;
+        DevBuf<double> d_planes;
+        DevBuf<unsigned> d_task, d_redo_n;
+        DevBuf<dcp_f64_pair> d_redo;
+        bool redo_pending = false; // the last scan's redo counters have not been checked yet
         void release()
         {
             profs.clear();
             d_profs.release(), d_tab.release(), d_trans.release(), d_xe.release();
             d_xt.release(), d_null.release(), d_alt.release(), d_col.release();
             d_hits.release(), d_nhits.release();
+            d_order.release(), d_qorder.release(), d_planes.release(), d_task.release(), d_redo_n.release();
+            d_redo.release();
+            redo_pending = false;
             hit_cap = 0;
             have_scores = false;
         }
@@ -1026,6 +1037,16 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     HIP_TRY(c, d_jobs.alloc(jobs.size()));
     HIP_TRY(c, d_xe_jobs.alloc(xe_jobs.size()));
     HIP_TRY(c, hipMemcpy(F.d_profs.p, F.profs.data(), nprofiles * sizeof(dcp_f64_prof), hipMemcpyHostToDevice));
+    {
+        // the query-lane kernel's task order: largest profiles first
+        std::vector<uint32_t> by_size(nprofiles);
+        for (unsigned i = 0; i < nprofiles; ++i)
+            by_size[i] = i;
+        std::stable_sort(by_size.begin(), by_size.end(),
+                         [&](uint32_t x, uint32_t y) { return F.profs[x].core_size > F.profs[y].core_size; });
+        HIP_TRY(c, F.d_order.alloc(nprofiles));
+        HIP_TRY(c, hipMemcpy(F.d_order.p, by_size.data(), nprofiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
     HIP_TRY(c, hipMemcpy(F.d_trans.p, h_trans.data(), trans * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_dists.p, h_dists.data(), h_dists.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(c, hipMemcpy(d_jobs.p, jobs.data(), jobs.size() * sizeof(dcp_f64_expand_job), hipMemcpyHostToDevice));
@@ -1054,6 +1075,7 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     HIP_TRY(c, hipSetDevice(c->device));
     c->scanned = false;
     c->redo_pending = false;           // the previous batch's scan is void
+    c->f64.redo_pending = false;
     c->ring_check_pending = false;
     c->qorder_q0 = c->qorder_q1 = ~0u; // also when this upload fails half way
     std::vector<uint32_t> woff(nseqs), len(nseqs);
@@ -1396,15 +1418,20 @@ static void rowsweep_variant(dcp_gpu_ctx const *c, int R, int W, unsigned nchunk
     if (forced && g > 0) *pf = c->rs_force_pf;
 }
 
-// A scan of the resident double DB: viterbi64_kernel<R> per launch group (dcp_f64.hip), the LRT filter in its
-// epilogue, results in the f64 buffers.
+// A scan of the resident double DB: viterbi64_kernel<R> per launch group (dcp_f64.hip), or -- kernel 4 -- the
+// query-lane kernel (dcp_f64_qlane.hip) with the row sweep behind it on the pairs it could not finish; the LRT
+// filter in their epilogues, results in the f64 buffers.
 static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_begin, unsigned q_end)
 {
-    if (prm->kernel != 0 && prm->kernel != 1)
-        return c->fail(DCP_EINVAL, "a double DB is scanned by the f64 row sweep only (kernel 0 or 1, not %d)", prm->kernel);
+    if (prm->kernel != 0 && prm->kernel != 1 && prm->kernel != 4)
+        return c->fail(DCP_EINVAL, "a double DB is scanned by the f64 row sweep (kernel 0 or 1) or the f64 query-lane kernel (4), not %d", prm->kernel);
     if (c->xt_explicit)
         return c->fail(DCP_EINVAL, "explicit special transitions are float: a double DB derives them from the lengths");
     auto &F = c->f64;
+    // one scan is outstanding per context: a query-lane scan whose redo counters have not been looked at is
+    // completed first (its overflow re-run included)
+    if (F.redo_pending)
+        if (int rc = finish_scan(c)) return rc;
     c->scanned = false;
     unsigned const nq = q_end - q_begin;
     // protein_profile_setup in double, once per length
@@ -1472,10 +1499,97 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     std::memcpy(&thr_bits, &c->lrt_threshold64, sizeof thr_bits);
     bool const thr_unset = (thr_bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
     a.lrt_threshold = thr_unset ? (double)prm->lrt_threshold : c->lrt_threshold64;
+    bool const qlane = prm->kernel == 4;
+    dcp_f64_qlane_args qa{};
+    unsigned ql_blocks = 0;
+    if (qlane)
+    {
+        // blocks of 256 consecutive queries of the length order; a persistent grid of at most two blocks per CU,
+        // fewer where their boundary planes ([row 0 .. lmax + 4][3][256] doubles each) would take too much memory
+        unsigned const nqb = (nq + DCP_F64_QL_LANES - 1u) / DCP_F64_QL_LANES;
+        uint64_t const ntasks = (uint64_t)c->nprof * nqb;
+        uint64_t const plane_stride = ((uint64_t)lmax + 5u) * 3u * DCP_F64_QL_LANES;
+        if (plane_stride > (1ull << 31) || ntasks > 0xf0000000ull)
+            return c->fail(DCP_ENOMEM, "batch too large for the f64 query-lane kernel (%u rows, %llu tasks): use kernel = 1", lmax,
+                           (unsigned long long)ntasks);
+        size_t free_b = 0, total_b = 0;
+        HIP_TRY(c, hipMemGetInfo(&free_b, &total_b));
+        // (two blocks on each of 256 CUs at 10 kbp are 31 GB of planes; at 1 kbp 3 GB)
+        uint64_t const budget = std::min<uint64_t>(((uint64_t)free_b + F.d_planes.n * sizeof(double)) / 2u, 40ull << 30);
+        ql_blocks = (unsigned)std::min<uint64_t>(std::min<uint64_t>(2ull * c->num_cus, ntasks), budget / (plane_stride * sizeof(double)));
+        if (ql_blocks == 0)
+            return c->fail(DCP_ENOMEM, "sequences too long for the f64 query-lane kernel (%u rows of boundary planes do not fit the device): use kernel = 1", lmax);
+        if (F.d_planes.n < ql_blocks * plane_stride) HIP_TRY(c, F.d_planes.alloc(ql_blocks * plane_stride));
+        std::vector<uint32_t> qorder(nq);
+        for (unsigned q = 0; q < nq; ++q)
+            qorder[q] = q;
+        std::stable_sort(qorder.begin(), qorder.end(),
+                         [&](uint32_t x, uint32_t y) { return c->seq_len[q_begin + x] < c->seq_len[q_begin + y]; });
+        if (F.d_qorder.n < nq) HIP_TRY(c, F.d_qorder.alloc(nq));
+        HIP_TRY(c, hipMemcpyAsync(F.d_qorder.p, qorder.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // qorder and xt leave scope
+        if (!F.d_task.p) HIP_TRY(c, F.d_task.alloc(1));
+        if (!F.d_redo_n.p) HIP_TRY(c, F.d_redo_n.alloc(5));
+        // a redo list per launch group; uni-hit scans have no feedback and no lists
+        uint64_t redo_total = 0;
+        for (int g = 0; g < 4; ++g)
+        {
+            uint64_t const pairs = (uint64_t)(F.group_first[g + 1] - F.group_first[g]) * nq;
+            qa.redo_first[g] = (unsigned)redo_total;
+            qa.redo_cap[g] = prm->multi_hits ? (unsigned)std::min<uint64_t>(pairs, c->redo_cap_limit) : 0u;
+            redo_total += qa.redo_cap[g];
+        }
+        if (redo_total > 0xffffffffull)
+            return c->fail(DCP_ENOMEM, "batch too large for the f64 query-lane kernel's redo lists: use kernel = 1");
+        if (F.d_redo.n < redo_total) HIP_TRY(c, F.d_redo.alloc(redo_total));
+        qa.profs = F.d_profs.p;
+        qa.order = F.d_order.p;
+        qa.nprof_total = c->nprof;
+        qa.tab = a.tab, qa.trans = a.trans, qa.xe = a.xe;
+        qa.seq_words = a.seq_words, qa.seq_woff = a.seq_woff, qa.seq_len = a.seq_len;
+        qa.xtrans = a.xtrans;
+        qa.qorder = F.d_qorder.p;
+        qa.nq = nq, qa.q_base = q_begin, qa.nqb = nqb, qa.ntasks = (unsigned)ntasks;
+        qa.out_null = a.out_null, qa.out_alt = a.out_alt;
+        qa.hits = a.hits, qa.nhits = a.nhits, qa.hit_cap = a.hit_cap;
+        qa.lrt_threshold = a.lrt_threshold;
+        qa.planes = F.d_planes.p;
+        qa.plane_stride = plane_stride;
+        qa.task_counter = F.d_task.p;
+        qa.redo = F.d_redo.p;
+        qa.redo_n = F.d_redo_n.p;
+        HIP_TRY(c, hipMemsetAsync(F.d_task.p, 0, sizeof(unsigned), c->stream));
+        HIP_TRY(c, hipMemsetAsync(F.d_redo_n.p, 0, 5 * sizeof(unsigned), c->stream));
+    }
     HIP_TRY(c, hipMemsetAsync(F.d_nhits.p, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     unsigned launches = 0;
-    for (int g = 0; g < 4; ++g)
+    if (qlane)
+    {
+        dcp_f64_launch_qlane(&qa, ql_blocks, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        ++launches;
+        // the pairs whose B(j) was not B0(j): the row sweep over each group's list, right behind
+        for (int g = 0; g < 4 && prm->multi_hits; ++g)
+        {
+            if (qa.redo_cap[g] == 0) continue;
+            dcp_f64_pairs_args pa{};
+            static_cast<dcp_f64_scan_args &>(pa) = a;
+            pa.profs = F.d_profs.p;
+            pa.nprof = c->nprof;
+            pa.pairs = F.d_redo.p + qa.redo_first[g];
+            pa.npairs_dev = F.d_redo_n.p + g;
+            pa.pair_cap = qa.redo_cap[g];
+            uint64_t const waves = std::min<uint64_t>(g == 3 ? seg_waves : 4096u, std::min<uint64_t>(qa.redo_cap[g], 4096u));
+            pa.col = g == 3 ? F.d_col.p : nullptr;
+            pa.col_stride = g == 3 ? col_stride : 0;
+            if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, (unsigned)waves, c->stream))
+                return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
+            HIP_TRY(c, hipGetLastError());
+            ++launches;
+        }
+    }
+    for (int g = 0; g < 4 && !qlane; ++g)
     {
         unsigned const n = F.group_first[g + 1] - F.group_first[g];
         if (n == 0) continue;
@@ -1495,9 +1609,12 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     c->last_q0 = q_begin;
     c->last_q1 = q_end;
     c->last_launches = launches;
-    c->n_launched = 0; // no per-launch records (dcp_gpu_last_scan_launch_info) for the f64 kernel
-    c->last_kernel = 1;
-    c->last_kernel_variant = 1;
+    c->n_launched = 0; // no per-launch records (dcp_gpu_last_scan_launch_info) for the f64 kernels
+    c->last_kernel = qlane ? 2 : 1;
+    c->last_kernel_variant = qlane ? 4 : 1;
+    c->last_prm = *prm;
+    c->last_redo_pairs = 0;
+    F.redo_pending = qlane && prm->multi_hits;
     c->last_overlapped = false;
     c->have_scores = false;
     c->last_f64 = true;
@@ -2011,6 +2128,22 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
 static int finish_scan(dcp_gpu_ctx *c)
 {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->f64.redo_pending) // the f64 query-lane kernel's lists: [4] pairs appended, [1] overflow flag
+    {
+        c->f64.redo_pending = false;
+        unsigned n[5];
+        HIP_TRY(c, hipMemcpy(n, c->f64.d_redo_n.p, sizeof n, hipMemcpyDeviceToHost));
+        c->last_redo_pairs = (unsigned)std::min<uint64_t>((uint64_t)n[0] + n[1] + n[2] + n[3], 0xffffffffull);
+        if (n[4] == 0) return DCP_OK;
+        // a list was full and lost pairs: the scan is repeated with the row sweep, which needs none
+        unsigned const redone = c->last_redo_pairs;
+        struct dcp_scan_params prm = c->last_prm;
+        prm.kernel = 1;
+        if (int rc = dcp_gpu_scan_range(c, &prm, c->last_q0, c->last_q1)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        c->last_redo_pairs = redone;
+        return DCP_OK;
+    }
     if (!c->redo_pending && !c->ring_check_pending) return DCP_OK;
     bool const redo = c->redo_pending;
     c->redo_pending = false;

@@ -274,8 +274,9 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
 /* Upload a DB of double-build profiles (dcp_profile_new64 / dcp_profile_sample64): their frame tables are
  * expanded on the device in double, [1364][core_size padded to the kernel's columns] per profile -- one layout.
  * DCP_EINVAL if any profile was built in float.  A context holds ONE resident DB, float or double: either upload
- * replaces the other.  Scans of a double DB run the f64 kernel (dcp_scan_params.kernel 0 or 1; 2 and 3 are
- * DCP_EINVAL) and leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
+ * replaces the other.  Scans of a double DB run the f64 row sweep (dcp_scan_params.kernel 0 or 1) or the f64
+ * query-lane kernel (4: the throughput path for batches of a few hundred queries and more; same bits); 2 and 3,
+ * the float query-lane kernels, are DCP_EINVAL.  They leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
  * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table,
  * dcp_gpu_hit_buffer, explicit xtrans) return DCP_EINVAL on it. */
 int dcp_gpu_db_upload64(dcp_gpu_ctx *, dcp_profile *const *profiles, unsigned nprofiles);
@@ -322,7 +323,10 @@ struct dcp_scan_params
     int kernel;          /* 0 = choose by a cost model (DB size x batch size); 1 = row sweep (one wavefront
                           * group per pair: any batch size); 2 = query lane (one lane per query, tiles in
                           * LDS: throughput path); 3 = query lane, two-stage blocks (even / odd tiles of a
-                          * profile pipelined through an LDS ring: half the scratch traffic) */
+                          * profile pipelined through an LDS ring: half the scratch traffic);
+                          * 4 = the double DB's query lane (one lane per query in double, the pairs whose
+                          * multi-hit feedback it cannot carry re-scored by the f64 row sweep behind it).
+                          * 2 and 3 are DCP_EINVAL on a double DB, 4 on a float one; 0 on a double DB is 1 */
 };
 /* The LRT threshold of the scans of a double DB, in double.  NaN -- the sentinel, and the default -- means
  * "(double) dcp_scan_params.lrt_threshold".  (Not a field of dcp_scan_params: callers that initialise it
@@ -418,8 +422,9 @@ float dcp_gpu_last_scan_ms(dcp_gpu_ctx *);
 /* Number of DP kernel launches of the last scan (row sweep: one per profile
  * size class; query lane: one, plus one redo launch per size class). */
 unsigned dcp_gpu_last_scan_launches(dcp_gpu_ctx const *);
-/* The kernel the last scan ran with, as dcp_scan_params.kernel names it (1, 2 or 3): what the cost
- * model chose when the scan asked for 0.  0 before any scan. */
+/* The kernel the last scan ran with, as dcp_scan_params.kernel names it (1, 2, 3, or 4 on a double DB): what
+ * the cost model chose when the scan asked for 0.  A query-lane scan (2, 3 or 4) whose redo list overflowed was
+ * repeated with the row sweep by dcp_gpu_sync and reports 1 from then on.  0 before any scan. */
 int dcp_gpu_last_scan_kernel(dcp_gpu_ctx const *);
 /* Launch i of the last scan: its kernel shape, HIP-event duration on the
  * context's stream, DP cells and algorithmic bytes.  The cells

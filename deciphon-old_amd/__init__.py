@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "dcp_profile_trans8_64", "dcp_profile_null_dist64", "dcp_profile_insert_dist64", "dcp_profile_match_dist64",
     "dcp_xtrans64", "dcp_gpu_db_upload64", "dcp_gpu_db_precision", "dcp_gpu_set_lrt_threshold64", "dcp_gpu_fetch_scores64", "dcp_gpu_fetch_hits64",
     "dcp_gpu_db_fetch_match_table64", "dcp_gpu_db_fetch_insert_null64", "dcp_gpu_trace_paths64",
+    "dcp_gpu_seqs_set_xtrans64", "dcp_profile_from_parts64", "dcp_lprob_normalize64",
 ]
 
 
@@ -209,6 +210,9 @@ def _load(path=None, hooks=False):
         "dcp_gpu_db_fetch_match_table64": (I, [P, U, P]),
         "dcp_gpu_db_fetch_insert_null64": (I, [P, U, P, P]),
         "dcp_gpu_trace_paths64": (I, [P, P, U, I, I, I, P, U, P, P]),
+        "dcp_gpu_seqs_set_xtrans64": (I, [P, P, U]),
+        "dcp_lprob_normalize64": (None, [U, P]),
+        "dcp_profile_from_parts64": (P, [C.c_char_p, U, I, C.c_double, C.c_char_p, P, P, P, P, C.POINTER(I)]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -361,6 +365,22 @@ class ProteinProfile:
                 self._view(lib.dcp_profile_null_dist64(self._h), (NDIST,), d),
                 self._view(lib.dcp_profile_insert_dist64(self._h), (NDIST,), d),
                 self._view(lib.dcp_profile_match_dist64(self._h), (M, NDIST), d))
+
+    @classmethod
+    def from_parts64(cls, trans8, null_dist, insert_dist, match_dist, cfg=PROTEIN_CFG_DEFAULT,
+                     accession="accession", consensus=None):
+        """A double profile from stored double parts (dcp_profile_from_parts64): what parts64() returns."""
+        t8, nd, idist, md = _f64(trans8), _f64(null_dist), _f64(insert_dist), _f64(match_dist)
+        M = t8.shape[1] if t8.ndim == 2 else 0
+        if t8.shape != (8, M) or nd.shape != (NDIST,) or idist.shape != (NDIST,) or md.shape != (M, NDIST):
+            raise DcpError(RC_EINVAL, "bad part shapes")
+        rc = C.c_int(0)
+        h = lib.dcp_profile_from_parts64(accession.encode(), M, cfg.entry_dist, cfg.epsilon64,
+                                         consensus.encode() if consensus else None, t8.ctypes.data, nd.ctypes.data,
+                                         idist.ctypes.data, md.ctypes.data, C.byref(rc))
+        if not h:
+            raise DcpError(rc.value, "dcp_profile_from_parts64")
+        return cls(h)
 
     @property
     def epsilon64(self):
@@ -647,9 +667,19 @@ class Scanner:
 
     def set_xtrans(self, xt):
         """Explicit special transitions [nseqs, 13] for the resident sequences (dcp_gpu_seqs_set_xtrans):
-        what imm_dp_viterbi uses for a profile whose transitions were not set from the sequence length."""
+        what imm_dp_viterbi uses for a profile whose transitions were not set from the sequence length.
+        A float64 array on a double DB goes to dcp_gpu_seqs_set_xtrans64 (see set_xtrans64); anything else is
+        taken as float, which a scan of a double DB refuses."""
+        if self.precision == 64 and np.asarray(xt).dtype == np.float64:
+            return self.set_xtrans64(xt)
         xt = np.ascontiguousarray(xt, np.float32).reshape(-1, NXTRANS)
         self._check(self._lib.dcp_gpu_seqs_set_xtrans(self._c, xt.ctypes.data, len(xt)))
+
+    def set_xtrans64(self, xt):
+        """Explicit special transitions [nseqs, 13] in double, in xtrans64 order (dcp_gpu_seqs_set_xtrans64): the
+        scans and traces of a double DB use them until the next upload_seqs; a float DB refuses them."""
+        xt = np.ascontiguousarray(xt, np.float64).reshape(-1, NXTRANS)
+        self._check(self._lib.dcp_gpu_seqs_set_xtrans64(self._c, xt.ctypes.data, len(xt)))
 
     def scan(self, multi_hits=True, hmmer3_compat=False, lrt_threshold=10.0, keep_scores=True,
              sync=True, q_range=None, kernel=KERNEL_AUTO):

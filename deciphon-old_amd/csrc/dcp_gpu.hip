@@ -175,6 +175,9 @@ struct dcp_gpu_ctx
     DevBuf<float> d_xtrans;
     int xt_multi = -1, xt_h3 = -1;
     bool xt_explicit = false; // dcp_gpu_seqs_set_xtrans: the caller's transitions, not the length-derived ones
+    // dcp_gpu_seqs_set_xtrans64: the caller's transitions in double, [nseqs][13] on the host (the scans and traces of a
+    // double DB copy the rows of their queries / hits from here); empty while the derived ones hold
+    std::vector<double> xt64;
 
     // results
     DevBuf<float> d_null, d_alt;
@@ -1131,6 +1134,7 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     c->total_len = total;
     c->xt_multi = c->xt_h3 = -1;
     c->xt_explicit = false;
+    c->xt64.clear();
     // the length order and the transposed word planes belong to the batch that was resident
     c->qorder_q0 = c->qorder_q1 = ~0u;
     return DCP_OK;
@@ -1194,6 +1198,23 @@ int dcp_gpu_seqs_set_xtrans(dcp_gpu_ctx *c, float const *xt, unsigned nseqs)
         }
     HIP_TRY(c, hipMemcpy(c->d_xtrans.p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
     c->xt_explicit = true;
+    c->xt64.clear(); // one explicit set holds: the last one given
+    c->xt_multi = c->xt_h3 = -1;
+    return DCP_OK;
+}
+
+int dcp_gpu_seqs_set_xtrans64(dcp_gpu_ctx *c, double const *xt, unsigned nseqs)
+{
+    if (!c) return DCP_EINVAL;
+    if (!xt || nseqs == 0 || nseqs != c->nseqs) return c->fail(DCP_EINVAL, "xtrans must cover the resident sequences");
+    for (size_t i = 0; i < (size_t)nseqs * DCP_NXTRANS; ++i)
+    {
+        uint64_t bits; // this file is built with -fno-honor-nans: test the encoding, not v != v
+        std::memcpy(&bits, &xt[i], sizeof bits);
+        if ((bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return c->fail(DCP_EINVAL, "NaN special transition");
+    }
+    c->xt64.assign(xt, xt + (size_t)nseqs * DCP_NXTRANS);
+    c->xt_explicit = false; // one explicit set holds: the last one given
     c->xt_multi = c->xt_h3 = -1;
     return DCP_OK;
 }
@@ -1426,7 +1447,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     if (prm->kernel != 0 && prm->kernel != 1 && prm->kernel != 4)
         return c->fail(DCP_EINVAL, "a double DB is scanned by the f64 row sweep (kernel 0 or 1) or the f64 query-lane kernel (4), not %d", prm->kernel);
     if (c->xt_explicit)
-        return c->fail(DCP_EINVAL, "explicit special transitions are float: a double DB derives them from the lengths");
+        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
     auto &F = c->f64;
     // one scan is outstanding per context: a query-lane scan whose redo counters have not been looked at is
     // completed first (its overflow re-run included)
@@ -1434,7 +1455,8 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         if (int rc = finish_scan(c)) return rc;
     c->scanned = false;
     unsigned const nq = q_end - q_begin;
-    // protein_profile_setup in double, once per length
+    bool const xt_given = !c->xt64.empty(); // dcp_gpu_seqs_set_xtrans64: the flags are ignored
+    // protein_profile_setup in double, once per length -- or the caller's rows
     std::vector<double> xt((size_t)nq * DCP_F64_XSTRIDE, 0.0);
     std::map<uint32_t, size_t> first_of_len;
     uint32_t lmax = 0;
@@ -1442,6 +1464,11 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     {
         uint32_t const L = c->seq_len[q_begin + q];
         lmax = std::max(lmax, L);
+        if (xt_given)
+        {
+            std::memcpy(&xt[(size_t)q * DCP_F64_XSTRIDE], &c->xt64[(size_t)(q_begin + q) * DCP_NXTRANS], sizeof(double) * DCP_NXTRANS);
+            continue;
+        }
         auto it = first_of_len.find(L);
         if (it != first_of_len.end())
         {
@@ -1500,6 +1527,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     bool const thr_unset = (thr_bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
     a.lrt_threshold = thr_unset ? (double)prm->lrt_threshold : c->lrt_threshold64;
     bool const qlane = prm->kernel == 4;
+    bool const redo = prm->multi_hits != 0 || xt_given;
     dcp_f64_qlane_args qa{};
     unsigned ql_blocks = 0;
     if (qlane)
@@ -1530,13 +1558,14 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // qorder and xt leave scope
         if (!F.d_task.p) HIP_TRY(c, F.d_task.alloc(1));
         if (!F.d_redo_n.p) HIP_TRY(c, F.d_redo_n.alloc(5));
-        // a redo list per launch group; uni-hit scans have no feedback and no lists
+        // a redo list per launch group; uni-hit scans have no feedback and no lists (explicit transitions may carry
+        // E -> B / J -> B feedback whatever the flag says)
         uint64_t redo_total = 0;
         for (int g = 0; g < 4; ++g)
         {
             uint64_t const pairs = (uint64_t)(F.group_first[g + 1] - F.group_first[g]) * nq;
             qa.redo_first[g] = (unsigned)redo_total;
-            qa.redo_cap[g] = prm->multi_hits ? (unsigned)std::min<uint64_t>(pairs, c->redo_cap_limit) : 0u;
+            qa.redo_cap[g] = redo ? (unsigned)std::min<uint64_t>(pairs, c->redo_cap_limit) : 0u;
             redo_total += qa.redo_cap[g];
         }
         if (redo_total > 0xffffffffull)
@@ -1570,7 +1599,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         HIP_TRY(c, hipGetLastError());
         ++launches;
         // the pairs whose B(j) was not B0(j): the row sweep over each group's list, right behind
-        for (int g = 0; g < 4 && prm->multi_hits; ++g)
+        for (int g = 0; g < 4 && redo; ++g)
         {
             if (qa.redo_cap[g] == 0) continue;
             dcp_f64_pairs_args pa{};
@@ -1614,7 +1643,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     c->last_kernel_variant = qlane ? 4 : 1;
     c->last_prm = *prm;
     c->last_redo_pairs = 0;
-    F.redo_pending = qlane && prm->multi_hits;
+    F.redo_pending = qlane && redo;
     c->last_overlapped = false;
     c->have_scores = false;
     c->last_f64 = true;
@@ -1637,6 +1666,8 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     // that one (its overflow re-run included), so nothing of it is silently half done.
     if (c->redo_pending || c->ring_check_pending)
         if (int rc = finish_scan(c)) return rc;
+    if (!c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
 
     if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
 
@@ -2401,6 +2432,8 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     for (unsigned h = 0; h < nhits; ++h)
         if (hits[h].seq_idx >= c->nseqs || hits[h].profile_idx >= c->nprof)
             return c->fail(DCP_EINVAL, "hit %u is outside the resident batch / DB", h);
+    if (!c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
     if (int rc = ensure_xtrans(c, multi_hits, hmmer3_compat)) return rc;
     if (int rc = ensure_rowsweep_layout(c)) return rc;
 
@@ -2686,6 +2719,13 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
                 acc += need[h];
                 soff[i + 1] = soff[i] + cap[h];
                 pairs[i] = dcp_f64_pair{hits[h].seq_idx, slot[hits[h].profile_idx]};
+                gfirst[grp[h] + 1] = i + 1u;
+                if (grp[h] == 3) seg_lmax = std::max(seg_lmax, L);
+                if (!c->xt64.empty()) // dcp_gpu_seqs_set_xtrans64: the hit's sequence's row, the flags ignored
+                {
+                    std::memcpy(&xt[(size_t)i * DCP_F64_XSTRIDE], &c->xt64[(size_t)hits[h].seq_idx * DCP_NXTRANS], sizeof(double) * DCP_NXTRANS);
+                    continue;
+                }
                 auto it = xt_of_len.find(L);
                 if (it == xt_of_len.end())
                 {
@@ -2694,8 +2734,6 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
                     it = xt_of_len.emplace(L, std::move(x)).first;
                 }
                 std::memcpy(&xt[(size_t)i * DCP_F64_XSTRIDE], it->second.data(), sizeof(double) * DCP_NXTRANS);
-                gfirst[grp[h] + 1] = i + 1u;
-                if (grp[h] == 3) seg_lmax = std::max(seg_lmax, L);
             }
             for (int g = 1; g < 5; ++g)
                 if (gfirst[g] < gfirst[g - 1]) gfirst[g] = gfirst[g - 1];

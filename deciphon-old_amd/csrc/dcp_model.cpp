@@ -565,6 +565,63 @@ dcp_profile *dcp_profile_sample64(char const *accession, unsigned seed, unsigned
     return dcp_profile_new64(accession, M, entry_dist, epsilon, null_lp, match.data(), trans.data(), nullptr, rc);
 }
 
+dcp_profile *dcp_profile_from_parts64(char const *accession, unsigned core_size, int entry_dist, double epsilon,
+                                      char const *consensus, double const *trans8, double const *null_dist,
+                                      double const *insert_dist, double const *match_dist, int *rc)
+{
+    auto fail = [&](int code) -> dcp_profile * {
+        if (rc) *rc = code;
+        return nullptr;
+    };
+    if (core_size == 0 || core_size > DCP_CORE_SIZE_MAX) return fail(DCP_EINVAL);
+    if (!trans8 || !null_dist || !insert_dist || !match_dist) return fail(DCP_EINVAL);
+    if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(DCP_EINVAL);
+    dcp_profile *p = new (std::nothrow) dcp_profile();
+    if (!p) return fail(DCP_ENOMEM);
+    unsigned const M = core_size;
+    std::memset(p->accession, 0, sizeof p->accession);
+    if (accession) std::strncpy(p->accession, accession, sizeof p->accession - 1);
+    p->core_size = M;
+    p->entry_dist = entry_dist;
+    p->f64 = true;
+    p->epsilon64 = epsilon;
+    p->epsilon = (float)epsilon;
+    p->consensus.assign(M + 1, '\0');
+    bool ended = !consensus;
+    for (unsigned i = 0; i < M; ++i)
+    {
+        if (!ended && consensus[i] == '\0') ended = true;
+        p->consensus[i] = ended ? '-' : consensus[i];
+    }
+    p->trans8_64.assign(trans8, trans8 + (size_t)8 * M);
+    p->match_dist64.assign(match_dist, match_dist + (size_t)M * DCP_NDIST);
+    p->null_dist64.assign(null_dist, null_dist + DCP_NDIST);
+    p->insert_dist64.assign(insert_dist, insert_dist + DCP_NDIST);
+    // a NaN anywhere would poison every max: reject it here rather than on the device
+    auto has_nan = [](std::vector<double> const &v) {
+        for (double x : v)
+            if (x != x) return true;
+        return false;
+    };
+    if (has_nan(p->trans8_64) || has_nan(p->match_dist64) || has_nan(p->null_dist64) || has_nan(p->insert_dist64))
+    {
+        delete p;
+        return fail(DCP_EINVAL);
+    }
+    // the float parts: the double values rounded once, as dcp_profile_new64 leaves them
+    p->trans8.assign(p->trans8_64.begin(), p->trans8_64.end());
+    p->match_dist.assign(p->match_dist64.begin(), p->match_dist64.end());
+    for (int i = 0; i < DCP_NDIST; ++i)
+    {
+        p->null_dist[i] = (float)p->null_dist64[i];
+        p->insert_dist[i] = (float)p->insert_dist64[i];
+    }
+    if (rc) *rc = DCP_OK;
+    return p;
+}
+
+void dcp_lprob_normalize64(unsigned n, double *lprobs) { lp_normalize64(n, lprobs); }
+
 int dcp_profile_precision(dcp_profile const *p) { return p && p->f64 ? 64 : 32; }
 double dcp_profile_epsilon64(dcp_profile const *p) { return p->f64 ? p->epsilon64 : (double)p->epsilon; }
 double const *dcp_profile_trans8_64(dcp_profile const *p) { return p->f64 ? p->trans8_64.data() : nullptr; }

@@ -30,7 +30,7 @@
 enum hdr_wire
 {
     W_UINT,  /* MessagePack unsigned */
-    W_F32,   /* float32 */
+    W_F32,   /* the build's imm_float: float32, or float64 in the double build */
     W_ABC,   /* imm_abc value (map) */
     W_SIZES, /* 1darray of uint32: bytes of every profile */
 };
@@ -52,7 +52,7 @@ enum hdr_row
 struct hdr_values
 {
     unsigned magic, typeid_, float_size, entry_dist;
-    float epsilon;
+    imm_float epsilon;
     struct imm_abc *nuclt, *amino; /* only the rows W_ABC touch them */
     struct db_reader *reader;      /* W_SIZES fills nprofiles / profile_sizes */
     unsigned want_typeid;
@@ -99,7 +99,7 @@ static enum rc hdr_read(struct lip_file *file, struct hdr_values *v, enum hdr_ro
         if (got) switch (hdr_schema[r].wire)
             {
             case W_UINT: got = lip_read_unsigned(file, slot); break;
-            case W_F32: got = lip_read_f32(file, slot); break;
+            case W_F32: got = dcph_read_float(file, slot); break;
             case W_ABC: got = imm_abc_unpack(r == H_NUCLT ? v->nuclt : v->amino, file) == IMM_OK; break;
             case W_SIZES:
             {
@@ -136,7 +136,7 @@ static enum rc hdr_write(struct lip_file *out, struct hdr_values const *v, enum 
     if (ok) switch (hdr_schema[r].wire)
         {
         case W_UINT: ok = lip_write_uint(out, *(unsigned const *)slot); break;
-        case W_F32: ok = lip_write_f32(out, *(float const *)slot); break;
+        case W_F32: ok = dcph_write_float(out, *(imm_float const *)slot); break;
         case W_ABC: ok = imm_abc_pack(r == H_NUCLT ? v->nuclt : v->amino, out) == IMM_OK; break;
         case W_SIZES: ok = false; break; /* written by db_writer_close from the sizes it collected */
         }

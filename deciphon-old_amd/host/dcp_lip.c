@@ -109,6 +109,9 @@ static unsigned elem_bytes(unsigned type)
     case LIP_1DARRAY_UINT16: return 2;
     case LIP_1DARRAY_UINT32: return 4;
     case LIP_1DARRAY_F32: return 4;
+#ifdef IMM_DOUBLE_PRECISION
+    case LIP_1DARRAY_F64: return 8;
+#endif
     default: return 0;
     }
 }
@@ -166,6 +169,31 @@ bool lip_write_1darray_f32_data(struct lip_file *f, unsigned size, float const *
 }
 
 bool lip_write_1darray_u8_data(struct lip_file *f, unsigned size, uint8_t const *data) { return put(f, data, size); }
+
+#ifdef IMM_DOUBLE_PRECISION
+bool lip_write_f64(struct lip_file *f, double val)
+{
+    uint64_t bits;
+    memcpy(&bits, &val, 8);
+    return put_tag(f, 0xcb) && put_be(f, bits, 8);
+}
+
+bool lip_write_1darray_f64_data(struct lip_file *f, unsigned size, double const *data)
+{
+    uint64_t chunk[128];
+    unsigned char const *src = (unsigned char const *)data;
+    while (size)
+    {
+        unsigned const n = size < 128u ? size : 128u;
+        memcpy(chunk, src, (size_t)n * 8);
+        for (unsigned i = 0; i < n; ++i)
+            chunk[i] = __builtin_bswap64(chunk[i]);
+        if (!put(f, chunk, (size_t)n * 8)) return false;
+        src += (size_t)n * 8, size -= n;
+    }
+    return true;
+}
+#endif
 
 /* ---- readers ------------------------------------------------------------------------------------ */
 static bool get_tag(struct lip_file *f, unsigned char *tag) { return get(f, tag, 1); }
@@ -319,6 +347,46 @@ bool lip_read_1darray_f32_data(struct lip_file *f, unsigned size, float *data)
 }
 
 bool lip_read_1darray_u8_data(struct lip_file *f, unsigned size, uint8_t *data) { return get(f, data, size); }
+
+#ifdef IMM_DOUBLE_PRECISION
+/* a float64; a float32 of another writer widens exactly */
+bool lip_read_f64(struct lip_file *f, double *val)
+{
+    unsigned char tag;
+    uint64_t raw;
+    if (!get_tag(f, &tag)) return false;
+    if (tag == 0xcb)
+    {
+        if (!get_be(f, &raw, 8)) return false;
+        memcpy(val, &raw, 8);
+        return true;
+    }
+    if (tag == 0xca)
+    {
+        if (!get_be(f, &raw, 4)) return false;
+        uint32_t const bits = (uint32_t)raw;
+        float v;
+        memcpy(&v, &bits, 4);
+        *val = v;
+        return true;
+    }
+    return fail(f);
+}
+
+bool lip_read_1darray_f64_data(struct lip_file *f, unsigned size, double *data)
+{
+    if (!get(f, data, (size_t)size * 8)) return false;
+    unsigned char *p = (unsigned char *)data;
+    for (unsigned i = 0; i < size; ++i, p += 8)
+    {
+        uint64_t v;
+        memcpy(&v, p, 8);
+        v = __builtin_bswap64(v);
+        memcpy(p, &v, 8);
+    }
+    return true;
+}
+#endif
 
 /* Skip one object of any type.  Iterative over a counter of pending objects, so a hostile depth
  * cannot exhaust the stack; payloads are skipped with fseek. */

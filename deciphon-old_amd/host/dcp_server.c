@@ -341,7 +341,7 @@ static enum rc thread_prepare(struct scan_thread *t, int tid)
         if (reader->profile_sizes && end != reader->partition_offset[t->id + 1])
             rc = fail(RC_EPARSE, "partition %u: %u profiles do not end at the partition's end offset", t->id, n);
     }
-    if (!rc && dcp_gpu_db_upload(t->gpu, t->impls, n, 0)) rc = fail(RC_EFAIL, "%s", dcp_gpu_last_error(t->gpu));
+    if (!rc && dcph_db_upload(t->gpu, t->impls, n)) rc = fail(RC_EFAIL, "%s", dcp_gpu_last_error(t->gpu));
     if (rc) return rc;
     t->db_resident = true;
     return RC_OK;
@@ -356,15 +356,15 @@ static enum rc profile_view(struct scan_thread *t, unsigned i, struct protein_pr
     view->impl = impl; /* borrowed: never profile_del() a view */
     view->core_size = dcp_profile_core_size(impl);
     memcpy(view->consensus, dcp_profile_consensus(impl), (size_t)view->core_size + 1);
-    memcpy(view->null.ndist.nucltp.lprobs, dcp_profile_null_dist(impl), sizeof view->null.ndist.nucltp.lprobs);
-    memcpy(view->null.ndist.codonm.lprobs, dcp_profile_null_dist(impl) + IMM_NUCLT_SIZE,
+    memcpy(view->null.ndist.nucltp.lprobs, dcph_profile_null_dist(impl), sizeof view->null.ndist.nucltp.lprobs);
+    memcpy(view->null.ndist.codonm.lprobs, dcph_profile_null_dist(impl) + IMM_NUCLT_SIZE,
            sizeof view->null.ndist.codonm.lprobs);
-    memcpy(view->alt.insert_ndist.nucltp.lprobs, dcp_profile_insert_dist(impl), sizeof view->alt.insert_ndist.nucltp.lprobs);
-    memcpy(view->alt.insert_ndist.codonm.lprobs, dcp_profile_insert_dist(impl) + IMM_NUCLT_SIZE,
+    memcpy(view->alt.insert_ndist.nucltp.lprobs, dcph_profile_insert_dist(impl), sizeof view->alt.insert_ndist.nucltp.lprobs);
+    memcpy(view->alt.insert_ndist.codonm.lprobs, dcph_profile_insert_dist(impl) + IMM_NUCLT_SIZE,
            sizeof view->alt.insert_ndist.codonm.lprobs);
     view->alt.match_ndists = malloc((size_t)view->core_size * sizeof *view->alt.match_ndists);
     if (!view->alt.match_ndists) return fail(RC_ENOMEM, "alloc nuclt dists");
-    float const *md = dcp_profile_match_dist(impl);
+    imm_float const *md = dcph_profile_match_dist(impl);
     for (unsigned k = 0; k < view->core_size; ++k)
     {
         struct nuclt_dist *d = view->alt.match_ndists + k;
@@ -387,7 +387,7 @@ static enum rc profile_view(struct scan_thread *t, unsigned i, struct protein_pr
 struct batch_result
 {
     unsigned nhits;
-    struct dcp_hit *hits;
+    dcph_hit *hits;
     struct dcp_step *steps;
     uint32_t *soff;
 };
@@ -449,6 +449,11 @@ static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const
     free(ids);
     free(off);
     struct dcp_scan_params prm = {t->multi_hits, t->hmmer3_compat, (float)t->lrt_threshold, 0, 0};
+#ifdef IMM_DOUBLE_PRECISION
+    /* the device filter of a double DB compares in double, like xmath_lrt's imm_float: the caller's threshold as it is
+     * (a NaN -- the call's "unset" -- keeps no pair either way) */
+    if (!rc && (drc = dcp_gpu_set_lrt_threshold64(t->gpu, t->lrt_threshold))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+#else
     if ((double)prm.lrt_threshold != t->lrt_threshold && !rc)
     {
         /* the device filter compares in float32 like xmath_lrt's imm_float (scan_thread.c:121-123); a
@@ -456,6 +461,7 @@ static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const
          * lower float and re-apply the caller's double when the rows are written */
         prm.lrt_threshold = nextafterf(prm.lrt_threshold, -INFINITY);
     }
+#endif
     if (!rc && (drc = dcp_gpu_scan(t->gpu, &prm))) rc = fail((enum rc)drc, "failed to run viterbi: %s", dcp_gpu_last_error(t->gpu));
     stat_add(&g_stats.submit_s, stat_now() - t_loaded);
     return rc;
@@ -473,13 +479,13 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
     /* the LRT filter ran on the device: only hits come back, sorted by (seq, profile) */
     enum rc rc = RC_OK;
     unsigned nhits = 0;
-    drc = dcp_gpu_fetch_hits(t->gpu, NULL, 0, &nhits); /* count first */
+    drc = dcph_fetch_hits(t->gpu, NULL, 0, &nhits); /* count first */
     if (drc && drc != DCP_ENOMEM) return fail((enum rc)drc, "fetch hits");
     if ((uint64_t)nhits > (uint64_t)nprofiles * nseqs) return fail(RC_EFAIL, "more hits than pairs");
     if (nhits == 0) return RC_OK;
     res->hits = malloc((size_t)nhits * sizeof *res->hits);
     if (!res->hits) rc = fail(RC_ENOMEM, "alloc hits");
-    if (!rc && (drc = dcp_gpu_fetch_hits(t->gpu, res->hits, nhits, &nhits))) rc = fail((enum rc)drc, "fetch hits");
+    if (!rc && (drc = dcph_fetch_hits(t->gpu, res->hits, nhits, &nhits))) rc = fail((enum rc)drc, "fetch hits");
     uint64_t cap = 0;
     for (unsigned h = 0; !rc && h < nhits; ++h)
         cap += 2 * (uint64_t)seqs[res->hits[h].seq_idx].size +
@@ -491,8 +497,8 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
         res->soff = calloc((size_t)nhits + 1, sizeof *res->soff);
         if (!res->steps || !res->soff) rc = fail(RC_ENOMEM, "alloc paths");
     }
-    if (!rc && (drc = dcp_gpu_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
-                                          (unsigned)cap, res->soff, NULL)) == DCP_ENOMEM &&
+    if (!rc && (drc = dcph_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
+                                       (unsigned)cap, res->soff, NULL)) == DCP_ENOMEM &&
         res->soff[nhits] > cap)
     {
         /* 2L + 2M + 16 per hit is an estimate: multi-domain paths through long delete runs are longer.  Again at the
@@ -503,8 +509,8 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
         else
         {
             res->steps = more;
-            drc = dcp_gpu_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
-                                      (unsigned)cap, res->soff, NULL);
+            drc = dcph_trace_paths(t->gpu, res->hits, nhits, t->multi_hits, t->hmmer3_compat, 0, res->steps,
+                                   (unsigned)cap, res->soff, NULL);
         }
     }
     if (!rc && drc) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
@@ -534,7 +540,7 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
 {
     enum rc rc = RC_OK;
     unsigned const nhits = res->nhits;
-    struct dcp_hit const *hits = res->hits;
+    dcph_hit const *hits = res->hits;
     if (nhits)
     {
         /* Product rows: one per hit, each formatted into its own memory stream -- every emitting step of a
@@ -564,7 +570,7 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
                 cur = shared;
                 if (cur) continue;
                 unsigned const q = hits[h].seq_idx;
-                imm_float const lrt = xmath_lrt_f32(hits[h].null_loglik, hits[h].alt_loglik);
+                imm_float const lrt = xmath_lrt(hits[h].null_loglik, hits[h].alt_loglik);
                 if (!imm_lprob_is_finite(lrt) || lrt < t->lrt_threshold) continue; /* scan_thread.c:123 */
                 struct protein_profile view;
                 struct imm_path path = {0};

@@ -131,7 +131,7 @@ void imm_lprob_sample(struct imm_rnd *rnd, unsigned len, imm_float *lprobs)
         lprobs[i] = (imm_float)log(imm_rnd_dbl(rnd));
 }
 
-void imm_lprob_normalize(unsigned len, imm_float *lprobs) { dcp_lprob_normalize(len, lprobs); }
+void imm_lprob_normalize(unsigned len, imm_float *lprobs) { dcph_lprob_normalize(len, lprobs); }
 
 struct imm_frame_epsilon imm_frame_epsilon(imm_float epsilon)
 {
@@ -288,7 +288,7 @@ static enum imm_rc viterbi_locked(struct imm_dp const *dp, struct imm_task *task
     {
         dcp_profile *one[1] = {prof->impl};
         g_ctx_db = NULL;
-        if (dcp_gpu_db_upload(ctx, one, 1, 0))
+        if (dcph_db_upload(ctx, one, 1))
         {
             free(ids);
             return IMM_FAILURE;
@@ -300,19 +300,19 @@ static enum imm_rc viterbi_locked(struct imm_dp const *dp, struct imm_task *task
     free(ids);
     if (drc) return IMM_FAILURE;
     /* the transitions the profile holds NOW: protein_profile_setup's, or the LOG1 defaults */
-    if (dcp_gpu_seqs_set_xtrans(ctx, prof->xtrans, 1)) return IMM_FAILURE;
+    if (dcph_seqs_set_xtrans(ctx, prof->xtrans, 1)) return IMM_FAILURE;
     struct dcp_scan_params prm = {1, 0, 10.0f, 1, 1 /* row sweep */};
     if (dcp_gpu_scan(ctx, &prm) || dcp_gpu_sync(ctx)) return IMM_FAILURE;
-    float nul = NAN, alt = NAN;
-    if (dcp_gpu_fetch_scores(ctx, &nul, &alt)) return IMM_FAILURE;
+    imm_float nul = NAN, alt = NAN;
+    if (dcph_fetch_scores(ctx, &nul, &alt)) return IMM_FAILURE;
 
-    struct dcp_hit pair = {0, 0, nul, alt};
+    dcph_hit pair = {0, 0, nul, alt};
     unsigned cap = 2 * seq->size + 2 * prof->core_size + 16;
     struct dcp_step *steps = malloc((size_t)cap * sizeof *steps);
     if (!steps) return IMM_FAILURE;
     uint32_t soff[2] = {0, 0};
-    float traced = NAN;
-    drc = dcp_gpu_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
+    imm_float traced = NAN;
+    drc = dcph_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
     if (drc == DCP_ENOMEM && soff[1] > cap)
     {
         /* a multi-domain path can be longer than the estimate: again at its true count */
@@ -324,7 +324,7 @@ static enum imm_rc viterbi_locked(struct imm_dp const *dp, struct imm_task *task
             return IMM_FAILURE;
         }
         steps = more;
-        drc = dcp_gpu_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
+        drc = dcph_trace_paths(ctx, &pair, 1, 1, 0, dp->null_model, steps, cap, soff, &traced);
     }
     enum imm_rc out = IMM_FAILURE;
     if (!drc && !dcp_host_path_assign(&prod->path, steps, soff[1]))
@@ -382,7 +382,7 @@ void imm_dp_write_dot(struct imm_dp const *dp, FILE *fp, imm_state_name *name)
     fprintf(fp, "digraph hmm {\n");
     if (p && p->impl && !dp->null_model)
     {
-        float const *t8 = dcp_profile_trans8(p->impl);
+        imm_float const *t8 = dcph_profile_trans8(p->impl);
         unsigned const M = p->core_size;
         char a[IMM_STATE_NAME_SIZE], b[IMM_STATE_NAME_SIZE];
         for (unsigned k = 0; k < M; ++k)
@@ -507,14 +507,14 @@ int profile_typeid(struct profile const *prof) { return prof->vtable.typeid; }
 struct imm_dp const *profile_null_dp(struct profile const *prof) { return prof->vtable.null_dp(prof); }
 struct imm_dp const *profile_alt_dp(struct profile const *prof) { return prof->vtable.alt_dp(prof); }
 
-/* ---- nuclt_dist <-> the compact profile's 129-float rows ------------------------------------------------ */
-static void ndist_from_row(struct nuclt_dist *d, float const row[DCP_NDIST])
+/* ---- nuclt_dist <-> the compact profile's 129-value rows ------------------------------------------------ */
+static void ndist_from_row(struct nuclt_dist *d, imm_float const row[DCP_NDIST])
 {
     memcpy(d->nucltp.lprobs, row, sizeof d->nucltp.lprobs);
     memcpy(d->codonm.lprobs, row + IMM_NUCLT_SIZE, sizeof d->codonm.lprobs);
 }
 
-static void ndist_to_row(struct nuclt_dist const *d, float row[DCP_NDIST])
+static void ndist_to_row(struct nuclt_dist const *d, imm_float row[DCP_NDIST])
 {
     memcpy(row, d->nucltp.lprobs, sizeof d->nucltp.lprobs);
     memcpy(row + IMM_NUCLT_SIZE, d->codonm.lprobs, sizeof d->codonm.lprobs);
@@ -595,8 +595,8 @@ enum rc protein_profile_setup(struct protein_profile *prof, unsigned seq_size, b
 {
     /* the 13 values protein_profile.c:155-216 computes, written through imm_dp_trans_idx /
      * imm_dp_change_trans like there */
-    float xt[DCP_NXTRANS];
-    if (dcp_xtrans(seq_size, multi_hits, hmmer3_compat, xt)) return fail(RC_EINVAL, "sequence cannot be empty");
+    imm_float xt[DCP_NXTRANS];
+    if (dcph_xtrans(seq_size, multi_hits, hmmer3_compat, xt)) return fail(RC_EINVAL, "sequence cannot be empty");
     struct imm_dp *dp = &prof->null.dp;
     unsigned const R = prof->null.R;
     imm_dp_change_trans(dp, imm_dp_trans_idx(dp, R, R), xt[DCP_HOST_X_RR]);
@@ -638,9 +638,9 @@ enum rc dcp_host_adopt(struct protein_profile *p, dcp_profile *impl, int rc)
     p->impl = impl;
     p->core_size = M;
     memcpy(p->consensus, dcp_profile_consensus(impl), (size_t)M + 1);
-    ndist_from_row(&p->null.ndist, dcp_profile_null_dist(impl));
-    ndist_from_row(&p->alt.insert_ndist, dcp_profile_insert_dist(impl));
-    float const *md = dcp_profile_match_dist(impl);
+    ndist_from_row(&p->null.ndist, dcph_profile_null_dist(impl));
+    ndist_from_row(&p->alt.insert_ndist, dcph_profile_insert_dist(impl));
+    imm_float const *md = dcph_profile_match_dist(impl);
     for (unsigned k = 0; k < M; ++k)
     {
         nuclt_dist_init(nd + k, p->code->nuclt);
@@ -660,17 +660,17 @@ enum rc protein_profile_absorb(struct protein_profile *p, struct protein_model c
                                         m->alt.node_idx == UINT_MAX ? 0 : m->alt.node_idx, m->core_size,
                                         m->alt.trans_idx == UINT_MAX ? 0 : m->alt.trans_idx, m->core_size + 1);
     int rc = 0;
-    dcp_profile *impl = dcp_profile_new(p->super.accession, m->core_size, (int)m->cfg.entry_dist, m->cfg.epsilon,
-                                        m->null.lprobs, &m->alt.match_lprobs[0][0], &m->alt.trans[0].data[0],
-                                        m->consensus, &rc);
+    dcp_profile *impl = dcph_profile_new(p->super.accession, m->core_size, (int)m->cfg.entry_dist, m->cfg.epsilon,
+                                         m->null.lprobs, &m->alt.match_lprobs[0][0], &m->alt.trans[0].data[0],
+                                         m->consensus, &rc);
     return dcp_host_adopt(p, impl, rc);
 }
 
 enum rc protein_profile_sample(struct protein_profile *p, unsigned seed, unsigned core_size)
 {
     int rc = 0;
-    dcp_profile *impl = dcp_profile_sample(p->super.accession, seed, core_size, (int)p->cfg.entry_dist,
-                                           p->cfg.epsilon, &rc);
+    dcp_profile *impl = dcph_profile_sample(p->super.accession, seed, core_size, (int)p->cfg.entry_dist,
+                                            p->cfg.epsilon, &rc);
     return dcp_host_adopt(p, impl, rc);
 }
 
@@ -678,8 +678,8 @@ enum rc protein_profile_from_params(struct protein_profile *p, unsigned core_siz
                                     imm_float const *match_lprobs, imm_float const *trans)
 {
     int rc = 0;
-    dcp_profile *impl = dcp_profile_new(p->super.accession, core_size, (int)p->cfg.entry_dist, p->cfg.epsilon,
-                                        null_lprobs, match_lprobs, trans, NULL, &rc);
+    dcp_profile *impl = dcph_profile_new(p->super.accession, core_size, (int)p->cfg.entry_dist, p->cfg.epsilon,
+                                         null_lprobs, match_lprobs, trans, NULL, &rc);
     return dcp_host_adopt(p, impl, rc);
 }
 
@@ -711,8 +711,8 @@ void protein_profile_write_dot(struct protein_profile const *p, FILE *fp)
  * Key order and value types are the reference's.  The two imm_dp values are imm's own serialisation
  * there (its layout lives in the absent imm library); this library writes its own dp value
  *     map(3) {"fmt": "dcp-dp-1", "xtrans": 1darray f32 [13 | 1], "trans8": 1darray f32 [8 * M | 0]}
- * (alt: all 13 specials + the core transitions; null: RR alone) and on reading accepts exactly
- * that.  A dp value in any other layout -- a file pressed by the reference -- is skipped as one
+ * (alt: all 13 specials + the core transitions; null: RR alone; the double build writes both arrays, like
+ * the nuclt_dist blocks, as 1darray f64) and on reading accepts exactly that.  A dp value in any other layout -- a file pressed by the reference -- is skipped as one
  * MessagePack object, everything else of the profile is still parsed and validated, and the
  * unpack ends with RC_EPARSE "transitions live in imm's dp serialisation: unsupported". */
 static char const kDpFormat[] = "dcp-dp-1";
@@ -725,10 +725,10 @@ enum imm_rc imm_dp_pack(struct imm_dp const *dp, struct lip_file *file)
     bool const alt = p && !dp->null_model;
     unsigned const nx = alt ? DCP_NXTRANS : (p ? 1u : 0u);
     unsigned const nt = alt && p->impl ? 8u * p->core_size : 0u;
-    if (!lip_write_cstr(file, "xtrans") || !lip_write_1darray_size_type(file, nx, LIP_1DARRAY_F32)) return IMM_FAILURE;
-    if (nx && !lip_write_1darray_f32_data(file, nx, p->xtrans)) return IMM_FAILURE;
-    if (!lip_write_cstr(file, "trans8") || !lip_write_1darray_size_type(file, nt, LIP_1DARRAY_F32)) return IMM_FAILURE;
-    if (nt && !lip_write_1darray_f32_data(file, nt, dcp_profile_trans8(p->impl))) return IMM_FAILURE;
+    if (!lip_write_cstr(file, "xtrans") || !lip_write_1darray_size_type(file, nx, DCPH_1DARRAY_FLOAT)) return IMM_FAILURE;
+    if (nx && !dcph_write_1darray_float_data(file, nx, p->xtrans)) return IMM_FAILURE;
+    if (!lip_write_cstr(file, "trans8") || !lip_write_1darray_size_type(file, nt, DCPH_1DARRAY_FLOAT)) return IMM_FAILURE;
+    if (nt && !dcph_write_1darray_float_data(file, nt, dcph_profile_trans8(p->impl))) return IMM_FAILURE;
     return IMM_OK;
 }
 
@@ -736,8 +736,8 @@ struct dp_blob
 {
     bool foreign;
     unsigned nx, nt;
-    float xtrans[DCP_NXTRANS];
-    float *trans8;
+    imm_float xtrans[DCP_NXTRANS];
+    imm_float *trans8;
 };
 
 static enum imm_rc dp_blob_read(struct dp_blob *b, struct lip_file *file)
@@ -751,15 +751,15 @@ static enum imm_rc dp_blob_read(struct dp_blob *b, struct lip_file *file)
     {
         enum lip_1darray_type ty;
         if (!expect_map_key(file, "xtrans") || !lip_read_1darray_size_type(file, &b->nx, &ty) ||
-            ty != LIP_1DARRAY_F32 || b->nx > DCP_NXTRANS || !lip_read_1darray_f32_data(file, b->nx, b->xtrans))
+            ty != DCPH_1DARRAY_FLOAT || b->nx > DCP_NXTRANS || !dcph_read_1darray_float_data(file, b->nx, b->xtrans))
             return IMM_FAILURE;
         if (!expect_map_key(file, "trans8") || !lip_read_1darray_size_type(file, &b->nt, &ty) ||
-            ty != LIP_1DARRAY_F32 || b->nt > 8u * PROTEIN_MODEL_CORE_SIZE_MAX)
+            ty != DCPH_1DARRAY_FLOAT || b->nt > 8u * PROTEIN_MODEL_CORE_SIZE_MAX)
             return IMM_FAILURE;
         if (b->nt)
         {
-            b->trans8 = malloc((size_t)b->nt * sizeof(float));
-            if (!b->trans8 || !lip_read_1darray_f32_data(file, b->nt, b->trans8))
+            b->trans8 = malloc((size_t)b->nt * sizeof *b->trans8);
+            if (!b->trans8 || !dcph_read_1darray_float_data(file, b->nt, b->trans8))
             {
                 free(b->trans8);
                 b->trans8 = NULL;
@@ -812,7 +812,7 @@ enum rc protein_profile_unpack(struct protein_profile *p, struct lip_file *file)
         return fail(file->error ? RC_EIO : RC_EFAIL, "read alt dp");
     }
     enum rc rc = RC_OK;
-    float *rows = NULL;
+    imm_float *rows = NULL;
     char consensus[PROTEIN_MODEL_CORE_SIZE_MAX + 1];
 
     if (!expect_map_key(file, "core_size") || !lip_read_unsigned(file, &size))
@@ -837,7 +837,7 @@ enum rc protein_profile_unpack(struct protein_profile *p, struct lip_file *file)
         rc = read_state_idx(file, keys[i], &st[i]);
     if (rc) goto done;
 
-    rows = malloc(((size_t)M + 2) * DCP_NDIST * sizeof(float)); /* null, insert, match[M] */
+    rows = malloc(((size_t)M + 2) * DCP_NDIST * sizeof *rows); /* null, insert, match[M] */
     if (!rows)
     {
         rc = fail(RC_ENOMEM, "alloc nuclt dists");
@@ -892,8 +892,8 @@ enum rc protein_profile_unpack(struct protein_profile *p, struct lip_file *file)
         goto done;
     }
     int drc = 0;
-    dcp_profile *impl = dcp_profile_from_parts(prof->accession, M, (int)p->cfg.entry_dist, p->cfg.epsilon, consensus,
-                                               alt.trans8, rows, rows + DCP_NDIST, rows + 2 * DCP_NDIST, &drc);
+    dcp_profile *impl = dcph_profile_from_parts(prof->accession, M, (int)p->cfg.entry_dist, p->cfg.epsilon, consensus,
+                                                alt.trans8, rows, rows + DCP_NDIST, rows + 2 * DCP_NDIST, &drc);
     rc = dcp_host_adopt(p, impl, drc);
     if (rc) goto done;
     p->null.R = st[0];
@@ -987,18 +987,18 @@ enum imm_rc imm_abc_unpack(struct imm_abc *abc, struct lip_file *file)
 
 enum imm_rc imm_nuclt_lprob_pack(struct imm_nuclt_lprob const *nucltp, struct lip_file *file)
 {
-    return lip_write_1darray_size_type(file, IMM_NUCLT_SIZE, LIP_1DARRAY_F32) &&
-                   lip_write_1darray_f32_data(file, IMM_NUCLT_SIZE, nucltp->lprobs)
+    return lip_write_1darray_size_type(file, IMM_NUCLT_SIZE, DCPH_1DARRAY_FLOAT) &&
+                   dcph_write_1darray_float_data(file, IMM_NUCLT_SIZE, nucltp->lprobs)
                ? IMM_OK
                : IMM_FAILURE;
 }
 
-static enum imm_rc read_f32_block(struct lip_file *file, unsigned want, float *out)
+static enum imm_rc read_float_block(struct lip_file *file, unsigned want, imm_float *out)
 {
     unsigned n = 0;
     enum lip_1darray_type ty;
-    if (!lip_read_1darray_size_type(file, &n, &ty) || ty != LIP_1DARRAY_F32 || n != want) return IMM_FAILURE;
-    if (!lip_read_1darray_f32_data(file, n, out)) return IMM_FAILURE;
+    if (!lip_read_1darray_size_type(file, &n, &ty) || ty != DCPH_1DARRAY_FLOAT || n != want) return IMM_FAILURE;
+    if (!dcph_read_1darray_float_data(file, n, out)) return IMM_FAILURE;
     for (unsigned i = 0; i < n; ++i)
         if (isnan(out[i])) return IMM_FAILURE;
     return IMM_OK;
@@ -1006,21 +1006,21 @@ static enum imm_rc read_f32_block(struct lip_file *file, unsigned want, float *o
 
 enum imm_rc imm_nuclt_lprob_unpack(struct imm_nuclt_lprob *nucltp, struct lip_file *file)
 {
-    return read_f32_block(file, IMM_NUCLT_SIZE, nucltp->lprobs);
+    return read_float_block(file, IMM_NUCLT_SIZE, nucltp->lprobs);
 }
 
 enum imm_rc imm_codon_marg_pack(struct imm_codon_marg const *codonm, struct lip_file *file)
 {
     unsigned const n = sizeof codonm->lprobs / sizeof(imm_float);
-    return lip_write_1darray_size_type(file, n, LIP_1DARRAY_F32) &&
-                   lip_write_1darray_f32_data(file, n, &codonm->lprobs[0][0][0])
+    return lip_write_1darray_size_type(file, n, DCPH_1DARRAY_FLOAT) &&
+                   dcph_write_1darray_float_data(file, n, &codonm->lprobs[0][0][0])
                ? IMM_OK
                : IMM_FAILURE;
 }
 
 enum imm_rc imm_codon_marg_unpack(struct imm_codon_marg *codonm, struct lip_file *file)
 {
-    return read_f32_block(file, sizeof codonm->lprobs / sizeof(imm_float), &codonm->lprobs[0][0][0]);
+    return read_float_block(file, sizeof codonm->lprobs / sizeof(imm_float), &codonm->lprobs[0][0][0]);
 }
 
 /* ---- standard_profile: typed shell (src/model/standard_profile.c, standard_state.c:5-10) ------------------ */
@@ -1085,8 +1085,13 @@ enum rc protein_codec_next(struct protein_codec *codec, struct imm_seq const *se
 void protein_h3reader_init(struct protein_h3reader *reader, struct imm_amino const *amino,
                            struct imm_nuclt_code const *code, struct protein_cfg cfg, FILE *fp)
 {
-    reader->impl = dcp_h3reader_open_fp(fp, (int)cfg.entry_dist, cfg.epsilon);
-    dcp_swissprot_null_lprobs(reader->null_lprobs); /* protein_h3reader.c:79-103 */
+    /* the HMMER3 text parser and the Swiss-Prot background are float (dcp_h3reader_*): the double build takes
+     * their values widened, it does not parse the text again in double */
+    reader->impl = dcp_h3reader_open_fp(fp, (int)cfg.entry_dist, (float)cfg.epsilon);
+    float null32[IMM_AMINO_SIZE];
+    dcp_swissprot_null_lprobs(null32); /* protein_h3reader.c:79-103 */
+    for (int i = 0; i < IMM_AMINO_SIZE; ++i)
+        reader->null_lprobs[i] = null32[i];
     protein_model_init(&reader->model, amino, code, cfg, reader->null_lprobs);
     reader->name[0] = reader->acc[0] = '\0';
 }
@@ -1102,13 +1107,17 @@ enum rc protein_h3reader_next(struct protein_h3reader *reader)
     enum rc rc = protein_model_setup(&reader->model, prm.core_size);
     if (rc) return rc;
     struct protein_trans t;
-    memcpy(t.data, prm.trans, sizeof t.data);
+    imm_float lp[IMM_AMINO_SIZE];
+    for (int i = 0; i < PROTEIN_TRANS_SIZE; ++i)
+        t.data[i] = prm.trans[i];
     if ((rc = protein_model_add_trans(&reader->model, t))) return rc;
     for (unsigned k = 0; k < prm.core_size; ++k)
     {
-        if ((rc = protein_model_add_node(&reader->model, prm.match_lprobs + 20 * (size_t)k, prm.consensus[k])))
-            return rc;
-        memcpy(t.data, prm.trans + 7 * ((size_t)k + 1), sizeof t.data);
+        for (int i = 0; i < IMM_AMINO_SIZE; ++i)
+            lp[i] = prm.match_lprobs[20 * (size_t)k + i];
+        if ((rc = protein_model_add_node(&reader->model, lp, prm.consensus[k]))) return rc;
+        for (int i = 0; i < PROTEIN_TRANS_SIZE; ++i)
+            t.data[i] = prm.trans[7 * ((size_t)k + 1) + i];
         if ((rc = protein_model_add_trans(&reader->model, t))) return rc;
     }
     snprintf(reader->name, sizeof reader->name, "%s", prm.name);

@@ -202,6 +202,14 @@ dcp_profile *dcp_profile_new64(char const *accession, unsigned core_size, int en
                                char const *consensus, int *rc);
 dcp_profile *dcp_profile_sample64(char const *accession, unsigned seed, unsigned core_size, int entry_dist,
                                   double epsilon, int *rc);
+/* dcp_profile_from_parts in double: a double profile from its stored scan-time parts (what unpacking a profile of a
+ * double .dcp needs).  The float parts are those values rounded once, as dcp_profile_new64 leaves them.  NULL +
+ * DCP_EINVAL for core_size outside 1..4096, epsilon outside [0,1] or a NaN value. */
+dcp_profile *dcp_profile_from_parts64(char const *accession, unsigned core_size, int entry_dist, double epsilon,
+                                      char const *consensus, double const *trans8, double const *null_dist,
+                                      double const *insert_dist, double const *match_dist, int *rc);
+/* imm_lprob_normalize on doubles, as dcp_profile_sample64 applies it. */
+void dcp_lprob_normalize64(unsigned n, double *lprobs);
 /* 64 for a profile of the double build, 32 otherwise. */
 int dcp_profile_precision(dcp_profile const *);
 /* The double parts (same layouts as the float views below); NULL for a float profile. */
@@ -278,7 +286,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
  * query-lane kernel (4: the throughput path for batches of a few hundred queries and more; same bits); 2 and 3,
  * the float query-lane kernels, are DCP_EINVAL.  They leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
  * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table,
- * dcp_gpu_hit_buffer, explicit xtrans) return DCP_EINVAL on it. */
+ * dcp_gpu_hit_buffer, float explicit xtrans) return DCP_EINVAL on it. */
 int dcp_gpu_db_upload64(dcp_gpu_ctx *, dcp_profile *const *profiles, unsigned nprofiles);
 /* 32 or 64: the precision of the resident DB; 0 without one. */
 int dcp_gpu_db_precision(dcp_gpu_ctx const *);
@@ -313,6 +321,13 @@ unsigned dcp_gpu_nseqs(dcp_gpu_ctx const *);
  * it -- passes them here.  They stay in force until the next sequence upload; the scan flags
  * multi_hits / hmmer3_compat are then ignored.  NaN values are rejected (DCP_EINVAL). */
 int dcp_gpu_seqs_set_xtrans(dcp_gpu_ctx *, float const *xt, unsigned nseqs);
+/* The same for a double DB: xt [nseqs][13] in dcp_xtrans64 order.  Scans of a double DB (kernel 0, 1 or 4) and
+ * dcp_gpu_trace_paths64 then use these rows instead of deriving them from the lengths and the flags; with them the
+ * query-lane scan (4) keeps its redo lists whatever multi_hits says, since EB / EJ may be finite.  Until the next
+ * sequence upload; a NaN (tested by its bit pattern) is DCP_EINVAL.  One explicit set holds, the last one given, and
+ * it must fit the DB: float transitions before a scan of a double DB, or double ones before a scan or a
+ * dcp_gpu_trace_paths of a float DB, are DCP_EINVAL with a message -- they are never rounded or widened. */
+int dcp_gpu_seqs_set_xtrans64(dcp_gpu_ctx *, double const *xt, unsigned nseqs);
 
 struct dcp_scan_params
 {
@@ -485,7 +500,7 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *, struct dcp_hit const *hits, unsigned nhit
                         float *alt_out);
 /* dcp_gpu_trace_paths on a double DB (dcp_gpu_db_upload64), word for word, with dcp_hit64 records and double
  * log-likelihoods: the paths of the double build's recursion on the DB's own tables, special transitions
- * dcp_xtrans64 of each hit's length and the flags.  DCP_EINVAL on a float DB.
+ * dcp_xtrans64 of each hit's length and the flags (or the rows of dcp_gpu_seqs_set_xtrans64).  DCP_EINVAL on a float DB.
  * Device work: viterbi64_kernel's forward pass per launch group over the round's pairs parks every row's M, I, D
  * (24 bytes per column of the DB's padded width) and N, B, E, J, C (40 bytes) in the context's traceback work area,
  * at most 8 GiB per round of launches; one wavefront per hit walks back through it. */

@@ -92,8 +92,17 @@ static inline double xmath_lrt_f64(double null_loglik, double alt_loglik) { retu
 #endif
 
 /* ============================== imm subset ================================================== */
+/* The reference is compiled in float or, with IMM_DOUBLE_PRECISION, in double; so is this layer.  A program
+ * compiled with -DIMM_DOUBLE_PRECISION links libdeciphon_host_f64.so (the same sources built with that macro:
+ * profiles, databases and the device path in double -- dcp_gpu.h's "double build"), every other program
+ * libdeciphon_host.so.  The two are never mixed in one process: they export the same names. */
+#ifdef IMM_DOUBLE_PRECISION
+typedef double imm_float;
+#define IMM_FLOAT_BYTES 8
+#else
 typedef float imm_float; /* the reference's default build (IMM_FLOAT_BYTES == 4) */
 #define IMM_FLOAT_BYTES 4
+#endif
 #define IMM_STATE_NAME_SIZE 8
 #define IMM_AMINO_SIZE 20
 #define IMM_NUCLT_SIZE 4
@@ -105,7 +114,11 @@ enum imm_rc
     IMM_OK = 0,
     IMM_FAILURE = 1,
 };
+#ifdef IMM_DOUBLE_PRECISION
+#define imm_log(x) log(x)
+#else
 static inline imm_float imm_log(imm_float x) { return logf(x); }
+#endif
 static inline bool imm_lprob_is_nan(imm_float x) { return isnan(x); }
 static inline bool imm_lprob_is_finite(imm_float x) { return isfinite(x); }
 static inline bool imm_lprob_is_zero(imm_float x) { return isinf(x) && x < 0; }
@@ -328,6 +341,7 @@ enum lip_1darray_type
     LIP_1DARRAY_UINT16 = 0x12,
     LIP_1DARRAY_UINT32 = 0x13,
     LIP_1DARRAY_F32 = 0x21,
+    LIP_1DARRAY_F64 = 0x22, /* the double build's files */
 };
 bool lip_write_map_size(struct lip_file *file, unsigned size);
 bool lip_write_array_size(struct lip_file *file, unsigned size);
@@ -356,10 +370,14 @@ bool lip_read_unsigned(struct lip_file *file, unsigned *val);
 bool lip_read_int_as_int(struct lip_file *file, int *val);
 #ifndef __cplusplus
 #define lip_write_int(file, val) lip_write_uint((file), (uint64_t)(val))
+#ifndef IMM_DOUBLE_PRECISION /* (the double build writes and reads its float64 values inside the library) */
 #define lip_write_float(file, val) lip_write_f32((file), (float)(val))
+#endif
 #define lip_read_int(file, ptr)                                                                                      \
     _Generic((ptr), unsigned * : lip_read_unsigned, default : lip_read_int_as_int)((file), (void *)(ptr))
+#ifndef IMM_DOUBLE_PRECISION
 #define lip_read_float(file, ptr) lip_read_f32((file), (ptr))
+#endif
 #endif
 /* include/deciphon/core/expect.h */
 bool expect_map_size(struct lip_file *file, unsigned size);

@@ -5,12 +5,15 @@
  *
  *   gcc -std=gnu11 -O2 -I include profiles/host_scan_probe.c -o /tmp/host_scan_probe \
  *       -L deciphon-old_amd -ldeciphon_host -ldcp_hip -lm -fopenmp -Wl,-rpath,$PWD/deciphon-old_amd
- *   /tmp/host_scan_probe [nprofiles=2000] [nseqs=2000] [seq_len=1000] [batch=1000] [lrt_threshold=10] [batch_symbols=0]
+ *   /tmp/host_scan_probe [nprofiles=2000] [nseqs=2000] [seq_len=1000] [batch=1000] [lrt_threshold=10] [batch_symbols=0] [sizes=c3]
+ *   The double build: add -DIMM_DOUBLE_PRECISION and link -ldeciphon_host_f64 instead (same source; the first line
+ *   printed says which one ran).
  *   seq_len = 0: mixed lengths, log-uniform on 100 .. 10 000 nt (BASELINE configs[4]'s queries); batch_symbols: a device
  *   pass also closes at that many bases (scan_cfg.batch_symbols; the scan_run adapter asks for 2 Mi)
  *
  * Core sizes: the lognormal draw of BASELINE config C3 restated with this file's own generator (median 150,
- * sigma 0.6, clipped to 30..2000); sequences uniform over ACGT.  Prints one line per phase. */
+ * sigma 0.6, clipped to 30..2000), or with sizes=c2 bench.py's C2 rule 100 + (37 p) mod 201; sequences uniform
+ * over ACGT.  Prints one line per phase. */
 #include "deciphon_host.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -56,6 +59,8 @@ int main(int argc, char **argv)
     unsigned const batch = argc > 4 ? (unsigned)atoi(argv[4]) : 1000u;
     double const threshold = argc > 5 ? atof(argv[5]) : 10.0; /* 1e30: no hits, i.e. no traceback and no product rows */
     unsigned long const batch_symbols = argc > 6 ? strtoul(argv[6], NULL, 10) : 0ul;
+    int const c2_sizes = argc > 7 && !strcmp(argv[7], "c2");
+    printf("host layer build: imm_float is %zu bytes\n", sizeof(imm_float));
 
     struct imm_nuclt const *nuclt = imm_super(&imm_dna_iupac);
     struct imm_nuclt_code code;
@@ -73,7 +78,7 @@ int main(int argc, char **argv)
     for (unsigned p = 0; p < nprof; ++p)
     {
         double m = exp(log(150.0) + 0.6 * next_normal());
-        unsigned const M = (unsigned)(m < 30 ? 30 : m > 2000 ? 2000 : m + 0.5);
+        unsigned const M = c2_sizes ? 100u + (p * 37u) % 201u : (unsigned)(m < 30 ? 30 : m > 2000 ? 2000 : m + 0.5);
         struct protein_profile prof;
         char acc[16];
         snprintf(acc, sizeof acc, "PF%05u", p);

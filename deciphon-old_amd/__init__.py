@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "dcp_xtrans64", "dcp_gpu_db_upload64", "dcp_gpu_db_precision", "dcp_gpu_set_lrt_threshold64", "dcp_gpu_fetch_scores64", "dcp_gpu_fetch_hits64",
     "dcp_gpu_db_fetch_match_table64", "dcp_gpu_db_fetch_insert_null64", "dcp_gpu_trace_paths64",
     "dcp_gpu_seqs_set_xtrans64", "dcp_profile_from_parts64", "dcp_lprob_normalize64",
+    "dcp_gpu_last_scan_query_plan",
 ]
 
 
@@ -161,6 +162,7 @@ def _load(path=None, hooks=False):
         "dcp_gpu_scan": (I, [P, C.POINTER(ScanParams)]),
         "dcp_gpu_sync": (I, [P]),
         "dcp_gpu_last_scan_redo_pairs": (I, [P, C.POINTER(U)]),
+        "dcp_gpu_last_scan_query_plan": (I, [P, C.POINTER(U), C.POINTER(C.c_ulonglong), C.POINTER(U), C.POINTER(U)]),
         "dcp_gpu_last_scan_ms": (F, [P]),
         "dcp_gpu_last_scan_launches": (U, [P]),
         "dcp_gpu_last_scan_kernel": (I, [P]),
@@ -761,6 +763,18 @@ class Scanner:
     @property
     def last_scan_launches(self):
         return self._lib.dcp_gpu_last_scan_launches(self._c)
+
+    @property
+    def last_scan_query_plan(self):
+        """The batch plan the last scan ran with, if it ran KERNEL_QLANE64 (synchronises): a dict of the plan's
+        blocks, the rows a tile costs summed over the blocks, the rows of a block's planes and the most groups any
+        wavefront slot holds.  DcpError (RC_EINVAL) after any other scan -- an overflowed kernel-4 scan that was
+        repeated with the row sweep included -- and before the first."""
+        nb, rows, prow, mg = C.c_uint(0), C.c_ulonglong(0), C.c_uint(0), C.c_uint(0)
+        self._check(self._lib.dcp_gpu_last_scan_query_plan(self._c, C.byref(nb), C.byref(rows), C.byref(prow),
+                                                           C.byref(mg)))
+        return dict(nblocks=nb.value, sum_block_rows=rows.value, plane_rows=prow.value,
+                    max_groups_per_slot=mg.value)
 
     @property
     def last_scan_redo_pairs(self):

@@ -127,9 +127,13 @@ struct dcp_f64_pairs_args : dcp_f64_scan_args
 };
 int dcp_f64_launch_scan_pairs(int R, dcp_f64_pairs_args const *a, unsigned nwaves, void *stream);
 
-// The query-lane kernel (dcp_f64_qlane.hip): a persistent grid of blocks of DCP_F64_QL_LANES queries pulling
-// (profile, query block) tasks from *task_counter; task i is profile order[i / nqb] against queries
-// qorder[256 (i % nqb) ..] (relative to the scan's first query, ascending length).
+// The query-lane kernel (dcp_f64_qlane.hip): a persistent grid of blocks of DCP_F64_QL_LANES lanes pulling
+// (profile, plan block) tasks from *task_counter; task i is profile order[i / nqb] against block i % nqb of the
+// batch plan (plan_query_groups, dcp_gpu.hip: the float query-lane kernels' plan with four wavefront slots per
+// block).  Wavefront slot s of block b sweeps groups[slot_first[4 b + s] .. slot_first[4 b + s + 1]) one after the
+// other per tile, lane l of the slot the query qorder[group.qfirst + l] (relative to the scan's first query,
+// ascending length), in rows group.rowbase .. of its own columns of the block's planes.
+struct dcp_ql_group; // dcp_kernels.h
 struct dcp_f64_qlane_args
 {
     dcp_f64_prof const *profs; // the whole resident DB
@@ -139,13 +143,15 @@ struct dcp_f64_qlane_args
     uint32_t const *seq_words, *seq_woff, *seq_len; // relative to the scan's first query
     double const *xtrans;                           // [nq][DCP_F64_XSTRIDE]
     uint32_t const *qorder;                         // [nq]
+    struct dcp_ql_group const *groups;              // [groups of the plan], in slot order
+    uint32_t const *slot_first;                     // [4 nqb + 1]
     unsigned nq, q_base, nqb, ntasks;
     double *out_null, *out_alt;
     struct dcp_hit64 *hits;
     unsigned *nhits;
     unsigned hit_cap;
     double lrt_threshold;
-    double *planes;        // plane_stride doubles per block of the grid: [row 0 .. lmax][3][DCP_F64_QL_LANES]
+    double *planes;        // plane_stride doubles per block of the grid: [the plan's plane rows][3][DCP_F64_QL_LANES]
     uint64_t plane_stride;
     unsigned *task_counter;
     dcp_f64_pair *redo;    // one list per launch group of the DB, group g at redo_first[g], redo_cap[g] long

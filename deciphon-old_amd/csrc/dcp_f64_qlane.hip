@@ -1,11 +1,13 @@
 // dcp_f64_qlane.hip -- the query-lane kernel of the double build ("query-lane kernel").
 //
-//  viterbi64_qlane_kernel   null + alt Viterbi in double, one LANE per query: a block is 256 threads = 256 queries of
-//                           the length-sorted batch against ONE profile.  The profile is cut into tiles of KT = 4
-//                           consecutive nodes; a tile is swept over all rows with the five-row P_k / Q_k history of
-//                           its nodes in registers, the delete chain sequential in k inside the lane, E(j) a running
-//                           maximum, N / J / C and the null model's R per lane.  No cross-lane operation, no polling:
-//                           the only synchronisation is the block barrier around the LDS images.
+//  viterbi64_qlane_kernel   null + alt Viterbi in double, one LANE per query: a block is 256 threads = four
+//                           wavefront slots against ONE profile, each slot sweeping a list of 64-query groups of the
+//                           length-sorted batch one after the other (the batch plan, dcp_f64.h).  The profile is cut
+//                           into tiles of KT = 4 consecutive nodes; a tile is swept over all rows of a group with the
+//                           five-row P_k / Q_k history of its nodes in registers, the delete chain sequential in k
+//                           inside the lane, E(j) a running maximum, N / J / C and the null model's R per lane.  No
+//                           cross-lane operation, no polling: the only synchronisation is the block barrier around
+//                           the LDS images.
 //
 // Arithmetic contract: dcp_f64.hip's -- every candidate is one double add of the oracle's operands, combined with
 // max only, -ffp-contract=off.  What differs from the row sweep is the ORDER in which exact maxima are taken
@@ -21,7 +23,8 @@
 // E(j) is taken over M_k AND D_k of every node always (as the row sweep does), so profiles with positive MD / DD
 // need no flag.  Padding columns (core_size .. ldk) have -inf emissions and transitions: their M, I, D are -inf.
 //
-// Tile t hands row j to tile t + 1 through three per-block planes in global memory, [row][plane][lane] doubles:
+// Tile t hands row j to tile t + 1 through three per-block planes in global memory, [row][plane][lane] doubles (a
+// group's rows in its own region of the slot's columns, from the group's rowbase on):
 //   Xd = D of tile t + 1's first node (the end of tile t's delete chain),
 //   Xm = max over the M / I / D edges into that node's M (the entry edge B + ENTRY is added by tile t + 1),
 //   E  = the running maximum.
@@ -30,6 +33,7 @@
 // read it.  The last tile hands nothing over and does not touch the transition column behind it (which does not
 // exist when core_size == ldk).
 #include "dcp_f64.h"
+#include "dcp_kernels.h" // dcp_ql_group
 
 #include <hip/hip_runtime.h>
 
@@ -92,8 +96,8 @@ struct SState // the special states' sweep behind the last tile
     bool fb;
 };
 
-// Every lane of a block runs the rows of the block's LONGEST query (Lb: the barrier makes it wait for that one
-// anyway) in whole turns of the five-row ring, so the row loops' control flow is uniform and has one exit; a lane
+// Every lane of a group runs the rows of the group's LONGEST query (Lb, wave-uniform: the wavefront waits for that
+// one anyway) in whole turns of the five-row ring, so the row loops' control flow is scalar and has one exit; a lane
 // past its own L computes on values nobody reads, with its reads clamped to its own words and plane rows.
 //
 // The bases of a turn: ten bits cut from a 64-bit window of the query's words that was loaded one turn ahead --
@@ -313,6 +317,37 @@ __device__ __forceinline__ int group_of(unsigned M) // the launch group of dcp_g
     return M <= 64u ? 0 : M <= 128u ? 1 : M <= (unsigned)DCP_F64_SEG ? 2 : 3;
 }
 
+// One group of a wavefront slot as its lanes see it.  The record is read through wave-uniform values only (the
+// bound of the row loops must be scalar); lane l of the slot has the group's l-th query, a lane past group.nq is idle:
+// L = 0, and nothing of it is read.
+struct QLaneGroup
+{
+    unsigned q, L, Lb;
+    bool active;
+    uint32_t const *words;
+    double const *xt;
+    double *plane;
+};
+__device__ __forceinline__ QLaneGroup lane_group(dcp_f64_qlane_args const &a, unsigned gi, double *slot_plane)
+{
+    dcp_ql_group const g = a.groups[gi];
+    unsigned const wl = threadIdx.x & 63u;
+    unsigned const gq = (unsigned)__builtin_amdgcn_readfirstlane((int)g.nq);
+    unsigned const gfirst = (unsigned)__builtin_amdgcn_readfirstlane((int)g.qfirst);
+    unsigned const rowbase = (unsigned)__builtin_amdgcn_readfirstlane((int)g.rowbase);
+    QLaneGroup r;
+    r.Lb = (unsigned)__builtin_amdgcn_readfirstlane((int)g.lmax);
+    r.active = wl < gq;
+    r.q = r.active ? a.qorder[gfirst + wl] : 0u;
+    r.L = r.active ? a.seq_len[r.q] : 0u;
+    r.words = a.seq_words + a.seq_woff[r.q];
+    r.xt = a.xtrans + (size_t)r.q * DCP_F64_XSTRIDE;
+    // The group's region is dcp_qlane_group_rows(Lb) = (Lb + 11) & ~1 rows from rowbase on.  The sweeps touch its
+    // rows 0 .. ceil(Lb / 5) * 5 <= Lb + 4 and prefetch clamped to L <= Lb: inside the region.
+    r.plane = slot_plane + (uint64_t)rowbase * PLANE_ROW;
+    return r;
+}
+
 __global__ __launch_bounds__(NT, 2) void viterbi64_qlane_kernel(dcp_f64_qlane_args a)
 {
     __shared__ double2 img[2 * DCP_NCODES]; // [code][KT] match emissions of the tile
@@ -332,14 +367,10 @@ __global__ __launch_bounds__(NT, 2) void viterbi64_qlane_kernel(dcp_f64_qlane_ar
         double const *const ei = a.xe + pr.xe_off;
         for (unsigned c = lane; c < (unsigned)DCP_NCODES; c += NT)
             lxe[c] = double2{ei[c], ei[DCP_NCODES + c]};
-        unsigned const slot = qb * NT + lane;
-        bool const active = slot < a.nq;
-        unsigned const q = active ? a.qorder[slot] : 0u;
-        unsigned const L = active ? a.seq_len[q] : 0u; // an idle lane of the last block: nothing of it is read
-        unsigned const qlast = qb * NT + NT - 1u < a.nq ? qb * NT + NT - 1u : a.nq - 1u;
-        unsigned const Lb = (unsigned)__builtin_amdgcn_readfirstlane((int)a.seq_len[a.qorder[qlast]]); // ascending
-        uint32_t const *const words = a.seq_words + a.seq_woff[q];
-        double const *const xt = a.xtrans + (size_t)q * DCP_F64_XSTRIDE;
+        // this wavefront slot's groups; a slot with none only takes part in the barriers
+        unsigned const sidx = qb * (NT / 64u) + (lane >> 6);
+        unsigned const g0 = (unsigned)__builtin_amdgcn_readfirstlane((int)a.slot_first[sidx]);
+        unsigned const g1 = (unsigned)__builtin_amdgcn_readfirstlane((int)a.slot_first[sidx + 1u]);
         unsigned const ntiles = (pr.core_size + (unsigned)KT - 1u) / (unsigned)KT;
         double const *const tab = a.tab + pr.tab_off;
         double const *const tr = a.trans + pr.trans_off;
@@ -377,37 +408,53 @@ __global__ __launch_bounds__(NT, 2) void viterbi64_qlane_kernel(dcp_f64_qlane_ar
                 tt.ndd = uni(tb[DCP_T_DD * (uint64_t)pr.ldk + KT]);
             }
             __syncthreads();
-            if (first && last) qtile<true, false>(tt, xt, img, lxe, words, plane, L, Lb);
-            else if (first) qtile<true, true>(tt, xt, img, lxe, words, plane, L, Lb);
-            else if (!last) qtile<false, true>(tt, xt, img, lxe, words, plane, L, Lb);
-            else qtile<false, false>(tt, xt, img, lxe, words, plane, L, Lb);
+            // the slot's groups one after the other; the group loop goes around the four sweeps, each of which
+            // stands here once
+            for (unsigned gi = g0; gi < g1; ++gi)
+            {
+                QLaneGroup const g = lane_group(a, gi, plane);
+                if (first && last) qtile<true, false>(tt, g.xt, img, lxe, g.words, g.plane, g.L, g.Lb);
+                else if (first) qtile<true, true>(tt, g.xt, img, lxe, g.words, g.plane, g.L, g.Lb);
+                else if (!last) qtile<false, true>(tt, g.xt, img, lxe, g.words, g.plane, g.L, g.Lb);
+                else qtile<false, false>(tt, g.xt, img, lxe, g.words, g.plane, g.L, g.Lb);
+            }
         }
-        QX const x{xt[DCP_X_RR], xt[DCP_X_SB], xt[DCP_X_SN], xt[DCP_X_NN], xt[DCP_X_NB], xt[DCP_X_ET], xt[DCP_X_EC],
-                   xt[DCP_X_CC], xt[DCP_X_CT], xt[DCP_X_EB], xt[DCP_X_EJ], xt[DCP_X_JJ], xt[DCP_X_JB]};
-        SState s;
-        qspecials(s, x, lxe, words, plane, L, Lb); // reads lxe only: no barrier between the last tile and this
-        if (!active) continue;
-        if (s.fb) // the E -> B / J -> B feedback won in some row: the exact kernel scores this pair
+        // The special states of every group over its own region, and its lanes' results: nothing was parked between
+        // the tiles, every per-lane result comes out of this sweep.  (Reads lxe only: no barrier between the last
+        // tile and this.)
+        for (unsigned gi = g0; gi < g1; ++gi)
         {
-            int const g = group_of(pr.core_size);
-            unsigned const k = atomicAdd(a.redo_n + g, 1u);
-            if (k < a.redo_cap[g]) a.redo[a.redo_first[g] + k] = dcp_f64_pair{q, pi};
-            else atomicOr(a.redo_n + 4, 1u); // the list is full: dcp_gpu_sync repeats the scan with the row sweep
-            continue;
-        }
-        // E(L) from the plane again: a loaded value that lives out of the row loop costs the loop a full wait
-        double const EL = plane[L * PLANE_ROW + 2u * NT];
-        double const null_ll = s.Rr, alt_ll = fmax(EL + x.ET, s.Cc + x.CT);
-        if (a.out_null)
-        {
-            a.out_null[(size_t)q * a.nprof_total + pr.pidx] = null_ll;
-            a.out_alt[(size_t)q * a.nprof_total + pr.pidx] = alt_ll;
-        }
-        double const lrt = -2 * (null_ll - alt_ll);
-        if (finite64(lrt) && lrt >= a.lrt_threshold)
-        {
-            unsigned const k = atomicAdd(a.nhits, 1u);
-            if (k < a.hit_cap) a.hits[k] = dcp_hit64{a.q_base + q, pr.pidx, null_ll, alt_ll};
+            QLaneGroup const g = lane_group(a, gi, plane);
+            double const *const xt = g.xt;
+            unsigned const q = g.q, L = g.L;
+            QX const x{xt[DCP_X_RR], xt[DCP_X_SB], xt[DCP_X_SN], xt[DCP_X_NN], xt[DCP_X_NB], xt[DCP_X_ET],
+                       xt[DCP_X_EC], xt[DCP_X_CC], xt[DCP_X_CT], xt[DCP_X_EB], xt[DCP_X_EJ], xt[DCP_X_JJ],
+                       xt[DCP_X_JB]};
+            SState s;
+            qspecials(s, x, lxe, g.words, g.plane, L, g.Lb);
+            if (!g.active) continue;
+            if (s.fb) // the E -> B / J -> B feedback won in some row: the exact kernel scores this pair
+            {
+                int const lg = group_of(pr.core_size);
+                unsigned const k = atomicAdd(a.redo_n + lg, 1u);
+                if (k < a.redo_cap[lg]) a.redo[a.redo_first[lg] + k] = dcp_f64_pair{q, pi};
+                else atomicOr(a.redo_n + 4, 1u); // the list is full: dcp_gpu_sync repeats the scan with the row sweep
+                continue;
+            }
+            // E(L) from the plane again: a loaded value that lives out of the row loop costs the loop a full wait
+            double const EL = g.plane[L * PLANE_ROW + 2u * NT];
+            double const null_ll = s.Rr, alt_ll = fmax(EL + x.ET, s.Cc + x.CT);
+            if (a.out_null)
+            {
+                a.out_null[(size_t)q * a.nprof_total + pr.pidx] = null_ll;
+                a.out_alt[(size_t)q * a.nprof_total + pr.pidx] = alt_ll;
+            }
+            double const lrt = -2 * (null_ll - alt_ll);
+            if (finite64(lrt) && lrt >= a.lrt_threshold)
+            {
+                unsigned const k = atomicAdd(a.nhits, 1u);
+                if (k < a.hit_cap) a.hits[k] = dcp_hit64{a.q_base + q, pr.pidx, null_ll, alt_ll};
+            }
         }
     }
 }

@@ -231,9 +231,14 @@ struct dcp_gpu_ctx
         unsigned hit_cap = 0;
         bool have_scores = false;
         // the query-lane kernel (dcp_f64_qlane.hip): profiles by falling core size, the scan's queries by rising
-        // length, the resident blocks' boundary planes, the task counter, the redo lists of the four launch groups
-        // and their counters ([4] pairs, [1] overflow flag); kept between scans
-        DevBuf<uint32_t> d_order, d_qorder;
+        // length and their batch plan (group records, slot table), the resident blocks' boundary planes, the task
+        // counter, the redo lists of the four launch groups and their counters ([4] pairs, [1] overflow flag); kept
+        // between scans
+        DevBuf<uint32_t> d_order, d_qorder, d_slot_first;
+        DevBuf<dcp_ql_group> d_groups;
+        // the plan of the last kernel-4 scan (dcp_gpu_last_scan_query_plan)
+        unsigned plan_blocks = 0, plan_rows = 0, plan_max_groups = 0;
+        uint64_t plan_sum_rows = 0;
         DevBuf<double> d_planes;
         DevBuf<unsigned> d_task, d_redo_n;
         DevBuf<dcp_f64_pair> d_redo;
@@ -245,7 +250,7 @@ struct dcp_gpu_ctx
             d_xt.release(), d_null.release(), d_alt.release(), d_col.release();
             d_hits.release(), d_nhits.release();
             d_order.release(), d_qorder.release(), d_planes.release(), d_task.release(), d_redo_n.release();
-            d_redo.release();
+            d_redo.release(), d_slot_first.release(), d_groups.release();
             redo_pending = false;
             hit_cap = 0;
             have_scores = false;
@@ -1532,11 +1537,21 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     unsigned ql_blocks = 0;
     if (qlane)
     {
-        // blocks of 256 consecutive queries of the length order; a persistent grid of at most two blocks per CU,
-        // fewer where their boundary planes ([row 0 .. lmax + 4][3][256] doubles each) would take too much memory
-        unsigned const nqb = (nq + DCP_F64_QL_LANES - 1u) / DCP_F64_QL_LANES;
+        // the range's queries by rising length, packed into blocks of four wavefront slots as the float query-lane
+        // kernels' batches are (plan_query_groups); a persistent grid of at most two blocks per CU, fewer where their
+        // boundary planes ([the plan's plane rows][3][256] doubles each) would take too much memory
+        std::vector<uint32_t> qorder(nq);
+        for (unsigned q = 0; q < nq; ++q)
+            qorder[q] = q;
+        std::stable_sort(qorder.begin(), qorder.end(),
+                         [&](uint32_t x, uint32_t y) { return c->seq_len[q_begin + x] < c->seq_len[q_begin + y]; });
+        std::vector<unsigned> len_sorted(nq);
+        for (unsigned i = 0; i < nq; ++i)
+            len_sorted[i] = c->seq_len[q_begin + qorder[i]];
+        QlPlan const plan = plan_query_groups(len_sorted.data(), nq, DCP_F64_QL_LANES / 64u);
+        unsigned const nqb = plan.nqb;
         uint64_t const ntasks = (uint64_t)c->nprof * nqb;
-        uint64_t const plane_stride = ((uint64_t)lmax + 5u) * 3u * DCP_F64_QL_LANES;
+        uint64_t const plane_stride = (uint64_t)plan.plane_rows * 3u * DCP_F64_QL_LANES;
         if (plane_stride > (1ull << 31) || ntasks > 0xf0000000ull)
             return c->fail(DCP_ENOMEM, "batch too large for the f64 query-lane kernel (%u rows, %llu tasks): use kernel = 1", lmax,
                            (unsigned long long)ntasks);
@@ -1548,14 +1563,19 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         if (ql_blocks == 0)
             return c->fail(DCP_ENOMEM, "sequences too long for the f64 query-lane kernel (%u rows of boundary planes do not fit the device): use kernel = 1", lmax);
         if (F.d_planes.n < ql_blocks * plane_stride) HIP_TRY(c, F.d_planes.alloc(ql_blocks * plane_stride));
-        std::vector<uint32_t> qorder(nq);
-        for (unsigned q = 0; q < nq; ++q)
-            qorder[q] = q;
-        std::stable_sort(qorder.begin(), qorder.end(),
-                         [&](uint32_t x, uint32_t y) { return c->seq_len[q_begin + x] < c->seq_len[q_begin + y]; });
         if (F.d_qorder.n < nq) HIP_TRY(c, F.d_qorder.alloc(nq));
+        if (F.d_slot_first.n < plan.slot_first.size()) HIP_TRY(c, F.d_slot_first.alloc(plan.slot_first.size()));
+        if (F.d_groups.n < plan.groups.size()) HIP_TRY(c, F.d_groups.alloc(plan.groups.size()));
         HIP_TRY(c, hipMemcpyAsync(F.d_qorder.p, qorder.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream)); // qorder and xt leave scope
+        HIP_TRY(c, hipMemcpyAsync(F.d_slot_first.p, plan.slot_first.data(), plan.slot_first.size() * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(F.d_groups.p, plan.groups.data(), plan.groups.size() * sizeof(dcp_ql_group),
+                                  hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // qorder, the plan and xt leave scope
+        F.plan_blocks = nqb, F.plan_rows = plan.plane_rows, F.plan_sum_rows = plan.sum_block_rows;
+        F.plan_max_groups = 0;
+        for (size_t i = 0; i + 1u < plan.slot_first.size(); ++i)
+            F.plan_max_groups = std::max<unsigned>(F.plan_max_groups, plan.slot_first[i + 1u] - plan.slot_first[i]);
         if (!F.d_task.p) HIP_TRY(c, F.d_task.alloc(1));
         if (!F.d_redo_n.p) HIP_TRY(c, F.d_redo_n.alloc(5));
         // a redo list per launch group; uni-hit scans have no feedback and no lists (explicit transitions may carry
@@ -1578,6 +1598,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         qa.seq_words = a.seq_words, qa.seq_woff = a.seq_woff, qa.seq_len = a.seq_len;
         qa.xtrans = a.xtrans;
         qa.qorder = F.d_qorder.p;
+        qa.groups = F.d_groups.p, qa.slot_first = F.d_slot_first.p;
         qa.nq = nq, qa.q_base = q_begin, qa.nqb = nqb, qa.ntasks = (unsigned)ntasks;
         qa.out_null = a.out_null, qa.out_alt = a.out_alt;
         qa.hits = a.hits, qa.nhits = a.nhits, qa.hit_cap = a.hit_cap;
@@ -2281,6 +2302,22 @@ int dcp_gpu_last_scan_redo_pairs(dcp_gpu_ctx *c, unsigned *npairs)
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc;
     *npairs = c->last_redo_pairs;
+    return DCP_OK;
+}
+
+int dcp_gpu_last_scan_query_plan(dcp_gpu_ctx *c, unsigned *nblocks, unsigned long long *sum_block_rows,
+                                 unsigned *plane_rows, unsigned *max_groups_per_slot)
+{
+    if (!c) return DCP_EINVAL;
+    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc; // an overflowed kernel-4 scan is repeated with the row sweep
+    if (!c->last_f64 || c->last_kernel_variant != 4)
+        return c->fail(DCP_EINVAL, "the last scan did not run the f64 query-lane kernel (kernel = 4): it has no batch plan");
+    if (nblocks) *nblocks = c->f64.plan_blocks;
+    if (sum_block_rows) *sum_block_rows = c->f64.plan_sum_rows;
+    if (plane_rows) *plane_rows = c->f64.plan_rows;
+    if (max_groups_per_slot) *max_groups_per_slot = c->f64.plan_max_groups;
     return DCP_OK;
 }
 

@@ -283,7 +283,8 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
  * expanded on the device in double, [1364][core_size padded to the kernel's columns] per profile -- one layout.
  * DCP_EINVAL if any profile was built in float.  A context holds ONE resident DB, float or double: either upload
  * replaces the other.  Scans of a double DB run the f64 row sweep (dcp_scan_params.kernel 0 or 1) or the f64
- * query-lane kernel (4: the throughput path for batches of a few hundred queries and more; same bits); 2 and 3,
+ * query-lane kernel (4: the throughput path for batches, of one length or mixed -- it packs the queries by length as
+ * dcp_plan_query_slots says, see dcp_gpu_last_scan_query_plan; same bits); 2 and 3,
  * the float query-lane kernels, are DCP_EINVAL.  They leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
  * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table,
  * dcp_gpu_hit_buffer, float explicit xtrans) return DCP_EINVAL on it. */
@@ -431,6 +432,12 @@ int dcp_gpu_sync(dcp_gpu_ctx *);
  * Their number in the last scan (0 for row-sweep and uni-hit scans);
  * synchronises. */
 int dcp_gpu_last_scan_redo_pairs(dcp_gpu_ctx *, unsigned *npairs);
+/* The batch plan the last scan ran with, if that scan ran kernel 4: plan blocks, rows a tile costs summed over
+ * the blocks, rows of a block's planes, the most groups any slot holds.  DCP_EINVAL if the last scan ran another
+ * kernel (also after an overflowed kernel-4 scan that was repeated with the row sweep) or none ran.  The plan is
+ * dcp_plan_query_slots' for the scanned range's lengths in ascending order, four slots per block; synchronises. */
+int dcp_gpu_last_scan_query_plan(dcp_gpu_ctx *, unsigned *nblocks, unsigned long long *sum_block_rows,
+                                 unsigned *plane_rows, unsigned *max_groups_per_slot);
 /* Milliseconds between HIP events recorded on the context's stream around the
  * kernels of the LAST dcp_gpu_scan (valid after dcp_gpu_sync). */
 float dcp_gpu_last_scan_ms(dcp_gpu_ctx *);

@@ -18,8 +18,10 @@
 #include <limits>
 #include <map>
 #include <new>
+#include <numeric>
 #include <string>
 #include <queue>
+#include <type_traits>
 #include <vector>
 
 namespace
@@ -90,6 +92,60 @@ template <class T> struct DevBuf
     }
     ~DevBuf() { release(); }
 };
+
+// What a scan leaves on the device, in the DB's precision: the dense scores (keep_scores) and the hit list with its
+// counter -- the context's own, or a caller-owned buffer (e.g. a torch tensor that RCCL gathers; float DBs only).
+template <class Real, class Hit> struct ScanResults
+{
+    DevBuf<Real> d_null, d_alt;
+    DevBuf<Hit> d_hits;
+    DevBuf<unsigned> d_nhits;
+    unsigned hit_cap = 0;
+    bool have_scores = false;
+    Hit *ext_hits = nullptr;
+    unsigned *ext_nhits = nullptr;
+    unsigned ext_cap = 0;
+    Hit *hits() const { return ext_hits ? ext_hits : d_hits.p; }
+    unsigned *nhits() const { return ext_hits ? ext_nhits : d_nhits.p; }
+    unsigned cap() const { return ext_hits ? ext_cap : hit_cap; }
+    hipError_t ensure(size_t npairs, bool keep_scores)
+    {
+        hipError_t e = hipSuccess;
+        if (keep_scores && d_null.n != npairs)
+        {
+            if ((e = d_null.alloc(npairs)) != hipSuccess) return e;
+            if ((e = d_alt.alloc(npairs)) != hipSuccess) return e;
+        }
+        have_scores = keep_scores;
+        unsigned const want_cap = (unsigned)std::min<size_t>(npairs, (size_t)1 << 22);
+        if (!ext_hits && hit_cap < want_cap)
+        {
+            if ((e = d_hits.alloc(want_cap)) != hipSuccess) return e;
+            hit_cap = want_cap;
+        }
+        return d_nhits.p ? hipSuccess : d_nhits.alloc(1);
+    }
+    void release()
+    {
+        d_null.release(), d_alt.release(), d_hits.release(), d_nhits.release();
+        hit_cap = 0;
+        have_scores = false;
+    }
+};
+
+// This file is built with -fno-honor-nans: a NaN is found by its encoding, not by v != v.
+bool is_nan(float v)
+{
+    uint32_t bits;
+    std::memcpy(&bits, &v, sizeof bits);
+    return (bits & 0x7fffffffu) > 0x7f800000u;
+}
+bool is_nan(double v)
+{
+    uint64_t bits;
+    std::memcpy(&bits, &v, sizeof bits);
+    return (bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
+}
 
 } // namespace
 
@@ -180,18 +236,10 @@ struct dcp_gpu_ctx
     std::vector<double> xt64;
 
     // results
-    DevBuf<float> d_null, d_alt;
-    DevBuf<dcp_hit> d_hits;
-    DevBuf<unsigned> d_nhits;
-    unsigned hit_cap = 0;
-    bool have_scores = false;
+    ScanResults<float, dcp_hit> res;
     unsigned last_launches = 0;
     bool scanned = false;
     unsigned last_q0 = 0, last_q1 = 0;
-    // caller-owned hit buffer (e.g. a torch tensor that RCCL gathers)
-    dcp_hit *ext_hits = nullptr;
-    unsigned *ext_nhits = nullptr;
-    unsigned ext_cap = 0;
     // one HIP event after each size-class launch of the last scan
     static constexpr int kMaxLaunches = 2 * kNumClasses + 1; // a segmented class is two launches
     hipEvent_t ev_class[kMaxLaunches] = {nullptr};
@@ -225,11 +273,8 @@ struct dcp_gpu_ctx
         unsigned group_first[5] = {0, 0, 0, 0, 0};
         DevBuf<dcp_f64_prof> d_profs;
         DevBuf<double> d_tab, d_trans, d_xe; // match tables, trans8 rows, insert + null tables
-        DevBuf<double> d_xt, d_null, d_alt, d_col;
-        DevBuf<dcp_hit64> d_hits;
-        DevBuf<unsigned> d_nhits;
-        unsigned hit_cap = 0;
-        bool have_scores = false;
+        DevBuf<double> d_xt, d_col;
+        ScanResults<double, dcp_hit64> res;
         // the query-lane kernel (dcp_f64_qlane.hip): profiles by falling core size, the scan's queries by rising
         // length and their batch plan (group records, slot table), the resident blocks' boundary planes, the task
         // counter, the redo lists of the four launch groups and their counters ([4] pairs, [1] overflow flag); kept
@@ -247,13 +292,10 @@ struct dcp_gpu_ctx
         {
             profs.clear();
             d_profs.release(), d_tab.release(), d_trans.release(), d_xe.release();
-            d_xt.release(), d_null.release(), d_alt.release(), d_col.release();
-            d_hits.release(), d_nhits.release();
+            d_xt.release(), d_col.release(), res.release();
             d_order.release(), d_qorder.release(), d_planes.release(), d_task.release(), d_redo_n.release();
             d_redo.release(), d_slot_first.release(), d_groups.release();
             redo_pending = false;
-            hit_cap = 0;
-            have_scores = false;
         }
     } f64;
 
@@ -278,6 +320,220 @@ struct dcp_gpu_ctx
             return (ctx)->fail(e_ == hipErrorOutOfMemory ? DCP_ENOMEM : DCP_EFAIL, \
                                "%s: %s", #call, hipGetErrorString(e_));        \
     } while (0)
+
+// A new DB or a new batch: the last scan is void, and so is whatever of it has not been looked at yet.
+static void void_last_scan(dcp_gpu_ctx *c)
+{
+    c->scanned = false;
+    c->redo_pending = false;
+    c->f64.redo_pending = false;
+    c->ring_check_pending = false;
+}
+
+// What the float and the double path share (templates: outside the extern "C" block)
+extern "C" { static int finish_scan(dcp_gpu_ctx *c); } // defined behind dcp_gpu_scan_range
+
+namespace
+{
+
+// the size class / launch group k whose DB slots [first[k], first[k + 1]) hold `slot`
+int range_of(unsigned const *first, int n, unsigned slot)
+{
+    int k = 0;
+    while (k + 1 < n && slot >= first[k + 1])
+        ++k;
+    return k;
+}
+
+template <class Real> int fetch_table_rows(dcp_gpu_ctx *c, Real const *src, unsigned ldk, unsigned core_size, Real *out)
+{
+    // rows of (possibly shared) length ldk from the profile's first column to its last row's last node
+    std::vector<Real> tab((size_t)(DCP_NCODES - 1) * ldk + core_size);
+    HIP_TRY(c, hipMemcpy(tab.data(), src, tab.size() * sizeof(Real), hipMemcpyDeviceToHost));
+    for (unsigned code = 0; code < DCP_NCODES; ++code)
+        std::memcpy(out + (size_t)code * core_size, &tab[(size_t)code * ldk], sizeof(Real) * core_size);
+    return DCP_OK;
+}
+
+int xtrans_of_length(unsigned L, int multi_hits, int hmmer3_compat, float *out) { return dcp_xtrans(L, multi_hits, hmmer3_compat, out); }
+int xtrans_of_length(unsigned L, int multi_hits, int hmmer3_compat, double *out) { return dcp_xtrans64(L, multi_hits, hmmer3_compat, out); }
+
+// protein_profile_setup once per sequence length instead of once per pair: row i of xt ([seqs.size()][stride], the tail
+// of a row zero) gets the special transitions of the resident sequence seqs[i].  In double the caller's own rows
+// (dcp_gpu_seqs_set_xtrans64) are copied instead while they hold: the flags are then ignored.
+template <class Real>
+int fill_xtrans(dcp_gpu_ctx *c, std::vector<uint32_t> const &seqs, int multi_hits, int hmmer3_compat, unsigned stride,
+                std::vector<Real> &xt)
+{
+    bool const given = std::is_same<Real, double>::value && !c->xt64.empty();
+    xt.assign(seqs.size() * stride, Real(0));
+    std::map<uint32_t, size_t> row_of_len;
+    for (size_t i = 0; i < seqs.size(); ++i)
+    {
+        Real *const row = &xt[i * stride];
+        if (given)
+        {
+            std::memcpy(row, &c->xt64[(size_t)seqs[i] * DCP_NXTRANS], sizeof(double) * DCP_NXTRANS);
+            continue;
+        }
+        uint32_t const L = c->seq_len[seqs[i]];
+        auto const it = row_of_len.find(L);
+        if (it != row_of_len.end())
+        {
+            std::memcpy(row, &xt[it->second * stride], sizeof(Real) * DCP_NXTRANS);
+            continue;
+        }
+        if (int rc = xtrans_of_length(L, multi_hits, hmmer3_compat, row)) return c->fail(rc, "sequence cannot be empty");
+        row_of_len.emplace(L, i);
+    }
+    return DCP_OK;
+}
+
+// dcp_gpu_fetch_scores[64] / dcp_gpu_fetch_hits[64] once the last scan is known to be of the precision asked for
+template <class Real, class Hit> int fetch_scores(dcp_gpu_ctx *c, ScanResults<Real, Hit> const &r, Real *null_out, Real *alt_out)
+{
+    if (!c->scanned || !r.have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc;
+    size_t const bytes = (size_t)c->nseqs * c->nprof * sizeof(Real);
+    if (null_out) HIP_TRY(c, hipMemcpy(null_out, r.d_null.p, bytes, hipMemcpyDeviceToHost));
+    if (alt_out) HIP_TRY(c, hipMemcpy(alt_out, r.d_alt.p, bytes, hipMemcpyDeviceToHost));
+    return DCP_OK;
+}
+
+template <class Real, class Hit> int fetch_hits(dcp_gpu_ctx *c, ScanResults<Real, Hit> const &r, Hit *hits, unsigned cap, unsigned *nhits)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc;
+    unsigned n = 0;
+    HIP_TRY(c, hipMemcpy(&n, r.nhits(), sizeof n, hipMemcpyDeviceToHost));
+    *nhits = n;
+    if (n > r.cap()) return c->fail(DCP_ENOMEM, "device hit buffer overflow: %u > %u", n, r.cap());
+    if (n > cap || (n && !hits)) return DCP_ENOMEM;
+    if (n == 0) return DCP_OK;
+    HIP_TRY(c, hipMemcpy(hits, r.hits(), (size_t)n * sizeof(Hit), hipMemcpyDeviceToHost));
+    std::sort(hits, hits + n, [](Hit const &x, Hit const &y) {
+        return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
+    });
+    return DCP_OK;
+}
+
+static_assert((uint32_t)DCP_F64_TRACE_NO_PATH == (uint32_t)DCP_TRACE_NO_PATH && (uint32_t)DCP_F64_TRACE_TOO_LONG == (uint32_t)DCP_TRACE_TOO_LONG,
+              "the walks of both precisions report a missing and an overlong path alike");
+
+// One round of a traceback: n hits in launch order and the device buffers that the kernels of either precision share.
+template <class Real> struct TraceRound
+{
+    unsigned n = 0;
+    std::vector<unsigned> ord, first; // [n] the caller's index of each hit; [classes + 1] where each launch class starts
+    Real *work = nullptr;             // the context's work area
+    DevBuf<uint64_t> woff;            // [n] each hit's part of it, in values
+    DevBuf<Real> alt;                 // [n]
+    DevBuf<uint32_t> soff, nsteps;    // [n + 1] each hit's part of steps; [n] its steps, or DCP_TRACE_NO_PATH / _TOO_LONG
+    DevBuf<dcp_step> steps;
+};
+
+// The traceback of both precisions around its launches.  Per hit h: need[h] values of work area, cap[h] steps of
+// capacity (an estimate -- the walk counts past it, and a hit whose path is longer is traced once more at its exact
+// count) and its launch class cls[h].  The hits are cut into rounds of at most `budget` values of work area and 2^32 - 1
+// steps; round(TraceRound) uploads what only its precision needs and enqueues forward pass and walk on the context
+// stream.  `model` names the path in the "no finite path" error.
+template <class Hit, class Real, class Round>
+int trace_rounds(dcp_gpu_ctx *c, Hit const *hits, unsigned nhits, std::vector<uint64_t> const &need, std::vector<uint32_t> &cap,
+                 std::vector<int> const &cls, int nclasses, bool sort_by_class, uint64_t budget, char const *model,
+                 struct dcp_step *steps_out, unsigned cap_steps, uint32_t *step_off, Real *alt_out, Round round)
+{
+    int rc = DCP_OK;
+    std::vector<std::vector<dcp_step>> got(nhits);
+    std::vector<unsigned> todo(nhits);
+    std::iota(todo.begin(), todo.end(), 0u);
+    for (int pass = 0; !todo.empty(); ++pass)
+    {
+        std::vector<unsigned> again; // hits whose paths exceeded their capacity
+        for (size_t t0 = 0; t0 < todo.size();)
+        {
+            size_t t1 = t0;
+            uint64_t work = 0, scap = 0;
+            while (t1 < todo.size() &&
+                   (t1 == t0 || (work + need[todo[t1]] <= budget && scap + cap[todo[t1]] <= UINT32_MAX)))
+                work += need[todo[t1]], scap += cap[todo[t1]], ++t1;
+            unsigned const n = (unsigned)(t1 - t0);
+            TraceRound<Real> r;
+            r.n = n;
+            // this round's hits in launch-class order (the forward launches take contiguous pair lists); results go back
+            // to the caller's order on the host
+            std::vector<unsigned> &ord = r.ord, &first = r.first;
+            ord.assign(todo.begin() + t0, todo.begin() + t1);
+            if (sort_by_class) std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return cls[x] < cls[y]; });
+            std::vector<uint64_t> woff(n);
+            std::vector<uint32_t> soff(n + 1, 0);
+            first.assign(nclasses + 1, 0u);
+            uint64_t acc = 0;
+            for (unsigned i = 0; i < n; ++i)
+            {
+                unsigned const h = ord[i];
+                woff[i] = acc;
+                acc += need[h];
+                soff[i + 1] = soff[i] + cap[h];
+                first[cls[h] + 1] = i + 1u;
+            }
+            for (int k = 1; k <= nclasses; ++k)
+                if (first[k] < first[k - 1]) first[k] = first[k - 1];
+            // one work area per context, kept between calls: floats, or the double traceback's values in the same bytes
+            size_t const work_floats = (size_t)(work * (sizeof(Real) / sizeof(float)));
+            if (c->d_trace_work.n < work_floats) HIP_TRY(c, c->d_trace_work.alloc(work_floats));
+            r.work = reinterpret_cast<Real *>(c->d_trace_work.p);
+            HIP_TRY(c, r.alt.alloc(n));
+            HIP_TRY(c, r.woff.alloc(n));
+            HIP_TRY(c, r.soff.alloc(n + 1));
+            HIP_TRY(c, r.nsteps.alloc(n));
+            HIP_TRY(c, r.steps.alloc(scap));
+            HIP_TRY(c, hipMemcpy(r.woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(r.soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (int e = round(r)) return e;
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            std::vector<uint32_t> ns(n);
+            std::vector<dcp_step> st(scap);
+            std::vector<Real> alts(n);
+            HIP_TRY(c, hipMemcpy(ns.data(), r.nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(st.data(), r.steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(alts.data(), r.alt.p, n * sizeof(Real), hipMemcpyDeviceToHost));
+            for (unsigned i = 0; i < n; ++i)
+            {
+                unsigned const h = ord[i];
+                if (alt_out) alt_out[h] = alts[i];
+                if (ns[i] == DCP_TRACE_NO_PATH)
+                    rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite %s path", hits[h].seq_idx, hits[h].profile_idx, model);
+                else if (ns[i] == DCP_TRACE_TOO_LONG)
+                    rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
+                                 hits[h].profile_idx);
+                else if (ns[i] > cap[h] && pass == 0)
+                    cap[h] = ns[i], again.push_back(h);
+                else if (ns[i] > cap[h])
+                    rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
+                else
+                    got[h].assign(st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
+            }
+            t0 = t1;
+        }
+        if (rc) return rc;
+        todo.swap(again);
+    }
+    uint64_t total_steps = 0;
+    for (unsigned h = 0; h < nhits; ++h)
+    {
+        total_steps += got[h].size();
+        if (total_steps > UINT32_MAX) return c->fail(DCP_EFAIL, "the paths of %u hits exceed 2^32 - 1 steps", nhits);
+        step_off[h + 1] = (uint32_t)total_steps;
+    }
+    if (total_steps > cap_steps || (total_steps && !steps_out)) return DCP_ENOMEM;
+    for (unsigned h = 0; h < nhits; ++h)
+        if (!got[h].empty()) std::memcpy(steps_out + step_off[h], got[h].data(), got[h].size() * sizeof(dcp_step));
+    return DCP_OK;
+}
+
+} // namespace
 
 extern "C" {
 
@@ -436,8 +692,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
         if (profiles[p] && dcp_profile_precision(profiles[p]) == 64)
             return c->fail(DCP_EINVAL, "profile %u was built in double: upload it with dcp_gpu_db_upload64", p);
     HIP_TRY(c, hipSetDevice(c->device));
-    c->scanned = false;
-    c->redo_pending = false;
+    void_last_scan(c);
     if (c->precision == 64) // one resident DB per context: the double one goes
     {
         c->f64.release();
@@ -894,15 +1149,7 @@ int dcp_gpu_db_fetch_match_table(dcp_gpu_ctx *c, unsigned p, float *out)
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = ensure_rowsweep_layout(c)) return rc;
     for (dcp_prof_meta const &m : c->metas)
-        if (m.pidx == p)
-        {
-            // rows of (possibly shared) length ldk from the profile's first column to its last row's last node
-            std::vector<float> tab((size_t)(DCP_NCODES - 1) * m.ldk + m.core_size);
-            HIP_TRY(c, hipMemcpy(tab.data(), c->d_emis_match.p + m.emis_off, tab.size() * sizeof(float), hipMemcpyDeviceToHost));
-            for (unsigned code = 0; code < DCP_NCODES; ++code)
-                std::memcpy(out + (size_t)code * m.core_size, &tab[(size_t)code * m.ldk], sizeof(float) * m.core_size);
-            return DCP_OK;
-        }
+        if (m.pidx == p) return fetch_table_rows(c, c->d_emis_match.p + m.emis_off, m.ldk, m.core_size, out);
     return DCP_EINVAL;
 }
 
@@ -912,14 +1159,7 @@ int dcp_gpu_db_fetch_match_table64(dcp_gpu_ctx *c, unsigned p, double *out)
     if (c->precision != 64) return c->fail(DCP_EINVAL, "the resident DB is float: it has no double match tables");
     HIP_TRY(c, hipSetDevice(c->device));
     for (dcp_f64_prof const &m : c->f64.profs)
-        if (m.pidx == p)
-        {
-            std::vector<double> tab((size_t)(DCP_NCODES - 1) * m.ldk + m.core_size);
-            HIP_TRY(c, hipMemcpy(tab.data(), c->f64.d_tab.p + m.tab_off, tab.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (unsigned code = 0; code < DCP_NCODES; ++code)
-                std::memcpy(out + (size_t)code * m.core_size, &tab[(size_t)code * m.ldk], sizeof(double) * m.core_size);
-            return DCP_OK;
-        }
+        if (m.pidx == p) return fetch_table_rows(c, c->f64.d_tab.p + m.tab_off, m.ldk, m.core_size, out);
     return DCP_EINVAL;
 }
 
@@ -963,9 +1203,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // one resident DB per context: whatever was there goes, also if this upload fails half way
-    c->scanned = false;
-    c->redo_pending = false;
-    c->ring_check_pending = false;
+    void_last_scan(c);
     c->precision = 0;
     c->nprof = 0;
     c->f64.release();
@@ -1081,10 +1319,8 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     if (!c) return DCP_EINVAL;
     if (!seqs || !seq_off || nseqs == 0) return c->fail(DCP_EINVAL, "empty sequence batch");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->scanned = false;
-    c->redo_pending = false;           // the previous batch's scan is void
-    c->f64.redo_pending = false;
-    c->ring_check_pending = false;
+    void_last_scan(c); // the previous batch's scan
+    // the length order and the transposed word planes belong to the batch that was resident
     c->qorder_q0 = c->qorder_q1 = ~0u; // also when this upload fails half way
     std::vector<uint32_t> woff(nseqs), len(nseqs);
     uint64_t nwords = 0, total = 0;
@@ -1140,8 +1376,6 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     c->xt_multi = c->xt_h3 = -1;
     c->xt_explicit = false;
     c->xt64.clear();
-    // the length order and the transposed word planes belong to the batch that was resident
-    c->qorder_q0 = c->qorder_q1 = ~0u;
     return DCP_OK;
 }
 
@@ -1158,26 +1392,15 @@ int dcp_gpu_seqs_upload_text(dcp_gpu_ctx *c, char const *text, uint32_t const *s
 // ---------------------------------------------------------------------------
 // Scan
 // ---------------------------------------------------------------------------
-static int finish_scan(dcp_gpu_ctx *c);
-// protein_profile_setup once per sequence (length) instead of once per pair
+// the float DB's special transitions: resident for the whole batch, rebuilt when the flags change
 static int ensure_xtrans(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
 {
     if (c->xt_explicit) return DCP_OK;
     if (c->xt_multi == !!multi_hits && c->xt_h3 == !!hmmer3_compat) return DCP_OK;
-    std::vector<float> xt((size_t)c->nseqs * DCP_XSTRIDE, 0.0f);
-    std::map<uint32_t, std::vector<float>> by_len;
-    for (unsigned q = 0; q < c->nseqs; ++q)
-    {
-        auto it = by_len.find(c->seq_len[q]);
-        if (it == by_len.end())
-        {
-            std::vector<float> v(DCP_XSTRIDE, 0.0f);
-            int rc = dcp_xtrans(c->seq_len[q], multi_hits, hmmer3_compat, v.data());
-            if (rc) return c->fail(rc, "sequence cannot be empty");
-            it = by_len.emplace(c->seq_len[q], std::move(v)).first;
-        }
-        std::memcpy(&xt[(size_t)q * DCP_XSTRIDE], it->second.data(), sizeof(float) * DCP_XSTRIDE);
-    }
+    std::vector<uint32_t> seqs(c->nseqs);
+    std::iota(seqs.begin(), seqs.end(), 0u);
+    std::vector<float> xt;
+    if (int rc = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_XSTRIDE, xt)) return rc;
     HIP_TRY(c, hipMemcpyAsync(c->d_xtrans.p, xt.data(), xt.size() * sizeof(float),
                               hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1196,9 +1419,7 @@ int dcp_gpu_seqs_set_xtrans(dcp_gpu_ctx *c, float const *xt, unsigned nseqs)
         for (int i = 0; i < DCP_NXTRANS; ++i)
         {
             float const v = xt[(size_t)q * DCP_NXTRANS + i];
-            uint32_t bits; // this file is built with -fno-honor-nans: test the encoding, not v != v
-            std::memcpy(&bits, &v, sizeof bits);
-            if ((bits & 0x7fffffffu) > 0x7f800000u) return c->fail(DCP_EINVAL, "NaN special transition");
+            if (is_nan(v)) return c->fail(DCP_EINVAL, "NaN special transition");
             buf[(size_t)q * DCP_XSTRIDE + i] = v;
         }
     HIP_TRY(c, hipMemcpy(c->d_xtrans.p, buf.data(), buf.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -1213,11 +1434,7 @@ int dcp_gpu_seqs_set_xtrans64(dcp_gpu_ctx *c, double const *xt, unsigned nseqs)
     if (!c) return DCP_EINVAL;
     if (!xt || nseqs == 0 || nseqs != c->nseqs) return c->fail(DCP_EINVAL, "xtrans must cover the resident sequences");
     for (size_t i = 0; i < (size_t)nseqs * DCP_NXTRANS; ++i)
-    {
-        uint64_t bits; // this file is built with -fno-honor-nans: test the encoding, not v != v
-        std::memcpy(&bits, &xt[i], sizeof bits);
-        if ((bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return c->fail(DCP_EINVAL, "NaN special transition");
-    }
+        if (is_nan(xt[i])) return c->fail(DCP_EINVAL, "NaN special transition");
     c->xt64.assign(xt, xt + (size_t)nseqs * DCP_NXTRANS);
     c->xt_explicit = false; // one explicit set holds: the last one given
     c->xt_multi = c->xt_h3 = -1;
@@ -1242,9 +1459,9 @@ int dcp_gpu_set_hit_buffer(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void *n
     if (!c) return DCP_EINVAL;
     if ((hits_dev == nullptr) != (nhits_dev == nullptr) || (hits_dev && cap == 0))
         return c->fail(DCP_EINVAL, "hit buffer and counter must be given together");
-    c->ext_hits = (dcp_hit *)hits_dev;
-    c->ext_nhits = (unsigned *)nhits_dev;
-    c->ext_cap = hits_dev ? cap : 0;
+    c->res.ext_hits = (dcp_hit *)hits_dev;
+    c->res.ext_nhits = (unsigned *)nhits_dev;
+    c->res.ext_cap = hits_dev ? cap : 0;
     return DCP_OK;
 }
 
@@ -1253,9 +1470,9 @@ int dcp_gpu_hit_buffer(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsign
     if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
     if (c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a double DB: its hits are struct dcp_hit64 (dcp_gpu_fetch_hits64)");
-    *hits_dev = c->ext_hits ? (void *)c->ext_hits : (void *)c->d_hits.p;
-    *nhits_dev = c->ext_hits ? (void *)c->ext_nhits : (void *)c->d_nhits.p;
-    *cap = c->ext_hits ? c->ext_cap : c->hit_cap;
+    *hits_dev = c->res.hits();
+    *nhits_dev = c->res.nhits();
+    *cap = c->res.cap();
     return DCP_OK;
 }
 
@@ -1371,6 +1588,32 @@ static QlPlan plan_query_groups(unsigned const *len_sorted, unsigned nq, unsigne
     return pl;
 }
 
+// The queries [q_begin, q_end) by rising length (stable; entries relative to q_begin), their lengths in that order and
+// the plan that packs them into blocks of `slots` wavefront slots.
+namespace
+{
+struct SortedQueries
+{
+    std::vector<uint32_t> order;
+    std::vector<unsigned> len;
+    QlPlan plan;
+};
+} // namespace
+static SortedQueries sorted_query_plan(dcp_gpu_ctx const *c, unsigned q_begin, unsigned q_end, unsigned slots)
+{
+    unsigned const nq = q_end - q_begin;
+    SortedQueries s;
+    s.order.resize(nq);
+    std::iota(s.order.begin(), s.order.end(), 0u);
+    std::stable_sort(s.order.begin(), s.order.end(),
+                     [&](uint32_t x, uint32_t y) { return c->seq_len[q_begin + x] < c->seq_len[q_begin + y]; });
+    s.len.resize(nq);
+    for (unsigned i = 0; i < nq; ++i)
+        s.len[i] = c->seq_len[q_begin + s.order[i]];
+    s.plan = plan_query_groups(s.len.data(), nq, slots);
+    return s;
+}
+
 // The plan as plain arrays (host only; tests/test_query_slots.py checks its invariants on the CPU).
 extern "C" int dcp_plan_query_slots(unsigned const *len_sorted, unsigned nq, unsigned slots_per_block, unsigned *nblocks,
                                     unsigned long long *sum_block_rows, unsigned *plane_rows, unsigned *groups4,
@@ -1444,6 +1687,16 @@ static void rowsweep_variant(dcp_gpu_ctx const *c, int R, int W, unsigned nchunk
     if (forced && g > 0) *pf = c->rs_force_pf;
 }
 
+// Boundary columns of the f64 DB's segmented launch group, for the npairs pairs of it that a scan or a traceback round
+// sweeps: 5 doubles per row and wavefront, at most 1 GiB of them; the wavefronts stride over the pairs.
+static int f64_seg_columns(dcp_gpu_ctx *c, uint32_t lmax, uint64_t npairs, uint64_t *col_stride, uint64_t *seg_waves)
+{
+    *col_stride = 5ull * ((uint64_t)lmax + 1u);
+    *seg_waves = npairs ? std::min<uint64_t>(npairs, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / *col_stride)) : 0;
+    if (c->f64.d_col.n < *seg_waves * *col_stride) HIP_TRY(c, c->f64.d_col.alloc(*seg_waves * *col_stride));
+    return DCP_OK;
+}
+
 // A scan of the resident double DB: viterbi64_kernel<R> per launch group (dcp_f64.hip), or -- kernel 4 -- the
 // query-lane kernel (dcp_f64_qlane.hip) with the row sweep behind it on the pairs it could not finish; the LRT
 // filter in their epilogues, results in the f64 buffers.
@@ -1461,55 +1714,17 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     c->scanned = false;
     unsigned const nq = q_end - q_begin;
     bool const xt_given = !c->xt64.empty(); // dcp_gpu_seqs_set_xtrans64: the flags are ignored
-    // protein_profile_setup in double, once per length -- or the caller's rows
-    std::vector<double> xt((size_t)nq * DCP_F64_XSTRIDE, 0.0);
-    std::map<uint32_t, size_t> first_of_len;
-    uint32_t lmax = 0;
-    for (unsigned q = 0; q < nq; ++q)
-    {
-        uint32_t const L = c->seq_len[q_begin + q];
-        lmax = std::max(lmax, L);
-        if (xt_given)
-        {
-            std::memcpy(&xt[(size_t)q * DCP_F64_XSTRIDE], &c->xt64[(size_t)(q_begin + q) * DCP_NXTRANS], sizeof(double) * DCP_NXTRANS);
-            continue;
-        }
-        auto it = first_of_len.find(L);
-        if (it != first_of_len.end())
-        {
-            std::memcpy(&xt[(size_t)q * DCP_F64_XSTRIDE], &xt[it->second * DCP_F64_XSTRIDE], sizeof(double) * DCP_NXTRANS);
-            continue;
-        }
-        if (int rc = dcp_xtrans64(L, prm->multi_hits, prm->hmmer3_compat, &xt[(size_t)q * DCP_F64_XSTRIDE]))
-            return c->fail(rc, "sequence cannot be empty");
-        first_of_len.emplace(L, q);
-    }
+    std::vector<uint32_t> seqs(nq);
+    std::iota(seqs.begin(), seqs.end(), q_begin);
+    std::vector<double> xt;
+    if (int rc = fill_xtrans(c, seqs, prm->multi_hits, prm->hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
+    uint32_t const lmax = *std::max_element(c->seq_len.begin() + q_begin, c->seq_len.begin() + q_end);
     if (F.d_xt.n < xt.size()) HIP_TRY(c, F.d_xt.alloc(xt.size()));
     HIP_TRY(c, hipMemcpyAsync(F.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
 
-    size_t const npairs = (size_t)c->nseqs * c->nprof;
-    if (prm->keep_scores && F.d_null.n != npairs)
-    {
-        HIP_TRY(c, F.d_null.alloc(npairs));
-        HIP_TRY(c, F.d_alt.alloc(npairs));
-    }
-    F.have_scores = prm->keep_scores != 0;
-    unsigned const want_cap = (unsigned)std::min<size_t>(npairs, (size_t)1 << 22);
-    if (F.hit_cap < want_cap)
-    {
-        HIP_TRY(c, F.d_hits.alloc(want_cap));
-        F.hit_cap = want_cap;
-    }
-    if (!F.d_nhits.p) HIP_TRY(c, F.d_nhits.alloc(1));
-    // boundary columns of the segmented group: 5 doubles per row and wavefront, at most 1 GiB
-    uint64_t const col_stride = 5ull * ((uint64_t)lmax + 1u);
-    unsigned const nseg_prof = F.group_first[4] - F.group_first[3];
-    uint64_t seg_waves = 0;
-    if (nseg_prof)
-    {
-        seg_waves = std::min<uint64_t>((uint64_t)nseg_prof * nq, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / col_stride));
-        if (F.d_col.n < seg_waves * col_stride) HIP_TRY(c, F.d_col.alloc(seg_waves * col_stride));
-    }
+    HIP_TRY(c, F.res.ensure((size_t)c->nseqs * c->nprof, prm->keep_scores != 0));
+    uint64_t col_stride = 0, seg_waves = 0;
+    if (int rc = f64_seg_columns(c, lmax, (uint64_t)(F.group_first[4] - F.group_first[3]) * nq, &col_stride, &seg_waves)) return rc;
 
     dcp_f64_scan_args a{};
     a.nprof_total = c->nprof;
@@ -1522,15 +1737,12 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     a.xtrans = F.d_xt.p;
     a.nq = nq;
     a.q_base = q_begin;
-    a.out_null = F.have_scores ? F.d_null.p + (size_t)q_begin * c->nprof : nullptr;
-    a.out_alt = F.have_scores ? F.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
-    a.hits = F.d_hits.p;
-    a.nhits = F.d_nhits.p;
-    a.hit_cap = F.hit_cap;
-    uint64_t thr_bits; // this file is built with -fno-honor-nans: test the encoding for the NaN sentinel
-    std::memcpy(&thr_bits, &c->lrt_threshold64, sizeof thr_bits);
-    bool const thr_unset = (thr_bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
-    a.lrt_threshold = thr_unset ? (double)prm->lrt_threshold : c->lrt_threshold64;
+    a.out_null = F.res.have_scores ? F.res.d_null.p + (size_t)q_begin * c->nprof : nullptr;
+    a.out_alt = F.res.have_scores ? F.res.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
+    a.hits = F.res.hits();
+    a.nhits = F.res.nhits();
+    a.hit_cap = F.res.cap();
+    a.lrt_threshold = is_nan(c->lrt_threshold64) ? (double)prm->lrt_threshold : c->lrt_threshold64; // NaN: not set
     bool const qlane = prm->kernel == 4;
     bool const redo = prm->multi_hits != 0 || xt_given;
     dcp_f64_qlane_args qa{};
@@ -1540,15 +1752,9 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         // the range's queries by rising length, packed into blocks of four wavefront slots as the float query-lane
         // kernels' batches are (plan_query_groups); a persistent grid of at most two blocks per CU, fewer where their
         // boundary planes ([the plan's plane rows][3][256] doubles each) would take too much memory
-        std::vector<uint32_t> qorder(nq);
-        for (unsigned q = 0; q < nq; ++q)
-            qorder[q] = q;
-        std::stable_sort(qorder.begin(), qorder.end(),
-                         [&](uint32_t x, uint32_t y) { return c->seq_len[q_begin + x] < c->seq_len[q_begin + y]; });
-        std::vector<unsigned> len_sorted(nq);
-        for (unsigned i = 0; i < nq; ++i)
-            len_sorted[i] = c->seq_len[q_begin + qorder[i]];
-        QlPlan const plan = plan_query_groups(len_sorted.data(), nq, DCP_F64_QL_LANES / 64u);
+        SortedQueries const sorted = sorted_query_plan(c, q_begin, q_end, DCP_F64_QL_LANES / 64u);
+        std::vector<uint32_t> const &qorder = sorted.order;
+        QlPlan const &plan = sorted.plan;
         unsigned const nqb = plan.nqb;
         uint64_t const ntasks = (uint64_t)c->nprof * nqb;
         uint64_t const plane_stride = (uint64_t)plan.plane_rows * 3u * DCP_F64_QL_LANES;
@@ -1611,7 +1817,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         HIP_TRY(c, hipMemsetAsync(F.d_task.p, 0, sizeof(unsigned), c->stream));
         HIP_TRY(c, hipMemsetAsync(F.d_redo_n.p, 0, 5 * sizeof(unsigned), c->stream));
     }
-    HIP_TRY(c, hipMemsetAsync(F.d_nhits.p, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     unsigned launches = 0;
     if (qlane)
@@ -1666,53 +1872,15 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     c->last_redo_pairs = 0;
     F.redo_pending = qlane && redo;
     c->last_overlapped = false;
-    c->have_scores = false;
+    c->res.have_scores = false;
     c->last_f64 = true;
     c->scanned = true;
     return DCP_OK;
 }
 
-int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_begin,
-                       unsigned q_end)
+// The row-sweep kernels' argument block for the queries [q_begin, q_end) of the resident batch.
+static dcp_scan_args scan_args(dcp_gpu_ctx const *c, struct dcp_scan_params const *prm, unsigned q_begin, unsigned q_end)
 {
-    if (!c || !prm) return DCP_EINVAL;
-    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
-    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
-    if (q_begin >= q_end || q_end > c->nseqs) return c->fail(DCP_EINVAL, "bad sequence range");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (c->precision == 64) return scan64(c, prm, q_begin, q_end);
-    c->last_f64 = false;
-    // One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST
-    // scan.  A scan enqueued while the previous one still has unchecked redo lists first completes
-    // that one (its overflow re-run included), so nothing of it is silently half done.
-    if (c->redo_pending || c->ring_check_pending)
-        if (int rc = finish_scan(c)) return rc;
-    if (!c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
-
-    if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
-
-    size_t const npairs = (size_t)c->nseqs * c->nprof;
-    if (prm->keep_scores)
-    {
-        if (c->d_null.n != npairs)
-        {
-            HIP_TRY(c, c->d_null.alloc(npairs));
-            HIP_TRY(c, c->d_alt.alloc(npairs));
-        }
-    }
-    c->have_scores = prm->keep_scores != 0;
-    unsigned want_cap = (unsigned)std::min<size_t>(npairs, (size_t)1 << 22);
-    if (!c->ext_hits && c->hit_cap < want_cap)
-    {
-        HIP_TRY(c, c->d_hits.alloc(want_cap));
-        c->hit_cap = want_cap;
-    }
-    if (!c->d_nhits.p) HIP_TRY(c, c->d_nhits.alloc(1));
-    dcp_hit *const hits_p = c->ext_hits ? c->ext_hits : c->d_hits.p;
-    unsigned *const nhits_p = c->ext_hits ? c->ext_nhits : c->d_nhits.p;
-    unsigned const hits_cap = c->ext_hits ? c->ext_cap : c->hit_cap;
-
     dcp_scan_args a{};
     a.profs = c->d_metas.p;
     a.emis_match = c->d_emis_match.p;
@@ -1725,11 +1893,11 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     a.seq_woff = c->d_seq_woff.p + q_begin;
     a.seq_len = c->d_seq_len.p + q_begin;
     a.xtrans = c->d_xtrans.p + (size_t)q_begin * DCP_XSTRIDE;
-    a.out_null = c->have_scores ? c->d_null.p + (size_t)q_begin * c->nprof : nullptr;
-    a.out_alt = c->have_scores ? c->d_alt.p + (size_t)q_begin * c->nprof : nullptr;
-    a.hits = hits_p;
-    a.nhits = nhits_p;
-    a.hit_cap = hits_cap;
+    a.out_null = c->res.have_scores ? c->res.d_null.p + (size_t)q_begin * c->nprof : nullptr;
+    a.out_alt = c->res.have_scores ? c->res.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
+    a.hits = c->res.hits();
+    a.nhits = c->res.nhits();
+    a.hit_cap = c->res.cap();
     a.lrt_threshold = prm->lrt_threshold;
     a.nprof_total = c->nprof;
     a.nseqs = nq;
@@ -1740,286 +1908,265 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     // 4 MB L2 holds tables of (C3 step: 848 -> 879 Gcell/s from 8 to 1; 25 profiles x 256 queries: 8.8 -> 1.8 ms).
     a.qchunk = 1u;
     a.nchunks = (nq + a.qchunk - 1) / a.qchunk;
-    c->last_q0 = q_begin;
-    c->last_q1 = q_end;
+    return a;
+}
 
-    // Queries per block of the single-stage query-lane kernel.  (Narrow 64- / 128-query blocks were tried for
-    // small batches: hipOccupancyMaxActiveBlocksPerMultiprocessor reports three 54.5 KB blocks per CU, the
-    // measured rate is that of two -- profiles/r02/latency_probe_narrow_blocks_attempt.txt -- so they are gone.)
-    unsigned ql_nt = dcp_qlane_block_size(), ql_blocks_per_cu = 2; // 2 x 54.5 KB of LDS, 2 x 4 wavefronts of 256 VGPRs
-    // up to 64 queries: the three-independent-wavefronts variant (64 queries per task, 3 busy wavefronts per CU)
-    // (since the row sweep went from 370 to 850 Gcell/s the automatic choice no longer reaches it:
-    // 64 queries 283 ms there against 330 ms here; it is what kernel = 2 runs for such batches)
-    bool const w3 = nq <= 64u;
-    if (w3) ql_nt = 64u, ql_blocks_per_cu = 3; // counted in wavefront slots
-    // kernel choice: the query-lane kernel needs enough queries to fill its lanes
-    int kernel = prm->kernel;
-    if (kernel == 0)
-    {
-        {
-            // Cost model fitted to profiles/latency_probe.py and profiles/smalldb_probe.py:
-            //   row sweep    cells of each size class / that class's rate (kClassRate: 0.5-1.05 Tcell/s with one
-            //                wavefront per pair, 0.4-0.6 with 4-16) + one pass over the emission tables at
-            //                3 TB/s (a small batch streams them from HBM: 20k profiles, 16 queries: 103 ms =
-            //                67 + 36) + the last task's row chain
-            //   query lane   max(longest task, all tile rows / resident blocks); a tile row of a block
-            //                takes 0.52 us with one busy wavefront, 0.73 us with four.
-            // On the 20k-profile DB the switch comes at about 150 queries since round 3 (128 queries: 484 ms in
-            // the row sweep, 480 in the single-stage query-lane kernel; round 2: at about 115); a DB of a few
-            // hundred profiles stays with the row sweep up to several hundred queries (its tasks cannot fill the grid).
-            unsigned const NTq = ql_nt;
-            std::vector<unsigned> len(c->seq_len.begin() + q_begin, c->seq_len.begin() + q_end);
-            std::sort(len.begin(), len.end());
-            double sum_len = 0;
-            for (unsigned L : len)
-                sum_len += L;
-            // rows a tile costs, summed over the blocks of wavefront slots the batch is packed into (plan_query_groups)
-            QlPlan const plan = plan_query_groups(len.data(), nq, NTq / 64u);
-            unsigned const nqb = plan.nqb;
-            double const sum_block_lmax = (double)plan.sum_block_rows;
-            unsigned const lmax = len.back();
-            double t_rs = (double)c->sum_core * (DCP_NCODES * 4.0) / 3e12 + a.qchunk * lmax * 1.2e-6; // 1.2 us per row
-            // (the class rates are those of a 1 000-query step; between 64 and 256 queries the row sweep runs 5 %
-            // below them -- 128 queries 450 ms, 160: 558 -- profiles/r03/switch_probe.txt)
-            for (int k = 0; k < kNumClasses; ++k)
-                t_rs += 1.05 * (double)c->class_core[k] * sum_len / kClassRate[k];
-            unsigned const waves = std::max(1u, std::min(4u, plan.busy_slots));
-            // (round 3, 20k-profile DB: 96 and 128 queries 477 / 480 ms, 256 queries 659 ms in the single-stage kernel)
-            static double const kTrow[4] = {0.52, 0.54, 0.62, 0.73}; // 144..191 queries: 544-555 ms
-            double const trow = (w3 ? 0.56 : kTrow[waves - 1u]) * 1e-6; // w3: + one add per gather
-            double const resident = (double)std::min<uint64_t>((uint64_t)c->nprof * nqb, (uint64_t)ql_blocks_per_cu * c->num_cus);
-            double const t_ql = std::max((double)c->max_tiles * lmax * 0.52e-6,
-                                         (double)c->sum_tiles * sum_block_lmax * trow / resident) +
-                                1e-4; // its redo launches
-            // The two-stage variant (512-thread blocks, two tiles of a profile in flight) wins once the
-            // query blocks are mostly full -- measured on the C3 DB (profiles/r02/latency_probe.txt):
-            // 256 queries 641 vs 678 ms, 1024 queries 2508 vs 2657 ms (0.94); below that its idle
-            // wavefronts still sit through every barrier (128 queries 583 vs 514 ms).  With fewer tasks
-            // than blocks fit on the chip it takes 0.66 of the single-stage time (profiles/smalldb_probe.py).
-            bool const stage2 = nq > 192u; // 192 queries (three full wavefronts per block): 555 ms single-stage, 569 two-stage; 224: 654 / 628
-            double const fill = std::min(1.0, (double)c->nprof * nqb / (4.0 * c->num_cus));
-            double const t_q = stage2 ? t_ql * (0.66 + 0.28 * fill) : t_ql;
-            kernel = t_q < t_rs ? (stage2 ? 3 : 2) : 1;
-            // a batch with very long sequences cannot keep enough blocks resident: row sweep instead
-            if (lmax > 200000u) kernel = 1;
-        }
-    }
-    if (kernel < 1 || kernel > 3) return c->fail(DCP_EINVAL, "unknown kernel %d", kernel);
-    bool const two_stage = kernel == 3; // the query-lane kernel's two-stage variant (dcp_qlane.hip)
-    c->last_kernel_variant = kernel;
-    if (two_stage) kernel = 2;
-    c->last_kernel = kernel;
-    if (two_stage) ql_nt = dcp_qlane_block_size(), ql_blocks_per_cu = 1; // 2 x 256 queries' wavefronts, one block per CU
-    bool const use_w3 = w3 && !two_stage;
-    if (kernel == 2)
-    {
-        // queries sorted by length, cut into 64-query groups, the groups packed into wavefront slots (plan_query_groups)
-        if (c->qorder_q0 != q_begin || c->qorder_q1 != q_end || c->qorder_nt != ql_nt)
-        {
-            unsigned const NTq = ql_nt, slots = NTq / 64u;
-            std::vector<uint32_t> ord(nq);
-            for (unsigned i = 0; i < nq; ++i)
-                ord[i] = i;
-            std::stable_sort(ord.begin(), ord.end(), [&](uint32_t x, uint32_t y) {
-                return c->seq_len[q_begin + x] < c->seq_len[q_begin + y];
-            });
-            std::vector<unsigned> len_sorted(nq);
-            for (unsigned i = 0; i < nq; ++i)
-                len_sorted[i] = c->seq_len[q_begin + ord[i]];
-            QlPlan const plan = plan_query_groups(len_sorted.data(), nq, slots);
-            unsigned const nqb = plan.nqb;
-            if ((uint64_t)plan.plane_rows * NTq * 4u > 0xffffffffull) // 32-bit byte offsets into a block's planes
-                return c->fail(DCP_ENOMEM, "sequences too long for the query-lane kernel (%u plane rows): use kernel = 1", plan.plane_rows);
-            // pinned staging: [nq] order, [nqb + 1] plane offsets, [nslots + 1] slot table, 4 words per group
-            size_t const nslot_words = (size_t)nqb * slots + 1u, ngroup_words = plan.groups.size() * 4u;
-            size_t const need_stage = (size_t)nq + nqb + 1u + nslot_words + ngroup_words;
-            if (!c->ev_qstage) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_qstage, hipEventDisableTiming));
-            else HIP_TRY(c, hipEventSynchronize(c->ev_qstage)); // the previous layout's copies have left the buffer
-            if (c->h_qstage_n < need_stage)
-            {
-                if (c->h_qstage) (void)hipHostFree(c->h_qstage);
-                c->h_qstage = nullptr, c->h_qstage_n = 0;
-                HIP_TRY(c, hipHostMalloc((void **)&c->h_qstage, need_stage * sizeof(uint32_t), hipHostMallocDefault));
-                c->h_qstage_n = need_stage;
-            }
-            uint32_t *const h_ord = c->h_qstage, *const wt_off = h_ord + nq, *const h_slots = wt_off + nqb + 1u,
-                           *const h_groups = h_slots + nslot_words;
-            static_assert(sizeof(dcp_ql_group) == 4 * sizeof(uint32_t), "group records travel as four words");
-            std::memcpy(h_ord, ord.data(), nq * sizeof(uint32_t));
-            std::memcpy(h_slots, plan.slot_first.data(), nslot_words * sizeof(uint32_t));
-            std::memcpy(h_groups, plan.groups.data(), ngroup_words * sizeof(uint32_t));
-            // per block: its window plane, uint16 [block rows + 8][NTq] (the prefetch runs a few rows past the end)
-            uint64_t tot = 0;
-            wt_off[0] = 0u;
-            for (unsigned b = 0; b < nqb; ++b)
-            {
-                tot += ((uint64_t)plan.block_rows[b] + 8u) * NTq / 2u;
-                if (tot > 0xffffffffull) return c->fail(DCP_EINVAL, "sequence batch too large");
-                wt_off[b + 1u] = (uint32_t)tot;
-            }
-            if (c->d_qorder.n < nq) HIP_TRY(c, c->d_qorder.alloc(nq));
-            if (c->d_wt_off.n < nqb + 1u) HIP_TRY(c, c->d_wt_off.alloc(nqb + 1u));
-            if (c->d_slot_first.n < nslot_words) HIP_TRY(c, c->d_slot_first.alloc(nslot_words));
-            if (c->d_ql_groups.n < plan.groups.size()) HIP_TRY(c, c->d_ql_groups.alloc(plan.groups.size()));
-            if (c->d_words_t.n < tot) HIP_TRY(c, c->d_words_t.alloc((size_t)tot));
-            HIP_TRY(c, hipMemcpyAsync(c->d_qorder.p, h_ord, nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->d_wt_off.p, wt_off, (nqb + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->d_slot_first.p, h_slots, nslot_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->d_ql_groups.p, h_groups, ngroup_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipEventRecord(c->ev_qstage, c->stream));
-            dcp_qlane_args ta{};
-            ta.seq_words = a.seq_words, ta.seq_woff = a.seq_woff, ta.seq_len = a.seq_len;
-            ta.qorder = c->d_qorder.p, ta.words_t = c->d_words_t.p, ta.wt_off = c->d_wt_off.p;
-            ta.groups = c->d_ql_groups.p, ta.slot_first = c->d_slot_first.p;
-            ta.nseqs = nq, ta.nqblocks = nqb;
-            if (dcp_launch_qlane_transpose(&ta, NTq, c->stream)) return c->fail(DCP_EFAIL, "no kernel for %u-query blocks", NTq);
-            HIP_TRY(c, hipGetLastError());
-            c->qorder_q0 = q_begin, c->qorder_q1 = q_end, c->qorder_nt = NTq;
-            c->ql_nqb = nqb, c->ql_plane_rows = plan.plane_rows + 8u;
-        }
-        if (!c->d_task_counter.p) HIP_TRY(c, c->d_task_counter.alloc(1));
-    }
+// Kernel 0: 1 (row sweep), 2 (query lane) or 3 (its two-stage variant) for the queries [q_begin, q_end), by a
+// cost model fitted to profiles/latency_probe.py and profiles/smalldb_probe.py:
+//   row sweep    cells of each size class / that class's rate (kClassRate: 0.5-1.05 Tcell/s with one
+//                wavefront per pair, 0.4-0.6 with 4-16) + one pass over the emission tables at
+//                3 TB/s (a small batch streams them from HBM: 20k profiles, 16 queries: 103 ms =
+//                67 + 36) + the last task's row chain
+//   query lane   max(longest task, all tile rows / resident blocks); a tile row of a block
+//                takes 0.52 us with one busy wavefront, 0.73 us with four.
+// On the 20k-profile DB the switch comes at about 150 queries since round 3 (128 queries: 484 ms in
+// the row sweep, 480 in the single-stage query-lane kernel; round 2: at about 115); a DB of a few
+// hundred profiles stays with the row sweep up to several hundred queries (its tasks cannot fill the grid).
+// ql_nt, ql_blocks_per_cu, w3: how the single-stage query-lane kernel would take the batch.
+static int choose_kernel(dcp_gpu_ctx const *c, unsigned q_begin, unsigned q_end, unsigned qchunk, unsigned ql_nt,
+                         unsigned ql_blocks_per_cu, bool w3)
+{
+    unsigned const nq = q_end - q_begin;
+    // rows a tile costs, summed over the blocks of wavefront slots the batch is packed into (plan_query_groups)
+    SortedQueries const sorted = sorted_query_plan(c, q_begin, q_end, ql_nt / 64u);
+    QlPlan const &plan = sorted.plan;
+    double sum_len = 0;
+    for (unsigned L : sorted.len)
+        sum_len += L;
+    unsigned const nqb = plan.nqb;
+    double const sum_block_lmax = (double)plan.sum_block_rows;
+    unsigned const lmax = sorted.len.back();
+    double t_rs = (double)c->sum_core * (DCP_NCODES * 4.0) / 3e12 + qchunk * lmax * 1.2e-6; // 1.2 us per row
+    // (the class rates are those of a 1 000-query step; between 64 and 256 queries the row sweep runs 5 %
+    // below them -- 128 queries 450 ms, 160: 558 -- profiles/r03/switch_probe.txt)
+    for (int k = 0; k < kNumClasses; ++k)
+        t_rs += 1.05 * (double)c->class_core[k] * sum_len / kClassRate[k];
+    unsigned const waves = std::max(1u, std::min(4u, plan.busy_slots));
+    // (round 3, 20k-profile DB: 96 and 128 queries 477 / 480 ms, 256 queries 659 ms in the single-stage kernel)
+    static double const kTrow[4] = {0.52, 0.54, 0.62, 0.73}; // 144..191 queries: 544-555 ms
+    double const trow = (w3 ? 0.56 : kTrow[waves - 1u]) * 1e-6; // w3: + one add per gather
+    double const resident = (double)std::min<uint64_t>((uint64_t)c->nprof * nqb, (uint64_t)ql_blocks_per_cu * c->num_cus);
+    double const t_ql = std::max((double)c->max_tiles * lmax * 0.52e-6,
+                                 (double)c->sum_tiles * sum_block_lmax * trow / resident) +
+                        1e-4; // its redo launches
+    // The two-stage variant (512-thread blocks, two tiles of a profile in flight) wins once the
+    // query blocks are mostly full -- measured on the C3 DB (profiles/r02/latency_probe.txt):
+    // 256 queries 641 vs 678 ms, 1024 queries 2508 vs 2657 ms (0.94); below that its idle
+    // wavefronts still sit through every barrier (128 queries 583 vs 514 ms).  With fewer tasks
+    // than blocks fit on the chip it takes 0.66 of the single-stage time (profiles/smalldb_probe.py).
+    bool const stage2 = nq > 192u; // 192 queries (three full wavefronts per block): 555 ms single-stage, 569 two-stage; 224: 654 / 628
+    double const fill = std::min(1.0, (double)c->nprof * nqb / (4.0 * c->num_cus));
+    double const t_q = stage2 ? t_ql * (0.66 + 0.28 * fill) : t_ql;
+    // a batch with very long sequences cannot keep enough blocks resident: row sweep instead
+    if (lmax > 200000u) return 1;
+    return t_q < t_rs ? (stage2 ? 3 : 2) : 1;
+}
 
-    HIP_TRY(c, hipMemsetAsync(nhits_p, 0, sizeof(unsigned), c->stream));
-    c->last_launches = 0;
-    c->n_launched = 0;
-    if (kernel == 2)
+// What a query-lane launch with ql_nt queries per block needs of the range's queries: their length order, the plan that
+// packs 64-query groups into wavefront slots (plan_query_groups) and the blocks' transposed window planes.  Kept
+// between scans of the same range and block size.
+static int ensure_qlane_layout(dcp_gpu_ctx *c, dcp_scan_args const &a, unsigned q_begin, unsigned q_end, unsigned ql_nt)
+{
+    if (!c->d_task_counter.p) HIP_TRY(c, c->d_task_counter.alloc(1));
+    if (c->qorder_q0 == q_begin && c->qorder_q1 == q_end && c->qorder_nt == ql_nt) return DCP_OK;
+    unsigned const nq = q_end - q_begin, NTq = ql_nt, slots = NTq / 64u;
+    SortedQueries const sorted = sorted_query_plan(c, q_begin, q_end, slots);
+    QlPlan const &plan = sorted.plan;
+    unsigned const nqb = plan.nqb;
+    if ((uint64_t)plan.plane_rows * NTq * 4u > 0xffffffffull) // 32-bit byte offsets into a block's planes
+        return c->fail(DCP_ENOMEM, "sequences too long for the query-lane kernel (%u plane rows): use kernel = 1", plan.plane_rows);
+    // The length-sorted query order and the plane offsets travel through pinned host memory -- [nq] order, [nqb + 1]
+    // plane offsets, [nslots + 1] slot table, 4 words per group
+    size_t const nslot_words = (size_t)nqb * slots + 1u, ngroup_words = plan.groups.size() * 4u;
+    size_t const need_stage = (size_t)nq + nqb + 1u + nslot_words + ngroup_words;
+    if (!c->ev_qstage) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_qstage, hipEventDisableTiming));
+    else HIP_TRY(c, hipEventSynchronize(c->ev_qstage)); // the previous layout's copies have left the buffer
+    if (c->h_qstage_n < need_stage)
     {
-        dcp_qlane_args qa{};
-        qa.profs = c->d_ql_metas.p;
-        qa.emis_tiles = c->one_layout ? c->d_emis_match.p : c->d_emis_tiles.p;
-        qa.tiles_from_rows = c->one_layout ? 1u : 0u;
-        qa.emis_insert = c->d_emis_insert.p;
-        qa.emis_null = c->d_emis_null.p;
-        qa.ttrans = c->d_ttrans.p;
-        qa.seq_words = a.seq_words;
-        qa.seq_woff = a.seq_woff;
-        qa.seq_len = a.seq_len;
-        qa.xtrans = a.xtrans;
-        qa.qorder = c->d_qorder.p;
-        qa.words_t = c->d_words_t.p;
-        qa.wt_off = c->d_wt_off.p;
-        qa.groups = c->d_ql_groups.p;
-        qa.slot_first = c->d_slot_first.p;
-        qa.ring_stall = c->ring_stall;
-        qa.task_counter = c->d_task_counter.p;
-        qa.out_null = a.out_null;
-        qa.out_alt = a.out_alt;
-        qa.hits = hits_p;
-        qa.nhits = nhits_p;
-        qa.hit_cap = hits_cap;
-        qa.lrt_threshold = prm->lrt_threshold;
-        qa.nprof = c->nprof;
-        qa.nprof_total = c->nprof;
-        qa.nseqs = nq;
-        qa.q_base = q_begin;
-        qa.plane_rows = c->ql_plane_rows;
-        unsigned const NT = ql_nt;
-        qa.nqblocks = c->ql_nqb;
-        uint64_t const ntasks = (uint64_t)c->nprof * qa.nqblocks;
-        if (ntasks > 0xffffffffull) return c->fail(DCP_EINVAL, "scan too large for one launch");
-        qa.ntasks = (unsigned)ntasks;
-        // redo lists: pairs whose multi-hit feedback beat B0 go to the row-sweep kernel, which
-        // runs right behind the query-lane kernel on this stream (uni-hit scans have no feedback)
-        // (explicit transitions may carry E->B feedback; flagged profiles leave the kernel through the lists too)
-        bool const redo = prm->multi_hits != 0 || c->xt_explicit || (dcp_qlane_exact_e_by_redo() && c->any_exact_e);
-        unsigned redo_grid[kNumClasses] = {0};
-        if (redo)
-        {
-            if (int rc = ensure_rowsweep_layout(c)) return rc;
-            a.emis_match = c->d_emis_match.p;
-            uint64_t tot = 0;
-            uint64_t const cap_limit = c->redo_cap_limit; // per size class (2^26: 512 MB of pairs at most)
-            for (int k = 0; k < kNumClasses; ++k)
-            {
-                uint64_t const pairs = (uint64_t)nq * (c->class_first[k + 1] - c->class_first[k]);
-                unsigned const cap = (unsigned)std::min<uint64_t>(pairs, cap_limit);
-                qa.redo_base[k] = (unsigned)tot;
-                qa.redo_cap[k] = cap;
-                tot += cap;
-                uint64_t const tpb = dcp_rowsweep_tasks_per_block(kClasses[k].W);
-                uint64_t g = std::min<uint64_t>((cap + tpb - 1) / tpb, 8ull * c->num_cus);
-                redo_grid[k] = (unsigned)((g + 7) / 8 * 8);
-            }
-            if (c->d_redo.n < tot) HIP_TRY(c, c->d_redo.alloc((size_t)tot));
-        }
-        // counters, overflow flag and the ring's error word start every query-lane scan at zero (without redo the
-        // lists' capacities are 0: the counters are never written)
-        if (!c->d_redo_n.p) HIP_TRY(c, c->d_redo_n.alloc(DCP_MAX_CLASSES + 2));
-        HIP_TRY(c, hipMemsetAsync(c->d_redo_n.p, 0, (DCP_MAX_CLASSES + 2) * sizeof(unsigned), c->stream));
-        qa.redo = c->d_redo.p;
-        qa.redo_n = c->d_redo_n.p;
-        qa.redo_overflow = c->d_redo_n.p + DCP_MAX_CLASSES;
-        qa.ring_error = c->d_redo_n.p + DCP_MAX_CLASSES + 1;
-        // scratch = 3 planes x plane rows x NT floats per resident block; long sequences
-        // (SCHED_SEQ_SIZE allows 1 MiB) get fewer resident blocks so the planes stay within budget
-        uint64_t const per_block = (uint64_t)dcp_qlane_scratch_planes() * (uint64_t)qa.plane_rows * NT; // floats
-        uint64_t const budget = (uint64_t)64 << 28;                      // 64 GiB of floats / 4
-        uint64_t fit = per_block ? budget / per_block : 0;
-        // one 512-thread block per CU (two-stage) or two 256-thread blocks (single-stage)
-        uint64_t const resident_blocks = (uint64_t)ql_blocks_per_cu * c->num_cus; // w3: wavefront slots, 3 per block
-        unsigned nblocks = (unsigned)std::min<uint64_t>(std::min<uint64_t>(ntasks, resident_blocks), fit);
-        if (use_w3) nblocks = (nblocks + 2u) / 3u * 3u; // whole 3-slot blocks (scratch is sized for every slot)
-        if (nblocks == 0)
-            return c->fail(DCP_ENOMEM, "sequences too long for the query-lane kernel (%u plane rows): use kernel = 1", qa.plane_rows);
-        size_t const need = (size_t)nblocks * per_block;
-        if (c->d_scratch.n < need) HIP_TRY(c, c->d_scratch.alloc(need));
-        qa.scratch = c->d_scratch.p;
-        HIP_TRY(c, hipMemsetAsync(c->d_task_counter.p, 0, sizeof(unsigned), c->stream));
-        HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-        if (two_stage ? dcp_launch_qlane2(&qa, nblocks, c->stream)
-                      : use_w3 ? dcp_launch_qlane_w3(&qa, nblocks / 3u, c->stream)
-                               : dcp_launch_qlane(&qa, nblocks, NT, c->stream))
-            return c->fail(DCP_EFAIL, "query-lane launch failed");
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], c->stream));
-        c->launched_class[c->n_launched++] = -1;
-        c->last_launches = 1;
-        for (int k = 0; redo && k < kNumClasses; ++k)
-        {
-            if (redo_grid[k] == 0) continue;
-            a.pairs = c->d_redo.p + qa.redo_base[k];
-            a.npairs = c->d_redo_n.p + k;
-            a.pair_cap = qa.redo_cap[k];
-            a.first_prof = 0;
-            a.nprof = c->nprof;
-            SizeClass const sc = kClasses[k];
-            if (dcp_launch_rowsweep(sc.R, sc.W, &a, redo_grid[k], c->stream))
-                return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
-            HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], c->stream));
-            c->launched_class[c->n_launched++] = k;
-            c->last_launches++;
-        }
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-        c->scanned = true;
-        c->redo_pending = redo;
-        c->ring_check_pending = two_stage;
-        c->last_redo_pairs = 0;
-        c->last_prm = *prm;
-        return DCP_OK;
+        if (c->h_qstage) (void)hipHostFree(c->h_qstage);
+        c->h_qstage = nullptr, c->h_qstage_n = 0;
+        HIP_TRY(c, hipHostMalloc((void **)&c->h_qstage, need_stage * sizeof(uint32_t), hipHostMallocDefault));
+        c->h_qstage_n = need_stage;
     }
-    if (int rc = ensure_rowsweep_layout(c)) return rc;
-    a.emis_match = c->d_emis_match.p;
-    c->redo_pending = false;
-    c->last_redo_pairs = 0;
+    uint32_t *const h_ord = c->h_qstage, *const wt_off = h_ord + nq, *const h_slots = wt_off + nqb + 1u,
+                   *const h_groups = h_slots + nslot_words;
+    static_assert(sizeof(dcp_ql_group) == 4 * sizeof(uint32_t), "group records travel as four words");
+    std::memcpy(h_ord, sorted.order.data(), nq * sizeof(uint32_t));
+    std::memcpy(h_slots, plan.slot_first.data(), nslot_words * sizeof(uint32_t));
+    std::memcpy(h_groups, plan.groups.data(), ngroup_words * sizeof(uint32_t));
+    // per block: its window plane, uint16 [block rows + 8][NTq] (the prefetch runs a few rows past the end)
+    uint64_t tot = 0;
+    wt_off[0] = 0u;
+    for (unsigned b = 0; b < nqb; ++b)
+    {
+        tot += ((uint64_t)plan.block_rows[b] + 8u) * NTq / 2u;
+        if (tot > 0xffffffffull) return c->fail(DCP_EINVAL, "sequence batch too large");
+        wt_off[b + 1u] = (uint32_t)tot;
+    }
+    if (c->d_qorder.n < nq) HIP_TRY(c, c->d_qorder.alloc(nq));
+    if (c->d_wt_off.n < nqb + 1u) HIP_TRY(c, c->d_wt_off.alloc(nqb + 1u));
+    if (c->d_slot_first.n < nslot_words) HIP_TRY(c, c->d_slot_first.alloc(nslot_words));
+    if (c->d_ql_groups.n < plan.groups.size()) HIP_TRY(c, c->d_ql_groups.alloc(plan.groups.size()));
+    if (c->d_words_t.n < tot) HIP_TRY(c, c->d_words_t.alloc((size_t)tot));
+    HIP_TRY(c, hipMemcpyAsync(c->d_qorder.p, h_ord, nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_wt_off.p, wt_off, (nqb + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_slot_first.p, h_slots, nslot_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ql_groups.p, h_groups, ngroup_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_qstage, c->stream));
+    dcp_qlane_args ta{};
+    ta.seq_words = a.seq_words, ta.seq_woff = a.seq_woff, ta.seq_len = a.seq_len;
+    ta.qorder = c->d_qorder.p, ta.words_t = c->d_words_t.p, ta.wt_off = c->d_wt_off.p;
+    ta.groups = c->d_ql_groups.p, ta.slot_first = c->d_slot_first.p;
+    ta.nseqs = nq, ta.nqblocks = nqb;
+    if (dcp_launch_qlane_transpose(&ta, NTq, c->stream)) return c->fail(DCP_EFAIL, "no kernel for %u-query blocks", NTq);
+    HIP_TRY(c, hipGetLastError());
+    c->qorder_q0 = q_begin, c->qorder_q1 = q_end, c->qorder_nt = NTq;
+    c->ql_nqb = nqb, c->ql_plane_rows = plan.plane_rows + 8u;
+    return DCP_OK;
+}
+
+// A launch of the scan has been enqueued on `stream`: the event behind it (dcp_gpu_last_scan_launch_info times the
+// launches by them), the context stream's join on it when the launch ran on a forked stream, and the launch's record.
+static int record_launch(dcp_gpu_ctx *c, int k, bool is_redo, hipStream_t stream, bool join)
+{
+    HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], stream));
+    if (join) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->n_launched], 0));
+    c->launched_redo[c->n_launched] = is_redo; // the exact kernel behind a segmented sweep
+    c->launched_class[c->n_launched++] = k;    // -1: the query-lane launch
+    c->last_launches++;
+    return DCP_OK;
+}
+
+// The query-lane kernel (single-stage, its three-independent-wavefronts variant or two-stage) on the layout of
+// ensure_qlane_layout, and behind it the row sweep of each size class over the pairs the kernel handed on.
+static int launch_qlane_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, dcp_scan_args &a, unsigned NT,
+                             unsigned ql_blocks_per_cu, bool two_stage, bool use_w3)
+{
+    dcp_qlane_args qa{};
+    qa.profs = c->d_ql_metas.p;
+    qa.emis_tiles = c->one_layout ? c->d_emis_match.p : c->d_emis_tiles.p;
+    qa.tiles_from_rows = c->one_layout ? 1u : 0u;
+    qa.emis_insert = c->d_emis_insert.p;
+    qa.emis_null = c->d_emis_null.p;
+    qa.ttrans = c->d_ttrans.p;
+    qa.seq_words = a.seq_words;
+    qa.seq_woff = a.seq_woff;
+    qa.seq_len = a.seq_len;
+    qa.xtrans = a.xtrans;
+    qa.qorder = c->d_qorder.p;
+    qa.words_t = c->d_words_t.p;
+    qa.wt_off = c->d_wt_off.p;
+    qa.groups = c->d_ql_groups.p;
+    qa.slot_first = c->d_slot_first.p;
+    qa.ring_stall = c->ring_stall;
+    qa.task_counter = c->d_task_counter.p;
+    qa.out_null = a.out_null;
+    qa.out_alt = a.out_alt;
+    qa.hits = a.hits;
+    qa.nhits = a.nhits;
+    qa.hit_cap = a.hit_cap;
+    qa.lrt_threshold = prm->lrt_threshold;
+    qa.nprof = c->nprof;
+    qa.nprof_total = c->nprof;
+    qa.nseqs = a.nseqs;
+    qa.q_base = a.q_base;
+    qa.plane_rows = c->ql_plane_rows;
+    qa.nqblocks = c->ql_nqb;
+    uint64_t const ntasks = (uint64_t)c->nprof * qa.nqblocks;
+    if (ntasks > 0xffffffffull) return c->fail(DCP_EINVAL, "scan too large for one launch");
+    qa.ntasks = (unsigned)ntasks;
+    // redo lists: pairs whose multi-hit feedback beat B0 go to the row-sweep kernel, which
+    // runs right behind the query-lane kernel on this stream (uni-hit scans have no feedback)
+    // (explicit transitions may carry E->B feedback; flagged profiles leave the kernel through the lists too)
+    bool const redo = prm->multi_hits != 0 || c->xt_explicit || (dcp_qlane_exact_e_by_redo() && c->any_exact_e);
+    unsigned redo_grid[kNumClasses] = {0};
+    if (redo)
+    {
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+        a.emis_match = c->d_emis_match.p;
+        uint64_t tot = 0;
+        uint64_t const cap_limit = c->redo_cap_limit; // per size class (2^26: 512 MB of pairs at most)
+        for (int k = 0; k < kNumClasses; ++k)
+        {
+            uint64_t const pairs = (uint64_t)a.nseqs * (c->class_first[k + 1] - c->class_first[k]);
+            unsigned const cap = (unsigned)std::min<uint64_t>(pairs, cap_limit);
+            qa.redo_base[k] = (unsigned)tot;
+            qa.redo_cap[k] = cap;
+            tot += cap;
+            uint64_t const tpb = dcp_rowsweep_tasks_per_block(kClasses[k].W);
+            uint64_t g = std::min<uint64_t>((cap + tpb - 1) / tpb, 8ull * c->num_cus);
+            redo_grid[k] = (unsigned)((g + 7) / 8 * 8);
+        }
+        if (c->d_redo.n < tot) HIP_TRY(c, c->d_redo.alloc((size_t)tot));
+    }
+    // counters, overflow flag and the ring's error word start every query-lane scan at zero (without redo the
+    // lists' capacities are 0: the counters are never written)
+    if (!c->d_redo_n.p) HIP_TRY(c, c->d_redo_n.alloc(DCP_MAX_CLASSES + 2));
+    HIP_TRY(c, hipMemsetAsync(c->d_redo_n.p, 0, (DCP_MAX_CLASSES + 2) * sizeof(unsigned), c->stream));
+    qa.redo = c->d_redo.p;
+    qa.redo_n = c->d_redo_n.p;
+    qa.redo_overflow = c->d_redo_n.p + DCP_MAX_CLASSES;
+    qa.ring_error = c->d_redo_n.p + DCP_MAX_CLASSES + 1;
+    // scratch = 3 planes x plane rows x NT floats per resident block; long sequences
+    // (SCHED_SEQ_SIZE allows 1 MiB) get fewer resident blocks so the planes stay within budget
+    uint64_t const per_block = (uint64_t)dcp_qlane_scratch_planes() * (uint64_t)qa.plane_rows * NT; // floats
+    uint64_t const budget = (uint64_t)64 << 28;                      // 64 GiB of floats / 4
+    uint64_t fit = per_block ? budget / per_block : 0;
+    // one 512-thread block per CU (two-stage) or two 256-thread blocks (single-stage)
+    uint64_t const resident_blocks = (uint64_t)ql_blocks_per_cu * c->num_cus; // w3: wavefront slots, 3 per block
+    unsigned nblocks = (unsigned)std::min<uint64_t>(std::min<uint64_t>(ntasks, resident_blocks), fit);
+    if (use_w3) nblocks = (nblocks + 2u) / 3u * 3u; // whole 3-slot blocks (scratch is sized for every slot)
+    if (nblocks == 0)
+        return c->fail(DCP_ENOMEM, "sequences too long for the query-lane kernel (%u plane rows): use kernel = 1", qa.plane_rows);
+    size_t const need = (size_t)nblocks * per_block;
+    if (c->d_scratch.n < need) HIP_TRY(c, c->d_scratch.alloc(need));
+    qa.scratch = c->d_scratch.p;
+    HIP_TRY(c, hipMemsetAsync(c->d_task_counter.p, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    // fork / join around the class launches when no single one fills the chip for long (2^22 pairs: 20 000 profiles x 209
-    // queries, i.e. every batch the automatic choice gives the row sweep; 112 .. 160 queries: 1 % faster than one launch
-    // after the other, profiles/r04/class_launch_order.txt)
-    bool const overlap = (uint64_t)nq * c->nprof < ((uint64_t)1 << 22);
-    c->last_overlapped = overlap;
-    // Multi-wavefront classes with a segmented-sweep kernel (dcp_kernels.hip): one wavefront per pair, one SEGMENT of
-    // the profile per launch, B(j) = N(j) + NB, the pairs with feedback finished by the exact kernel behind it.
-    // Per class: two boundary columns of lmax + 2 rows of 16 bytes per pair, and a redo list of all its pairs.  The
-    // columns of a class are capped at kSegColBytes: beyond, its queries are swept chunk by chunk.
-    unsigned lmax_scan = 0;
-    for (unsigned q = q_begin; q < q_end; ++q)
-        lmax_scan = std::max(lmax_scan, c->seq_len[q]);
-    unsigned const seg_stride = lmax_scan + 2u; // rows of 16 bytes per column
-    uint64_t const kSegColBytes = c->seg_col_bytes;
-    unsigned seg_blocks[kNumClasses] = {0}, seg_chunk[kNumClasses] = {0};
-    uint64_t seg_redo_off[kNumClasses] = {0}, seg_col_rows = 0, seg_redo_tot = 0;
+    if (two_stage ? dcp_launch_qlane2(&qa, nblocks, c->stream)
+                  : use_w3 ? dcp_launch_qlane_w3(&qa, nblocks / 3u, c->stream)
+                           : dcp_launch_qlane(&qa, nblocks, NT, c->stream))
+        return c->fail(DCP_EFAIL, "query-lane launch failed");
+    HIP_TRY(c, hipGetLastError());
+    if (int rc = record_launch(c, -1, false, c->stream, false)) return rc;
+    for (int k = 0; redo && k < kNumClasses; ++k)
+    {
+        if (redo_grid[k] == 0) continue;
+        a.pairs = c->d_redo.p + qa.redo_base[k];
+        a.npairs = c->d_redo_n.p + k;
+        a.pair_cap = qa.redo_cap[k];
+        a.first_prof = 0;
+        a.nprof = c->nprof;
+        SizeClass const sc = kClasses[k];
+        if (dcp_launch_rowsweep(sc.R, sc.W, &a, redo_grid[k], c->stream))
+            return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
+        if (int rc = record_launch(c, k, true, c->stream, false)) return rc;
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->scanned = true;
+    c->redo_pending = redo;
+    c->ring_check_pending = two_stage;
+    c->last_redo_pairs = 0;
+    c->last_prm = *prm;
+    return DCP_OK;
+}
+
+// Multi-wavefront classes with a segmented-sweep kernel (dcp_kernels.hip): one wavefront per pair, one SEGMENT of
+// the profile per launch, B(j) = N(j) + NB, the pairs with feedback finished by the exact kernel behind it.
+// Per class: two boundary columns of lmax + 2 rows of 16 bytes per pair, and a redo list of all its pairs.  The
+// columns of a class are capped at seg_col_bytes: beyond, its queries are swept chunk by chunk.
+struct SegSweepPlan
+{
+    unsigned stride = 0;                                     // rows of 16 bytes per column
+    unsigned chunk[kNumClasses] = {0};                       // queries per pass; 0: the class is not swept in segments
+    uint64_t redo_off[kNumClasses] = {0}, col_rows = 0, redo_tot = 0;
+};
+static SegSweepPlan plan_segsweep(dcp_gpu_ctx const *c, unsigned q_begin, unsigned q_end)
+{
+    SegSweepPlan sp;
+    unsigned const nq = q_end - q_begin;
+    sp.stride = *std::max_element(c->seq_len.begin() + q_begin, c->seq_len.begin() + q_end) + 2u;
     for (int k = 0; k < kNumClasses; ++k)
     {
         unsigned const np = c->class_first[k + 1] - c->class_first[k];
@@ -2032,22 +2179,87 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
         bool const want = c->seg_mode == 1 || (c->seg_mode < 0 && pairs >= 16ull * c->num_cus);
         bool const have = sc.W > 1 && want && np > 0 && pairs <= ((uint64_t)1 << 26);
         if (!have) continue;
-        // queries per chunk: np x chunk pairs x 2 columns x seg_stride x 16 bytes within the cap
-        uint64_t const per_query = (uint64_t)np * 2u * seg_stride * 16u;
-        uint64_t const chunk = std::min<uint64_t>(nq, kSegColBytes / per_query);
+        // queries per chunk: np x chunk pairs x 2 columns x stride x 16 bytes within the cap
+        uint64_t const per_query = (uint64_t)np * 2u * sp.stride * 16u;
+        uint64_t const chunk = std::min<uint64_t>(nq, c->seg_col_bytes / per_query);
         if (chunk == 0) continue; // very long sequences: the exact kernel
         if ((uint64_t)np * ((chunk + 3u) / 4u) > 0x7ffffff0ull) continue;
-        seg_blocks[k] = dcp_segsweep_blocks(np, (unsigned)chunk);
-        seg_chunk[k] = (unsigned)chunk;
+        sp.chunk[k] = (unsigned)chunk;
         // (classes run one after the other on a stream, or side by side on their own streams when the scan is small:
         // every class gets columns of its own)
-        seg_col_rows += (uint64_t)np * chunk * 2u * seg_stride;
-        seg_redo_off[k] = seg_redo_tot, seg_redo_tot += pairs;
+        sp.col_rows += (uint64_t)np * chunk * 2u * sp.stride;
+        sp.redo_off[k] = sp.redo_tot, sp.redo_tot += pairs;
     }
-    if (seg_col_rows)
+    return sp;
+}
+
+// Class k of a row-sweep scan in segments (a.first_prof / a.nprof: the class; col_base: its boundary columns), on ls.
+static int launch_segsweep_class(dcp_gpu_ctx *c, dcp_scan_args &a, int k, SegSweepPlan const &sp, float *col_base,
+                                 hipStream_t ls, bool overlap)
+{
+    unsigned const first = a.first_prof, last = first + a.nprof, np = a.nprof, chunk = sp.chunk[k], nq = a.nseqs;
+    uint64_t const ntasks = (uint64_t)a.nprof * a.nchunks;
+    SizeClass const sc = kClasses[k];
+    a.seg_stride = sp.stride;
+    a.seg_redo = c->d_seg_redo.p + sp.redo_off[k];
+    a.seg_redo_n = c->d_seg_redo_n.p + k;
+    a.seg_redo_cap = (unsigned)ntasks;
+    // Segment-major: launch s sweeps segment s of every pair of the chunk; the kernel boundary is the hand-off.
+    // The class's profiles are ordered by their segments' lane width: one run of launches per width.
+    for (unsigned sub = first; sub < last;)
     {
-        if (c->d_seg_scratch.n < seg_col_rows * 4u) HIP_TRY(c, c->d_seg_scratch.alloc((size_t)seg_col_rows * 4u));
-        if (c->d_seg_redo.n < seg_redo_tot) HIP_TRY(c, c->d_seg_redo.alloc((size_t)seg_redo_tot));
+        unsigned const segR = seg_r_of(c->metas[sub].core_size);
+        unsigned sub_end = sub, max_m = 0;
+        while (sub_end < last && seg_r_of(c->metas[sub_end].core_size) == segR)
+            max_m = std::max(max_m, c->metas[sub_end].core_size), ++sub_end;
+        unsigned const nsub = sub_end - sub, nseg_max = (max_m + 64u * segR - 1u) / (64u * segR);
+        a.first_prof = sub, a.nprof = nsub;
+        a.seg_col0 = col_base + (size_t)(sub - first) * chunk * 2u * sp.stride * 4u;
+        a.seg_col1 = a.seg_col0 + (size_t)nsub * chunk * sp.stride * 4u;
+        for (unsigned qc = 0; qc < nq; qc += chunk)
+        {
+            a.seg_q0 = qc, a.seg_nq = std::min(chunk, nq - qc);
+            for (unsigned sg = 0; sg < nseg_max; ++sg)
+            {
+                a.seg_index = sg;
+                if (dcp_launch_segsweep((int)segR, &a, dcp_segsweep_blocks(nsub, a.seg_nq), ls))
+                    return c->fail(DCP_EFAIL, "no segmented kernel for %u nodes per lane", segR);
+            }
+        }
+        sub = sub_end;
+    }
+    a.first_prof = first, a.nprof = np;
+    if (int rc = record_launch(c, k, false, ls, false)) return rc;
+    // the pairs it could not finish: the exact kernel in pair mode, right behind
+    a.pairs = a.seg_redo, a.npairs = a.seg_redo_n, a.pair_cap = a.seg_redo_cap;
+    a.first_prof = 0, a.nprof = c->nprof;
+    uint64_t g = std::min<uint64_t>(ntasks, 8ull * c->num_cus);
+    g = (g + 7u) / 8u * 8u;
+    if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)g, ls))
+        return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
+    return record_launch(c, k, true, ls, overlap);
+}
+
+// The row sweep over every pair of the range: one launch per non-empty size class (segmented, K profiles per
+// wavefront, or plain), one after the other or -- small scans -- side by side on the classes' own streams.
+static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_begin, unsigned q_end)
+{
+    unsigned const nq = q_end - q_begin;
+    if (int rc = ensure_rowsweep_layout(c)) return rc;
+    a.emis_match = c->d_emis_match.p;
+    c->redo_pending = false;
+    c->last_redo_pairs = 0;
+    HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    // fork / join around the class launches when no single one fills the chip for long (2^22 pairs: 20 000 profiles x 209
+    // queries, i.e. every batch the automatic choice gives the row sweep; 112 .. 160 queries: 1 % faster than one launch
+    // after the other, profiles/r04/class_launch_order.txt)
+    bool const overlap = (uint64_t)nq * c->nprof < ((uint64_t)1 << 22);
+    c->last_overlapped = overlap;
+    SegSweepPlan const sp = plan_segsweep(c, q_begin, q_end);
+    if (sp.col_rows)
+    {
+        if (c->d_seg_scratch.n < sp.col_rows * 4u) HIP_TRY(c, c->d_seg_scratch.alloc((size_t)sp.col_rows * 4u));
+        if (c->d_seg_redo.n < sp.redo_tot) HIP_TRY(c, c->d_seg_redo.alloc((size_t)sp.redo_tot));
         if (!c->d_seg_redo_n.p) HIP_TRY(c, c->d_seg_redo_n.alloc(DCP_MAX_CLASSES));
         HIP_TRY(c, hipMemsetAsync(c->d_seg_redo_n.p, 0, DCP_MAX_CLASSES * sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_start, c->stream)); // the forked streams wait for the counters' reset too
@@ -2071,56 +2283,11 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
         SizeClass const sc = kClasses[k];
         uint64_t const ntasks = (uint64_t)a.nprof * a.nchunks;
         if (ntasks > 0xffffffffull) return c->fail(DCP_EINVAL, "scan too large for one launch");
-        if (seg_blocks[k])
+        if (sp.chunk[k])
         {
-            unsigned const np = a.nprof, chunk = seg_chunk[k];
             float *const col_base = c->d_seg_scratch.p + seg_col_at;
-            seg_col_at += (uint64_t)np * chunk * 2u * seg_stride * 4u;
-            a.seg_stride = seg_stride;
-            a.seg_redo = c->d_seg_redo.p + seg_redo_off[k];
-            a.seg_redo_n = c->d_seg_redo_n.p + k;
-            a.seg_redo_cap = (unsigned)ntasks;
-            // Segment-major: launch s sweeps segment s of every pair of the chunk; the kernel boundary is the hand-off.
-            // The class's profiles are ordered by their segments' lane width: one run of launches per width.
-            for (unsigned sub = first; sub < last;)
-            {
-                unsigned const segR = seg_r_of(c->metas[sub].core_size);
-                unsigned sub_end = sub, max_m = 0;
-                while (sub_end < last && seg_r_of(c->metas[sub_end].core_size) == segR)
-                    max_m = std::max(max_m, c->metas[sub_end].core_size), ++sub_end;
-                unsigned const nsub = sub_end - sub, nseg_max = (max_m + 64u * segR - 1u) / (64u * segR);
-                a.first_prof = sub, a.nprof = nsub;
-                a.seg_col0 = col_base + (size_t)(sub - first) * chunk * 2u * seg_stride * 4u;
-                a.seg_col1 = a.seg_col0 + (size_t)nsub * chunk * seg_stride * 4u;
-                for (unsigned qc = 0; qc < nq; qc += chunk)
-                {
-                    a.seg_q0 = qc, a.seg_nq = std::min(chunk, nq - qc);
-                    for (unsigned sg = 0; sg < nseg_max; ++sg)
-                    {
-                        a.seg_index = sg;
-                        if (dcp_launch_segsweep((int)segR, &a, dcp_segsweep_blocks(nsub, a.seg_nq), ls))
-                            return c->fail(DCP_EFAIL, "no segmented kernel for %u nodes per lane", segR);
-                    }
-                }
-                sub = sub_end;
-            }
-            a.first_prof = first, a.nprof = np;
-            HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], ls));
-            c->launched_redo[c->n_launched] = false;
-            c->launched_class[c->n_launched++] = k;
-            c->last_launches++;
-            // the pairs it could not finish: the exact kernel in pair mode, right behind
-            a.pairs = a.seg_redo, a.npairs = a.seg_redo_n, a.pair_cap = a.seg_redo_cap;
-            a.first_prof = 0, a.nprof = c->nprof;
-            uint64_t g = std::min<uint64_t>(ntasks, 8ull * c->num_cus);
-            g = (g + 7u) / 8u * 8u;
-            if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)g, ls))
-                return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
-            HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], ls));
-            if (overlap) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->n_launched], 0));
-            c->launched_redo[c->n_launched] = true;
-            c->launched_class[c->n_launched++] = k;
-            c->last_launches++;
+            seg_col_at += (uint64_t)a.nprof * sp.chunk[k] * 2u * sp.stride * 4u;
+            if (int rc = launch_segsweep_class(c, a, k, sp, col_base, ls, overlap)) return rc;
             continue;
         }
         // K profiles per wavefront: the class of at most 64 nodes always (855-890 Gcell/s against 600 with one node
@@ -2148,24 +2315,17 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
                     return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch") : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
             }
             a.first_prof = first, a.nprof = last - first;
-            HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], ls));
-            if (overlap) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->n_launched], 0));
-            c->launched_redo[c->n_launched] = false;
-            c->launched_class[c->n_launched++] = k;
-            c->last_launches++;
-            continue;
         }
-        int stg, pf;
-        unsigned bw;
-        rowsweep_variant(c, sc.R, sc.W, a.nchunks, &stg, &bw, &pf);
-        if (int lrc = dcp_launch_rowsweep_grid(sc.R, sc.W, &a, stg, bw, ls, c->rs_pad_lds, pf))
-            return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch")
-                             : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d (stage %d, %u wavefronts)", sc.R, sc.W, stg, bw);
-        HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], ls));
-        if (overlap) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->n_launched], 0));
-        c->launched_redo[c->n_launched] = false;
-        c->launched_class[c->n_launched++] = k;
-        c->last_launches++;
+        else
+        {
+            int stg, pf;
+            unsigned bw;
+            rowsweep_variant(c, sc.R, sc.W, a.nchunks, &stg, &bw, &pf);
+            if (int lrc = dcp_launch_rowsweep_grid(sc.R, sc.W, &a, stg, bw, ls, c->rs_pad_lds, pf))
+                return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch")
+                                 : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d (stage %d, %u wavefronts)", sc.R, sc.W, stg, bw);
+        }
+        if (int rc = record_launch(c, k, false, ls, overlap)) return rc;
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
@@ -2173,10 +2333,73 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     return DCP_OK;
 }
 
-// (declared above dcp_gpu_scan_range)
+int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_begin,
+                       unsigned q_end)
+{
+    if (!c || !prm) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
+    if (q_begin >= q_end || q_end > c->nseqs) return c->fail(DCP_EINVAL, "bad sequence range");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->precision == 64) return scan64(c, prm, q_begin, q_end);
+    c->last_f64 = false;
+    // One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST
+    // scan.  A scan enqueued while the previous one still has unchecked redo lists first completes
+    // that one (its overflow re-run included), so nothing of it is silently half done.
+    if (c->redo_pending || c->ring_check_pending)
+        if (int rc = finish_scan(c)) return rc;
+    if (!c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+
+    if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
+    HIP_TRY(c, c->res.ensure((size_t)c->nseqs * c->nprof, prm->keep_scores != 0));
+    dcp_scan_args a = scan_args(c, prm, q_begin, q_end);
+    unsigned const nq = q_end - q_begin;
+    c->last_q0 = q_begin;
+    c->last_q1 = q_end;
+
+    // Queries per block of the single-stage query-lane kernel.  (Narrow 64- / 128-query blocks were tried for
+    // small batches: hipOccupancyMaxActiveBlocksPerMultiprocessor reports three 54.5 KB blocks per CU, the
+    // measured rate is that of two -- profiles/r02/latency_probe_narrow_blocks_attempt.txt -- so they are gone.)
+    unsigned ql_nt = dcp_qlane_block_size(), ql_blocks_per_cu = 2; // 2 x 54.5 KB of LDS, 2 x 4 wavefronts of 256 VGPRs
+    // up to 64 queries: the three-independent-wavefronts variant (64 queries per task, 3 busy wavefronts per CU)
+    // (since the row sweep went from 370 to 850 Gcell/s the automatic choice no longer reaches it:
+    // 64 queries 283 ms there against 330 ms here; it is what kernel = 2 runs for such batches)
+    bool const w3 = nq <= 64u;
+    if (w3) ql_nt = 64u, ql_blocks_per_cu = 3; // counted in wavefront slots
+    // kernel choice: the query-lane kernel needs enough queries to fill its lanes
+    int kernel = prm->kernel;
+    if (kernel == 0) kernel = choose_kernel(c, q_begin, q_end, a.qchunk, ql_nt, ql_blocks_per_cu, w3);
+    if (kernel < 1 || kernel > 3) return c->fail(DCP_EINVAL, "unknown kernel %d", kernel);
+    bool const two_stage = kernel == 3; // the query-lane kernel's two-stage variant (dcp_qlane.hip)
+    c->last_kernel_variant = kernel;
+    if (two_stage) kernel = 2;
+    c->last_kernel = kernel;
+    if (two_stage) ql_nt = dcp_qlane_block_size(), ql_blocks_per_cu = 1; // 2 x 256 queries' wavefronts, one block per CU
+    if (kernel == 2)
+        if (int rc = ensure_qlane_layout(c, a, q_begin, q_end, ql_nt)) return rc;
+
+    HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
+    c->last_launches = 0;
+    c->n_launched = 0;
+    if (kernel == 2) return launch_qlane_scan(c, prm, a, ql_nt, ql_blocks_per_cu, two_stage, w3 && !two_stage);
+    return launch_rowsweep_scan(c, a, q_begin, q_end);
+}
+
+// A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
+static int rerun_with_rowsweep(dcp_gpu_ctx *c)
+{
+    struct dcp_scan_params prm = c->last_prm;
+    prm.kernel = 1;
+    if (int rc = dcp_gpu_scan_range(c, &prm, c->last_q0, c->last_q1)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return DCP_OK;
+}
+
+// (declared ahead of the shared templates)
 // Wait for the stream; after a query-lane scan also look at the redo counters.  A redo list
 // that overflowed (> 2^26 pairs of one size class needed the row sweep) lost pairs: the scan is
-// repeated with the row-sweep kernel, which needs no list.
+// repeated with the row-sweep kernel (rerun_with_rowsweep).
 static int finish_scan(dcp_gpu_ctx *c)
 {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2187,12 +2410,10 @@ static int finish_scan(dcp_gpu_ctx *c)
         HIP_TRY(c, hipMemcpy(n, c->f64.d_redo_n.p, sizeof n, hipMemcpyDeviceToHost));
         c->last_redo_pairs = (unsigned)std::min<uint64_t>((uint64_t)n[0] + n[1] + n[2] + n[3], 0xffffffffull);
         if (n[4] == 0) return DCP_OK;
-        // a list was full and lost pairs: the scan is repeated with the row sweep, which needs none
+        // the double scan's rerun sets the count to 0 (scan64): what the lists took stays the figure reported.  (The
+        // float row sweep's does the same, and there 0 is what is reported.)
         unsigned const redone = c->last_redo_pairs;
-        struct dcp_scan_params prm = c->last_prm;
-        prm.kernel = 1;
-        if (int rc = dcp_gpu_scan_range(c, &prm, c->last_q0, c->last_q1)) return rc;
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (int rc = rerun_with_rowsweep(c)) return rc;
         c->last_redo_pairs = redone;
         return DCP_OK;
     }
@@ -2215,11 +2436,7 @@ static int finish_scan(dcp_gpu_ctx *c)
         tot += n[k];
     c->last_redo_pairs = (unsigned)std::min<uint64_t>(tot, 0xffffffffull);
     if (n[DCP_MAX_CLASSES] == 0) return DCP_OK;
-    struct dcp_scan_params prm = c->last_prm;
-    prm.kernel = 1;
-    if (int rc = dcp_gpu_scan_range(c, &prm, c->last_q0, c->last_q1)) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return DCP_OK;
+    return rerun_with_rowsweep(c);
 }
 
 #ifdef DCP_TEST_HOOKS
@@ -2343,36 +2560,28 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_
     if (hipEventSynchronize(c->ev_class[i]) != hipSuccess) return DCP_EFAIL;
     float ms = 0;
     if (hipEventElapsedTime(&ms, before, c->ev_class[i]) != hipSuccess) return DCP_EFAIL;
+    out->ms = ms;
     if (k < 0) // the query-lane launch: every pair of the scan
     {
         out->nodes_per_lane = 4 * c->ql_G; // KT nodes per tile, one query per lane
         out->waves_per_pair = 0;
         out->nprofiles = c->nprof;
-        out->ms = ms;
         out->cells = dcp_gpu_scan_cells(c);
         out->algorithmic_bytes = dcp_gpu_scan_algorithmic_bytes(c);
         return DCP_OK;
     }
-    if (c->last_kernel == 2 || c->launched_redo[i]) // a redo launch: its pairs are counted in the launch before it
-    {
-        out->nodes_per_lane = kClasses[k].R;
-        out->waves_per_pair = kClasses[k].W;
-        out->nprofiles = c->class_first[k + 1] - c->class_first[k];
-        out->ms = ms;
-        out->cells = 0;
-        out->algorithmic_bytes = 0;
-        return DCP_OK;
-    }
-    uint64_t sumM = 0, np = 0, len = 0;
-    for (unsigned j = c->class_first[k]; j < c->class_first[k + 1]; ++j, ++np)
+    uint64_t const np = c->class_first[k + 1] - c->class_first[k];
+    out->nodes_per_lane = kClasses[k].R;
+    out->waves_per_pair = kClasses[k].W;
+    out->nprofiles = (unsigned)np;
+    out->cells = out->algorithmic_bytes = 0;
+    if (c->last_kernel == 2 || c->launched_redo[i]) return DCP_OK; // a redo launch: its pairs are counted in the launch before it
+    uint64_t sumM = 0, len = 0;
+    for (unsigned j = c->class_first[k]; j < c->class_first[k + 1]; ++j)
         sumM += c->metas[j].core_size;
     for (unsigned q = c->last_q0; q < c->last_q1; ++q)
         len += c->seq_len[q];
     uint64_t const nq = c->last_q1 - c->last_q0;
-    out->nodes_per_lane = kClasses[k].R;
-    out->waves_per_pair = kClasses[k].W;
-    out->nprofiles = (unsigned)np;
-    out->ms = ms;
     out->cells = sumM * len;
     out->algorithmic_bytes = 20ull * sumM * len + 32ull * (sumM + np) * nq + len * np + 8ull * np * nq;
     return DCP_OK;
@@ -2383,13 +2592,7 @@ int dcp_gpu_fetch_scores(dcp_gpu_ctx *c, float *null_out, float *alt_out)
     if (!c) return DCP_EINVAL;
     if (c->scanned && c->last_f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its scores with dcp_gpu_fetch_scores64");
-    if (!c->scanned || !c->have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = finish_scan(c)) return rc;
-    size_t const bytes = (size_t)c->nseqs * c->nprof * sizeof(float);
-    if (null_out) HIP_TRY(c, hipMemcpy(null_out, c->d_null.p, bytes, hipMemcpyDeviceToHost));
-    if (alt_out) HIP_TRY(c, hipMemcpy(alt_out, c->d_alt.p, bytes, hipMemcpyDeviceToHost));
-    return DCP_OK;
+    return fetch_scores(c, c->res, null_out, alt_out);
 }
 
 int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsigned *nhits)
@@ -2398,21 +2601,7 @@ int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsig
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
     if (c->last_f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its hits with dcp_gpu_fetch_hits64");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = finish_scan(c)) return rc;
-    unsigned n = 0;
-    dcp_hit const *const hits_p = c->ext_hits ? c->ext_hits : c->d_hits.p;
-    unsigned const hits_cap = c->ext_hits ? c->ext_cap : c->hit_cap;
-    HIP_TRY(c, hipMemcpy(&n, c->ext_hits ? c->ext_nhits : c->d_nhits.p, sizeof n, hipMemcpyDeviceToHost));
-    *nhits = n;
-    if (n > hits_cap) return c->fail(DCP_ENOMEM, "device hit buffer overflow: %u > %u", n, hits_cap);
-    if (n > cap || (n && !hits)) return DCP_ENOMEM;
-    if (n == 0) return DCP_OK;
-    HIP_TRY(c, hipMemcpy(hits, hits_p, (size_t)n * sizeof(dcp_hit), hipMemcpyDeviceToHost));
-    std::sort(hits, hits + n, [](dcp_hit const &x, dcp_hit const &y) {
-        return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
-    });
-    return DCP_OK;
+    return fetch_hits(c, c->res, hits, cap, nhits);
 }
 
 int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
@@ -2420,13 +2609,7 @@ int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
     if (!c) return DCP_EINVAL;
     if (c->scanned && !c->last_f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its scores with dcp_gpu_fetch_scores");
-    if (!c->scanned || !c->f64.have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = finish_scan(c)) return rc;
-    size_t const bytes = (size_t)c->nseqs * c->nprof * sizeof(double);
-    if (null_out) HIP_TRY(c, hipMemcpy(null_out, c->f64.d_null.p, bytes, hipMemcpyDeviceToHost));
-    if (alt_out) HIP_TRY(c, hipMemcpy(alt_out, c->f64.d_alt.p, bytes, hipMemcpyDeviceToHost));
-    return DCP_OK;
+    return fetch_scores(c, c->f64.res, null_out, alt_out);
 }
 
 int dcp_gpu_fetch_hits64(dcp_gpu_ctx *c, struct dcp_hit64 *hits, unsigned cap, unsigned *nhits)
@@ -2435,21 +2618,8 @@ int dcp_gpu_fetch_hits64(dcp_gpu_ctx *c, struct dcp_hit64 *hits, unsigned cap, u
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
     if (!c->last_f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its hits with dcp_gpu_fetch_hits");
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = finish_scan(c)) return rc;
-    unsigned n = 0;
-    HIP_TRY(c, hipMemcpy(&n, c->f64.d_nhits.p, sizeof n, hipMemcpyDeviceToHost));
-    *nhits = n;
-    if (n > c->f64.hit_cap) return c->fail(DCP_ENOMEM, "device hit buffer overflow: %u > %u", n, c->f64.hit_cap);
-    if (n > cap || (n && !hits)) return DCP_ENOMEM;
-    if (n == 0) return DCP_OK;
-    HIP_TRY(c, hipMemcpy(hits, c->f64.d_hits.p, (size_t)n * sizeof(dcp_hit64), hipMemcpyDeviceToHost));
-    std::sort(hits, hits + n, [](dcp_hit64 const &x, dcp_hit64 const &y) {
-        return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
-    });
-    return DCP_OK;
+    return fetch_hits(c, c->f64.res, hits, cap, nhits);
 }
-
 
 // ---------------------------------------------------------------------------
 // Hits -> alt paths (device traceback)
@@ -2482,8 +2652,7 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     // (trace_mode) and for the null model's one-state path.
     bool const sweep_forward = !null_model && c->trace_mode != 1;
     // per-hit work area and step capacity.  2L + 2M + 16 steps is an estimate, not a bound: a multi-hit path crosses up
-    // to M + 1 silent states per domain.  The walk counts past its capacity, so a hit whose path is longer is traced
-    // once more at its exact count.
+    // to M + 1 silent states per domain.
     std::vector<uint64_t> need(nhits);
     std::vector<uint32_t> cap(nhits), wld(nhits);
     std::vector<int> cls(nhits);
@@ -2492,186 +2661,109 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
         unsigned const slot = c->slot_of_pidx[hits[h].profile_idx];
         dcp_prof_meta const &m = c->metas[slot];
         uint64_t const L = c->seq_len[hits[h].seq_idx];
-        int k = 0;
-        while (k + 1 < kNumClasses && slot >= c->class_first[k + 1])
-            ++k;
-        cls[h] = k;
+        int const k = cls[h] = range_of(c->class_first, kNumClasses, slot);
         wld[h] = sweep_forward ? 64u * (unsigned)kClasses[k].R * (unsigned)kClasses[k].W : m.width;
         need[h] = 3ull * (L + 1) * wld[h] + 5ull * (L + 1);
         cap[h] = (uint32_t)(2 * L + 2ull * m.core_size + 16);
     }
     uint64_t const budget = c->trace_budget ? c->trace_budget : 1ull << 31; // floats (8 GiB) of work area per round of launches
-    int rc = DCP_OK;
-    std::vector<std::vector<dcp_step>> got(nhits);
-    std::vector<unsigned> todo(nhits);
-    for (unsigned h = 0; h < nhits; ++h)
-        todo[h] = h;
-    for (int pass = 0; !todo.empty(); ++pass)
-    {
-        std::vector<unsigned> again; // hits whose paths exceeded their capacity
-        for (size_t t0 = 0; t0 < todo.size();)
+    DevBuf<uint32_t> d_ld, d_counts; // a round's own buffers: in use until trace_rounds has waited for the stream
+    DevBuf<dcp_hit> d_hits;
+    DevBuf<dcp_pair> d_pairs;
+    auto round = [&](TraceRound<float> const &r) -> int {
+        unsigned const n = r.n, *const cfirst = r.first.data();
+        std::vector<uint32_t> ld(n);
+        std::vector<dcp_hit> shits(n);
+        std::vector<dcp_pair> pairs(n);
+        for (unsigned i = 0; i < n; ++i)
         {
-            size_t t1 = t0;
-            uint64_t work = 0, scap = 0;
-            while (t1 < todo.size() &&
-                   (t1 == t0 || (work + need[todo[t1]] <= budget && scap + cap[todo[t1]] <= UINT32_MAX)))
-                work += need[todo[t1]], scap += cap[todo[t1]], ++t1;
-            unsigned const n = (unsigned)(t1 - t0);
-            // this round's hits in size-class order (the forward launches take contiguous pair lists); results go back
-            // to the caller's order on the host
-            std::vector<unsigned> ord(todo.begin() + t0, todo.begin() + t1);
-            if (sweep_forward) std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return cls[x] < cls[y]; });
-            std::vector<uint64_t> woff(n);
-            std::vector<uint32_t> soff(n + 1, 0), ld(n);
-            std::vector<dcp_hit> shits(n);
-            std::vector<dcp_pair> pairs(n);
-            unsigned cfirst[kNumClasses + 1] = {0};
-            uint64_t acc = 0;
-            for (unsigned i = 0; i < n; ++i)
-            {
-                unsigned const h = ord[i];
-                woff[i] = acc;
-                acc += need[h];
-                soff[i + 1] = soff[i] + cap[h];
-                ld[i] = wld[h];
-                shits[i] = hits[h];
-                pairs[i] = dcp_pair{hits[h].seq_idx, c->slot_of_pidx[hits[h].profile_idx]}; // {q, slot}
-                cfirst[cls[h] + 1] = i + 1u;
-            }
-            for (int k = 1; k <= kNumClasses; ++k)
-                if (cfirst[k] < cfirst[k - 1]) cfirst[k] = cfirst[k - 1];
-            if (c->d_trace_work.n < work) HIP_TRY(c, c->d_trace_work.alloc(work));
-            DevBuf<float> d_alt;
-            DevBuf<uint64_t> d_woff;
-            DevBuf<uint32_t> d_soff, d_nsteps, d_ld, d_counts;
-            DevBuf<dcp_step> d_steps;
-            DevBuf<dcp_hit> d_hits;
-            DevBuf<dcp_pair> d_pairs;
-            HIP_TRY(c, d_alt.alloc(n));
-            HIP_TRY(c, d_woff.alloc(n));
-            HIP_TRY(c, d_soff.alloc(n + 1));
-            HIP_TRY(c, d_nsteps.alloc(n));
-            HIP_TRY(c, d_ld.alloc(n));
-            HIP_TRY(c, d_steps.alloc(scap));
-            HIP_TRY(c, d_hits.alloc(n));
-            HIP_TRY(c, hipMemcpy(d_woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_ld.p, ld.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_hits.p, shits.data(), n * sizeof(dcp_hit), hipMemcpyHostToDevice));
-            if (sweep_forward)
-            {
-                unsigned counts[kNumClasses];
-                for (int k = 0; k < kNumClasses; ++k)
-                    counts[k] = cfirst[k + 1] - cfirst[k];
-                HIP_TRY(c, d_pairs.alloc(n));
-                HIP_TRY(c, d_counts.alloc(kNumClasses));
-                HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_pair), hipMemcpyHostToDevice));
-                HIP_TRY(c, hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
-                dcp_scan_args fa{};
-                fa.profs = c->d_metas.p;
-                fa.emis_match = c->d_emis_match.p;
-                fa.emis_insert = c->d_emis_insert.p;
-                fa.emis_null = c->d_emis_null.p;
-                fa.trans8 = c->d_trans8.p;
-                fa.seq_words = c->d_seq_words.p;
-                fa.seq_woff = c->d_seq_woff.p;
-                fa.seq_len = c->d_seq_len.p;
-                fa.xtrans = c->d_xtrans.p;
-                fa.nprof_total = c->nprof;
-                fa.nprof = c->nprof;
-                fa.nseqs = c->nseqs;
-                fa.qchunk = 1u;
-                fa.nchunks = c->nseqs;
-                fa.trace_work = c->d_trace_work.p;
-                // the classes' launches side by side on their own streams, largest profiles first: a class's launch lasts as
-                // long as its longest hit and seldom fills the chip (one after the other they took 0.31 of a job's 0.40 s of
-                // traceback, profiles/r04/host_scan_probe_mixed_kernel_stats.csv)
-                for (int k = 0; k <= kNumClasses; ++k)
-                    if (!c->ev_trace[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_trace[k], hipEventDisableTiming));
-                HIP_TRY(c, hipEventRecord(c->ev_trace[kNumClasses], c->stream));
-                for (int k = kNumClasses - 1; k >= 0; --k)
-                {
-                    if (counts[k] == 0u) continue;
-                    SizeClass const sc = kClasses[k];
-                    hipStream_t const ls = c->class_stream[k];
-                    HIP_TRY(c, hipStreamWaitEvent(ls, c->ev_trace[kNumClasses], 0));
-                    fa.pairs = d_pairs.p + cfirst[k];
-                    fa.npairs = d_counts.p + k;
-                    fa.pair_cap = counts[k];
-                    fa.trace_woff = d_woff.p + cfirst[k];
-                    fa.trace_alt = d_alt.p + cfirst[k];
-                    unsigned const tpb = dcp_rowsweep_tasks_per_block(sc.W);
-                    unsigned const nb = ((counts[k] + tpb - 1u) / tpb + 7u) / 8u * 8u;
-                    if (dcp_launch_trace_forward(sc.R, sc.W, &fa, nb, ls))
-                        return c->fail(DCP_EFAIL, "no traceback kernel for class R=%d W=%d", sc.R, sc.W);
-                    HIP_TRY(c, hipEventRecord(c->ev_trace[k], ls));
-                    HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trace[k], 0));
-                }
-                HIP_TRY(c, hipGetLastError());
-            }
-            dcp_trace_args ta{};
-            ta.profs = c->d_metas.p;
-            ta.slot_of_pidx = c->d_slot_of_pidx.p;
-            ta.emis_match = c->d_emis_match.p;
-            ta.emis_insert = c->d_emis_insert.p;
-            ta.emis_null = c->d_emis_null.p;
-            ta.trans8 = c->d_trans8.p;
-            ta.seq_words = c->d_seq_words.p;
-            ta.seq_woff = c->d_seq_woff.p;
-            ta.seq_len = c->d_seq_len.p;
-            ta.xtrans = c->d_xtrans.p;
-            ta.hits = d_hits.p;
-            ta.nhits = n;
-            ta.work = c->d_trace_work.p;
-            ta.work_off = d_woff.p;
-            ta.steps = d_steps.p;
-            ta.step_off = d_soff.p;
-            ta.nsteps = d_nsteps.p;
-            ta.alt_out = d_alt.p;
-            ta.null_model = null_model ? 1 : 0;
-            ta.skip_forward = sweep_forward ? 1 : 0;
-            ta.work_ld = d_ld.p;
-            dcp_launch_trace(&ta, n, c->stream);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            std::vector<uint32_t> ns(n);
-            std::vector<dcp_step> st(scap);
-            std::vector<float> alts(n);
-            HIP_TRY(c, hipMemcpy(ns.data(), d_nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(st.data(), d_steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(alts.data(), d_alt.p, n * sizeof(float), hipMemcpyDeviceToHost));
-            for (unsigned i = 0; i < n; ++i)
-            {
-                unsigned const h = ord[i];
-                if (alt_out) alt_out[h] = alts[i];
-                if (ns[i] == DCP_TRACE_NO_PATH)
-                    rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite alt path", hits[h].seq_idx, hits[h].profile_idx);
-                else if (ns[i] == DCP_TRACE_TOO_LONG)
-                    rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
-                                 hits[h].profile_idx);
-                else if (ns[i] > cap[h] && pass == 0)
-                    cap[h] = ns[i], again.push_back(h);
-                else if (ns[i] > cap[h])
-                    rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
-                else
-                    got[h].assign(st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
-            }
-            t0 = t1;
+            unsigned const h = r.ord[i];
+            ld[i] = wld[h];
+            shits[i] = hits[h];
+            pairs[i] = dcp_pair{hits[h].seq_idx, c->slot_of_pidx[hits[h].profile_idx]}; // {q, slot}
         }
-        if (rc) return rc;
-        todo.swap(again);
-    }
-    uint64_t total_steps = 0;
-    for (unsigned h = 0; h < nhits; ++h)
-    {
-        total_steps += got[h].size();
-        if (total_steps > UINT32_MAX) return c->fail(DCP_EFAIL, "the paths of %u hits exceed 2^32 - 1 steps", nhits);
-        step_off[h + 1] = (uint32_t)total_steps;
-    }
-    if (total_steps > cap_steps || (total_steps && !steps_out)) return DCP_ENOMEM;
-    for (unsigned h = 0; h < nhits; ++h)
-        if (!got[h].empty()) std::memcpy(steps_out + step_off[h], got[h].data(), got[h].size() * sizeof(dcp_step));
-    return DCP_OK;
+        HIP_TRY(c, d_ld.alloc(n));
+        HIP_TRY(c, d_hits.alloc(n));
+        HIP_TRY(c, hipMemcpy(d_ld.p, ld.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d_hits.p, shits.data(), n * sizeof(dcp_hit), hipMemcpyHostToDevice));
+        if (sweep_forward)
+        {
+            unsigned counts[kNumClasses];
+            for (int k = 0; k < kNumClasses; ++k)
+                counts[k] = cfirst[k + 1] - cfirst[k];
+            HIP_TRY(c, d_pairs.alloc(n));
+            HIP_TRY(c, d_counts.alloc(kNumClasses));
+            HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_pair), hipMemcpyHostToDevice));
+            HIP_TRY(c, hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
+            dcp_scan_args fa{};
+            fa.profs = c->d_metas.p;
+            fa.emis_match = c->d_emis_match.p;
+            fa.emis_insert = c->d_emis_insert.p;
+            fa.emis_null = c->d_emis_null.p;
+            fa.trans8 = c->d_trans8.p;
+            fa.seq_words = c->d_seq_words.p;
+            fa.seq_woff = c->d_seq_woff.p;
+            fa.seq_len = c->d_seq_len.p;
+            fa.xtrans = c->d_xtrans.p;
+            fa.nprof_total = c->nprof;
+            fa.nprof = c->nprof;
+            fa.nseqs = c->nseqs;
+            fa.qchunk = 1u;
+            fa.nchunks = c->nseqs;
+            fa.trace_work = r.work;
+            // the classes' launches side by side on their own streams, largest profiles first: a class's launch lasts as
+            // long as its longest hit and seldom fills the chip (one after the other they took 0.31 of a job's 0.40 s of
+            // traceback, profiles/r04/host_scan_probe_mixed_kernel_stats.csv)
+            for (int k = 0; k <= kNumClasses; ++k)
+                if (!c->ev_trace[k]) HIP_TRY(c, hipEventCreateWithFlags(&c->ev_trace[k], hipEventDisableTiming));
+            HIP_TRY(c, hipEventRecord(c->ev_trace[kNumClasses], c->stream));
+            for (int k = kNumClasses - 1; k >= 0; --k)
+            {
+                if (counts[k] == 0u) continue;
+                SizeClass const sc = kClasses[k];
+                hipStream_t const ls = c->class_stream[k];
+                HIP_TRY(c, hipStreamWaitEvent(ls, c->ev_trace[kNumClasses], 0));
+                fa.pairs = d_pairs.p + cfirst[k];
+                fa.npairs = d_counts.p + k;
+                fa.pair_cap = counts[k];
+                fa.trace_woff = r.woff.p + cfirst[k];
+                fa.trace_alt = r.alt.p + cfirst[k];
+                unsigned const tpb = dcp_rowsweep_tasks_per_block(sc.W);
+                unsigned const nb = ((counts[k] + tpb - 1u) / tpb + 7u) / 8u * 8u;
+                if (dcp_launch_trace_forward(sc.R, sc.W, &fa, nb, ls))
+                    return c->fail(DCP_EFAIL, "no traceback kernel for class R=%d W=%d", sc.R, sc.W);
+                HIP_TRY(c, hipEventRecord(c->ev_trace[k], ls));
+                HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_trace[k], 0));
+            }
+            HIP_TRY(c, hipGetLastError());
+        }
+        dcp_trace_args ta{};
+        ta.profs = c->d_metas.p;
+        ta.slot_of_pidx = c->d_slot_of_pidx.p;
+        ta.emis_match = c->d_emis_match.p;
+        ta.emis_insert = c->d_emis_insert.p;
+        ta.emis_null = c->d_emis_null.p;
+        ta.trans8 = c->d_trans8.p;
+        ta.seq_words = c->d_seq_words.p;
+        ta.seq_woff = c->d_seq_woff.p;
+        ta.seq_len = c->d_seq_len.p;
+        ta.xtrans = c->d_xtrans.p;
+        ta.hits = d_hits.p;
+        ta.nhits = n;
+        ta.work = r.work;
+        ta.work_off = r.woff.p;
+        ta.steps = r.steps.p;
+        ta.step_off = r.soff.p;
+        ta.nsteps = r.nsteps.p;
+        ta.alt_out = r.alt.p;
+        ta.null_model = null_model ? 1 : 0;
+        ta.skip_forward = sweep_forward ? 1 : 0;
+        ta.work_ld = d_ld.p;
+        dcp_launch_trace(&ta, n, c->stream);
+        return DCP_OK;
+    };
+    return trace_rounds(c, hits, nhits, need, cap, cls, kNumClasses, sweep_forward, budget, "alt", steps_out, cap_steps, step_off,
+                        alt_out, round);
 }
 
 // The double DB's traceback: dcp_gpu_trace_paths' contract on dcp_hit64 records.  Forward pass: viterbi64_kernel<R,
@@ -2699,14 +2791,7 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
     std::vector<uint32_t> slot(c->nprof);
     for (unsigned i = 0; i < (unsigned)F.profs.size(); ++i)
         slot[F.profs[i].pidx] = i;
-    auto group_of = [&](unsigned s) {
-        int g = 0;
-        while (g < 3 && s >= F.group_first[g + 1])
-            ++g;
-        return g;
-    };
-    // per-hit work area (doubles) and step capacity: 2L + 2M + 16 is an estimate, not a bound; the walk counts past its
-    // capacity, so a hit whose path is longer is traced once more at its exact count
+    // per-hit work area (doubles) and step capacity: 2L + 2M + 16 is an estimate, not a bound
     std::vector<uint64_t> need(nhits);
     std::vector<uint32_t> cap(nhits);
     std::vector<int> grp(nhits);
@@ -2714,182 +2799,88 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
     {
         dcp_f64_prof const &m = F.profs[slot[hits[h].profile_idx]];
         uint64_t const L = c->seq_len[hits[h].seq_idx];
-        grp[h] = group_of(slot[hits[h].profile_idx]);
+        grp[h] = range_of(F.group_first, 4, slot[hits[h].profile_idx]);
         need[h] = null_model ? L + 1 : 3ull * (L + 1) * m.ldk + 5ull * (L + 1);
         cap[h] = (uint32_t)(2 * L + 2ull * m.core_size + 16);
     }
     // the budget of dcp_gpu_trace_paths in bytes (its test hook counts 4-byte units); the work area is the same buffer
     uint64_t const budget = (c->trace_budget ? c->trace_budget : 1ull << 31) * sizeof(float) / sizeof(double);
-    std::map<uint32_t, std::vector<double>> xt_of_len; // protein_profile_setup in double, as scan64 does
-    int rc = DCP_OK;
-    std::vector<std::vector<dcp_step>> got(nhits);
-    std::vector<unsigned> todo(nhits);
-    for (unsigned h = 0; h < nhits; ++h)
-        todo[h] = h;
-    for (int pass = 0; !todo.empty(); ++pass)
-    {
-        std::vector<unsigned> again; // hits whose paths exceeded their capacity
-        for (size_t t0 = 0; t0 < todo.size();)
+    DevBuf<double> d_xt; // a round's own buffers: in use until trace_rounds has waited for the stream
+    DevBuf<dcp_f64_pair> d_pairs;
+    auto round = [&](TraceRound<double> const &r) -> int {
+        unsigned const n = r.n, *const gfirst = r.first.data();
+        std::vector<dcp_f64_pair> pairs(n);
+        std::vector<uint32_t> seqs(n);
+        uint32_t seg_lmax = 0;
+        for (unsigned i = 0; i < n; ++i)
         {
-            size_t t1 = t0;
-            uint64_t work = 0, scap = 0;
-            while (t1 < todo.size() &&
-                   (t1 == t0 || (work + need[todo[t1]] <= budget && scap + cap[todo[t1]] <= UINT32_MAX)))
-                work += need[todo[t1]], scap += cap[todo[t1]], ++t1;
-            unsigned const n = (unsigned)(t1 - t0);
-            // this round's hits by launch group (each forward launch takes a contiguous pair list); results go back to
-            // the caller's order on the host
-            std::vector<unsigned> ord(todo.begin() + t0, todo.begin() + t1);
-            std::stable_sort(ord.begin(), ord.end(), [&](unsigned x, unsigned y) { return grp[x] < grp[y]; });
-            std::vector<uint64_t> woff(n);
-            std::vector<uint32_t> soff(n + 1, 0);
-            std::vector<dcp_f64_pair> pairs(n);
-            std::vector<double> xt((size_t)n * DCP_F64_XSTRIDE, 0.0);
-            unsigned gfirst[5] = {0, 0, 0, 0, 0};
-            uint32_t seg_lmax = 0;
-            uint64_t acc = 0;
-            for (unsigned i = 0; i < n; ++i)
-            {
-                unsigned const h = ord[i];
-                uint32_t const L = c->seq_len[hits[h].seq_idx];
-                woff[i] = acc;
-                acc += need[h];
-                soff[i + 1] = soff[i] + cap[h];
-                pairs[i] = dcp_f64_pair{hits[h].seq_idx, slot[hits[h].profile_idx]};
-                gfirst[grp[h] + 1] = i + 1u;
-                if (grp[h] == 3) seg_lmax = std::max(seg_lmax, L);
-                if (!c->xt64.empty()) // dcp_gpu_seqs_set_xtrans64: the hit's sequence's row, the flags ignored
-                {
-                    std::memcpy(&xt[(size_t)i * DCP_F64_XSTRIDE], &c->xt64[(size_t)hits[h].seq_idx * DCP_NXTRANS], sizeof(double) * DCP_NXTRANS);
-                    continue;
-                }
-                auto it = xt_of_len.find(L);
-                if (it == xt_of_len.end())
-                {
-                    std::vector<double> x(DCP_NXTRANS);
-                    if (int e = dcp_xtrans64(L, multi_hits, hmmer3_compat, x.data())) return c->fail(e, "sequence cannot be empty");
-                    it = xt_of_len.emplace(L, std::move(x)).first;
-                }
-                std::memcpy(&xt[(size_t)i * DCP_F64_XSTRIDE], it->second.data(), sizeof(double) * DCP_NXTRANS);
-            }
-            for (int g = 1; g < 5; ++g)
-                if (gfirst[g] < gfirst[g - 1]) gfirst[g] = gfirst[g - 1];
-            size_t const work_floats = (size_t)(work * (sizeof(double) / sizeof(float)));
-            if (c->d_trace_work.n < work_floats) HIP_TRY(c, c->d_trace_work.alloc(work_floats));
-            double *const d_work = reinterpret_cast<double *>(c->d_trace_work.p);
-            DevBuf<double> d_alt, d_xt;
-            DevBuf<uint64_t> d_woff;
-            DevBuf<uint32_t> d_soff, d_nsteps;
-            DevBuf<dcp_step> d_steps;
-            DevBuf<dcp_f64_pair> d_pairs;
-            HIP_TRY(c, d_alt.alloc(n));
-            HIP_TRY(c, d_xt.alloc(xt.size()));
-            HIP_TRY(c, d_woff.alloc(n));
-            HIP_TRY(c, d_soff.alloc(n + 1));
-            HIP_TRY(c, d_nsteps.alloc(n));
-            HIP_TRY(c, d_steps.alloc(scap));
-            HIP_TRY(c, d_pairs.alloc(n));
-            HIP_TRY(c, hipMemcpy(d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_woff.p, woff.data(), n * sizeof(uint64_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_soff.p, soff.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));
-            HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_f64_pair), hipMemcpyHostToDevice));
-            if (!null_model)
-            {
-                // boundary columns of the segmented group: 5 doubles per row and wavefront, at most 1 GiB (scan64's)
-                uint64_t const col_stride = 5ull * ((uint64_t)seg_lmax + 1u);
-                uint64_t const nseg_pairs = gfirst[4] - gfirst[3];
-                uint64_t const seg_waves =
-                    nseg_pairs ? std::min<uint64_t>(nseg_pairs, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / col_stride)) : 0;
-                if (seg_waves && F.d_col.n < seg_waves * col_stride) HIP_TRY(c, F.d_col.alloc(seg_waves * col_stride));
-                dcp_f64_trace_args fa{};
-                fa.profs = F.d_profs.p;
-                fa.nprof_total = c->nprof;
-                fa.tab = F.d_tab.p;
-                fa.trans = F.d_trans.p;
-                fa.xe = F.d_xe.p;
-                fa.seq_words = c->d_seq_words.p;
-                fa.seq_woff = c->d_seq_woff.p;
-                fa.seq_len = c->d_seq_len.p;
-                fa.trace_work = d_work;
-                // one launch per non-empty group on the context stream, one wavefront per pair (the segmented group
-                // strides over its pairs with one boundary column per wavefront)
-                for (int g = 0; g < 4; ++g)
-                {
-                    unsigned const cnt = gfirst[g + 1] - gfirst[g];
-                    if (cnt == 0) continue;
-                    fa.pairs = d_pairs.p + gfirst[g];
-                    fa.npairs = cnt;
-                    fa.xtrans = d_xt.p + (size_t)gfirst[g] * DCP_F64_XSTRIDE;
-                    fa.trace_woff = d_woff.p + gfirst[g];
-                    fa.trace_alt = d_alt.p + gfirst[g];
-                    fa.col = g == 3 ? F.d_col.p : nullptr;
-                    fa.col_stride = g == 3 ? col_stride : 0;
-                    uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(cnt, 1ull << 24);
-                    if (dcp_f64_launch_trace_forward(kF64R[g], &fa, (unsigned)waves, c->stream))
-                        return c->fail(DCP_EFAIL, "no f64 traceback kernel for %d nodes per lane", kF64R[g]);
-                }
-                HIP_TRY(c, hipGetLastError());
-            }
-            dcp_f64_walk_args wa{};
-            wa.profs = F.d_profs.p;
-            wa.pairs = d_pairs.p;
-            wa.nhits = n;
-            wa.tab = F.d_tab.p;
-            wa.trans = F.d_trans.p;
-            wa.xe = F.d_xe.p;
-            wa.seq_words = c->d_seq_words.p;
-            wa.seq_woff = c->d_seq_woff.p;
-            wa.seq_len = c->d_seq_len.p;
-            wa.xtrans = d_xt.p;
-            wa.work = d_work;
-            wa.work_off = d_woff.p;
-            wa.steps = d_steps.p;
-            wa.step_off = d_soff.p;
-            wa.nsteps = d_nsteps.p;
-            wa.alt_out = d_alt.p;
-            wa.null_model = null_model ? 1 : 0;
-            dcp_f64_launch_walk(&wa, c->stream);
-            HIP_TRY(c, hipGetLastError());
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            std::vector<uint32_t> ns(n);
-            std::vector<dcp_step> st(scap);
-            std::vector<double> alts(n);
-            HIP_TRY(c, hipMemcpy(ns.data(), d_nsteps.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(st.data(), d_steps.p, scap * sizeof(dcp_step), hipMemcpyDeviceToHost));
-            HIP_TRY(c, hipMemcpy(alts.data(), d_alt.p, n * sizeof(double), hipMemcpyDeviceToHost));
-            for (unsigned i = 0; i < n; ++i)
-            {
-                unsigned const h = ord[i];
-                if (alt_out) alt_out[h] = alts[i];
-                if (ns[i] == DCP_F64_TRACE_NO_PATH)
-                    rc = c->fail(DCP_EFAIL, "pair (seq %u, profile %u) has no finite %s path", hits[h].seq_idx,
-                                 hits[h].profile_idx, null_model ? "null" : "alt");
-                else if (ns[i] == DCP_F64_TRACE_TOO_LONG)
-                    rc = c->fail(DCP_EFAIL, "path of pair (seq %u, profile %u) has more than 2^32 - 3 steps", hits[h].seq_idx,
-                                 hits[h].profile_idx);
-                else if (ns[i] > cap[h] && pass == 0)
-                    cap[h] = ns[i], again.push_back(h);
-                else if (ns[i] > cap[h])
-                    rc = c->fail(DCP_EFAIL, "path of hit %u exceeds its step capacity", h);
-                else
-                    got[h].assign(st.begin() + soff[i], st.begin() + soff[i] + ns[i]);
-            }
-            t0 = t1;
+            unsigned const h = r.ord[i];
+            seqs[i] = hits[h].seq_idx;
+            pairs[i] = dcp_f64_pair{hits[h].seq_idx, slot[hits[h].profile_idx]};
+            if (grp[h] == 3) seg_lmax = std::max(seg_lmax, c->seq_len[hits[h].seq_idx]);
         }
-        if (rc) return rc;
-        todo.swap(again);
-    }
-    uint64_t total_steps = 0;
-    for (unsigned h = 0; h < nhits; ++h)
-    {
-        total_steps += got[h].size();
-        if (total_steps > UINT32_MAX) return c->fail(DCP_EFAIL, "the paths of %u hits exceed 2^32 - 1 steps", nhits);
-        step_off[h + 1] = (uint32_t)total_steps;
-    }
-    if (total_steps > cap_steps || (total_steps && !steps_out)) return DCP_ENOMEM;
-    for (unsigned h = 0; h < nhits; ++h)
-        if (!got[h].empty()) std::memcpy(steps_out + step_off[h], got[h].data(), got[h].size() * sizeof(dcp_step));
-    return DCP_OK;
+        std::vector<double> xt; // protein_profile_setup in double, as scan64 does
+        if (int e = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_F64_XSTRIDE, xt)) return e;
+        HIP_TRY(c, d_xt.alloc(xt.size()));
+        HIP_TRY(c, d_pairs.alloc(n));
+        HIP_TRY(c, hipMemcpy(d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_f64_pair), hipMemcpyHostToDevice));
+        if (!null_model)
+        {
+            uint64_t col_stride = 0, seg_waves = 0;
+            if (int e = f64_seg_columns(c, seg_lmax, gfirst[4] - gfirst[3], &col_stride, &seg_waves)) return e;
+            dcp_f64_trace_args fa{};
+            fa.profs = F.d_profs.p;
+            fa.nprof_total = c->nprof;
+            fa.tab = F.d_tab.p;
+            fa.trans = F.d_trans.p;
+            fa.xe = F.d_xe.p;
+            fa.seq_words = c->d_seq_words.p;
+            fa.seq_woff = c->d_seq_woff.p;
+            fa.seq_len = c->d_seq_len.p;
+            fa.trace_work = r.work;
+            // one launch per non-empty group on the context stream, one wavefront per pair (the segmented group
+            // strides over its pairs with one boundary column per wavefront)
+            for (int g = 0; g < 4; ++g)
+            {
+                unsigned const cnt = gfirst[g + 1] - gfirst[g];
+                if (cnt == 0) continue;
+                fa.pairs = d_pairs.p + gfirst[g];
+                fa.npairs = cnt;
+                fa.xtrans = d_xt.p + (size_t)gfirst[g] * DCP_F64_XSTRIDE;
+                fa.trace_woff = r.woff.p + gfirst[g];
+                fa.trace_alt = r.alt.p + gfirst[g];
+                fa.col = g == 3 ? F.d_col.p : nullptr;
+                fa.col_stride = g == 3 ? col_stride : 0;
+                uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(cnt, 1ull << 24);
+                if (dcp_f64_launch_trace_forward(kF64R[g], &fa, (unsigned)waves, c->stream))
+                    return c->fail(DCP_EFAIL, "no f64 traceback kernel for %d nodes per lane", kF64R[g]);
+            }
+            HIP_TRY(c, hipGetLastError());
+        }
+        dcp_f64_walk_args wa{};
+        wa.profs = F.d_profs.p;
+        wa.pairs = d_pairs.p;
+        wa.nhits = n;
+        wa.tab = F.d_tab.p;
+        wa.trans = F.d_trans.p;
+        wa.xe = F.d_xe.p;
+        wa.seq_words = c->d_seq_words.p;
+        wa.seq_woff = c->d_seq_woff.p;
+        wa.seq_len = c->d_seq_len.p;
+        wa.xtrans = d_xt.p;
+        wa.work = r.work;
+        wa.work_off = r.woff.p;
+        wa.steps = r.steps.p;
+        wa.step_off = r.soff.p;
+        wa.nsteps = r.nsteps.p;
+        wa.alt_out = r.alt.p;
+        wa.null_model = null_model ? 1 : 0;
+        dcp_f64_launch_walk(&wa, c->stream);
+        return DCP_OK;
+    };
+    return trace_rounds(c, hits, nhits, need, cap, grp, 4, true, budget, null_model ? "null" : "alt", steps_out, cap_steps, step_off,
+                        alt_out, round);
 }
 
 static void last_range(dcp_gpu_ctx const *c, uint64_t *sumM, uint64_t *len, uint64_t *nq)

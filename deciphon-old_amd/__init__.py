@@ -74,6 +74,9 @@ ABI_SYMBOLS = [
     "dcp_gpu_db_fetch_match_table64", "dcp_gpu_db_fetch_insert_null64", "dcp_gpu_trace_paths64",
     "dcp_gpu_seqs_set_xtrans64", "dcp_profile_from_parts64", "dcp_lprob_normalize64",
     "dcp_gpu_last_scan_query_plan",
+    # the double build across GPUs: the caller's hit buffer and the gather of struct dcp_hit64 records
+    "dcp_gpu_set_hit_buffer64", "dcp_gpu_hit_buffer64", "dcp_dist_gather_scan_hits64", "dcp_dist_gather_hits64",
+    "dcp_dist_merge_hits64", "dcp_dist_free_hits64",
 ]
 
 
@@ -170,6 +173,9 @@ def _load(path=None, hooks=False):
         "dcp_gpu_fetch_hits": (I, [P, P, U, C.POINTER(U)]),
         "dcp_gpu_scan_range": (I, [P, C.POINTER(ScanParams), U, U]),
         "dcp_gpu_set_hit_buffer": (I, [P, P, U, P]),
+        "dcp_gpu_hit_buffer": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(U)]),
+        "dcp_gpu_set_hit_buffer64": (I, [P, P, U, P]),
+        "dcp_gpu_hit_buffer64": (I, [P, C.POINTER(P), C.POINTER(P), C.POINTER(U)]),
         "dcp_gpu_last_scan_launch_info": (I, [P, U, C.POINTER(LaunchInfo)]),
         "dcp_gpu_trace_paths": (I, [P, P, U, I, I, I, P, U, P, P]),
         "dcp_state_name": (U, [U, C.c_char_p]),
@@ -703,6 +709,20 @@ class Scanner:
     def set_hit_buffer(self, hits_dev_ptr, cap, nhits_dev_ptr):
         """Route hit records into caller-owned device memory (e.g. a torch tensor for RCCL)."""
         self._check(self._lib.dcp_gpu_set_hit_buffer(self._c, hits_dev_ptr, cap, nhits_dev_ptr))
+
+    def set_hit_buffer64(self, hits_dev_ptr, cap, nhits_dev_ptr):
+        """The same for the scans of a double DB (dcp_gpu_set_hit_buffer64): cap records of HIT64_DTYPE -- 6 int32
+        words each -- and one counter in caller-owned device memory; (None, 0, None) restores the context's own
+        buffer.  Independent of set_hit_buffer: a scan writes to the registration of its DB's precision."""
+        self._check(self._lib.dcp_gpu_set_hit_buffer64(self._c, hits_dev_ptr, cap, nhits_dev_ptr))
+
+    def hit_buffer64(self):
+        """(records pointer, counter pointer, capacity) of the device memory the last scan of a double DB wrote its
+        hits to (dcp_gpu_hit_buffer64): the context's own or the caller's.  RC_EINVAL before any scan and after a
+        scan of a float DB."""
+        h, n, cap = C.c_void_p(), C.c_void_p(), C.c_uint(0)
+        self._check(self._lib.dcp_gpu_hit_buffer64(self._c, C.byref(h), C.byref(n), C.byref(cap)))
+        return h.value, n.value, cap.value
 
     def launch_infos(self):
         out = []

@@ -7,6 +7,10 @@
 // box without RCCL can still run everything else.  The pure bookkeeping (counts -> displacements ->
 // concatenation -> global profile indices -> (seq, profile) order) is a separate host function,
 // dcp_dist_merge_hits, so that it is covered on CPU by the gloo world_size-2 test.
+//
+// Two record types travel: struct dcp_hit (scans of a float DB) and struct dcp_hit64 (scans of a double DB, the ...64
+// entry points).  The merge and the gather are templates over the record; what differs is its size in bytes and in
+// the uint32 words RCCL carries.  Records are copied whole, never converted.
 #include "dcp_gpu.h"
 
 #include <hip/hip_runtime.h>
@@ -18,6 +22,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -96,8 +101,8 @@ struct dcp_dist
     hipStream_t stream = nullptr;
     // device staging: {records held, profile_offset, records found} of every rank; all ranks' records back to back
     uint32_t *d_meta_mine = nullptr, *d_meta_all = nullptr;
-    dcp_hit *d_recv = nullptr;
-    size_t recv_cap = 0;
+    unsigned char *d_recv = nullptr; // bytes: the float and the double gather share it
+    size_t recv_cap = 0;             // in bytes
     double last_gather_ms = 0.0; // wall time of the last gather on this rank (both exchanges + merge)
     std::string err;
 
@@ -286,11 +291,20 @@ void dcp_dist_shard(unsigned const *core_sizes, unsigned nprofiles, int nranks, 
     *end = b[(size_t)rank + 1];
 }
 
+} // extern "C"
+
+namespace
+{
+static_assert(sizeof(dcp_hit) == 16 && sizeof(dcp_hit) % sizeof(uint32_t) == 0, "struct dcp_hit travels as 4 words");
+static_assert(sizeof(dcp_hit64) == 24 && offsetof(dcp_hit64, null_loglik) == 8 && offsetof(dcp_hit64, alt_loglik) == 16,
+              "struct dcp_hit64 is {u32, u32, double, double}: 24 bytes, 6 words, no padding");
+
 // counts[r] records of rank r lie back to back in `records` (rank order).  Shard-local profile indices
 // become global (+ profile_offset[r]); the result is ordered by (seq_idx, profile_idx) -- the order
-// dcp_gpu_fetch_hits gives for one device.  Returns the total, or -1 if cap is too small.
-long dcp_dist_merge_hits(unsigned const *counts, unsigned const *profile_offset, int nranks,
-                         struct dcp_hit const *records, struct dcp_hit *out, unsigned cap)
+// dcp_gpu_fetch_hits[64] gives for one device.  Returns the total, or -1 if cap is too small.
+template <class Hit>
+long merge_impl(unsigned const *counts, unsigned const *profile_offset, int nranks, Hit const *records, Hit *out,
+                unsigned cap)
 {
     if (!counts || !profile_offset || nranks < 1 || (!records && !out)) return -1;
     uint64_t total = 0;
@@ -304,10 +318,25 @@ long dcp_dist_merge_hits(unsigned const *counts, unsigned const *profile_offset,
             out[at] = records[at];
             out[at].profile_idx += profile_offset[r];
         }
-    std::sort(out, out + total, [](dcp_hit const &x, dcp_hit const &y) {
+    std::sort(out, out + total, [](Hit const &x, Hit const &y) {
         return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
     });
     return (long)total;
+}
+} // namespace
+
+extern "C" {
+
+long dcp_dist_merge_hits(unsigned const *counts, unsigned const *profile_offset, int nranks,
+                         struct dcp_hit const *records, struct dcp_hit *out, unsigned cap)
+{
+    return merge_impl(counts, profile_offset, nranks, records, out, cap);
+}
+
+long dcp_dist_merge_hits64(unsigned const *counts, unsigned const *profile_offset, int nranks,
+                           struct dcp_hit64 const *records, struct dcp_hit64 *out, unsigned cap)
+{
+    return merge_impl(counts, profile_offset, nranks, records, out, cap);
 }
 
 // The decisions every rank takes from the gathered meta words {held, profile_offset, found} x nranks:
@@ -346,7 +375,7 @@ int dcp_dist_gather_plan(uint32_t const *meta, int nranks, unsigned *counts, uns
 
 // All ranks call this after their scan is COMPLETE (dcp_gpu_sync: a query-lane scan finishes its redo
 // pairs there -- dcp_dist_gather_scan_hits does that itself).
-// hits_dev / nhits_dev: the device hit buffer and counter the scan wrote (dcp_gpu_set_hit_buffer).
+// hits_dev / nhits_dev: the device hit buffer and counter the scan wrote (dcp_gpu_set_hit_buffer[64]).
 // root >= 0: only that rank receives (gather-v); root < 0: every rank receives (all-gather-v).
 // On a receiving rank *out is a malloc'ed array of *nout records (caller frees), global profile
 // indices, ordered by (seq_idx, profile_idx); elsewhere *out = NULL, *nout = the global total.
@@ -356,9 +385,12 @@ namespace
 {
 // my_scan_failed: this rank has no valid hit list (its scan failed).  It still takes part in both exchanges
 // (leaving would hang its peers inside the collective), holds nothing, and says so in the meta words.
+// Hit: struct dcp_hit or struct dcp_hit64 -- its bytes size the staging and the copies, its words the send / recv.
+template <class Hit>
 int gather_impl(dcp_dist *d, void const *hits_dev, void const *nhits_dev, unsigned cap, unsigned profile_offset,
-                int root, void *scan_stream, bool my_scan_failed, struct dcp_hit **out, unsigned *nout)
+                int root, void *scan_stream, bool my_scan_failed, Hit **out, unsigned *nout)
 {
+    constexpr size_t rec_bytes = sizeof(Hit), rec_words = sizeof(Hit) / sizeof(uint32_t);
     if (!d || !out || !nout || root >= d->nranks || (!my_scan_failed && (!hits_dev || !nhits_dev))) return DCP_EINVAL;
     *out = nullptr;
     *nout = 0;
@@ -402,20 +434,19 @@ int gather_impl(dcp_dist *d, void const *hits_dev, void const *nhits_dev, unsign
     *nout = (unsigned)total;
     bool const receiver = root < 0 || root == d->rank;
 
-    // 2. gather-v of the 16-byte records: grouped send / recv, peer to peer over xGMI
-    if (receiver && d->recv_cap < total)
+    // 2. gather-v of the records (16 or 24 bytes each): grouped send / recv, peer to peer over xGMI
+    if (receiver && d->recv_cap < (size_t)total * rec_bytes)
     {
         if (d->d_recv) (void)hipFree(d->d_recv);
         d->d_recv = nullptr;
         d->recv_cap = 0;
-        size_t const want = std::max<size_t>((size_t)total, 4096);
-        DIST_HIP(d, hipMalloc((void **)&d->d_recv, want * sizeof(dcp_hit)));
+        size_t const want = std::max<size_t>((size_t)total, 4096) * rec_bytes;
+        DIST_HIP(d, hipMalloc((void **)&d->d_recv, want));
         d->recv_cap = want;
     }
-    size_t const words = sizeof(dcp_hit) / sizeof(uint32_t);
     if (receiver && counts[(size_t)d->rank]) // my own records: a local copy, no self send
-        DIST_HIP(d, hipMemcpyAsync(d->d_recv + displ[(size_t)d->rank], hits_dev,
-                                   (size_t)counts[(size_t)d->rank] * sizeof(dcp_hit), hipMemcpyDeviceToDevice, d->stream));
+        DIST_HIP(d, hipMemcpyAsync(d->d_recv + displ[(size_t)d->rank] * rec_bytes, hits_dev,
+                                   (size_t)counts[(size_t)d->rank] * rec_bytes, hipMemcpyDeviceToDevice, d->stream));
     if (R > 1)
     {
         DIST_NCCL(d, rccl().GroupStart());
@@ -425,10 +456,10 @@ int gather_impl(dcp_dist *d, void const *hits_dev, void const *nhits_dev, unsign
             if (peer == d->rank) continue;
             bool const peer_receives = root < 0 || root == peer;
             if (peer_receives && counts[(size_t)d->rank])
-                gr = rccl().Send(hits_dev, (size_t)counts[(size_t)d->rank] * words, ncclUint32, peer, d->comm, d->stream);
+                gr = rccl().Send(hits_dev, (size_t)counts[(size_t)d->rank] * rec_words, ncclUint32, peer, d->comm, d->stream);
             if (gr == ncclSuccess && receiver && counts[(size_t)peer])
-                gr = rccl().Recv(d->d_recv + displ[(size_t)peer], (size_t)counts[(size_t)peer] * words, ncclUint32, peer,
-                                 d->comm, d->stream);
+                gr = rccl().Recv(d->d_recv + displ[(size_t)peer] * rec_bytes, (size_t)counts[(size_t)peer] * rec_words,
+                                 ncclUint32, peer, d->comm, d->stream);
         }
         ncclResult_t const ge = rccl().GroupEnd();
         if (gr != ncclSuccess) return d->fail(DCP_EFAIL, "ncclSend/ncclRecv", rccl().GetErrorString(gr));
@@ -447,19 +478,46 @@ int gather_impl(dcp_dist *d, void const *hits_dev, void const *nhits_dev, unsign
         return verdict();
     }
     // 3. to the host; global indices; (seq, profile) order
-    std::vector<dcp_hit> raw((size_t)total);
+    std::vector<Hit> raw((size_t)total);
     if (total)
-        DIST_HIP(d, hipMemcpyAsync(raw.data(), d->d_recv, (size_t)total * sizeof(dcp_hit), hipMemcpyDeviceToHost, d->stream));
+        DIST_HIP(d, hipMemcpyAsync(raw.data(), d->d_recv, (size_t)total * rec_bytes, hipMemcpyDeviceToHost, d->stream));
     DIST_HIP(d, hipStreamSynchronize(d->stream));
-    dcp_hit *res = (dcp_hit *)std::malloc(std::max<size_t>((size_t)total, 1) * sizeof(dcp_hit));
+    Hit *res = (Hit *)std::malloc(std::max<size_t>((size_t)total, 1) * rec_bytes);
     if (!res) return d->fail(DCP_ENOMEM, "malloc", "hit list");
-    if (dcp_dist_merge_hits(counts.data(), offs.data(), R, raw.data(), res, (unsigned)total) < 0)
+    if (merge_impl(counts.data(), offs.data(), R, raw.data(), res, (unsigned)total) < 0)
     {
         std::free(res);
         return d->fail(DCP_EFAIL, "merge", "inconsistent counts");
     }
     *out = res;
     return verdict();
+}
+
+// dcp_dist_gather_scan_hits[64]: completes the context's scan, takes the buffer it wrote from `hit_buffer_of`
+// (dcp_gpu_hit_buffer / dcp_gpu_hit_buffer64), gathers it.
+// A rank whose scan failed must still enter the collective, or its peers would wait for it forever: it holds
+// nothing and puts DCP_DIST_FOUND_FAILED into its meta words, so EVERY rank -- a root that receives the list
+// included -- returns an error instead of a list that silently lacks one shard.  This rank reports its own
+// scan's error code and message.  A context that holds no records of the type asked for (no scan yet, or the last
+// scan ran on a DB of the other precision: hit_buffer_of says so) is such a rank.
+template <class Hit>
+int gather_scan_impl(dcp_dist *d, dcp_gpu_ctx *ctx, int (*hit_buffer_of)(dcp_gpu_ctx *, void **, void **, unsigned *),
+                     unsigned profile_offset, int root, Hit **out, unsigned *nout)
+{
+    if (!d || !ctx || !out || !nout) return DCP_EINVAL;
+    *out = nullptr;
+    *nout = 0;
+    int const src = dcp_gpu_sync(ctx);
+    void *hits_dev = nullptr, *nhits_dev = nullptr;
+    unsigned cap = 0;
+    int const brc = src ? src : hit_buffer_of(ctx, &hits_dev, &nhits_dev, &cap);
+    if (brc)
+    {
+        std::string const why = dcp_gpu_last_error(ctx);
+        (void)gather_impl<Hit>(d, nullptr, nullptr, 0, profile_offset, root, nullptr, true, out, nout);
+        return d->fail(brc, "scan", why.c_str());
+    }
+    return gather_impl<Hit>(d, hits_dev, nhits_dev, cap, profile_offset, root, nullptr, false, out, nout);
 }
 } // namespace
 
@@ -478,26 +536,24 @@ int dcp_dist_gather_hits(dcp_dist *d, void const *hits_dev, void const *nhits_de
 int dcp_dist_gather_scan_hits(dcp_dist *d, dcp_gpu_ctx *ctx, unsigned profile_offset, int root,
                               struct dcp_hit **out, unsigned *nout)
 {
-    if (!d || !ctx || !out || !nout) return DCP_EINVAL;
-    *out = nullptr;
-    *nout = 0;
-    // A rank whose scan failed must still enter the collective, or its peers would wait for it forever: it holds
-    // nothing and puts DCP_DIST_FOUND_FAILED into its meta words, so EVERY rank -- a root that receives the list
-    // included -- returns an error instead of a list that silently lacks one shard.  This rank reports its own
-    // scan's error code and message.
-    int const src = dcp_gpu_sync(ctx);
-    void *hits_dev = nullptr, *nhits_dev = nullptr;
-    unsigned cap = 0;
-    int const brc = src ? src : dcp_gpu_hit_buffer(ctx, &hits_dev, &nhits_dev, &cap);
-    if (brc)
-    {
-        std::string const why = dcp_gpu_last_error(ctx);
-        (void)gather_impl(d, nullptr, nullptr, 0, profile_offset, root, nullptr, true, out, nout);
-        return d->fail(brc, "scan", why.c_str());
-    }
-    return gather_impl(d, hits_dev, nhits_dev, cap, profile_offset, root, nullptr, false, out, nout);
+    return gather_scan_impl(d, ctx, dcp_gpu_hit_buffer, profile_offset, root, out, nout);
+}
+
+// The double twins: the records of a scan of a double DB
+int dcp_dist_gather_hits64(dcp_dist *d, void const *hits_dev, void const *nhits_dev, unsigned cap,
+                           unsigned profile_offset, int root, void *scan_stream, struct dcp_hit64 **out,
+                           unsigned *nout)
+{
+    return gather_impl(d, hits_dev, nhits_dev, cap, profile_offset, root, scan_stream, false, out, nout);
+}
+
+int dcp_dist_gather_scan_hits64(dcp_dist *d, dcp_gpu_ctx *ctx, unsigned profile_offset, int root,
+                                struct dcp_hit64 **out, unsigned *nout)
+{
+    return gather_scan_impl(d, ctx, dcp_gpu_hit_buffer64, profile_offset, root, out, nout);
 }
 
 void dcp_dist_free_hits(struct dcp_hit *hits) { std::free(hits); }
+void dcp_dist_free_hits64(struct dcp_hit64 *hits) { std::free(hits); }
 
 } // extern "C"

@@ -94,7 +94,7 @@ template <class T> struct DevBuf
 };
 
 // What a scan leaves on the device, in the DB's precision: the dense scores (keep_scores) and the hit list with its
-// counter -- the context's own, or a caller-owned buffer (e.g. a torch tensor that RCCL gathers; float DBs only).
+// counter -- the context's own, or a caller-owned buffer (e.g. a torch tensor that RCCL gathers).
 template <class Real, class Hit> struct ScanResults
 {
     DevBuf<Real> d_null, d_alt;
@@ -415,6 +415,27 @@ template <class Real, class Hit> int fetch_hits(dcp_gpu_ctx *c, ScanResults<Real
     std::sort(hits, hits + n, [](Hit const &x, Hit const &y) {
         return x.seq_idx != y.seq_idx ? x.seq_idx < y.seq_idx : x.profile_idx < y.profile_idx;
     });
+    return DCP_OK;
+}
+
+// dcp_gpu_set_hit_buffer[64]: the registration of one precision's results; the scans of a DB of that precision use it
+template <class Real, class Hit>
+int set_hit_buffer(dcp_gpu_ctx *c, ScanResults<Real, Hit> &r, void *hits_dev, unsigned cap, void *nhits_dev)
+{
+    if ((hits_dev == nullptr) != (nhits_dev == nullptr) || (hits_dev && cap == 0))
+        return c->fail(DCP_EINVAL, "hit buffer and counter must be given together");
+    r.ext_hits = (Hit *)hits_dev;
+    r.ext_nhits = (unsigned *)nhits_dev;
+    r.ext_cap = hits_dev ? cap : 0;
+    return DCP_OK;
+}
+
+template <class Real, class Hit>
+int hit_buffer(ScanResults<Real, Hit> const &r, void **hits_dev, void **nhits_dev, unsigned *cap)
+{
+    *hits_dev = r.hits();
+    *nhits_dev = r.nhits();
+    *cap = r.cap();
     return DCP_OK;
 }
 
@@ -1457,12 +1478,7 @@ int dcp_gpu_set_lrt_threshold64(dcp_gpu_ctx *c, double lrt_threshold64)
 int dcp_gpu_set_hit_buffer(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void *nhits_dev)
 {
     if (!c) return DCP_EINVAL;
-    if ((hits_dev == nullptr) != (nhits_dev == nullptr) || (hits_dev && cap == 0))
-        return c->fail(DCP_EINVAL, "hit buffer and counter must be given together");
-    c->res.ext_hits = (dcp_hit *)hits_dev;
-    c->res.ext_nhits = (unsigned *)nhits_dev;
-    c->res.ext_cap = hits_dev ? cap : 0;
-    return DCP_OK;
+    return set_hit_buffer(c, c->res, hits_dev, cap, nhits_dev);
 }
 
 int dcp_gpu_hit_buffer(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsigned *cap)
@@ -1470,10 +1486,21 @@ int dcp_gpu_hit_buffer(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsign
     if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
     if (c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a double DB: its hits are struct dcp_hit64 (dcp_gpu_fetch_hits64)");
-    *hits_dev = c->res.hits();
-    *nhits_dev = c->res.nhits();
-    *cap = c->res.cap();
-    return DCP_OK;
+    return hit_buffer(c->res, hits_dev, nhits_dev, cap);
+}
+
+int dcp_gpu_set_hit_buffer64(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void *nhits_dev)
+{
+    if (!c) return DCP_EINVAL;
+    return set_hit_buffer(c, c->f64.res, hits_dev, cap, nhits_dev);
+}
+
+int dcp_gpu_hit_buffer64(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsigned *cap)
+{
+    if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
+    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (!c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a float DB: its hits are struct dcp_hit (dcp_gpu_hit_buffer)");
+    return hit_buffer(c->f64.res, hits_dev, nhits_dev, cap);
 }
 
 // ---- dynamic batching of the query-lane kernels (BASELINE configs[4]) ----------------------------

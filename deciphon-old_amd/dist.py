@@ -15,9 +15,10 @@ import ctypes as C
 
 import numpy as np
 
-from . import HIT_DTYPE, DcpError, RC_EFAIL, lib, partition_by_cells
+from . import HIT64_DTYPE, HIT_DTYPE, DcpError, RC_EFAIL, RC_EINVAL, lib, partition_by_cells
 
 HIT_WORDS = 4  # struct dcp_hit = 4 x 32-bit words
+HIT64_WORDS = 6  # struct dcp_hit64 (scans of a double DB) = 6 x 32-bit words: two indices, two doubles
 ID_BYTES = 128
 
 def bind(lib):
@@ -54,6 +55,15 @@ def bind(lib):
     lib.dcp_dist_free_hits.argtypes = [C.c_void_p]
     lib.dcp_dist_merge_hits.restype = C.c_long
     lib.dcp_dist_merge_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint]
+    # the double twins
+    lib.dcp_dist_gather_hits64.restype = C.c_int
+    lib.dcp_dist_gather_hits64.argtypes = lib.dcp_dist_gather_hits.argtypes
+    lib.dcp_dist_gather_scan_hits64.restype = C.c_int
+    lib.dcp_dist_gather_scan_hits64.argtypes = lib.dcp_dist_gather_scan_hits.argtypes
+    lib.dcp_dist_free_hits64.restype = None
+    lib.dcp_dist_free_hits64.argtypes = [C.c_void_p]
+    lib.dcp_dist_merge_hits64.restype = C.c_long
+    lib.dcp_dist_merge_hits64.argtypes = lib.dcp_dist_merge_hits.argtypes
 
     return lib
 
@@ -75,21 +85,38 @@ def hits_from_words(words):
     return w.view(HIT_DTYPE).reshape(-1)
 
 
-def merge_hits(counts, profile_offsets, records):
-    """dcp_dist_merge_hits: counts[r] records of rank r lie back to back in `records` (shard-local
-    profile indices) -> one list with global indices, ordered by (seq_idx, profile_idx)."""
+def hits64_from_words(words):
+    """[n, 6] int32 words -> structured records of a double scan (HIT64_DTYPE); the bits are kept."""
+    w = np.ascontiguousarray(words, dtype=np.int32)
+    return w.view(HIT64_DTYPE).reshape(-1)
+
+
+def _merge(merge, dtype, counts, profile_offsets, records):
     counts = np.ascontiguousarray(counts, np.uint32)
     offs = np.ascontiguousarray(profile_offsets, np.uint32)
-    rec = np.ascontiguousarray(records, HIT_DTYPE)
+    if np.asarray(records).dtype != dtype:  # never a conversion: float records are not double ones
+        raise DcpError(RC_EINVAL, f"records of {np.asarray(records).dtype}, not {dtype}")
+    rec = np.ascontiguousarray(records, dtype)
     total = int(counts.sum())
     if len(rec) != total or len(offs) != len(counts):
         raise DcpError(RC_EFAIL, "inconsistent counts")
-    out = np.zeros(max(total, 1), HIT_DTYPE)
-    n = lib.dcp_dist_merge_hits(counts.ctypes.data, offs.ctypes.data, len(counts), rec.ctypes.data,
-                                out.ctypes.data, total)
+    out = np.zeros(max(total, 1), dtype)
+    n = merge(counts.ctypes.data, offs.ctypes.data, len(counts), rec.ctypes.data, out.ctypes.data, total)
     if n != total:
         raise DcpError(RC_EFAIL, "dcp_dist_merge_hits failed")
     return out[:total]
+
+
+def merge_hits(counts, profile_offsets, records):
+    """dcp_dist_merge_hits: counts[r] records of rank r lie back to back in `records` (shard-local
+    profile indices) -> one list with global indices, ordered by (seq_idx, profile_idx)."""
+    return _merge(lib.dcp_dist_merge_hits, HIT_DTYPE, counts, profile_offsets, np.asarray(records, HIT_DTYPE))
+
+
+def merge_hits64(counts, profile_offsets, records):
+    """dcp_dist_merge_hits64: merge_hits for the HIT64_DTYPE records of double scans; the log-likelihoods come back
+    with the bits they came with."""
+    return _merge(lib.dcp_dist_merge_hits64, HIT64_DTYPE, counts, profile_offsets, records)
 
 
 META_WORDS = 3  # DCP_DIST_META_WORDS: records held, profile offset, records found
@@ -153,18 +180,34 @@ class CDist:
                                       C.byref(out), C.byref(n))
         return self._take(rc, out, n)
 
-    def _take(self, rc, out, n):
+    def gather_scan_hits64(self, scanner, profile_offset, root=-1):
+        """dcp_dist_gather_scan_hits64: gather_scan_hits for a scanner whose last scan ran on a double DB; the records
+        are HIT64_DTYPE."""
+        out, n = C.c_void_p(), C.c_uint(0)
+        rc = self._lib.dcp_dist_gather_scan_hits64(self._h, scanner._c, profile_offset, root, C.byref(out), C.byref(n))
+        return self._take(rc, out, n, True)
+
+    def gather_hits64(self, hits_dev_ptr, count_dev_ptr, cap, profile_offset, scan_stream, root=-1):
+        """dcp_dist_gather_hits64: gather_hits for a device buffer of cap HIT64_DTYPE records (Scanner.set_hit_buffer64)."""
+        out, n = C.c_void_p(), C.c_uint(0)
+        rc = self._lib.dcp_dist_gather_hits64(self._h, hits_dev_ptr, count_dev_ptr, cap, profile_offset, root,
+                                              scan_stream, C.byref(out), C.byref(n))
+        return self._take(rc, out, n, True)
+
+    def _take(self, rc, out, n, f64=False):
+        free = self._lib.dcp_dist_free_hits64 if f64 else self._lib.dcp_dist_free_hits
+        words, dtype = (HIT64_WORDS, HIT64_DTYPE) if f64 else (HIT_WORDS, HIT_DTYPE)
         if rc:
             if out.value:  # an overflow is reported after the exchange, with the (truncated) list allocated
-                self._lib.dcp_dist_free_hits(out)
+                free(out)
             raise DcpError(rc, self._lib.dcp_dist_last_error(self._h).decode())
         if not out.value:
             return None, n.value
         try:
-            arr = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint32)), shape=(max(n.value, 1) * HIT_WORDS,))
-            return arr[:n.value * HIT_WORDS].copy().view(HIT_DTYPE), n.value
+            arr = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint32)), shape=(max(n.value, 1) * words,))
+            return arr[:n.value * words].copy().view(dtype), n.value
         finally:
-            self._lib.dcp_dist_free_hits(out)
+            free(out)
 
     @property
     def comm_count(self):
@@ -191,10 +234,17 @@ def gather_hits(hit_words, hit_count, profile_offset, slab=4096, group=None):
     index of this rank's shard (records carry shard-local indices).
     Returns all ranks' hits as a HIT_DTYPE array sorted by (seq_idx, profile_idx), identical on
     every rank.  Two small collectives -- {count, offset} of every rank, then fixed-size slabs
-    (re-sized if a rank holds more than `slab` hits) -- and the C bookkeeping of merge_hits."""
+    (re-sized if a rank holds more than `slab` hits) -- and the C bookkeeping of merge_hits.
+
+    hit_words [cap, 6] are the records of a scan of a double DB (dcp_gpu_set_hit_buffer64): the same two
+    collectives, HIT64_DTYPE records and merge_hits64.  Every rank passes the same form."""
     import torch
     import torch.distributed as dist
 
+    if hit_words.dim() != 2 or hit_words.shape[1] not in (HIT_WORDS, HIT64_WORDS):
+        raise ValueError(f"hit_words is [cap, {HIT_WORDS}] (float DB) or [cap, {HIT64_WORDS}] (double DB) int32")
+    f64 = hit_words.shape[1] == HIT64_WORDS
+    from_words, merge, dtype = (hits64_from_words, merge_hits64, HIT64_DTYPE) if f64 else (hits_from_words, merge_hits, HIT_DTYPE)
     world = dist.get_world_size(group)
     meta = torch.stack([hit_count.reshape(()).to(torch.int32),
                         torch.tensor(profile_offset, dtype=torch.int32, device=hit_count.device)])
@@ -213,6 +263,13 @@ def gather_hits(hit_words, hit_count, profile_offset, slab=4096, group=None):
     mine = hit_words[:rows].contiguous()
     slabs = [torch.empty_like(mine) for _ in range(world)]
     dist.all_gather(slabs, mine, group=group)
-    parts = [hits_from_words(s[:n].cpu().numpy()) for s, n in zip(slabs, ns) if n]
-    records = np.concatenate(parts) if parts else np.zeros(0, HIT_DTYPE)
-    return merge_hits(ns, offs, records)
+    parts = [from_words(s[:n].cpu().numpy()) for s, n in zip(slabs, ns) if n]
+    records = np.concatenate(parts) if parts else np.zeros(0, dtype)
+    return merge(ns, offs, records)
+
+
+def gather_hits64(hit_words, hit_count, profile_offset, slab=4096, group=None):
+    """gather_hits for the records of a double scan: hit_words is [cap, 6] int32, the result HIT64_DTYPE."""
+    if hit_words.dim() != 2 or hit_words.shape[1] != HIT64_WORDS:
+        raise ValueError(f"hit_words is [cap, {HIT64_WORDS}] int32: records of struct dcp_hit64")
+    return gather_hits(hit_words, hit_count, profile_offset, slab, group)

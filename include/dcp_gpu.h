@@ -286,8 +286,9 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *, dcp_profile *const *profiles,
  * query-lane kernel (4: the throughput path for batches, of one length or mixed -- it packs the queries by length as
  * dcp_plan_query_slots says, see dcp_gpu_last_scan_query_plan; same bits); 2 and 3,
  * the float query-lane kernels, are DCP_EINVAL.  They leave double results: dcp_gpu_fetch_hits64 / dcp_gpu_fetch_scores64; their paths come from
- * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table,
- * dcp_gpu_hit_buffer, float explicit xtrans) return DCP_EINVAL on it. */
+ * dcp_gpu_trace_paths64.  The float-only calls (dcp_gpu_trace_paths, dcp_gpu_db_fetch_match_table, float explicit
+ * xtrans) return DCP_EINVAL on it; dcp_gpu_hit_buffer answers float scans only and is DCP_EINVAL after a scan of a
+ * double DB, whose buffer dcp_gpu_hit_buffer64 returns (a caller's own: dcp_gpu_set_hit_buffer64). */
 int dcp_gpu_db_upload64(dcp_gpu_ctx *, dcp_profile *const *profiles, unsigned nprofiles);
 /* 32 or 64: the precision of the resident DB; 0 without one. */
 int dcp_gpu_db_precision(dcp_gpu_ctx const *);
@@ -358,7 +359,8 @@ struct dcp_hit
     float alt_loglik;
 };
 
-/* The hit record of a scan of a double DB: same keep rule, evaluated in double */
+/* The hit record of a scan of a double DB: same keep rule, evaluated in double.  24 bytes, 6 uint32 words, no
+ * padding (asserted in csrc/dcp_dist.cpp, which sends it as words). */
 struct dcp_hit64
 {
     uint32_t seq_idx;
@@ -388,6 +390,19 @@ int dcp_gpu_set_hit_buffer(dcp_gpu_ctx *, void *hits_dev, unsigned cap,
  * caller's from dcp_gpu_set_hit_buffer) -- what a C host hands to dcp_dist_gather_hits without touching
  * the HIP API itself.  Call dcp_gpu_sync first: a query-lane scan completes its redo pairs there. */
 int dcp_gpu_hit_buffer(dcp_gpu_ctx *, void **hits_dev, void **nhits_dev, unsigned *cap);
+/* dcp_gpu_set_hit_buffer for the scans of a double DB: hits_dev is cap records of struct dcp_hit64, nhits_dev one
+ * uint32 counter.  NULL, 0, NULL restores the context's own buffer; the same argument checks.  The two registrations
+ * are independent and both may be set: this one applies to scans of a double DB only, the float one to scans of a
+ * float DB only.  Every path of a double scan honours it -- either kernel, kernel 4's redo launches, ranged scans
+ * and the repeat with the row sweep after kernel 4's redo lists overflowed (which zeroes the counter again, so no
+ * record appears twice).  Overflow as in float: the counter keeps counting past cap, nothing is written at or
+ * beyond record cap, and dcp_gpu_fetch_hits64 -- which reads whichever buffer the scan wrote -- returns DCP_ENOMEM
+ * with the true count in *nhits. */
+int dcp_gpu_set_hit_buffer64(dcp_gpu_ctx *, void *hits_dev, unsigned cap, void *nhits_dev);
+/* dcp_gpu_hit_buffer for the last scan of a double DB: what it wrote its struct dcp_hit64 records and counter to,
+ * the context's own buffer or the caller's.  DCP_EINVAL with a message before any scan and after a scan of a
+ * float DB.  Call dcp_gpu_sync first. */
+int dcp_gpu_hit_buffer64(dcp_gpu_ctx *, void **hits_dev, void **nhits_dev, unsigned *cap);
 #ifdef DCP_TEST_HOOKS
 /* NOT in the shipped library: exists only in libdcp_hip_testhooks.so (the same sources compiled with
  * -DDCP_TEST_HOOKS, loaded by the tests alone).  Shrinks the per-size-class capacity of the redo lists
@@ -542,7 +557,9 @@ char const *dcp_prod_header(void);
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum
  * of core sizes = DP cells) resident and scans ALL queries against it; the only exchange of the path
- * is the gather of the 16-byte hit records.  librccl.so is loaded on first use. */
+ * is the gather of the hit records: 16-byte struct dcp_hit after scans of a float DB, 24-byte struct dcp_hit64 after
+ * scans of a double DB (the ...64 calls below; one communicator serves both in turn).  librccl.so is loaded on first
+ * use. */
 typedef struct dcp_dist dcp_dist;
 enum { DCP_DIST_ID_BYTES = 128 }; /* NCCL_UNIQUE_ID_BYTES */
 enum { DCP_DIST_META_WORDS = 3 }; /* per rank in the meta all-gather: records held, profile offset, records found */
@@ -608,6 +625,21 @@ void dcp_dist_free_hits(struct dcp_hit *hits);
  * (seq_idx, profile_idx).  Returns the total, -1 if cap is too small. */
 long dcp_dist_merge_hits(unsigned const *counts, unsigned const *profile_offset, int nranks,
                          struct dcp_hit const *records, struct dcp_hit *out, unsigned cap);
+/* The double twins, for the shards of a double DB (dcp_dist_shard, dcp_gpu_db_upload64 of the shard, the scan): the
+ * same contracts word for word -- collective discipline, return codes and messages included -- on struct dcp_hit64.
+ * The meta all-gather and dcp_dist_gather_plan are shared; the records travel as 6 uint32 words each and are copied,
+ * never converted: a record leaves the gather with the bits the kernel wrote.  dcp_dist_gather_scan_hits64 runs
+ * dcp_gpu_sync, then dcp_gpu_hit_buffer64: a context whose last scan ran on a float DB, or that never scanned, holds no
+ * such records and counts as a rank whose scan failed (it returns that call's DCP_EINVAL and message, its peers
+ * DCP_EFAIL). */
+int dcp_dist_gather_scan_hits64(dcp_dist *, dcp_gpu_ctx *ctx, unsigned profile_offset, int root,
+                                struct dcp_hit64 **out, unsigned *nout);
+int dcp_dist_gather_hits64(dcp_dist *, void const *hits_dev, void const *nhits_dev, unsigned cap,
+                           unsigned profile_offset, int root, void *scan_stream, struct dcp_hit64 **out,
+                           unsigned *nout);
+void dcp_dist_free_hits64(struct dcp_hit64 *hits);
+long dcp_dist_merge_hits64(unsigned const *counts, unsigned const *profile_offset, int nranks,
+                           struct dcp_hit64 const *records, struct dcp_hit64 *out, unsigned cap);
 
 /* Dynamic batching of the query-lane kernels, host side only (what dcp_gpu_scan does with a batch whose automatic
  * or forced kernel is a query-lane one): the queries in ascending length order are cut into groups of 64 -- one

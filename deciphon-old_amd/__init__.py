@@ -77,6 +77,8 @@ ABI_SYMBOLS = [
     # the double build across GPUs: the caller's hit buffer and the gather of struct dcp_hit64 records
     "dcp_gpu_set_hit_buffer64", "dcp_gpu_hit_buffer64", "dcp_dist_gather_scan_hits64", "dcp_dist_gather_hits64",
     "dcp_dist_merge_hits64", "dcp_dist_free_hits64",
+    # both strands: the reverse complement of the resident batch
+    "dcp_gpu_seqs_add_revcomp", "dcp_gpu_seqs_strands", "dcp_gpu_seqs_fetch", "dcp_seq_revcomp",
 ]
 
 
@@ -221,6 +223,10 @@ def _load(path=None, hooks=False):
         "dcp_gpu_seqs_set_xtrans64": (I, [P, P, U]),
         "dcp_lprob_normalize64": (None, [U, P]),
         "dcp_profile_from_parts64": (P, [C.c_char_p, U, I, C.c_double, C.c_char_p, P, P, P, P, C.POINTER(I)]),
+        "dcp_gpu_seqs_add_revcomp": (I, [P]),
+        "dcp_gpu_seqs_strands": (U, [P]),
+        "dcp_gpu_seqs_fetch": (I, [P, U, P, U, C.POINTER(U)]),
+        "dcp_seq_revcomp": (None, [P, U, P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -229,6 +235,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_set_seg_col_bytes"] = (I, [P, C.c_ulonglong])
         sig["dcp_gpu_test_set_trace_mode"] = (I, [P, I, C.c_ulonglong])
         sig["dcp_gpu_test_fetch_table_span"] = (I, [P, U, P, C.c_ulonglong, C.POINTER(U), C.POINTER(U), C.POINTER(U)])
+        sig["dcp_gpu_test_fetch_seq_words"] = (I, [P, U, P, U, C.POINTER(U)])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -570,6 +577,15 @@ def encode_seq(text):
     return lut[np.frombuffer(text.encode() if isinstance(text, str) else text, np.uint8)]
 
 
+def revcomp(ids):
+    """The reverse complement of symbol ids 0..3 (A C G T): out[i] = 3 - ids[n - 1 - i] (dcp_seq_revcomp), the map
+    Scanner.add_reverse_strand applies on the device."""
+    ids = np.frombuffer(ids, np.uint8) if isinstance(ids, (bytes, bytearray)) else np.ascontiguousarray(ids, np.uint8)
+    out = np.empty_like(ids)
+    lib.dcp_seq_revcomp(ids.ctypes.data, len(ids), out.ctypes.data)
+    return out
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -672,6 +688,35 @@ class Scanner:
         off = np.ascontiguousarray(off, np.uint32)
         self._check(self._lib.dcp_gpu_seqs_upload(self._c, cat.ctypes.data, off.ctypes.data, len(off) - 1))
         self._seq_lens = np.diff(off.astype(np.int64))
+
+    def add_reverse_strand(self):
+        """Both strands (dcp_gpu_seqs_add_revcomp): the resident batch of n sequences becomes 2n, sequence n + q the
+        reverse complement of q, written on the device.  Scans, hits, scores and traces then carry indices 0 .. 2n - 1;
+        scan(q_range=(n, 2 * n)) is the minus strand alone.  Until the next upload_seqs."""
+        self._check(self._lib.dcp_gpu_seqs_add_revcomp(self._c))
+        self._seq_lens = np.concatenate([self._seq_lens, self._seq_lens])
+
+    @property
+    def strands(self):
+        """0 (no batch resident), 1, or 2 after add_reverse_strand."""
+        return self._lib.dcp_gpu_seqs_strands(self._c)
+
+    def fetch_seq(self, q):
+        """Resident sequence q as a uint8 array of symbol ids, unpacked from the device's words (dcp_gpu_seqs_fetch)."""
+        n = C.c_uint(0)
+        out = np.zeros(int(self._seq_lens[q]) if 0 <= q < self.nseqs else 1, np.uint8)
+        self._check(self._lib.dcp_gpu_seqs_fetch(self._c, q, out.ctypes.data, len(out), C.byref(n)))
+        return out[:n.value]
+
+    def test_seq_words(self, q):
+        """TEST-ONLY (test-hooks build): the raw L // 16 + 3 words of resident sequence q (uint32)."""
+        n = C.c_uint(0)
+        rc = self._lib.dcp_gpu_test_fetch_seq_words(self._c, q, None, 0, C.byref(n))
+        if rc != RC_ENOMEM:
+            self._check(rc or RC_EFAIL)
+        out = np.zeros(n.value, np.uint32)
+        self._check(self._lib.dcp_gpu_test_fetch_seq_words(self._c, q, out.ctypes.data, len(out), C.byref(n)))
+        return out
 
     def set_xtrans(self, xt):
         """Explicit special transitions [nseqs, 13] for the resident sequences (dcp_gpu_seqs_set_xtrans):

@@ -7,6 +7,7 @@
 // thread_run (src/server/scan_thread.c:99-123).  No CPU fallback exists.
 #include "dcp_kernels.h"
 #include "dcp_f64.h"
+#include "dcp_seqs.h"
 
 #include <hip/hip_runtime.h>
 
@@ -225,6 +226,7 @@ struct dcp_gpu_ctx
 
     // resident sequences
     unsigned nseqs = 0;
+    unsigned strands = 0; // 0 no batch, 1 as uploaded, 2 after dcp_gpu_seqs_add_revcomp: [nseqs / 2, nseqs) is the reverse strand
     uint64_t total_len = 0;
     std::vector<uint32_t> seq_len;
     DevBuf<uint32_t> d_seq_words, d_seq_woff, d_seq_len;
@@ -1382,6 +1384,7 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     }
     // a failed (re)allocation below must not leave the old batch's size paired with new buffers
     c->nseqs = 0;
+    c->strands = 0;
     c->total_len = 0;
     c->seq_len.clear();
     HIP_TRY(c, c->d_seq_words.alloc(nwords));
@@ -1393,6 +1396,7 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     HIP_TRY(c, hipMemcpy(c->d_seq_len.p, len.data(), nseqs * sizeof(uint32_t), hipMemcpyHostToDevice));
     c->seq_len = len;
     c->nseqs = nseqs;
+    c->strands = 1;
     c->total_len = total;
     c->xt_multi = c->xt_h3 = -1;
     c->xt_explicit = false;
@@ -1409,6 +1413,116 @@ int dcp_gpu_seqs_upload_text(dcp_gpu_ctx *c, char const *text, uint32_t const *s
 {
     return upload_seqs(c, (uint8_t const *)text, seq_off, nseqs, true);
 }
+
+unsigned dcp_gpu_seqs_strands(dcp_gpu_ctx const *c) { return c && c->nseqs ? c->strands : 0u; }
+
+// Both strands: the resident batch of n sequences becomes 2n, sequence n + q the reverse complement of q.  The forward
+// half of every array is copied on the device, the reverse half written by dcp_seqs.hip's kernels: no base goes
+// through the host again.  Dependent state is treated as by an upload.
+int dcp_gpu_seqs_add_revcomp(dcp_gpu_ctx *c)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: upload a batch before adding its reverse strand");
+    if (c->strands != 1) return c->fail(DCP_EINVAL, "the resident batch already holds both strands");
+    if (c->xt_explicit || !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "explicit special transitions are in force: they are per sequence -- set them after "
+                                   "dcp_gpu_seqs_add_revcomp, for %llu rows", 2ull * c->nseqs);
+    unsigned const n = c->nseqs;
+    uint64_t const nwords = c->d_seq_words.n;
+    if (2ull * n > 0xffffffffull || 2ull * nwords > 0xffffffffull)
+        return c->fail(DCP_EINVAL, "sequence batch too large for both strands (%llu sequences, %llu words)", 2ull * n,
+                       2ull * (unsigned long long)nwords);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a scan of the forward batch may still be running on the stream (and on the size classes' streams, which join
+    // it): it reads the arrays that are replaced below
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void_last_scan(c);
+    c->qorder_q0 = c->qorder_q1 = ~0u; // the length order and the word planes belong to the batch that was resident
+    std::vector<uint32_t> len(c->seq_len);
+    len.insert(len.end(), c->seq_len.begin(), c->seq_len.end());
+    uint64_t const total = c->total_len;
+    DevBuf<uint32_t> words, woff, dlen;
+    DevBuf<float> xt;
+    // as in an upload: a failed allocation must not leave the old batch's size paired with new buffers
+    auto drop = [&]() {
+        c->nseqs = 0, c->strands = 0, c->total_len = 0;
+        c->seq_len.clear();
+        c->xt_multi = c->xt_h3 = -1;
+    };
+#define SEQS_TRY(call)                                                                                                  \
+    do                                                                                                                  \
+    {                                                                                                                   \
+        hipError_t e_ = (call);                                                                                         \
+        if (e_ != hipSuccess)                                                                                           \
+        {                                                                                                               \
+            drop();                                                                                                     \
+            return c->fail(e_ == hipErrorOutOfMemory ? DCP_ENOMEM : DCP_EFAIL, "%s: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                                               \
+    } while (0)
+    SEQS_TRY(words.alloc(2u * (size_t)nwords));
+    SEQS_TRY(woff.alloc(2u * (size_t)n));
+    SEQS_TRY(dlen.alloc(2u * (size_t)n));
+    SEQS_TRY(xt.alloc(2u * (size_t)n * DCP_XSTRIDE));
+    SEQS_TRY(hipMemcpyAsync(words.p, c->d_seq_words.p, nwords * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    SEQS_TRY(hipMemcpyAsync(woff.p, c->d_seq_woff.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    SEQS_TRY(hipMemcpyAsync(dlen.p, c->d_seq_len.p, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    SEQS_TRY(hipMemcpyAsync(xt.p, c->d_xtrans.p, (size_t)n * DCP_XSTRIDE * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    SEQS_TRY((hipError_t)dcp_launch_revcomp(words.p, words.p + nwords, woff.p, dlen.p, n, (uint32_t)nwords, c->stream));
+    SEQS_TRY(hipStreamSynchronize(c->stream)); // the old arrays are freed below
+#undef SEQS_TRY
+    std::swap(c->d_seq_words.p, words.p), std::swap(c->d_seq_words.n, words.n);
+    std::swap(c->d_seq_woff.p, woff.p), std::swap(c->d_seq_woff.n, woff.n);
+    std::swap(c->d_seq_len.p, dlen.p), std::swap(c->d_seq_len.n, dlen.n);
+    std::swap(c->d_xtrans.p, xt.p), std::swap(c->d_xtrans.n, xt.n);
+    c->seq_len.swap(len);
+    c->nseqs = 2u * n;
+    c->strands = 2;
+    c->total_len = 2u * total;
+    c->xt_multi = c->xt_h3 = -1; // the rows of the reverse half are derived with the next scan's flags
+    c->xt64.clear();
+    return DCP_OK;
+}
+
+// the words of resident sequence q, as the device holds them
+static int fetch_seq_words(dcp_gpu_ctx *c, unsigned q, std::vector<uint32_t> &w)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    uint32_t woff = 0;
+    HIP_TRY(c, hipMemcpy(&woff, c->d_seq_woff.p + q, sizeof woff, hipMemcpyDeviceToHost));
+    w.resize((size_t)c->seq_len[q] / 16u + 3u);
+    if ((uint64_t)woff + w.size() > c->d_seq_words.n) return c->fail(DCP_EFAIL, "sequence %u lies outside the resident words", q);
+    HIP_TRY(c, hipMemcpy(w.data(), c->d_seq_words.p + woff, w.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return DCP_OK;
+}
+
+int dcp_gpu_seqs_fetch(dcp_gpu_ctx *c, unsigned q, uint8_t *ids, unsigned cap, unsigned *len)
+{
+    if (!c) return DCP_EINVAL;
+    if (q >= c->nseqs) return c->fail(DCP_EINVAL, "sequence %u is not resident (%u are)", q, c->nseqs);
+    uint32_t const L = c->seq_len[q];
+    if (len) *len = L;
+    if (cap < L || !ids) return c->fail(DCP_ENOMEM, "sequence %u has %u symbols: the buffer holds %u", q, L, cap);
+    std::vector<uint32_t> w;
+    if (int rc = fetch_seq_words(c, q, w)) return rc;
+    for (uint32_t i = 0; i < L; ++i)
+        ids[i] = (uint8_t)((w[i >> 4] >> ((i & 15u) * 2u)) & 3u);
+    return DCP_OK;
+}
+
+#ifdef DCP_TEST_HOOKS
+int dcp_gpu_test_fetch_seq_words(dcp_gpu_ctx *c, unsigned q, uint32_t *out, unsigned cap, unsigned *nwords)
+{
+    if (!c) return DCP_EINVAL;
+    if (q >= c->nseqs) return c->fail(DCP_EINVAL, "sequence %u is not resident (%u are)", q, c->nseqs);
+    unsigned const nw = c->seq_len[q] / 16u + 3u;
+    if (nwords) *nwords = nw;
+    if (cap < nw || !out) return DCP_ENOMEM;
+    std::vector<uint32_t> w;
+    if (int rc = fetch_seq_words(c, q, w)) return rc;
+    std::memcpy(out, w.data(), nw * sizeof(uint32_t));
+    return DCP_OK;
+}
+#endif
 
 // ---------------------------------------------------------------------------
 // Scan

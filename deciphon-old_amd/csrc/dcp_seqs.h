@@ -1,0 +1,22 @@
+// dcp_seqs.h -- kernels on the resident sequence batch itself (dcp_seqs.hip): the reverse strand.
+#ifndef DCP_SEQS_H
+#define DCP_SEQS_H
+
+#include "dcp_host.h"
+#include <stdint.h>
+
+extern "C" {
+// Sequences n .. 2n - 1 of a batch whose forward half [0, n) is in place: words_out [nwords] (the second half of the
+// word array) receives the reverse complements, woff[n + q] = woff[q] + nwords, len[n + q] = len[q].  words_in /
+// woff / len: the forward half ([nwords], [n] of [2n], [n] of [2n]).  Two launches on `stream`; HIP's error code.
+int dcp_launch_revcomp(uint32_t const *words_in, uint32_t *words_out, uint32_t *woff, uint32_t *len, unsigned nseqs,
+                       uint32_t nwords, void *stream);
+#ifdef DCP_TEST_HOOKS
+// NOT in the shipped library (libdcp_hip_testhooks.so only; declared here, not in include/dcp_gpu.h).  The raw
+// L / 16 + 3 words of resident sequence q as the device holds them: *nwords receives their number, out the words if
+// cap holds them (else DCP_ENOMEM).
+int dcp_gpu_test_fetch_seq_words(dcp_gpu_ctx *, unsigned q, uint32_t *out, unsigned cap, unsigned *nwords);
+#endif
+}
+
+#endif

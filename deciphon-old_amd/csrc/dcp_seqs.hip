@@ -1,0 +1,87 @@
+// dcp_seqs.hip -- the reverse strand of the resident batch (dcp_gpu_seqs_add_revcomp), and its host restatement.
+//
+// A resident sequence of L bases is L / 16 + 3 words, base i in bits 2 (i & 15) of word i >> 4 (A = 0, C = 1, G = 2,
+// T = 3), every bit behind base L - 1 zero.  Its reverse complement has base i = 3 - base(L - 1 - i): output word j
+// holds the input bases [e - 16, e), e = L - 16 j, in falling order -- at most two adjacent input words, aligned by one
+// 64-bit shift, their sixteen 2-bit groups reversed, all bits complemented (3 - b = ~b on two bits), the groups behind
+// the sequence's end masked off.  One lane per output word of the whole batch, consecutive lanes on consecutive
+// words; a lane finds its sequence by a binary search in woff (the lanes of a wavefront mostly share it: the probes
+// are broadcast reads of a few cache lines).  Sequences of 1 nt and of 2^20 nt in one batch cost the same per word.
+#include "dcp_seqs.h"
+
+#include <hip/hip_runtime.h>
+
+namespace
+{
+
+constexpr unsigned kBlock = 256;
+
+__device__ __forceinline__ uint32_t reverse_groups(uint32_t x)
+{
+    uint32_t const y = __brev(x); // groups in reverse order, the two bits of each swapped
+    return ((y >> 1) & 0x55555555u) | ((y & 0x55555555u) << 1);
+}
+
+__global__ __launch_bounds__(kBlock) void revcomp_words_kernel(uint32_t const *__restrict__ words_in,
+                                                               uint32_t *__restrict__ words_out,
+                                                               uint32_t const *__restrict__ woff,
+                                                               uint32_t const *__restrict__ len, unsigned nseqs,
+                                                               uint32_t nwords)
+{
+    uint64_t const g64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g64 >= nwords) return;
+    uint32_t const g = (uint32_t)g64;
+    // the sequence whose words [woff[q], woff[q + 1]) hold g: the last q with woff[q] <= g (woff[0] = 0)
+    unsigned lo = 0, hi = nseqs;
+    while (hi - lo > 1u)
+    {
+        unsigned const mid = lo + (hi - lo) / 2u;
+        if (woff[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    uint32_t const base = woff[lo], L = len[lo];
+    uint32_t const j = g - base; // < L / 16 + 3
+    uint32_t out = 0u;           // pad words stay zero
+    if ((uint64_t)j * 16u < L)
+    {
+        uint32_t const e = L - j * 16u;          // the word's bases come from [e - 16, e) of the input, e >= 1
+        uint32_t const we = e >> 4, r = e & 15u; // e >> 4 <= L / 16: inside the sequence's words
+        uint32_t const *w = words_in + base;
+        uint64_t const v = ((uint64_t)w[we] << 32) | (we ? w[we - 1u] : 0u);
+        uint32_t const x = (uint32_t)(v >> (2u * r)); // group k = input base e - 16 + k (zero below base 0)
+        uint32_t const cnt = e < 16u ? e : 16u;       // bases of this output word
+        uint32_t const mask = cnt == 16u ? 0xffffffffu : (1u << (2u * cnt)) - 1u;
+        out = ~reverse_groups(x) & mask;
+    }
+    words_out[g] = out;
+}
+
+__global__ __launch_bounds__(kBlock) void revcomp_index_kernel(uint32_t *__restrict__ woff, uint32_t *__restrict__ len,
+                                                               unsigned nseqs, uint32_t nwords)
+{
+    unsigned const q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nseqs) return;
+    woff[nseqs + q] = woff[q] + nwords;
+    len[nseqs + q] = len[q];
+}
+
+} // namespace
+
+extern "C" int dcp_launch_revcomp(uint32_t const *words_in, uint32_t *words_out, uint32_t *woff, uint32_t *len,
+                                  unsigned nseqs, uint32_t nwords, void *stream)
+{
+    if (nseqs == 0 || nwords == 0) return (int)hipErrorInvalidValue;
+    hipStream_t const s = (hipStream_t)stream;
+    unsigned const wblocks = (unsigned)(((uint64_t)nwords + kBlock - 1u) / kBlock);
+    // the word kernel reads the forward half of woff / len only: the index kernel may run behind it
+    revcomp_words_kernel<<<wblocks, kBlock, 0, s>>>(words_in, words_out, woff, len, nseqs, nwords);
+    revcomp_index_kernel<<<(nseqs + kBlock - 1u) / kBlock, kBlock, 0, s>>>(woff, len, nseqs, nwords);
+    return (int)hipGetLastError();
+}
+
+// The same map on symbol ids, on the host: what the tests and the host layer restate the kernel with.
+extern "C" void dcp_seq_revcomp(uint8_t const *ids, unsigned n, uint8_t *out)
+{
+    for (unsigned i = 0; i < n; ++i)
+        out[i] = (uint8_t)(3u - ids[n - 1u - i]);
+}

@@ -398,6 +398,16 @@ static void batch_result_free(struct batch_result *r)
     memset(r, 0, sizeof *r);
 }
 
+/* scan_cfg.minus_strand_id / minus_strand_arg: with id set a batch is scanned on both strands -- the device appends the
+ * reverse complements to the resident batch (dcp_gpu_seqs_add_revcomp), hits with seq_idx >= nseqs are the minus
+ * strand's.  NULL (what thread_run / thread_run_batch pass) or id == NULL: the forward strand only. */
+struct strands
+{
+    int64_t (*id)(int64_t seq_id, void *arg);
+    void *arg;
+};
+static bool both_strands(struct strands const *st) { return st && st->id; }
+
 static enum rc batch_check(struct scan_thread *t, struct imm_seq const *seqs, unsigned nseqs, unsigned *nprofiles)
 {
     struct profile_reader *reader = t->reader;
@@ -408,7 +418,8 @@ static enum rc batch_check(struct scan_thread *t, struct imm_seq const *seqs, un
     return RC_OK;
 }
 
-static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const *seqs, unsigned nseqs)
+static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const *seqs, unsigned nseqs,
+                            struct strands const *st)
 {
     double const t_in = stat_now();
     enum rc rc = thread_prepare(t, tid);
@@ -446,6 +457,8 @@ static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const
     }
     int drc = 0;
     if (!rc && (drc = dcp_gpu_seqs_upload(t->gpu, ids, off, nseqs))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+    /* the minus strand never leaves the device: sequences nseqs .. 2 nseqs - 1 of the resident batch */
+    if (!rc && both_strands(st) && (drc = dcp_gpu_seqs_add_revcomp(t->gpu))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
     free(ids);
     free(off);
     struct dcp_scan_params prm = {t->multi_hits, t->hmmer3_compat, (float)t->lrt_threshold, 0, 0};
@@ -468,7 +481,7 @@ static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const
 }
 
 static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, unsigned nseqs, unsigned nprofiles,
-                           struct batch_result *res)
+                           struct strands const *st, struct batch_result *res)
 {
     memset(res, 0, sizeof *res);
     double const t_in = stat_now();
@@ -481,15 +494,21 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
     unsigned nhits = 0;
     drc = dcph_fetch_hits(t->gpu, NULL, 0, &nhits); /* count first */
     if (drc && drc != DCP_ENOMEM) return fail((enum rc)drc, "fetch hits");
-    if ((uint64_t)nhits > (uint64_t)nprofiles * nseqs) return fail(RC_EFAIL, "more hits than pairs");
+    uint64_t const resident = both_strands(st) ? 2 * (uint64_t)nseqs : nseqs;
+    if ((uint64_t)nhits > (uint64_t)nprofiles * resident) return fail(RC_EFAIL, "more hits than pairs");
     if (nhits == 0) return RC_OK;
     res->hits = malloc((size_t)nhits * sizeof *res->hits);
     if (!res->hits) rc = fail(RC_ENOMEM, "alloc hits");
     if (!rc && (drc = dcph_fetch_hits(t->gpu, res->hits, nhits, &nhits))) rc = fail((enum rc)drc, "fetch hits");
     uint64_t cap = 0;
     for (unsigned h = 0; !rc && h < nhits; ++h)
-        cap += 2 * (uint64_t)seqs[res->hits[h].seq_idx].size +
-               2 * (uint64_t)dcp_profile_core_size(t->impls[res->hits[h].profile_idx]) + 16;
+    {
+        unsigned const q = res->hits[h].seq_idx; /* a minus-strand hit has its source's length */
+        if (q >= resident) rc = fail(RC_EFAIL, "hit of a sequence that is not resident");
+        else
+            cap += 2 * (uint64_t)seqs[q >= nseqs ? q - nseqs : q].size +
+                   2 * (uint64_t)dcp_profile_core_size(t->impls[res->hits[h].profile_idx]) + 16;
+    }
     if (!rc && cap > UINT32_MAX) rc = fail(RC_ENOMEM, "too many path steps in one batch");
     if (!rc)
     {
@@ -527,22 +546,67 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
     return rc;
 }
 
-static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, struct batch_result *res);
-static enum rc batch_rows(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, struct batch_result *res)
+static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, unsigned nseqs,
+                                struct strands const *st, struct batch_result *res);
+static enum rc batch_rows(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, unsigned nseqs,
+                          struct strands const *st, struct batch_result *res)
 {
     double const t_in = stat_now();
-    enum rc rc = batch_rows_timed(t, seqs, seq_ids, res);
+    enum rc rc = batch_rows_timed(t, seqs, seq_ids, nseqs, st, res);
     stat_add(&g_stats.rows_s, stat_now() - t_in);
     return rc;
 }
 
-static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, struct batch_result *res)
+/* The reverse complement of a sequence as text over its own alphabet (malloc'ed, NUL-terminated): dcp_seq_revcomp
+ * of its symbol ids, the map the device applied to the resident words. */
+static char *revcomp_text(struct imm_seq const *seq, enum rc *rc)
+{
+    uint8_t *ids = dcp_host_seq_ids(seq, rc);
+    uint8_t *rev = malloc(seq->size ? seq->size : 1);
+    char *text = malloc((size_t)seq->size + 1);
+    if (ids && rev && text)
+    {
+        dcp_seq_revcomp(ids, seq->size, rev);
+        for (unsigned i = 0; i < seq->size; ++i)
+            text[i] = seq->abc->symbols[rev[i]];
+        text[seq->size] = '\0';
+    }
+    else
+    {
+        if (ids) *rc = fail(RC_ENOMEM, "alloc sequence");
+        free(text);
+        text = NULL;
+    }
+    free(ids), free(rev);
+    return text;
+}
+
+static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seqs, int64_t const *seq_ids, unsigned nseqs,
+                                struct strands const *st, struct batch_result *res)
 {
     enum rc rc = RC_OK;
     unsigned const nhits = res->nhits;
     dcph_hit const *hits = res->hits;
     if (nhits)
     {
+        /* Rows leave in source order: per source sequence its plus-strand rows by profile, then its minus-strand rows
+         * by profile.  The hit list is sorted by (resident index, profile), the minus strand's hits behind all of the
+         * plus strand's: ord[] merges the two runs (the identity for a forward-only batch). */
+        unsigned *ord = malloc((size_t)nhits * sizeof *ord);
+        if (!ord)
+        {
+            batch_result_free(res);
+            return fail(RC_ENOMEM, "alloc product rows");
+        }
+        unsigned split = nhits;
+        if (both_strands(st))
+            for (split = 0; split < nhits && hits[split].seq_idx < nseqs; ++split)
+                ;
+        for (unsigned a = 0, b = split, k = 0; k < nhits; ++k)
+        {
+            bool const plus = a < split && (b >= nhits || hits[a].seq_idx <= hits[b].seq_idx - nseqs);
+            ord[k] = plus ? a++ : b++;
+        }
         /* Product rows: one per hit, each formatted into its own memory stream -- every emitting step of a
          * path is decoded against its state's codon distribution, a few hundred per row -- by however many
          * host threads OpenMP gives this call (none extra when the caller already runs it inside a parallel
@@ -569,7 +633,8 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
 #pragma omp atomic read
                 cur = shared;
                 if (cur) continue;
-                unsigned const q = hits[h].seq_idx;
+                bool const minus = both_strands(st) && hits[h].seq_idx >= nseqs; /* batch_trace checked the range */
+                unsigned const q = minus ? hits[h].seq_idx - nseqs : hits[h].seq_idx;
                 imm_float const lrt = xmath_lrt(hits[h].null_loglik, hits[h].alt_loglik);
                 if (!imm_lprob_is_finite(lrt) || lrt < t->lrt_threshold) continue; /* scan_thread.c:123 */
                 struct protein_profile view;
@@ -577,11 +642,21 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
                 struct protein_match pm;
                 struct prod pr = t->prod; /* job fields; the per-hit ones follow (:125-128) */
                 FILE *ms = NULL;
+                char *rtext = NULL;
+                struct imm_seq seq = seqs[q];
                 enum rc r = profile_view(t, hits[h].profile_idx, &view);
+                if (!r && minus)
+                {
+                    /* the row of a minus-strand hit: the bases the device scanned, under the caller's id for them */
+                    rtext = revcomp_text(&seqs[q], &r);
+                    if (rtext) seq.str = rtext;
+                }
+                if (r) free(view.alt.match_ndists);
                 if (!r)
                 {
                     snprintf(pr.profile_name, sizeof pr.profile_name, "%s", view.super.accession);
                     if (seq_ids) pr.seq_id = seq_ids[q];
+                    if (minus) pr.seq_id = st->id(pr.seq_id, st->arg);
                     pr.null_loglik = (double)hits[h].null_loglik;
                     pr.alt_loglik = (double)hits[h].alt_loglik;
                     r = dcp_host_path_assign(&path, res->steps + res->soff[h], res->soff[h + 1] - res->soff[h]);
@@ -589,12 +664,13 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
                     if (!r)
                     {
                         match_setup(&pm.match, &view.super);
-                        r = prod_fwrite_fp(ms, &pr, &seqs[q], &path, t->write_match_func, &pm.match);
+                        r = prod_fwrite_fp(ms, &pr, &seq, &path, t->write_match_func, &pm.match);
                     }
                     if (ms && fclose(ms) && !r) r = fail(RC_EIO, "failed to write prod");
                     free(view.alt.match_ndists);
                 }
                 free(path.steps);
+                free(rtext);
                 if (r)
                 {
 #pragma omp atomic write
@@ -603,23 +679,28 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
             }
             rc = shared;
         }
-        for (unsigned h = 0; row && h < nhits; ++h)
+        for (unsigned k = 0; row && k < nhits; ++k)
         {
+            unsigned const h = ord[k];
             if (!rc && row[h] && row_len && fwrite(row[h], 1, row_len[h], out) != row_len[h]) rc = fail(RC_EIO, "failed to write prod");
-            free(row[h]);
         }
+        for (unsigned h = 0; row && h < nhits; ++h)
+            free(row[h]);
         free(row);
         free(row_len);
         /* the thread's own prod / match keep what the serial loop left in them: the last hit's fields */
         if (!rc)
         {
-            unsigned const h = nhits - 1u;
+            unsigned const h = ord[nhits - 1u];
+            bool const minus = both_strands(st) && hits[h].seq_idx >= nseqs;
             t->prod.null_loglik = (double)hits[h].null_loglik;
             t->prod.alt_loglik = (double)hits[h].alt_loglik;
             t->null.prod.loglik = hits[h].null_loglik;
             t->alt.prod.loglik = hits[h].alt_loglik;
-            if (seq_ids) t->prod.seq_id = seq_ids[hits[h].seq_idx];
+            if (seq_ids) t->prod.seq_id = seq_ids[minus ? hits[h].seq_idx - nseqs : hits[h].seq_idx];
+            if (minus) t->prod.seq_id = st->id(t->prod.seq_id, st->arg);
         }
+        free(ord);
     }
     batch_result_free(res);
     return rc;
@@ -632,9 +713,9 @@ enum rc thread_run_batch(struct scan_thread *t, int tid, struct imm_seq const *s
     enum rc rc = batch_check(t, seqs, nseqs, &n);
     if (rc || n == 0) return rc;
     struct batch_result res;
-    if ((rc = batch_submit(t, tid, seqs, nseqs))) return rc;
-    if ((rc = batch_trace(t, seqs, nseqs, n, &res))) return rc;
-    return batch_rows(t, seqs, seq_ids, &res);
+    if ((rc = batch_submit(t, tid, seqs, nseqs, NULL))) return rc;
+    if ((rc = batch_trace(t, seqs, nseqs, n, NULL, &res))) return rc;
+    return batch_rows(t, seqs, seq_ids, nseqs, NULL, &res);
 }
 
 enum rc thread_run(struct scan_thread *t, int tid)
@@ -695,6 +776,10 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
     unsigned const limit_n = batch + batch / 2u;
     unsigned long const limit_s = cfg.batch_symbols + cfg.batch_symbols / 2u;
     unsigned const qcap = limit_n + 1u;
+    /* both strands: a pass's device work is twice its source's bases (batch_symbols counts device bases); `batch`
+     * and the progress units keep counting source sequences */
+    struct strands const strands = {cfg.minus_strand_id, cfg.minus_strand_arg};
+    unsigned long const bases_per_symbol = both_strands(&strands) ? 2u : 1u;
     memset(&g_stats, 0, sizeof g_stats);
     /* the partitions' host threads (one per device) each fan out once more: unpacking a partition and formatting a
      * batch's product rows are many-core jobs of their own */
@@ -822,7 +907,7 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
                 break;
             }
             qid[qn] = s.id;
-            qlen[qn] = (unsigned long)strlen(qtext[qn]);
+            qlen[qn] = (unsigned long)strlen(qtext[qn]) * bases_per_symbol;
             qs += qlen[qn];
             ++qn;
         }
@@ -857,14 +942,14 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
             unsigned n = 0;
             enum rc r = batch_check(&th[i], bseq[cur], nb, &n);
             bool const work = !r && n != 0;
-            if (work) r = batch_submit(&th[i], (int)i, bseq[cur], nb);
+            if (work) r = batch_submit(&th[i], (int)i, bseq[cur], nb, &strands);
             /* the device is busy with batch i: now the rows of batch i-1 */
             if (npend && pend[i].nhits)
             {
-                enum rc r2 = batch_rows(&th[i], bseq[prev], bid[prev], &pend[i]);
+                enum rc r2 = batch_rows(&th[i], bseq[prev], bid[prev], npend, &strands, &pend[i]);
                 if (!r) r = r2;
             }
-            if (work && !r) r = batch_trace(&th[i], bseq[cur], nb, n, &pend[i]);
+            if (work && !r) r = batch_trace(&th[i], bseq[cur], nb, n, &strands, &pend[i]);
             if (r)
             {
 #pragma omp atomic write
@@ -885,7 +970,7 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
 #pragma omp parallel for schedule(static, 1) num_threads(nparts)
         for (unsigned i = 0; i < nparts; ++i)
         {
-            enum rc r = pend[i].nhits ? batch_rows(&th[i], bseq[prev], bid[prev], &pend[i]) : RC_OK;
+            enum rc r = pend[i].nhits ? batch_rows(&th[i], bseq[prev], bid[prev], npend, &strands, &pend[i]) : RC_OK;
             if (r)
             {
 #pragma omp atomic write
@@ -960,7 +1045,7 @@ enum rc scan_run_local(char const *db_filename, struct scan_seq const *seqs, uns
 {
     if (!seqs || !prods || batch == 0) return fail(RC_EINVAL, "bad scan arguments");
     struct list_source src = {seqs, nseqs, 0};
-    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0};
+    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0, NULL, NULL};
     enum rc rc = scan_run_source(db_filename, cfg, nthreads, list_next, &src);
     if (rc) return rc;
     char buf[1 << 16];

@@ -316,6 +316,29 @@ int dcp_gpu_seqs_upload(dcp_gpu_ctx *, uint8_t const *seqs,
 int dcp_gpu_seqs_upload_text(dcp_gpu_ctx *, char const *text,
                              uint32_t const *seq_off, unsigned nseqs);
 unsigned dcp_gpu_nseqs(dcp_gpu_ctx const *);
+/* Both strands.  The frame model absorbs frame shifts inside a read, nothing absorbs the strand: a gene on the minus
+ * strand is found only in the read's reverse complement.  After this call the resident batch of n sequences is 2n:
+ * sequence n + q is the reverse complement of sequence q -- base i = 3 - base(L - 1 - i), ids A C G T = 0 1 2 3 --
+ * with the same length, written on the device from the resident 2-bit words (csrc/dcp_seqs.hip; the forward half is
+ * copied device to device, no base goes through the host again).  Everything downstream sees a batch of 2n:
+ * dcp_gpu_nseqs, the cells / bytes accounting, every kernel of either precision, hits, scores, traces and gathers carry
+ * resident indices 0 .. 2n - 1, and dcp_gpu_scan_range(.., n, 2n) is "minus strand only".  Dependent state is
+ * treated as by an upload (the last scan is void).  DCP_EINVAL, with a message and the batch untouched: no batch
+ * resident; the batch already holds both strands; explicit special transitions in force (they are per sequence: set
+ * them after this call, for 2n rows); 2n sequences or their words would pass 2^32 - 1 (checked before any allocation).
+ * A failed allocation leaves the context without a batch, as a failed upload does.  The next sequence upload
+ * returns the context to one strand.  Works on float and double DBs alike, and with no DB resident. */
+int dcp_gpu_seqs_add_revcomp(dcp_gpu_ctx *);
+/* 0 (no batch resident), 1, or 2 after dcp_gpu_seqs_add_revcomp. */
+unsigned dcp_gpu_seqs_strands(dcp_gpu_ctx const *);
+/* Resident sequence q as symbol ids, unpacked from the device's words: what a caller hands to dcp_prod_format_row /
+ * dcp_profile_decode for a minus-strand hit.  *len (may be NULL) receives its length; DCP_ENOMEM (with *len set) if
+ * cap is smaller, DCP_EINVAL if q is not resident.  (The tests' build also has dcp_gpu_test_fetch_seq_words, the raw
+ * L / 16 + 3 words of a sequence: declared in csrc/dcp_seqs.h, not here.) */
+int dcp_gpu_seqs_fetch(dcp_gpu_ctx *, unsigned q, uint8_t *ids, unsigned cap, unsigned *len);
+/* The reverse complement of n symbol ids 0..3 on the host: out[i] = 3 - ids[n - 1 - i] (out must not overlap ids).
+ * The restatement of the device kernel that the tests and the host layer use. */
+void dcp_seq_revcomp(uint8_t const *ids, unsigned n, uint8_t *out);
 /* Explicit special transitions for the resident sequences: xt [nseqs][13] in dcp_xtrans order.
  * By default a scan derives them from each sequence's length and the scan's flags (what
  * protein_profile_setup does per pair); imm_dp_viterbi on a profile whose transitions were set some

@@ -889,6 +889,18 @@ struct scan_cfg
      * packs the sequences by length itself (include/dcp_gpu.h, dcp_plan_query_slots); product rows keep the source's
      * order. */
     unsigned long batch_symbols;
+    /* Both strands: non-NULL -> every sequence is also scanned as its reverse complement, and the rows of those hits
+     * carry minus_strand_id(seq_id, arg) as their seq_id (the products format has no strand column; the caller owns the
+     * id space).  NULL = forward strand only, exactly as before.
+     * The reverse complements are made on the device from the resident batch (dcp_gpu_seqs_add_revcomp); a minus-strand
+     * row is formatted from dcp_seq_revcomp of the source's symbols.  Rows keep the source's order: per source sequence
+     * its plus-strand rows by profile, then its minus-strand rows by profile.  A pass's size counts device work: its
+     * bases are compared with batch_symbols as twice the source's; `batch` keeps counting source sequences, and
+     * `progress` keeps reporting (profile, source sequence) pairs -- not doubled.  scan_last_stats' hits / steps count
+     * both strands.  minus_strand_id may be called from several host threads at once.  thread_run / thread_run_batch
+     * take no scan_cfg and stay forward-only. */
+    int64_t (*minus_strand_id)(int64_t seq_id, void *arg);
+    void *minus_strand_arg;
 };
 /* Where the last scan_run_source spent its time (not in the reference; profiles/host_scan_probe.c prints it): host
  * seconds summed over the partitions' threads.  scan_wait_s is the wait for the device scans (the host has nothing

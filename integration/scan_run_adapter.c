@@ -169,7 +169,8 @@ enum rc scan_run(int64_t job_id, unsigned num_threads)
                            .keep_resident = true,    /* the next job on the same database starts at the sequences */
                            .progress = on_progress,
                            .progress_arg = NULL,
-                           .batch_symbols = SCAN_RUN_BATCH_SYMBOLS};
+                           .batch_symbols = SCAN_RUN_BATCH_SYMBOLS,
+                           .minus_strand_id = NULL}; /* forward strand only: the scheduler's scans have no notion of strands */
     rc = scan_run_source(ad.db.filename, cfg, num_threads, next_seq, NULL);
     if (rc)
     {

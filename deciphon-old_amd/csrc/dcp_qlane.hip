@@ -63,12 +63,14 @@ constexpr unsigned kPlanes = kRecomputeB ? 3u : 4u; // scratch planes per block:
 //           tile's sweep: -5 VALU per row (stage 1 of the two-stage kernel: -4, it ORs its image base in);
 //           2 bytes per row and lane instead of a quarter byte (+0.9 TB of the 6.3 TB a C3 launch moves)
 //   IN16    the insert / background table has 16-byte rows like the match images, so its gathers reuse the
-//           match table's byte offsets: -5 v_lshrrev per row, +10.9 KB of LDS per table.  Single-stage
-//           kernel only: the two-stage kernel's 160 KiB are spoken for -- two images, the table and a
-//           16-row ring -- and the ring cannot shrink: with the hand-shake once per five-row group the
-//           producer may start a group only when the consumer has taken row p + 4 - kRD (+ hysteresis),
-//           the consumer only when row c + 6 (+ hysteresis) is written, so fewer than 12 rows can leave
-//           both waiting (an 8-row ring did: a hung parity test, round 3).
+//           match table's byte offsets: -5 v_lshrrev per row, +10.9 KB of LDS per table.  The two-stage
+//           kernel has it too: its 160 KiB hold two images, ONE such table and the 16-row ring once the
+//           flags sit behind image 1, and stage 1 reaches table and image from a riding base of 32 KiB
+//           (the layout above kL2TabIN; -23..25 VALU per five rows in every sweep of that kernel).
+//           The ring is not what pays for it, and it cannot shrink: with the hand-shake once per five-row
+//           group the producer may start a group only when the consumer has taken row p + 4 - kRD
+//           (+ hysteresis), the consumer only when row c + 6 (+ hysteresis) is written, so fewer than
+//           12 rows can leave both waiting (an 8-row ring did: a hung parity test, round 3).
 //   EM      E(j) is the maximum over the MATCH states only: with MD, DD <= 0 -- every model whose
 //           transitions are log-probabilities -- D_k <= max_{i<k} M_i, so the delete states never decide
 //           it (exactly: an add of a non-positive number never rounds up); -4 v_max3 per row.  A profile
@@ -277,21 +279,39 @@ struct LdsLink
     unsigned seen;         // wave-uniform: the partner's progress as last read
 };
 // Block LDS of the two-stage kernel: all 160 KiB, laid out so that EVERY access keeps an immediate
-// offset.  Gathers address a tile image as (window bits) + 16-bit immediate: image 0 sits at 0, image 1
-// at 64 KiB with that base carried in the window register (gather_off<BASE>); the insert/background
-// table is reached from (window >> 1), i.e. from base/2 = 32 KiB for stage 1, so ONE copy at 43 648
-// serves both stages (immediates 43 648.. and 10 880..).  The ring's planes start at 7 x 16 KiB.
-constexpr unsigned kL2TabIN = 43648u;                 // = one tile image: 2 groups x 1364 codes x 16 B
-constexpr unsigned kL2FlagP = kL2TabIN + 2u * 1364u * 4u; // 54 560: producer flags [256]
-constexpr unsigned kL2FlagC = kL2FlagP + kRLanes * 4u;
-constexpr unsigned kL2Null = kL2FlagC + kRLanes * 4u;    // (round 2-3: null scores, stage 0 -> final stage; now parked in the planes)
-constexpr unsigned kL2Task = kL2Null + kRLanes * 4u;     // the task word
-constexpr unsigned kL2Abort = kL2Task + 4u;              // != 0: a wavefront of this block ran into the ring's poll bound during this task
-constexpr unsigned kL2Err = kL2Task + 8u;                // the address of the scan's error word (8 bytes), for ring_wait
+// offset.  A gather's address is (window bits | riding base) + 16-bit immediate, and the immediate is
+// (what is read - riding base) + the word length's first row.  Stage 0 rides base 0, stage 1 rides
+// kL2Base1 = 32 KiB in the window register (gather_off<BASE>): that is below the table AND below image 1,
+// so ONE copy of the insert/background table, with 16-byte rows like the images, is reached by both
+// stages with the match gather's own byte offset (no shift per word length):
+//        0 ..  43 648  image 0                 stage 0: immediates      0 .. 27 264
+//   43 648 ..  65 472  table, 1364 x 16 B      stage 0: 43 648 .. 49 088;  stage 1: 10 880 .. 16 320
+//   65 536 .. 109 184  image 1                                             stage 1: 32 768 .. 60 032
+//  109 184 .. 111 248  producer flags, consumer flags, task / abort / error words
+//  114 688 .. 163 840  the ring: 3 planes x 16 rows, planes at multiples of 16 KiB
+// (With image 1's own address, 64 KiB, as the riding base no table copy below it can be reached from
+// stage 1 without halving the offset: the 8-byte rows of rounds 2-4.)
+constexpr unsigned kL2ImageBytes = 2u * 1364u * 16u;   // one tile image: 2 groups x 1364 codes x 16 B
+constexpr unsigned kL2TabIN = kL2ImageBytes;           // 43 648: {insert, background, 0, 0} per code
+constexpr unsigned kL2TabINBytes = 1364u * 16u;
+constexpr unsigned kL2Base1 = 32768u;                  // stage 1's riding base
 constexpr unsigned kL2Tab1 = 65536u;                   // image of the odd tile
+constexpr unsigned kL2FlagP = kL2Tab1 + kL2ImageBytes; // 109 184: producer flags [256]
+constexpr unsigned kL2FlagC = kL2FlagP + kRLanes * 4u;
+constexpr unsigned kL2Task = kL2FlagC + kRLanes * 4u;  // the task word
+constexpr unsigned kL2Abort = kL2Task + 4u;            // != 0: a wavefront of this block ran into the ring's poll bound during this task
+constexpr unsigned kL2Err = kL2Task + 8u;              // the address of the scan's error word (8 bytes), for ring_wait
 constexpr unsigned kL2Ring = 7u * kRingPlaneBytes;     // 114 688 .. 163 840
 constexpr unsigned kL2Bytes = kL2Ring + 3u * kRingPlaneBytes;
-static_assert(kL2Task + 16u <= kL2Tab1 && kL2Tab1 + kL2TabIN <= kL2Ring && kL2Bytes == 160u * 1024u, "LDS layout");
+static_assert(kL2TabIN + kL2TabINBytes <= kL2Tab1, "LDS layout: the table ends in front of image 1");
+static_assert(kL2Err + 8u <= kL2Ring && (kL2Err & 7u) == 0u, "LDS layout: flags and words end in front of the ring");
+static_assert(kL2Bytes == 160u * 1024u, "LDS layout: all of the CU's LDS");
+// the largest immediate a gather can form: an image's second group, or the table, at the five-base words (first
+// row 340), plus the bytes read (16 of an image row, 8 of a table row) -- for stage 0 (base 0) and stage 1
+static_assert(kL2Base1 <= kL2TabIN && kL2Base1 <= kL2Tab1, "stage 1's base is below everything it gathers from");
+static_assert(0u + (340u + 1364u) * 16u + 16u <= 65535u && kL2TabIN + 340u * 16u + 8u <= 65535u, "stage 0: DS immediates are 16 bits");
+static_assert(kL2Tab1 - kL2Base1 + (340u + 1364u) * 16u + 16u <= 65535u && kL2TabIN - kL2Base1 + 340u * 16u + 8u <= 65535u,
+              "stage 1: DS immediates are 16 bits");
 static_assert((kL2Ring & (kRingPlaneBytes - 1u)) == 0u, "ring slots are addressed by OR");
 static_assert(kRD >= 12u, "a shorter ring can deadlock the two stages (five-row hand-shake groups)");
 
@@ -411,13 +431,16 @@ __device__ __forceinline__ void ring_fetch(Ring &r, int slot, float const *pB, f
 // Gather addresses.  Row `code` of a table group is 16 bytes (4 nodes), so the byte offset of
 // the word of length l+1 ending at the window w is  (w * 16 & mask_l * 16) + first_l * 16: one
 // v_and per length on the pre-shifted window, the constant part (and the group's base) folds
-// into the ds_read offset field.  The insert / background table has 8-byte rows: half of it.
+// into the ds_read offset field.  The insert / background table has 16-byte rows too (IN16: the same
+// offset) or 8-byte rows (half of it: the w3 kernel's slices).
 struct GatherOff
 {
     unsigned a[5]; // (w & (4^(l+1) - 1)) * 16
 };
-// BASE: LDS byte address of the tile image when it does not start at the block's LDS base (stage 1 of
-// the two-stage kernel: 64 KiB; a multiple of 16 KiB so that it does not overlap the window's 14 bits).
+// BASE: an LDS byte address below what the sweep gathers from, for a tile image too far from the block's
+// LDS base for a 16-bit immediate (stage 1 of the two-stage kernel: kL2Base1 = 32 KiB, below the shared
+// insert/background table and below its image; a multiple of 16 KiB so that it does not overlap the
+// window's 14 bits).  The sweep's table pointers are (address - BASE).
 // It rides in the window's high bits -- one v_lshl_or instead of the shift, and masks that keep it --
 // so that every gather keeps its 16-bit immediate offset.  The base is made opaque to the optimiser
 // (an SGPR that passed through an empty asm): knowing the constant, InstCombine rewrites
@@ -1126,7 +1149,7 @@ __global__ __launch_bounds__(512, 2) void viterbi_qlane2_kernel(dcp_qlane_args a
         {
             float const *__restrict__ gi = a.emis_insert + (size_t)pm.pidx * NC;
             float const *__restrict__ gn = a.emis_null + (size_t)pm.pidx * NC;
-            fill_tab_in<false>(lds + kL2TabIN / 4u, gi, gn, threadIdx.x, 512u);
+            fill_tab_in<true>(lds + kL2TabIN / 4u, gi, gn, threadIdx.x, 512u);
         }
         // TEST ONLY (dcp_qlane_args::ring_stall, 0 in the shipped library): stage 0 sits out the first step of the
         // first task, so stage 1 runs into ring_wait's bound -- the path that must end in an error, not in a hang
@@ -1160,21 +1183,24 @@ __global__ __launch_bounds__(512, 2) void viterbi_qlane2_kernel(dcp_qlane_args a
                 if (g.Lwave == 0u) continue;
                 SweepOut o{ninf(), ninf(), ninf()};
                 bool dirty = false;
-    /* tabIN as seen from the gather offsets: its 8-byte rows are reached from (window >> 1), i.e. from half the image base */
-#define QL2_SWEEP(F, L_, IN_, OUT_, TB_)                                                                  \
-    ql_sweep<G, F, L_, NT, D, IN_, OUT_, TB_, false>(tt, lds, reinterpret_cast<float2 const *>(lds + (kL2TabIN - TB_ / 2u) / 4u), \
+    /* image (IMG_) and table as seen from the gather offsets, which carry the stage's riding base TB_: both pointers */
+    /* are compile-time LDS addresses and fold into the gathers' immediates; the table's 16-byte rows (IN16) take the */
+    /* match gather's offset as it is                                                                                 */
+#define QL2_SWEEP(F, L_, IN_, OUT_, TB_, IMG_)                                                            \
+    ql_sweep<G, F, L_, NT, D, IN_, OUT_, TB_, true>(tt, lds + ((IMG_) - (TB_)) / 4u,                       \
+                                              reinterpret_cast<float2 const *>(lds + (kL2TabIN - (TB_)) / 4u), \
                                               wordsT, g.rowbase, g.L, g.Lwave, g.has, sc, plane, tid, g.xt, dirty, o, lk)
                 if (stage == 0u)
                 {
-                    if (first && last) QL2_SWEEP(true, true, IO_HBM, IO_HBM, 0u);
-                    else if (first) QL2_SWEEP(true, false, IO_HBM, IO_LDS, 0u);
-                    else if (last) QL2_SWEEP(false, true, IO_HBM, IO_HBM, 0u);
-                    else QL2_SWEEP(false, false, IO_HBM, IO_LDS, 0u);
+                    if (first && last) QL2_SWEEP(true, true, IO_HBM, IO_HBM, 0u, 0u);
+                    else if (first) QL2_SWEEP(true, false, IO_HBM, IO_LDS, 0u, 0u);
+                    else if (last) QL2_SWEEP(false, true, IO_HBM, IO_HBM, 0u, 0u);
+                    else QL2_SWEEP(false, false, IO_HBM, IO_LDS, 0u, 0u);
                 }
                 else
                 {
-                    if (last) QL2_SWEEP(false, true, IO_LDS, IO_HBM, kL2Tab1);
-                    else QL2_SWEEP(false, false, IO_LDS, IO_HBM, kL2Tab1);
+                    if (last) QL2_SWEEP(false, true, IO_LDS, IO_HBM, kL2Base1, kL2Tab1);
+                    else QL2_SWEEP(false, false, IO_LDS, IO_HBM, kL2Base1, kL2Tab1);
                 }
 #undef QL2_SWEEP
                 // What outlives the sweep is parked in the group's spare plane row (park_off): the null score by the

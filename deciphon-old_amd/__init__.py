@@ -236,6 +236,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_set_trace_mode"] = (I, [P, I, C.c_ulonglong])
         sig["dcp_gpu_test_fetch_table_span"] = (I, [P, U, P, C.c_ulonglong, C.POINTER(U), C.POINTER(U), C.POINTER(U)])
         sig["dcp_gpu_test_fetch_seq_words"] = (I, [P, U, P, U, C.POINTER(U)])
+        sig["dcp_gpu_test_last_rowsweep_plan"] = (I, [P, P, U, C.POINTER(U)])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -810,6 +811,26 @@ class Scanner:
         self._check(self._lib.dcp_gpu_test_fetch_table_span(self._c, p, out.ctypes.data, out.nbytes, C.byref(span),
                                                             C.byref(ldk), C.byref(eb)))
         return out, ldk.value
+
+    def test_rowsweep_plan(self):
+        """TEST-ONLY (test-hooks build, read-only): how the last float row-sweep scan ran each size class
+        (dcp_gpu_test_last_rowsweep_plan): {"forked": bool, "classes": {(R, W): {"path": "plain" | "mp" | "segmented",
+        "stage", "waves", "prefetch" (plain), "chunk", "seg_redo" (segmented), "flagged_rest" (mp)}}}; empty classes
+        are left out."""
+        n = C.c_uint(0)
+        rc = self._lib.dcp_gpu_test_last_rowsweep_plan(self._c, None, 0, C.byref(n))
+        if rc != RC_ENOMEM:
+            self._check(rc or RC_EFAIL)
+        w = np.zeros(n.value, np.uint32)
+        self._check(self._lib.dcp_gpu_test_last_rowsweep_plan(self._c, w.ctypes.data, len(w), C.byref(n)))
+        per = (len(w) - 2) // int(w[1])
+        classes = {}
+        for k in range(int(w[1])):
+            R, W, path, stage, waves, pf, chunk, redo, rest = (int(v) for v in w[2 + per * k:2 + per * k + 9])
+            if path:
+                classes[(R, W)] = dict(path=("plain", "mp", "segmented")[path - 1], stage=stage, waves=waves, prefetch=pf,
+                                       chunk=chunk, seg_redo=redo, flagged_rest=bool(rest))
+        return dict(forked=bool(w[0]), classes=classes)
 
     def test_set_rowsweep_variant(self, stage_rows, block_waves=0):
         """TEST-ONLY (test-hooks build): force the grid-mode row-sweep kernel variant; stage_rows < 0: automatic."""

@@ -8,6 +8,7 @@
 #include "dcp_kernels.h"
 #include "dcp_f64.h"
 #include "dcp_seqs.h"
+#include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
 
@@ -264,6 +265,16 @@ struct dcp_gpu_ctx
     int mp_mode = -1;              // test hook: 0 never K profiles per wavefront, 1 always, -1 automatic
     uint64_t seg_col_bytes = (uint64_t)6 << 30; // cap on one class's boundary columns (test hook: shrink it to reach the chunked path)
     unsigned n_launched = 0;
+#ifdef DCP_TEST_HOOKS
+    // test hook (dcp_gpu_test_last_rowsweep_plan): what launch_rowsweep_scan last did with each size class
+    struct RowsweepClassPlan
+    {
+        unsigned path = 0;         // DCP_RS_PATH_*: 0 = the class is empty
+        unsigned stage = 0, waves = 0, prefetch = 0; // plain grid: rowsweep_variant's answer
+        unsigned chunk = 0;        // segmented: queries per pass
+        unsigned flagged_rest = 0; // K profiles per wavefront: the flagged profiles got a launch of their own
+    } rs_plan[kNumClasses];
+#endif
 
     // The resident DB is float (dcp_gpu_db_upload) or double (dcp_gpu_db_upload64): 32 / 64, 0 while none is.
     int precision = 0;
@@ -2397,6 +2408,10 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
     bool const overlap = (uint64_t)nq * c->nprof < ((uint64_t)1 << 22);
     c->last_overlapped = overlap;
     SegSweepPlan const sp = plan_segsweep(c, q_begin, q_end);
+#ifdef DCP_TEST_HOOKS
+    for (int k = 0; k < kNumClasses; ++k)
+        c->rs_plan[k] = {};
+#endif
     if (sp.col_rows)
     {
         if (c->d_seg_scratch.n < sp.col_rows * 4u) HIP_TRY(c, c->d_seg_scratch.alloc((size_t)sp.col_rows * 4u));
@@ -2428,6 +2443,9 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
         {
             float *const col_base = c->d_seg_scratch.p + seg_col_at;
             seg_col_at += (uint64_t)a.nprof * sp.chunk[k] * 2u * sp.stride * 4u;
+#ifdef DCP_TEST_HOOKS
+            c->rs_plan[k].path = DCP_RS_PATH_SEGMENTED, c->rs_plan[k].chunk = sp.chunk[k];
+#endif
             if (int rc = launch_segsweep_class(c, a, k, sp, col_base, ls, overlap)) return rc;
             continue;
         }
@@ -2456,12 +2474,19 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
                     return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch") : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
             }
             a.first_prof = first, a.nprof = last - first;
+#ifdef DCP_TEST_HOOKS
+            c->rs_plan[k].path = DCP_RS_PATH_MP, c->rs_plan[k].flagged_rest = c->mp_flagged_first[k] != 0u;
+#endif
         }
         else
         {
             int stg, pf;
             unsigned bw;
             rowsweep_variant(c, sc.R, sc.W, a.nchunks, &stg, &bw, &pf);
+#ifdef DCP_TEST_HOOKS
+            c->rs_plan[k].path = DCP_RS_PATH_PLAIN;
+            c->rs_plan[k].stage = (unsigned)stg, c->rs_plan[k].waves = bw, c->rs_plan[k].prefetch = (unsigned)pf;
+#endif
             if (int lrc = dcp_launch_rowsweep_grid(sc.R, sc.W, &a, stg, bw, ls, c->rs_pad_lds, pf))
                 return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch")
                                  : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d (stage %d, %u wavefronts)", sc.R, sc.W, stg, bw);
@@ -2591,6 +2616,30 @@ int dcp_gpu_test_set_rowsweep_variant(dcp_gpu_ctx *c, int stg, unsigned bw)
     c->rs_force_R = (int)((bw >> 20) & 15u);      // bits 20..23: only the class with this many nodes per lane (0: all)
     c->seg_mode = ((bw >> 24) & 3u) == 1u ? 0 : ((bw >> 24) & 3u) == 2u ? 1 : -1; // bits 24..25: 1 = never the segmented sweep, 2 = always
     c->mp_mode = ((bw >> 26) & 3u) == 1u ? 0 : ((bw >> 26) & 3u) == 2u ? 1 : -1;  // bits 26..27: 1 = never K profiles per wavefront, 2 = always
+    return DCP_OK;
+}
+int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *c, unsigned *out, unsigned cap, unsigned *nwords)
+{
+    if (!c || !nwords) return DCP_EINVAL;
+    if (!c->scanned || c->last_kernel != 1 || c->last_f64) return c->fail(DCP_EINVAL, "the last scan was no float row sweep");
+    *nwords = 2u + DCP_RS_PLAN_WORDS * (unsigned)kNumClasses;
+    if (!out || cap < *nwords) return DCP_ENOMEM;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    unsigned redo[DCP_MAX_CLASSES] = {0};
+    bool segmented = false;
+    for (int k = 0; k < kNumClasses; ++k)
+        segmented = segmented || c->rs_plan[k].path == DCP_RS_PATH_SEGMENTED;
+    if (segmented) HIP_TRY(c, hipMemcpy(redo, c->d_seg_redo_n.p, sizeof redo, hipMemcpyDeviceToHost));
+    out[0] = c->last_overlapped ? 1u : 0u;
+    out[1] = (unsigned)kNumClasses;
+    for (int k = 0; k < kNumClasses; ++k)
+    {
+        unsigned *w = out + 2u + DCP_RS_PLAN_WORDS * (unsigned)k;
+        dcp_gpu_ctx::RowsweepClassPlan const &r = c->rs_plan[k];
+        w[0] = (unsigned)kClasses[k].R, w[1] = (unsigned)kClasses[k].W, w[2] = r.path, w[3] = r.stage, w[4] = r.waves;
+        w[5] = r.prefetch, w[6] = r.chunk, w[7] = r.path == DCP_RS_PATH_SEGMENTED ? redo[k] : 0u, w[8] = r.flagged_rest;
+    }
     return DCP_OK;
 }
 int dcp_gpu_test_set_seg_col_bytes(dcp_gpu_ctx *c, unsigned long long bytes)

@@ -1,0 +1,28 @@
+// dcp_test_hooks.h -- read-only hooks of the tests' own -DDCP_TEST_HOOKS build (libdcp_hip_testhooks.so) that
+// include/dcp_gpu.h does not list.  Only dcp_gpu.hip includes it: the DP kernels' objects do not change with it.
+#ifndef DCP_TEST_HOOKS_H
+#define DCP_TEST_HOOKS_H
+
+#include "dcp_host.h"
+
+#ifdef DCP_TEST_HOOKS
+// how launch_rowsweep_scan ran a size class
+#define DCP_RS_PATH_NONE 0u      // no profile of the class is resident
+#define DCP_RS_PATH_PLAIN 1u     // the grid-mode one-profile kernel rowsweep_variant chose (viterbi_rowsweep_kernel)
+#define DCP_RS_PATH_MP 2u        // K profiles per wavefront (viterbi_mp_kernel)
+#define DCP_RS_PATH_SEGMENTED 3u // one segment per launch (viterbi_segment_kernel), the exact kernel behind it
+#define DCP_RS_PLAN_WORDS 9u
+
+extern "C" {
+// What the last scan did, if it was a float row-sweep scan (else DCP_EINVAL); waits for it.  *nwords receives
+// 2 + DCP_RS_PLAN_WORDS x classes, out -- if cap holds them, else DCP_ENOMEM -- the words
+//   [0] 1 if the classes' launches were forked onto their own streams, [1] the number of size classes,
+//   then per class {nodes per lane, wavefronts per pair, DCP_RS_PATH_*, plain: rows staged, wavefronts per block,
+//   prefetch; segmented: queries per chunk, pairs its last segment handed to the exact kernel (seg_redo; they are
+//   not part of dcp_gpu_last_scan_redo_pairs); K profiles per wavefront: 1 if the flagged profiles of the class got
+//   a launch of the one-profile kernel}.  Changes nothing.
+int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *, unsigned *out, unsigned cap, unsigned *nwords);
+}
+#endif
+
+#endif

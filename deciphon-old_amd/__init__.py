@@ -79,6 +79,9 @@ ABI_SYMBOLS = [
     "dcp_dist_merge_hits64", "dcp_dist_free_hits64",
     # both strands: the reverse complement of the resident batch
     "dcp_gpu_seqs_add_revcomp", "dcp_gpu_seqs_strands", "dcp_gpu_seqs_fetch", "dcp_seq_revcomp",
+    # the decode of paths on the device
+    "dcp_gpu_db_keep_dists", "dcp_gpu_db_has_dists", "dcp_gpu_decode_paths", "dcp_profile_codon_joint",
+    "dcp_prod_format_row_codes",
 ]
 
 
@@ -120,6 +123,7 @@ class LaunchInfo(C.Structure):
                 ("ms", C.c_float), ("cells", C.c_uint64), ("algorithmic_bytes", C.c_uint64)]
 
 
+CODE_MUTE = 0xFF  # DCP_CODE_MUTE: the code of a step that emits nothing (Scanner.decode_paths)
 STEP_DTYPE = np.dtype([("state_id", np.uint16), ("seqlen", np.uint8), ("reserved", np.uint8)])
 HIT_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
                       ("null_loglik", np.float32), ("alt_loglik", np.float32)])
@@ -227,6 +231,12 @@ def _load(path=None, hooks=False):
         "dcp_gpu_seqs_strands": (U, [P]),
         "dcp_gpu_seqs_fetch": (I, [P, U, P, U, C.POINTER(U)]),
         "dcp_seq_revcomp": (None, [P, U, P]),
+        "dcp_gpu_db_keep_dists": (I, [P, I]),
+        "dcp_gpu_db_has_dists": (I, [P]),
+        "dcp_gpu_decode_paths": (I, [P, P, P, U, P, P, P]),
+        "dcp_profile_codon_joint": (I, [P, P, U, U, P, C.POINTER(C.c_double)]),
+        "dcp_prod_format_row_codes": (C.c_long, [C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p,
+                                                 C.c_double, C.c_double, C.c_char_p, C.c_char_p, P, P, U, P, U, P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -347,18 +357,43 @@ class ProteinProfile:
             raise DcpError(rc, "failed to decode sequence")
         return "".join("ACGT"[b] for b in out)
 
+    def codon_joint(self, frag, state_id, codon):
+        """p(fragment, codon) of ONE codon (dcp_profile_codon_joint): the quantity decode() maximises over the 64
+        codons, by the same arithmetic.  codon: an ACGT string, three ids, or its code 16a + 4b + c."""
+        f = encode_seq(frag) if isinstance(frag, str) else np.ascontiguousarray(frag, np.uint8)
+        if isinstance(codon, str):
+            cd = encode_seq(codon)
+        elif np.ndim(codon) == 0:
+            cd = np.array([int(codon) >> 4, (int(codon) >> 2) & 3, int(codon) & 3], np.uint8)
+        else:
+            cd = np.ascontiguousarray(codon, np.uint8)
+        if len(cd) != 3:
+            raise DcpError(RC_EINVAL, "a codon has three bases")
+        out = C.c_double(0.0)
+        rc = lib.dcp_profile_codon_joint(self._h, f.ctypes.data, len(f), int(state_id), cd.ctypes.data, C.byref(out))
+        if rc:
+            raise DcpError(rc, "no joint for this fragment, state and codon")
+        return out.value
+
     def prod_row(self, seq, steps, scan_id=0, seq_id=0, alt_loglik=0.0, null_loglik=0.0,
-                 abc_name="dna", profile_typeid="protein", version="0.0.0", profile_name=None):
+                 abc_name="dna", profile_typeid="protein", version="0.0.0", profile_name=None, codes=None):
         """One product TSV row as prod_fwrite + protein_match_write_func write it
-        (src/server/prod.c:153-181, src/server/protein_match.c:21-56)."""
+        (src/server/prod.c:153-181, src/server/protein_match.c:21-56).  codes: one code per step as
+        Scanner.decode_paths returns them (dcp_prod_format_row_codes) instead of decoding here."""
         s = encode_seq(seq) if isinstance(seq, str) else np.ascontiguousarray(seq, np.uint8)
         st = np.ascontiguousarray(steps, STEP_DTYPE)
         cap = 256 + 64 * (len(st) + 1) + 2 * len(s)
         buf = C.create_string_buffer(cap)
-        n = lib.dcp_prod_format_row(buf, cap, scan_id, seq_id, (profile_name or self.accession).encode(),
-                                    abc_name.encode(), float(alt_loglik), float(null_loglik),
-                                    profile_typeid.encode(), version.encode(), self._h, s.ctypes.data,
-                                    len(s), st.ctypes.data, len(st))
+        args = (buf, cap, scan_id, seq_id, (profile_name or self.accession).encode(),
+                abc_name.encode(), float(alt_loglik), float(null_loglik),
+                profile_typeid.encode(), version.encode(), self._h, s.ctypes.data,
+                len(s), st.ctypes.data, len(st))
+        if codes is None:
+            n = lib.dcp_prod_format_row(*args)
+        else:
+            cd = np.ascontiguousarray(codes, np.uint8)
+            # a wrong number of codes fails like any other row that cannot be written
+            n = lib.dcp_prod_format_row_codes(*args, cd.ctypes.data) if cd.shape == (len(st),) else -1
         if n < 0:
             raise DcpError(RC_EFAIL, "failed to write prod")
         return buf.raw[:n].decode()
@@ -908,6 +943,37 @@ class Scanner:
                        steps.ctypes.data, cap, off.ctypes.data, alt.ctypes.data)
         self._check(rc)
         return [steps[off[i]:off[i + 1]].copy() for i in range(n)], alt
+
+    def keep_dists(self, on=True):
+        """dcp_gpu_db_keep_dists: later uploads keep the profiles' compact distributions resident for decode_paths
+        (516 B per node of a float DB, 1 032 B of a double DB).  Default off."""
+        self._check(self._lib.dcp_gpu_db_keep_dists(self._c, int(bool(on))))
+
+    @property
+    def has_dists(self):
+        """True if the resident DB can decode (dcp_gpu_db_has_dists)."""
+        return bool(self._lib.dcp_gpu_db_has_dists(self._c))
+
+    def decode_paths(self, hits, paths):
+        """The codon of every step of the given paths, decoded on the device (dcp_gpu_decode_paths): a list of uint8
+        arrays, one per path, code 16a + 4b + c of the codon ProteinProfile.decode returns for the step, CODE_MUTE for
+        a step that emits nothing.  hits: any structured array with seq_idx / profile_idx (HIT_DTYPE, HIT64_DTYPE);
+        paths: what trace_paths returns (its list of STEP_DTYPE arrays, or the (list, logliks) pair itself)."""
+        if isinstance(paths, tuple):
+            paths = paths[0]
+        n = len(paths)
+        if len(hits) != n:
+            raise DcpError(RC_EINVAL, "one path per hit")
+        sq = np.ascontiguousarray(hits["seq_idx"], np.uint32)
+        pr = np.ascontiguousarray(hits["profile_idx"], np.uint32)
+        off = np.zeros(n + 1, np.uint32)
+        if n:
+            off[1:] = np.cumsum([len(p) for p in paths])
+        steps = np.ascontiguousarray(np.concatenate(paths), STEP_DTYPE) if n and off[n] else np.zeros(1, STEP_DTYPE)
+        codes = np.zeros(max(int(off[n]), 1), np.uint8)
+        self._check(self._lib.dcp_gpu_decode_paths(self._c, sq.ctypes.data, pr.ctypes.data, n, steps.ctypes.data,
+                                                   off.ctypes.data, codes.ctypes.data))
+        return [codes[off[i]:off[i + 1]].copy() for i in range(n)]
 
     def hits(self, cap=1 << 20):
         """Hit records of the last scan, sorted by (seq_idx, profile_idx): HIT64_DTYPE after a scan of a double DB."""

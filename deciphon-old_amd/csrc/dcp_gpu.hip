@@ -8,6 +8,7 @@
 #include "dcp_kernels.h"
 #include "dcp_f64.h"
 #include "dcp_seqs.h"
+#include "dcp_decode.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -311,6 +312,26 @@ struct dcp_gpu_ctx
             redo_pending = false;
         }
     } f64;
+
+    // The decode of paths (dcp_gpu_decode_paths, dcp_decode.hip).  keep_dists: dcp_gpu_db_keep_dists -- uploads keep the
+    // compact dists also where they would release them.  What the resident DB holds for it: the dists themselves
+    // (a float DB's are d_dists above, a double DB's d_dists64 here), each profile's first match row in them, the
+    // host's exp() of its null and insert dists ([2][68] doubles) and its epsilon in double, all by caller index.
+    bool keep_dists = false;
+    struct DecodeDb
+    {
+        bool ready = false;
+        DevBuf<double> d_dists64;
+        DevBuf<uint32_t> d_match_row;
+        DevBuf<double> d_exp, d_eps;
+        void release()
+        {
+            ready = false;
+            d_dists64.release(), d_match_row.release(), d_exp.release(), d_eps.release();
+        }
+    } dec;
+    DevBuf<dcp_decode_item> d_dec_items; // one round's work list and codes (kept between calls)
+    DevBuf<uint8_t> d_dec_codes;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -711,6 +732,23 @@ struct StagedUpload
     }
 };
 
+// What dcp_gpu_decode_paths needs besides the dists themselves: match_row[p], the row of profile p's first match dist in
+// the resident dists; the host's exp() of the null and insert dists; the epsilon of the decode.
+static int decode_db_setup(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned nprofiles, std::vector<uint32_t> const &match_row)
+{
+    std::vector<double> ex((size_t)nprofiles * 2u * DCP_DECODE_EXP), eps(nprofiles);
+    for (unsigned p = 0; p < nprofiles; ++p)
+        dcp_profile_decode_exp(profiles[p], &ex[(size_t)p * 2u * DCP_DECODE_EXP], &eps[p]);
+    HIP_TRY(c, c->dec.d_match_row.alloc(nprofiles));
+    HIP_TRY(c, c->dec.d_exp.alloc(ex.size()));
+    HIP_TRY(c, c->dec.d_eps.alloc(nprofiles));
+    HIP_TRY(c, hipMemcpy(c->dec.d_match_row.p, match_row.data(), nprofiles * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->dec.d_exp.p, ex.data(), ex.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->dec.d_eps.p, eps.data(), nprofiles * sizeof(double), hipMemcpyHostToDevice));
+    c->dec.ready = true;
+    return DCP_OK;
+}
+
 // ---------------------------------------------------------------------------
 // DB upload
 // ---------------------------------------------------------------------------
@@ -727,6 +765,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
             return c->fail(DCP_EINVAL, "profile %u was built in double: upload it with dcp_gpu_db_upload64", p);
     HIP_TRY(c, hipSetDevice(c->device));
     void_last_scan(c);
+    c->dec.release();
     if (c->precision == 64) // one resident DB per context: the double one goes
     {
         c->f64.release();
@@ -1016,6 +1055,14 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
         HIP_TRY(c, hipMemcpy(c->d_emis_match.p, emis_host.data(), emis_host.size() * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(c->d_emis_insert.p, ins.data(), ins.size() * sizeof(float), hipMemcpyHostToDevice));
         HIP_TRY(c, hipMemcpy(c->d_emis_null.p, nul.data(), nul.size() * sizeof(float), hipMemcpyHostToDevice));
+        if (c->keep_dists)
+        {
+            // the match dists in the rows they have after a device expansion (this path is the tests': small databases)
+            HIP_TRY(c, c->d_dists.alloc((size_t)match_rows * DCP_NDIST));
+            for (unsigned i = 0; i < nprofiles; ++i)
+                HIP_TRY(c, hipMemcpy(c->d_dists.p + (size_t)dist_row[i] * DCP_NDIST, dcp_profile_match_dist(profiles[c->metas[i].pidx]),
+                                     (size_t)c->metas[i].core_size * DCP_NDIST * sizeof(float), hipMemcpyHostToDevice));
+        }
     }
     else
     {
@@ -1125,9 +1172,9 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (c->one_layout)
         {
-            // nothing is rebuilt later: the compact dists go
+            // nothing is rebuilt later: the compact dists go, unless the decode was promised them
             c->rs_tiles.clear();
-            c->d_dists.release();
+            if (!c->keep_dists) c->d_dists.release();
             c->d_eps.release();
         }
     }
@@ -1143,6 +1190,13 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
         HIP_TRY(c, hipStreamSynchronize(c->stream));
     }
     c->rs_ready = expand_on_host != 0 || c->one_layout;
+    if (c->d_dists.p) // kept for the decode, or for the lazy row-sweep layout (a default two-layout DB): either way it can decode
+    {
+        std::vector<uint32_t> match_row(nprofiles);
+        for (unsigned i = 0; i < nprofiles; ++i)
+            match_row[c->metas[i].pidx] = dist_row[i];
+        if (int rc = decode_db_setup(c, profiles, nprofiles, match_row)) return rc;
+    }
     c->nprof = nprofiles;
     c->precision = 32;
     return DCP_OK;
@@ -1172,7 +1226,7 @@ uint64_t dcp_gpu_db_table_bytes(dcp_gpu_ctx const *c)
     if (!c || c->nprof == 0) return 0;
     if (c->precision == 64) return c->f64.d_tab.n * sizeof(double);
     // the lazily expanded row-sweep tables count once they are there
-    bool const lazy_there = !c->one_layout && c->rs_ready && c->d_dists.p;
+    bool const lazy_there = !c->one_layout && c->rs_ready && c->d_dists.p && !c->rs_tiles.empty();
     return c->table_bytes + (lazy_there ? c->rs_floats * sizeof(float) : 0);
 }
 
@@ -1238,6 +1292,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // one resident DB per context: whatever was there goes, also if this upload fails half way
     void_last_scan(c);
+    c->dec.release();
     c->precision = 0;
     c->nprof = 0;
     c->f64.release();
@@ -1285,6 +1340,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     std::vector<double> h_trans(trans, -std::numeric_limits<double>::infinity());
     std::vector<double> h_dists;
     std::vector<dcp_f64_expand_job> jobs, xe_jobs; // columns of the match tables; the insert / null tables
+    std::vector<uint32_t> match_row(nprofiles);    // by caller index: the decode's map
     jobs.reserve(tab / DCP_NCODES);
     xe_jobs.reserve(2ull * nprofiles);
     for (dcp_f64_prof const &m : F.profs)
@@ -1297,6 +1353,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
         double const eps = dcp_profile_epsilon64(pf);
         uint32_t const d0 = (uint32_t)(h_dists.size() / DCP_NDIST);
         double const *md = dcp_profile_match_dist64(pf);
+        match_row[m.pidx] = d0;
         h_dists.insert(h_dists.end(), md, md + (size_t)M * DCP_NDIST);
         h_dists.insert(h_dists.end(), dcp_profile_insert_dist64(pf), dcp_profile_insert_dist64(pf) + DCP_NDIST);
         h_dists.insert(h_dists.end(), dcp_profile_null_dist64(pf), dcp_profile_null_dist64(pf) + DCP_NDIST);
@@ -1336,11 +1393,145 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     dcp_f64_launch_expand(d_xe_jobs.p, (unsigned)xe_jobs.size(), d_dists.p, F.d_xe.p, c->stream);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->keep_dists)
+    {
+        if (int rc = decode_db_setup(c, profiles, nprofiles, match_row)) return rc;
+        std::swap(c->dec.d_dists64.p, d_dists.p), std::swap(c->dec.d_dists64.n, d_dists.n);
+    }
     c->core_sizes.assign(nprofiles, 0);
     for (unsigned p = 0; p < nprofiles; ++p)
         c->core_sizes[p] = dcp_profile_core_size(profiles[p]);
     c->nprof = nprofiles;
     c->precision = 64;
+    return DCP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The decode of paths on the device: dcp_decode.hip
+// ---------------------------------------------------------------------------
+int dcp_gpu_db_keep_dists(dcp_gpu_ctx *c, int on)
+{
+    if (!c) return DCP_EINVAL;
+    c->keep_dists = on != 0;
+    return DCP_OK;
+}
+
+int dcp_gpu_db_has_dists(dcp_gpu_ctx const *c) { return c && c->nprof && c->dec.ready ? 1 : 0; }
+
+// One step of a path as the decode sees it: 0 mute, else DCP_DECODE_NULL / _INSERT / _MATCH + 1; *k the node of an M
+// state.  -1: not a state of a profile of core_size nodes.
+static int decode_step_kind(unsigned id, unsigned core_size, unsigned *k)
+{
+    unsigned const msb = id & (3u << 14), idx = id & 0x3FFFu;
+    if (msb == (3u << 14))
+    {
+        // R S N B E J C T: R, N, J, C emit (the null dist)
+        if (idx > 7u) return -1;
+        return idx == 0u || idx == 2u || idx == 5u || idx == 6u ? DCP_DECODE_NULL + 1 : 0;
+    }
+    if (idx < 1u || idx > core_size) return -1;
+    *k = idx - 1u;
+    return msb == 0 ? DCP_DECODE_MATCH + 1 : msb == (1u << 14) ? DCP_DECODE_INSERT + 1 : 0;
+}
+
+int dcp_gpu_decode_paths(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                         struct dcp_step const *steps, uint32_t const *step_off, uint8_t *codes_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident: nothing to decode with");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing to decode");
+    if (!c->dec.ready)
+        return c->fail(DCP_EINVAL, "the resident DB's compact distributions are not resident: switch them on with "
+                                   "dcp_gpu_db_keep_dists before the upload");
+    if (npaths == 0) return DCP_OK;
+    if (!seq_idx || !profile_idx || !step_off) return c->fail(DCP_EINVAL, "null index array");
+    // everything is checked before anything is launched or written
+    uint64_t nemit = 0;
+    for (unsigned h = 0; h < npaths; ++h)
+    {
+        if (step_off[h + 1] < step_off[h]) return c->fail(DCP_EINVAL, "path %u: step offsets decrease", h);
+        if (seq_idx[h] >= c->nseqs) return c->fail(DCP_EINVAL, "path %u: sequence %u is not resident (%u are)", h, seq_idx[h], c->nseqs);
+        if (profile_idx[h] >= c->nprof) return c->fail(DCP_EINVAL, "path %u: profile %u is not resident (%u are)", h, profile_idx[h], c->nprof);
+        if (step_off[h + 1] > step_off[h] && !steps) return c->fail(DCP_EINVAL, "null steps");
+        unsigned const M = c->core_sizes[profile_idx[h]];
+        uint64_t pos = 0;
+        for (uint32_t i = step_off[h]; i < step_off[h + 1]; ++i)
+        {
+            unsigned k = 0;
+            unsigned const len = steps[i].seqlen;
+            int const kind = decode_step_kind(steps[i].state_id, M, &k);
+            if (kind < 0)
+                return c->fail(DCP_EINVAL, "path %u, step %u: state id 0x%04x is no state of a profile of %u nodes", h,
+                               i - step_off[h], (unsigned)steps[i].state_id, M);
+            if (kind == 0 && len != 0)
+                return c->fail(DCP_EINVAL, "path %u, step %u: a mute state with seqlen %u", h, i - step_off[h], len);
+            if (kind > 0 && (len < 1u || len > 5u))
+                return c->fail(DCP_EINVAL, "path %u, step %u: an emitting state with seqlen %u (1..5)", h, i - step_off[h], len);
+            pos += len;
+            nemit += kind > 0;
+        }
+        if (pos > c->seq_len[seq_idx[h]])
+            return c->fail(DCP_EINVAL, "path %u: its steps emit %llu bases, sequence %u has %u", h, (unsigned long long)pos,
+                           seq_idx[h], c->seq_len[seq_idx[h]]);
+    }
+    uint32_t const first = step_off[0], total = step_off[npaths] - step_off[0];
+    if (total == 0) return DCP_OK;
+    if (!codes_out) return c->fail(DCP_EINVAL, "null output");
+    std::vector<uint8_t> codes(total, (uint8_t)DCP_CODE_MUTE);
+    if (nemit)
+    {
+        HIP_TRY(c, hipSetDevice(c->device));
+        size_t const cap = (size_t)std::min<uint64_t>(nemit, (uint64_t)DCP_DECODE_MAX_ITEMS);
+        if (c->d_dec_items.n < cap || c->d_dec_codes.n < cap) // both or neither: a failed second allocation is tried again
+        {
+            HIP_TRY(c, c->d_dec_items.alloc(cap));
+            HIP_TRY(c, c->d_dec_codes.alloc(cap));
+        }
+        // rounds of at most DCP_DECODE_MAX_ITEMS emitting steps, cut wherever the list is full: the work list (path,
+        // fragment start, length, state) holds integers only
+        std::vector<dcp_decode_item> items;
+        std::vector<uint32_t> dst; // the step each item decodes, relative to `first`
+        std::vector<uint8_t> out(cap);
+        items.reserve(cap), dst.reserve(cap);
+        dcp_decode_args a{};
+        a.items = c->d_dec_items.p, a.codes = c->d_dec_codes.p;
+        a.words = c->d_seq_words.p, a.woff = c->d_seq_woff.p;
+        a.dists = c->precision == 64 ? (void const *)c->dec.d_dists64.p : (void const *)c->d_dists.p;
+        a.match_row = c->dec.d_match_row.p, a.exp_ni = c->dec.d_exp.p, a.eps = c->dec.d_eps.p;
+        auto flush = [&]() -> int {
+            if (items.empty()) return DCP_OK;
+            a.nitems = (unsigned)items.size();
+            HIP_TRY(c, hipMemcpyAsync(c->d_dec_items.p, items.data(), items.size() * sizeof(dcp_decode_item), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, (hipError_t)dcp_launch_decode(&a, c->precision == 64, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_dec_codes.p, items.size(), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            for (size_t j = 0; j < items.size(); ++j)
+                codes[dst[j]] = out[j];
+            items.clear(), dst.clear();
+            return DCP_OK;
+        };
+        for (unsigned h = 0; h < npaths; ++h)
+        {
+            unsigned const M = c->core_sizes[profile_idx[h]];
+            uint32_t pos = 0;
+            for (uint32_t i = step_off[h]; i < step_off[h + 1]; ++i)
+            {
+                unsigned k = 0;
+                unsigned const len = steps[i].seqlen;
+                int const kind = decode_step_kind(steps[i].state_id, M, &k);
+                if (kind > 0)
+                {
+                    items.push_back(dcp_decode_item{seq_idx[h], pos, profile_idx[h], len | ((unsigned)(kind - 1) << 3) | (k << 8)});
+                    dst.push_back(i - first);
+                    if (items.size() == cap)
+                        if (int rc = flush()) return rc;
+                }
+                pos += len;
+            }
+        }
+        if (int rc = flush()) return rc;
+    }
+    std::memcpy(codes_out + first, codes.data(), total);
     return DCP_OK;
 }
 

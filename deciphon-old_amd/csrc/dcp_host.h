@@ -40,4 +40,12 @@ enum
     DCP_XSTRIDE = 16, // floats per sequence in the device xtrans array
 };
 
+// What dcp_profile_decode reads of a profile's null and insert dists (dcp_model.cpp): exp() of the 4 base and 64
+// codon entries -- out[0..67] null {b[4], pc[64], codon 16a + 4b + c}, out[68..135] insert -- computed from the double
+// parts of a double profile, and the epsilon it decodes with.  The upload hands them to the device decode.
+#ifdef __cplusplus
+extern "C"
+#endif
+void dcp_profile_decode_exp(dcp_profile const *, double out[136], double *epsilon);
+
 #endif

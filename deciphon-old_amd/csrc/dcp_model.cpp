@@ -857,59 +857,8 @@ void dcp_partition_by_cells(unsigned const *core_sizes, unsigned nprofiles,
 // ---------------------------------------------------------------------------
 // Hit post-processing: state names, codon decode, product rows
 // ---------------------------------------------------------------------------
-namespace
-{
-// imm frame state: probability of emitting word x (1..5 bases) given base probs b and
-// codon marginals C (5x5x5, index 4 = wildcard) -- the formula of dcp_frame_table_host,
-// evaluated for one word.
-// C3(p, q, r): codon marginal with wildcard index 4 -- a table (below) or computed on the fly (decode)
-template <class C3> double frame_prob_word_of(double const *b, C3 const &c3, double e, double f, uint8_t const *x, unsigned len)
-{
-    auto s1 = [&](int p) { return c3(p, 4, 4) + c3(4, p, 4) + c3(4, 4, p); };
-    auto s2 = [&](int p, int q) { return c3(4, p, q) + c3(p, 4, q) + c3(p, q, 4); };
-    double const e2 = e * e, f2 = f * f;
-    switch (len)
-    {
-    case 1: return e2 * f2 / 3.0 * s1(x[0]);
-    case 2:
-        return 2.0 * e * f2 * f / 3.0 * s2(x[0], x[1]) +
-               e2 * e * f / 3.0 * (b[x[1]] * s1(x[0]) + b[x[0]] * s1(x[1]));
-    case 3:
-        return f2 * f2 * c3(x[0], x[1], x[2]) +
-               4.0 * e2 * f2 / 9.0 * (b[x[0]] * s2(x[1], x[2]) + b[x[1]] * s2(x[0], x[2]) + b[x[2]] * s2(x[0], x[1])) +
-               e2 * e2 / 9.0 * (b[x[0]] * b[x[1]] * s1(x[2]) + b[x[0]] * b[x[2]] * s1(x[1]) + b[x[1]] * b[x[2]] * s1(x[0]));
-    case 4:
-    {
-        double one = b[x[0]] * c3(x[1], x[2], x[3]) + b[x[1]] * c3(x[0], x[2], x[3]) +
-                     b[x[2]] * c3(x[0], x[1], x[3]) + b[x[3]] * c3(x[0], x[1], x[2]);
-        double two = 0;
-        for (int i = 0; i < 4; ++i)
-            for (int j = i + 1; j < 4; ++j)
-            {
-                int r[2], n = 0;
-                for (int k = 0; k < 4; ++k)
-                    if (k != i && k != j) r[n++] = x[k];
-                two += b[x[i]] * b[x[j]] * s2(r[0], r[1]);
-            }
-        return e * f2 * f / 2.0 * one + e2 * e * f / 9.0 * two;
-    }
-    case 5:
-    {
-        double s = 0;
-        for (int i = 0; i < 5; ++i)
-            for (int j = i + 1; j < 5; ++j)
-            {
-                int r[3], n = 0;
-                for (int k = 0; k < 5; ++k)
-                    if (k != i && k != j) r[n++] = x[k];
-                s += b[x[i]] * b[x[j]] * c3(r[0], r[1], r[2]);
-            }
-        return e2 * f2 / 10.0 * s;
-    }
-    default: return std::numeric_limits<double>::quiet_NaN();
-    }
-}
-} // namespace
+// the frame state's probability of one word (frame_prob_word_of): shared with the device decode
+#include "dcp_frame_word.h"
 
 extern "C" {
 
@@ -935,6 +884,89 @@ char dcp_gc_decode(uint8_t const codon[3])
     return g_codons.aa[codon[0] * 16 + codon[1] * 4 + codon[2]];
 }
 
+} // extern "C"
+
+namespace
+{
+// What a decode of (profile, state) reads: exp() of the 4 base and 64 codon entries of the state's distribution (the
+// insert dist for I states, the node's match dist for M states, the null dist otherwise) and epsilon.  Null and insert
+// come from the profile's cache, a match dist is exponentiated into `own`.  A profile of the double build decodes
+// with its double parts and epsilon, as the reference's IMM_DOUBLE_PRECISION build does: its float parts are those
+// rounded once, and a near-tie of two codons can fall either way after that rounding.
+void fill_decode_exp(float const *d, dcp_profile::DecodeExp &x)
+{
+    for (int i = 0; i < 4; ++i)
+        x.b[i] = std::exp((double)d[i]);
+    for (int a = 0; a < 4; ++a)
+        for (int bb = 0; bb < 4; ++bb)
+            for (int cc = 0; cc < 4; ++cc)
+                x.pc[a * 16 + bb * 4 + cc] = std::exp((double)d[4 + a * 25 + bb * 5 + cc]);
+}
+void fill_decode_exp(double const *d, dcp_profile::DecodeExp &x)
+{
+    for (int i = 0; i < 4; ++i)
+        x.b[i] = std::exp(d[i]);
+    for (int a = 0; a < 4; ++a)
+        for (int bb = 0; bb < 4; ++bb)
+            for (int cc = 0; cc < 4; ++cc)
+                x.pc[a * 16 + bb * 4 + cc] = std::exp(d[4 + a * 25 + bb * 5 + cc]);
+}
+// the cached exp() of the null (0) and insert (1) dists, in the profile's precision
+dcp_profile::DecodeExp const *cached_decode_exp(dcp_profile const *p)
+{
+    if (p->f64)
+    {
+        std::call_once(p->decode_once64, [&]() {
+            fill_decode_exp(p->null_dist64.data(), p->decode_exp64[0]), fill_decode_exp(p->insert_dist64.data(), p->decode_exp64[1]);
+        });
+        return p->decode_exp64;
+    }
+    std::call_once(p->decode_once, [&]() { fill_decode_exp(p->null_dist, p->decode_exp[0]), fill_decode_exp(p->insert_dist, p->decode_exp[1]); });
+    return p->decode_exp;
+}
+// DCP_EINVAL for a bad fragment, an M index outside the core or a mute state (assert(!protein_state_is_mute) :310)
+int decode_operands(dcp_profile const *p, uint8_t const *frag, unsigned len, unsigned state_id, dcp_profile::DecodeExp &own,
+                    dcp_profile::DecodeExp const **x, double *e)
+{
+    if (!p || !frag || len < 1 || len > 5) return DCP_EINVAL;
+    for (unsigned i = 0; i < len; ++i)
+        if (frag[i] > 3) return DCP_EINVAL;
+    unsigned const msb = state_id & (3u << 14);
+    unsigned const k = (state_id & 0x3FFFu) - 1u; // protein_state_idx of an M state
+    if (msb == 0 && k >= p->core_size) return DCP_EINVAL;
+    if (state_id == ((3u << 14) | 1u) || state_id == ((3u << 14) | 3u) || state_id == ((3u << 14) | 4u) ||
+        state_id == ((3u << 14) | 7u) || msb == (2u << 14))
+        return DCP_EINVAL;
+    int const which = msb == (1u << 14) ? 1 : msb == 0 ? 2 : 0; // the null, the insert or the node's match dist
+    if (which == 2)
+    {
+        if (p->f64) fill_decode_exp(&p->match_dist64[(size_t)k * DCP_NDIST], own);
+        else fill_decode_exp(&p->match_dist[(size_t)k * DCP_NDIST], own);
+        *x = &own;
+    }
+    else
+        *x = &cached_decode_exp(p)[which];
+    *e = p->f64 ? p->epsilon64 : (double)p->epsilon;
+    return DCP_OK;
+}
+} // namespace
+
+// csrc-internal (dcp_host.h): the exp() cache of the null and insert dists as dcp_profile_decode reads it --
+// out[0..67] null {b[4], pc[64]}, out[68..135] insert -- and the epsilon it decodes with.  The device decode takes its
+// operands for I, N, J, C, R steps from here, so both sides multiply the same doubles.
+extern "C" void dcp_profile_decode_exp(dcp_profile const *p, double out[136], double *epsilon)
+{
+    dcp_profile::DecodeExp const *x = cached_decode_exp(p);
+    for (int w = 0; w < 2; ++w)
+    {
+        std::memcpy(out + 68 * w, x[w].b, sizeof x[w].b);
+        std::memcpy(out + 68 * w + 4, x[w].pc, sizeof x[w].pc);
+    }
+    *epsilon = p->f64 ? p->epsilon64 : (double)p->epsilon;
+}
+
+extern "C" {
+
 // protein_profile_decode (src/model/protein_profile.c:306-331): the distribution is the
 // insert dist for I states, the node's match dist for M states, the null dist otherwise;
 // imm_frame_cond_decode = arg-max over the 64 codons of p(fragment, codon).  A profile of the double build decodes
@@ -943,49 +975,11 @@ char dcp_gc_decode(uint8_t const codon[3])
 int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, unsigned state_id,
                        uint8_t codon[3])
 {
-    if (!p || !frag || !codon || len < 1 || len > 5) return DCP_EINVAL;
-    for (unsigned i = 0; i < len; ++i)
-        if (frag[i] > 3) return DCP_EINVAL;
-    unsigned const msb = state_id & (3u << 14);
-    unsigned const k = (state_id & 0x3FFFu) - 1u; // protein_state_idx of an M state
-    if (msb == 0 && k >= p->core_size) return DCP_EINVAL;
-    if (state_id == ((3u << 14) | 1u) || state_id == ((3u << 14) | 3u) || state_id == ((3u << 14) | 4u) ||
-        state_id == ((3u << 14) | 7u) || msb == (2u << 14))
-        return DCP_EINVAL; // mute states emit nothing: assert(!protein_state_is_mute) :310
-    int const which = msb == (1u << 14) ? 1 : msb == 0 ? 2 : 0; // the null, the insert or the node's match dist
-    auto const fill = [](auto const *d, dcp_profile::DecodeExp &x) {
-        for (int i = 0; i < 4; ++i)
-            x.b[i] = std::exp((double)d[i]);
-        for (int a = 0; a < 4; ++a)
-            for (int bb = 0; bb < 4; ++bb)
-                for (int cc = 0; cc < 4; ++cc)
-                    x.pc[a * 16 + bb * 4 + cc] = std::exp((double)d[4 + a * 25 + bb * 5 + cc]);
-    };
+    if (!codon) return DCP_EINVAL;
     dcp_profile::DecodeExp own;
-    dcp_profile::DecodeExp const *x = &own;
+    dcp_profile::DecodeExp const *x = nullptr;
     double e;
-    if (p->f64)
-    {
-        if (which == 2) fill(&p->match_dist64[(size_t)k * DCP_NDIST], own);
-        else
-        {
-            std::call_once(p->decode_once64, [&]() {
-                fill(p->null_dist64.data(), p->decode_exp64[0]), fill(p->insert_dist64.data(), p->decode_exp64[1]);
-            });
-            x = &p->decode_exp64[which];
-        }
-        e = p->epsilon64;
-    }
-    else
-    {
-        if (which == 2) fill(&p->match_dist[(size_t)k * DCP_NDIST], own);
-        else
-        {
-            std::call_once(p->decode_once, [&]() { fill(p->null_dist, p->decode_exp[0]), fill(p->insert_dist, p->decode_exp[1]); });
-            x = &p->decode_exp[which];
-        }
-        e = (double)p->epsilon;
-    }
+    if (int rc = decode_operands(p, frag, len, state_id, own, &x, &e)) return rc;
     double const *b = x->b;
     double const f = 1.0 - e;
     double best = -1.0;
@@ -994,14 +988,10 @@ int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, 
         for (int bb = 0; bb < 4; ++bb)
             for (int cc = 0; cc < 4; ++cc)
             {
-                // the marginal table of "the codon IS (a, bb, cc)": pc where every index is that base or the
-                // wildcard, 0 elsewhere -- read entry by entry instead of being built (125 stores per codon,
-                // 64 codons per decoded step); the sums see the same operands in the same order, so the
-                // arg-max is the one the table gave
-                double const pc = x->pc[a * 16 + bb * 4 + cc];
-                auto const c3 = [&](int i, int j, int k) {
-                    return ((i == 4 || i == a) && (j == 4 || j == bb) && (k == 4 || k == cc)) ? pc : 0.0;
-                };
+                // the marginal table of "the codon IS (a, bb, cc)" (dcp_one_codon), read entry by entry instead of
+                // being built (125 stores per codon, 64 codons per decoded step); the sums see the same operands in
+                // the same order, so the arg-max is the one the table gave
+                dcp_one_codon const c3{a, bb, cc, x->pc[a * 16 + bb * 4 + cc]};
                 double const v = frame_prob_word_of(b, c3, e, f, frag, len);
                 if (v >= best)
                 {
@@ -1012,17 +1002,32 @@ int dcp_profile_decode(dcp_profile const *p, uint8_t const *frag, unsigned len, 
     return best >= 0.0 ? DCP_OK : DCP_EINVAL;
 }
 
+// p(fragment, codon) of ONE codon: the quantity dcp_profile_decode maximises, from the same operands
+int dcp_profile_codon_joint(dcp_profile const *p, uint8_t const *frag, unsigned len, unsigned state_id,
+                            uint8_t const codon[3], double *out)
+{
+    if (!codon || !out || codon[0] > 3 || codon[1] > 3 || codon[2] > 3) return DCP_EINVAL;
+    dcp_profile::DecodeExp own;
+    dcp_profile::DecodeExp const *x = nullptr;
+    double e;
+    if (int rc = decode_operands(p, frag, len, state_id, own, &x, &e)) return rc;
+    dcp_one_codon const c3{codon[0], codon[1], codon[2], x->pc[codon[0] * 16 + codon[1] * 4 + codon[2]]};
+    *out = frame_prob_word_of(x->b, c3, e, 1.0 - e, frag, len);
+    return DCP_OK;
+}
+
 char const *dcp_prod_header(void)
 {
     return "scan_id\tseq_id\tprofile_name\tabc_name\talt_loglik\tnull_loglik\tprofile_typeid\tversion\tmatch\n";
 }
 
-// prod_fwrite + protein_match_write_func (src/server/prod.c:13-41,153-181; protein_match.c:21-56)
-long dcp_prod_format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
-                         char const *profile_name, char const *abc_name, double alt_loglik,
-                         double null_loglik, char const *profile_typeid, char const *version,
-                         dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
-                         struct dcp_step const *steps, unsigned nsteps)
+// prod_fwrite + protein_match_write_func (src/server/prod.c:13-41,153-181; protein_match.c:21-56).  codes: NULL (every
+// emitting step is decoded here) or one code per step as dcp_gpu_decode_paths writes them.
+static long format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
+                       char const *profile_name, char const *abc_name, double alt_loglik,
+                       double null_loglik, char const *profile_typeid, char const *version,
+                       dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
+                       struct dcp_step const *steps, unsigned nsteps, uint8_t const *codes)
 {
     if (!buf || !prof || !seq || (nsteps && !steps)) return -1;
     std::string out;
@@ -1046,10 +1051,12 @@ long dcp_prod_format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
         out += name;
         out.push_back(',');
         bool const mute = len == 0; // S, B, E, T and D states (protein_state_is_mute)
+        if (codes && (mute ? codes[i] != DCP_CODE_MUTE : codes[i] > 63u)) return -1;
         if (!mute)
         {
             uint8_t codon[3];
-            if (dcp_profile_decode(prof, seq + start, len, id, codon)) return -1;
+            if (codes) codon[0] = (uint8_t)(codes[i] >> 4), codon[1] = (uint8_t)((codes[i] >> 2) & 3u), codon[2] = (uint8_t)(codes[i] & 3u);
+            else if (dcp_profile_decode(prof, seq + start, len, id, codon)) return -1;
             for (int k = 0; k < 3; ++k)
                 out.push_back("ACGT"[codon[k] & 3]);
             out.push_back(',');
@@ -1064,6 +1071,27 @@ long dcp_prod_format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
     std::memcpy(buf, out.data(), out.size());
     buf[out.size()] = '\0';
     return (long)out.size();
+}
+
+long dcp_prod_format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
+                         char const *profile_name, char const *abc_name, double alt_loglik,
+                         double null_loglik, char const *profile_typeid, char const *version,
+                         dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
+                         struct dcp_step const *steps, unsigned nsteps)
+{
+    return format_row(buf, cap, scan_id, seq_id, profile_name, abc_name, alt_loglik, null_loglik, profile_typeid, version,
+                      prof, seq, seq_len, steps, nsteps, nullptr);
+}
+
+long dcp_prod_format_row_codes(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
+                               char const *profile_name, char const *abc_name, double alt_loglik,
+                               double null_loglik, char const *profile_typeid, char const *version,
+                               dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
+                               struct dcp_step const *steps, unsigned nsteps, uint8_t const *codes)
+{
+    if (nsteps && !codes) return -1;
+    return format_row(buf, cap, scan_id, seq_id, profile_name, abc_name, alt_loglik, null_loglik, profile_typeid, version,
+                      prof, seq, seq_len, steps, nsteps, codes ? codes : (uint8_t const *)"");
 }
 
 } // extern "C"

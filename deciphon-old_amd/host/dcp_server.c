@@ -150,19 +150,24 @@ static enum rc prod_thread_fp(unsigned thread_num, FILE **fp)
 }
 
 static enum rc prod_fwrite_fp(FILE *fp, struct prod const *prod, struct imm_seq const *seq, struct imm_path const *path,
-                             prod_fwrite_match_func_t fwrite_match, struct match *match);
+                             prod_fwrite_match_func_t fwrite_match, struct match *match, uint8_t const *codes);
 
 enum rc prod_fwrite(struct prod const *prod, struct imm_seq const *seq, struct imm_path const *path,
                     unsigned thread_num, prod_fwrite_match_func_t fwrite_match, struct match *match)
 {
     FILE *fp = NULL;
     enum rc rc = prod_thread_fp(thread_num, &fp);
-    return rc ? rc : prod_fwrite_fp(fp, prod, seq, path, fwrite_match, match);
+    return rc ? rc : prod_fwrite_fp(fp, prod, seq, path, fwrite_match, match, NULL);
 }
 
+static enum rc protein_match_write_code(FILE *fp, struct match const *m, unsigned code);
+
+/* codes: NULL, or the path's steps decoded on the device (dcp_gpu_decode_paths) -- protein_match_write_func's columns
+ * are then written from them; any other match function is called as always and decodes itself. */
 static enum rc prod_fwrite_fp(FILE *fp, struct prod const *prod, struct imm_seq const *seq, struct imm_path const *path,
-                             prod_fwrite_match_func_t fwrite_match, struct match *match)
+                             prod_fwrite_match_func_t fwrite_match, struct match *match, uint8_t const *codes)
 {
+    if (fwrite_match != protein_match_write_func) codes = NULL;
     if (fprintf(fp, "%" PRId64 "\t%" PRId64 "\t%s\t%s\t%.17g\t%.17g\t%s\t%s\t", prod->scan_id, prod->seq_id,
                 prod->profile_name, prod->abc_name, prod->alt_loglik, prod->null_loglik, prod->profile_typeid,
                 prod->version) < 0)
@@ -176,7 +181,7 @@ static enum rc prod_fwrite_fp(FILE *fp, struct prod const *prod, struct imm_seq 
         struct imm_seq frag = imm_subseq(seq, start, match->step->seqlen);
         match->frag = &frag;
         if (idx > 0 && fputc(';', fp) == EOF) return fail(RC_EIO, "failed to write prod");
-        if (fwrite_match(fp, match)) return fail(RC_EIO, "write prod");
+        if (codes ? protein_match_write_code(fp, match, codes[idx]) : fwrite_match(fp, match)) return fail(RC_EIO, "write prod");
         start += match->step->seqlen;
     }
     match->frag = NULL;
@@ -198,6 +203,31 @@ enum rc protein_match_write_func(FILE *fp, void const *match)
     if (!protein_state_is_mute(step->state_id))
     {
         if (protein_profile_decode(prof, f, step->state_id, &codon)) return fail(RC_EIO, "failed to write match");
+        ccodon[0] = imm_codon_asym(&codon);
+        ccodon[1] = imm_codon_bsym(&codon);
+        ccodon[2] = imm_codon_csym(&codon);
+        camino[0] = imm_gc_decode(1, codon);
+    }
+    if (fprintf(fp, "%.*s,%s,%s,%s", (int)f->size, f->str, state, ccodon, camino) < 0)
+        return fail(RC_EIO, "failed to write match");
+    return RC_OK;
+}
+
+/* The same columns with the step's codon given as dcp_gpu_decode_paths codes it: 16a + 4b + c, DCP_CODE_MUTE for a
+ * mute step. */
+static enum rc protein_match_write_code(FILE *fp, struct match const *m, unsigned code)
+{
+    struct protein_profile const *prof = (struct protein_profile const *)m->profile;
+    struct imm_step const *step = m->step;
+    struct imm_seq const *f = m->frag;
+    char state[IMM_STATE_NAME_SIZE] = {0};
+    m->profile->state_name(step->state_id, state);
+    char ccodon[4] = {0}, camino[2] = {0};
+    bool const mute = protein_state_is_mute(step->state_id);
+    if (mute ? code != DCP_CODE_MUTE : code > 63u) return fail(RC_EIO, "failed to write match");
+    if (!mute)
+    {
+        struct imm_codon codon = imm_codon(prof->code->nuclt, code >> 4, (code >> 2) & 3u, code & 3u);
         ccodon[0] = imm_codon_asym(&codon);
         ccodon[1] = imm_codon_bsym(&codon);
         ccodon[2] = imm_codon_csym(&codon);
@@ -341,9 +371,13 @@ static enum rc thread_prepare(struct scan_thread *t, int tid)
         if (reader->profile_sizes && end != reader->partition_offset[t->id + 1])
             rc = fail(RC_EPARSE, "partition %u: %u profiles do not end at the partition's end offset", t->id, n);
     }
+    /* scan_cfg.device_decode: the upload keeps the compact distributions for dcp_gpu_decode_paths */
+    if (!rc && dcp_gpu_db_keep_dists(t->gpu, t->device_decode)) rc = fail(RC_EFAIL, "%s", dcp_gpu_last_error(t->gpu));
     if (!rc && dcph_db_upload(t->gpu, t->impls, n)) rc = fail(RC_EFAIL, "%s", dcp_gpu_last_error(t->gpu));
     if (rc) return rc;
     t->db_resident = true;
+#pragma omp atomic
+    ++g_stats.uploads;
     return RC_OK;
 }
 
@@ -390,11 +424,12 @@ struct batch_result
     dcph_hit *hits;
     struct dcp_step *steps;
     uint32_t *soff;
+    uint8_t *codes; /* scan_cfg.device_decode: one code per step (dcp_gpu_decode_paths), else NULL */
 };
 
 static void batch_result_free(struct batch_result *r)
 {
-    free(r->hits), free(r->steps), free(r->soff);
+    free(r->hits), free(r->steps), free(r->soff), free(r->codes);
     memset(r, 0, sizeof *r);
 }
 
@@ -533,6 +568,21 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
         }
     }
     if (!rc && drc) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+    double const t_traced = stat_now();
+    if (!rc && t->device_decode && t->write_match_func == protein_match_write_func)
+    {
+        /* the pass's paths decoded where the sequences and the distributions are: a hit's seq_idx is its resident
+         * sequence, a minus-strand hit's the reverse complement the device scanned */
+        uint32_t *sq = malloc((size_t)nhits * sizeof *sq), *pf = malloc((size_t)nhits * sizeof *pf);
+        res->codes = malloc(res->soff[nhits] ? res->soff[nhits] : 1);
+        if (!sq || !pf || !res->codes) rc = fail(RC_ENOMEM, "alloc codes");
+        for (unsigned h = 0; !rc && h < nhits; ++h)
+            sq[h] = res->hits[h].seq_idx, pf[h] = res->hits[h].profile_idx;
+        if (!rc && (drc = dcp_gpu_decode_paths(t->gpu, sq, pf, nhits, res->steps, res->soff, res->codes)))
+            rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+        free(sq), free(pf);
+        stat_add(&g_stats.decode_s, stat_now() - t_traced);
+    }
     if (rc) batch_result_free(res);
     else
     {
@@ -542,7 +592,7 @@ static enum rc batch_trace(struct scan_thread *t, struct imm_seq const *seqs, un
 #pragma omp atomic
         g_stats.steps += res->soff[nhits];
     }
-    stat_add(&g_stats.trace_s, stat_now() - t_scanned);
+    stat_add(&g_stats.trace_s, t_traced - t_scanned);
     return rc;
 }
 
@@ -664,7 +714,8 @@ static enum rc batch_rows_timed(struct scan_thread *t, struct imm_seq const *seq
                     if (!r)
                     {
                         match_setup(&pm.match, &view.super);
-                        r = prod_fwrite_fp(ms, &pr, &seq, &path, t->write_match_func, &pm.match);
+                        r = prod_fwrite_fp(ms, &pr, &seq, &path, t->write_match_func, &pm.match,
+                                           res->codes ? res->codes + res->soff[h] : NULL);
                     }
                     if (ms && fclose(ms) && !r) r = fail(RC_EIO, "failed to write prod");
                     free(view.alt.match_ndists);
@@ -737,6 +788,7 @@ static struct
     struct timespec mtime;
     unsigned nparts;
     bool by_cells;
+    bool device_decode; /* the partitions were uploaded with their compact distributions kept */
     struct
     {
         dcp_gpu_ctx *gpu;
@@ -758,8 +810,9 @@ void scan_resident_release(void)
     memset(&g_resident, 0, sizeof g_resident);
 }
 
-static bool resident_matches(struct stat const *st, unsigned nparts, bool by_cells)
+static bool resident_matches(struct stat const *st, unsigned nparts, bool by_cells, bool device_decode)
 {
+    if (g_resident.device_decode != device_decode) return false;
     return g_resident.valid && g_resident.dev == st->st_dev && g_resident.ino == st->st_ino &&
            g_resident.size == st->st_size && g_resident.mtime.tv_sec == st->st_mtim.tv_sec &&
            g_resident.mtime.tv_nsec == st->st_mtim.tv_nsec && g_resident.nparts == nparts && g_resident.by_cells == by_cells;
@@ -845,9 +898,10 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
     {
         thread_init(&th[i], i, reader, cfg.multi_hits, cfg.hmmer3_compat, cfg.lrt_threshold, protein_match_write_func);
         thread_setup_job(&th[i], imm_abc_typeid(abc), reader->profile_typeid, cfg.scan_id);
+        th[i].device_decode = cfg.device_decode;
     }
     have_stat = fstat(fileno(fp), &st) == 0;
-    if (have_stat && resident_matches(&st, nparts, cfg.balance_by_cells))
+    if (have_stat && resident_matches(&st, nparts, cfg.balance_by_cells, cfg.device_decode))
     {
         /* the previous scan's resident partitions: theirs to this scan's threads (thread_prepare finds
          * db_resident set and goes straight to the sequences) */
@@ -994,6 +1048,7 @@ cleanup:
             g_resident.dev = st.st_dev, g_resident.ino = st.st_ino, g_resident.size = st.st_size;
             g_resident.mtime = st.st_mtim;
             g_resident.nparts = nparts, g_resident.by_cells = cfg.balance_by_cells;
+            g_resident.device_decode = cfg.device_decode;
             for (unsigned i = 0; i < nparts; ++i)
             {
                 g_resident.part[i].gpu = th[i].gpu;
@@ -1045,7 +1100,7 @@ enum rc scan_run_local(char const *db_filename, struct scan_seq const *seqs, uns
 {
     if (!seqs || !prods || batch == 0) return fail(RC_EINVAL, "bad scan arguments");
     struct list_source src = {seqs, nseqs, 0};
-    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0, NULL, NULL};
+    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0, NULL, NULL, false};
     enum rc rc = scan_run_source(db_filename, cfg, nthreads, list_next, &src);
     if (rc) return rc;
     char buf[1 << 16];

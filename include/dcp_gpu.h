@@ -575,6 +575,52 @@ long dcp_prod_format_row(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
 /* The header line prod_fclose writes (src/server/prod.c:119-121). */
 char const *dcp_prod_header(void);
 
+/* ---- The decode on the device: hits and paths in, one codon code per step out ----------------
+ * The last numeric step of a product row -- for every emitting step of a path the arg-max over the 64 codons of
+ * p(fragment, codon), protein_profile_decode / imm_frame_cond_decode -- computed by one wavefront per step, lane =
+ * codon, from the resident 2-bit words and the profiles' compact distributions (csrc/dcp_decode.hip).
+ *
+ * dcp_gpu_db_keep_dists: later uploads (dcp_gpu_db_upload with any flags, dcp_gpu_db_upload64) keep the profiles'
+ * compact distributions resident for dcp_gpu_decode_paths: 516 B per node (float DB), 1 032 B (double DB), plus
+ * 1 104 B per profile.  Default off: uploads behave exactly as before.  A default two-layout float DB keeps them
+ * anyway (it expands its row-sweep layout from them on first use) and can decode without the setting. */
+int dcp_gpu_db_keep_dists(dcp_gpu_ctx *, int on);
+/* 1 if the resident DB can decode (its dists are resident), else 0. */
+int dcp_gpu_db_has_dists(dcp_gpu_ctx const *);
+
+#define DCP_CODE_MUTE 0xFFu
+/* For npaths (resident sequence, resident profile) pairs and their paths -- steps back to back, step_off[npaths + 1],
+ * as dcp_gpu_trace_paths / ...64 leave them; alt or null paths alike -- codes_out[i] for step i = 16a + 4b + c of the
+ * codon (a, b, c) dcp_profile_decode returns for that step's fragment and state, DCP_CODE_MUTE for a step that emits
+ * nothing.  Amino acid = dcp_gc_decode of the codon.  One call for callers of either hit record: the precision is the
+ * resident DB's (a double DB decodes from its double dists and epsilon, as dcp_profile_decode does for a double
+ * profile).  I, N, J, C, R steps agree with dcp_profile_decode bit for bit, ties included (their operands are the
+ * host's own exp() values, stored at upload); an M step takes exp() of its node's dist on the device and can differ
+ * from the host only where two codons' joints agree to about 2^-48 relative.
+ * Everything is validated on the host before any launch, and codes_out stays untouched on error.  DCP_EINVAL with a
+ * message: no DB or no batch resident; the dists are not resident (see dcp_gpu_db_keep_dists); an index out of range;
+ * a state id that is not M / I / D with index 1..core_size or R, S, N, B, E, J, C, T; an emitting state with seqlen
+ * outside 1..5 or a mute state with seqlen != 0; a path whose seqlens sum past its sequence's length.  npaths == 0 is
+ * DCP_OK.  The emitting steps go to the device in rounds of at most 2^20 (16 MiB work list, 1 MiB of codes); the call
+ * runs on the context's stream and returns synchronised; the last scan's results stay valid. */
+int dcp_gpu_decode_paths(dcp_gpu_ctx *, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                         struct dcp_step const *steps, uint32_t const *step_off, uint8_t *codes_out);
+
+/* p(fragment, codon) for ONE given codon: the quantity dcp_profile_decode maximises, by the same arithmetic (double
+ * parts for a double profile).  Host only.  DCP_EINVAL as dcp_profile_decode, or for a codon base > 3. */
+int dcp_profile_codon_joint(dcp_profile const *, uint8_t const *frag, unsigned len, unsigned state_id,
+                            uint8_t const codon[3], double *p);
+
+/* dcp_prod_format_row with the steps' codes given (codes[nsteps], as dcp_gpu_decode_paths wrote them) instead of
+ * decoded here.  -1 also for DCP_CODE_MUTE (or any value above 63) on an emitting step, or another value than
+ * DCP_CODE_MUTE on a mute one. */
+long dcp_prod_format_row_codes(char *buf, size_t cap, int64_t scan_id, int64_t seq_id,
+                               char const *profile_name, char const *abc_name,
+                               double alt_loglik, double null_loglik,
+                               char const *profile_typeid, char const *version,
+                               dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
+                               struct dcp_step const *steps, unsigned nsteps, uint8_t const *codes);
+
 /* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */

@@ -828,6 +828,9 @@ struct scan_thread
     bool db_resident;
     dcp_profile **impls; /* [nimpls]: the partition's compact profiles (decode / product rows) */
     unsigned nimpls;
+    /* scan_cfg.device_decode, set by scan_run_source (thread_init leaves it false: thread_run / thread_run_batch
+     * decode on the host) */
+    bool device_decode;
 };
 void thread_init(struct scan_thread *t, unsigned id, struct profile_reader *reader, bool multi_hits,
                  bool hmmer3_compat, double lrt_threshold, prod_fwrite_match_func_t write_match_func);
@@ -901,16 +904,29 @@ struct scan_cfg
      * take no scan_cfg and stay forward-only. */
     int64_t (*minus_strand_id)(int64_t seq_id, void *arg);
     void *minus_strand_arg;
+    /* Decode the paths on the device (dcp_gpu_decode_paths).  false = exactly as before: every emitting
+     * step of every row is decoded on the host (protein_profile_decode inside the match function), by up to 32 host
+     * threads per partition.  true: a partition's upload keeps the profiles' compact distributions resident
+     * (dcp_gpu_db_keep_dists), a pass's paths are decoded behind its traceback, and protein_match_write_func's columns
+     * codon and amino are written from those codes -- the same rows, except that an M-state step whose two best
+     * codons tie to about 2^-48 may name the other one.  A caller's own match function decodes itself, as before.
+     * Part of the key of keep_resident: a database left resident by a job with the other setting is uploaded again.
+     * thread_run / thread_run_batch take no scan_cfg and decode on the host. */
+    bool device_decode;
 };
 /* Where the last scan_run_source spent its time (not in the reference; profiles/host_scan_probe.c prints it): host
  * seconds summed over the partitions' threads.  scan_wait_s is the wait for the device scans (the host has nothing
  * else to do then); trace_s the hit fetch + the traceback of the hits' paths (device, the scan stream idle); rows_s the
- * product rows (host; all but the last pass's run under the next pass's scan). */
+ * product rows (host; all but the last pass's run under the next pass's scan); decode_s the device decode of the passes'
+ * paths (scan_cfg.device_decode; 0 without it); uploads the partitions this job unpacked and uploaded (0 for a job that
+ * picked every partition up from a keep_resident job before it). */
 struct scan_stats
 {
     unsigned passes;
     unsigned long hits, steps;
     double load_s, submit_s, scan_wait_s, trace_s, rows_s;
+    double decode_s;
+    unsigned uploads;
 };
 void scan_last_stats(struct scan_stats *out);
 void scan_resident_release(void);

@@ -507,8 +507,12 @@ template <int R> __device__ __forceinline__ float comp(float4 const &v)
 // One row of one tile for this lane's query.  PH = j % 5 (compile time).
 // `in` holds this row's prefetched inputs and is refilled for row j+1 (window
 // wn) as soon as group 0 has consumed it.
+// NV: the nodes of the tile the row runs, 0 .. NV - 1 (default: all 4 G).  Only a LAST tile may run fewer: the columns
+// behind core_size are -inf in its image, so a pad node's M is -inf in every row and never decides E, and a last tile
+// hands no boundary on -- nothing that leaves the sweep depends on nodes >= NV as long as NV >= the tile's real nodes.
+// NV is even (the kEM fold of E takes nodes in pairs); with NV <= 4 group 1 is not gathered at all.
 template <int G, bool FIRST, bool LAST, int PH, int NT, int D, int IN = IO_HBM, int OUT = IO_HBM, unsigned TBASE = 0u,
-          bool IN16 = kIn16>
+          bool IN16 = kIn16, int NV = 4 * G>
 __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, float const *tabM,
                                        float2 const *tabIN, GatherOff &go,
                                        unsigned wn, RowIn &in, Ring &ring, float *pB, float *pXm,
@@ -521,6 +525,9 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
                                        )
 {
     constexpr int KT = 4 * G;
+    static_assert(LAST || NV == 4 * G, "only a last tile has pad nodes to leave out");
+    static_assert(NV % 2 == 0 && NV >= 2 && NV <= 4 * G, "E is folded over node pairs");
+    constexpr bool kGroup1 = G > 1 && NV > 4; // group 1 holds a node this row runs
     constexpr int s1 = (PH + 4) % 5, s2 = (PH + 3) % 5, s3 = (PH + 2) % 5, s4 = (PH + 1) % 5, s5 = PH;
     float const ni = ninf();
 
@@ -528,7 +535,7 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
     // (`go` = this row's gather offsets, computed when the previous row prefetched group 0)
     static_assert(G <= 2, "gather_match<GROUP> is instantiated for groups 0 and 1");
     float4 e[G > 1 ? G - 1 : 1][5];
-    if constexpr (G > 1)
+    if constexpr (kGroup1)
     {
 #pragma unroll
         for (int l = 0; l < 5; ++l)
@@ -544,7 +551,7 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
         constexpr int per_row = ((FIRST || IN != IO_HBM) ? 0 : 3) + ((LAST || OUT != IO_HBM) ? 0 : 3) +
                                 ((!kRecomputeB && !FIRST) ? 1 : 0) + ((!kRecomputeB && FIRST) ? 1 : 0) + 1;
         constexpr int vm = ((D < (int)kWD ? D : (int)kWD) - 1) * per_row; // <= 32
-        constexpr int lgkm = G > 1 ? 5 : 0;
+        constexpr int lgkm = kGroup1 ? 5 : 0;
         __builtin_amdgcn_s_waitcnt((vm & 15) | ((vm >> 4) << 14) | (7 << 4) | (lgkm << 8));
     }
     __builtin_amdgcn_sched_barrier(0); // keep the gathers above: the scheduler would sink them to their use
@@ -614,8 +621,11 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
     // group 0 from the prefetched registers
     node(0, in.e0[0].x, in.e0[1].x, in.e0[2].x, in.e0[3].x, in.e0[4].x);
     node(1, in.e0[0].y, in.e0[1].y, in.e0[2].y, in.e0[3].y, in.e0[4].y);
-    node(2, in.e0[0].z, in.e0[1].z, in.e0[2].z, in.e0[3].z, in.e0[4].z);
-    node(3, in.e0[0].w, in.e0[1].w, in.e0[2].w, in.e0[3].w, in.e0[4].w);
+    if constexpr (NV > 2)
+    {
+        node(2, in.e0[0].z, in.e0[1].z, in.e0[2].z, in.e0[3].z, in.e0[4].z);
+        node(3, in.e0[0].w, in.e0[1].w, in.e0[2].w, in.e0[3].w, in.e0[4].w);
+    }
 
     // fetch row j+D's boundary into its ring slot (slot PH itself when D == 5).  The slot's
     // old values died in node 0; the empty asm ties the load's address to group 0's E so the
@@ -659,10 +669,16 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
     for (int g = 1; g < G; ++g)
     {
         float4 const *eg = e[g - 1];
-        node(4 * g + 0, eg[0].x, eg[1].x, eg[2].x, eg[3].x, eg[4].x);
-        node(4 * g + 1, eg[0].y, eg[1].y, eg[2].y, eg[3].y, eg[4].y);
-        node(4 * g + 2, eg[0].z, eg[1].z, eg[2].z, eg[3].z, eg[4].z);
-        node(4 * g + 3, eg[0].w, eg[1].w, eg[2].w, eg[3].w, eg[4].w);
+        if (4 * g + 0 < NV)
+        {
+            node(4 * g + 0, eg[0].x, eg[1].x, eg[2].x, eg[3].x, eg[4].x);
+            node(4 * g + 1, eg[0].y, eg[1].y, eg[2].y, eg[3].y, eg[4].y);
+        }
+        if (4 * g + 2 < NV)
+        {
+            node(4 * g + 2, eg[0].z, eg[1].z, eg[2].z, eg[3].z, eg[4].z);
+            node(4 * g + 3, eg[0].w, eg[1].w, eg[2].w, eg[3].w, eg[4].w);
+        }
     }
 
     if constexpr (!kRecomputeB && !FIRST)
@@ -718,7 +734,7 @@ __device__ __forceinline__ void ql_row(QState<G> &s, TileTrans<G> const &tr, flo
 // Sweep one tile over rows 1..L of this lane's query.  Scratch planes are
 // addressed as (wave-uniform plane base) + (32-bit lane/row offset).
 template <int G, bool FIRST, bool LAST, int NT, int D, int IN = IO_HBM, int OUT = IO_HBM, unsigned TBASE = 0u,
-          bool IN16 = kIn16>
+          bool IN16 = kIn16, int NV = 4 * G>
 __device__ __forceinline__ void ql_sweep(cfloat *tt, float const *tabM, float2 const *tabIN,
                                          uint32_t const *__restrict__ wordsT, unsigned rowbase,
                                          unsigned L, unsigned Lwave, bool active, float *sc,
@@ -860,7 +876,7 @@ __device__ __forceinline__ void ql_sweep(cfloat *tt, float const *tabM, float2 c
     {                                                                                      \
         /* base of row j+2 sits at position j+1 */                                         \
         unsigned const pos = j + 1u;                                                       \
-        ql_row<G, FIRST, LAST, PH, NT, D, IN, OUT, TBASE, IN16>(s, tr, tabM, tabIN, go,              \
+        ql_row<G, FIRST, LAST, PH, NT, D, IN, OUT, TBASE, IN16, NV>(s, tr, tabM, tabIN, go,          \
                                    (unsigned)wq[(PH + 1) % 5], in, ring, pB, pXm,                    \
                                    pXd, pEm, off, xt, active && j <= L, active && j == L,  \
                                    dirty, o, lk, rowbase + j, gm QL_DIAG4_ARGS);           \
@@ -1186,23 +1202,37 @@ __global__ __launch_bounds__(512, 2) void viterbi_qlane2_kernel(dcp_qlane_args a
     /* image (IMG_) and table as seen from the gather offsets, which carry the stage's riding base TB_: both pointers */
     /* are compile-time LDS addresses and fold into the gathers' immediates; the table's 16-byte rows (IN16) take the */
     /* match gather's offset as it is                                                                                 */
-#define QL2_SWEEP(F, L_, IN_, OUT_, TB_, IMG_)                                                            \
-    ql_sweep<G, F, L_, NT, D, IN_, OUT_, TB_, true>(tt, lds + ((IMG_) - (TB_)) / 4u,                       \
+#define QL2_SWEEP_NV(F, L_, IN_, OUT_, TB_, IMG_, NV_)                                                    \
+    ql_sweep<G, F, L_, NT, D, IN_, OUT_, TB_, true, NV_>(tt, lds + ((IMG_) - (TB_)) / 4u,                  \
                                               reinterpret_cast<float2 const *>(lds + (kL2TabIN - (TB_)) / 4u), \
                                               wordsT, g.rowbase, g.L, g.Lwave, g.has, sc, plane, tid, g.xt, dirty, o, lk)
+#define QL2_SWEEP(F, L_, IN_, OUT_, TB_, IMG_) QL2_SWEEP_NV(F, L_, IN_, OUT_, TB_, IMG_, KT)
+    /* A last tile behind the first runs only its real nodes, rounded up to a pair (ql_row's NV): the profile's v =      */
+    /* core_size - (T - 1) KT nodes there, 1 .. KT.  Wave-uniform; the branch is outside the row loops.                   */
+#define QL2_SWEEP_LAST(IN_, TB_, IMG_)                                                                    \
+    switch ((pm.core_size - t * (unsigned)KT + 1u) & ~1u)                                                 \
+    {                                                                                                     \
+    case 2u: QL2_SWEEP_NV(false, true, IN_, IO_HBM, TB_, IMG_, 2); break;                                 \
+    case 4u: QL2_SWEEP_NV(false, true, IN_, IO_HBM, TB_, IMG_, 4); break;                                 \
+    case 6u: QL2_SWEEP_NV(false, true, IN_, IO_HBM, TB_, IMG_, 6); break;                                 \
+    default: QL2_SWEEP_NV(false, true, IN_, IO_HBM, TB_, IMG_, KT); break;                                \
+    }
+                static_assert(KT == 8, "QL2_SWEEP_LAST names the node counts of an 8-node tile");
                 if (stage == 0u)
                 {
                     if (first && last) QL2_SWEEP(true, true, IO_HBM, IO_HBM, 0u, 0u);
                     else if (first) QL2_SWEEP(true, false, IO_HBM, IO_LDS, 0u, 0u);
-                    else if (last) QL2_SWEEP(false, true, IO_HBM, IO_HBM, 0u, 0u);
+                    else if (last) QL2_SWEEP_LAST(IO_HBM, 0u, 0u)
                     else QL2_SWEEP(false, false, IO_HBM, IO_LDS, 0u, 0u);
                 }
                 else
                 {
-                    if (last) QL2_SWEEP(false, true, IO_LDS, IO_HBM, kL2Base1, kL2Tab1);
+                    if (last) QL2_SWEEP_LAST(IO_LDS, kL2Base1, kL2Tab1)
                     else QL2_SWEEP(false, false, IO_LDS, IO_HBM, kL2Base1, kL2Tab1);
                 }
+#undef QL2_SWEEP_LAST
 #undef QL2_SWEEP
+#undef QL2_SWEEP_NV
                 // What outlives the sweep is parked in the group's spare plane row (park_off): the null score by the
                 // stage that swept the first tile, alt score and feedback flag by the one that swept the last; the
                 // epilogue below reads them after the block barrier (the two may be different wavefronts, and with

@@ -79,6 +79,9 @@ ABI_SYMBOLS = [
     "dcp_dist_merge_hits64", "dcp_dist_free_hits64",
     # both strands: the reverse complement of the resident batch
     "dcp_gpu_seqs_add_revcomp", "dcp_gpu_seqs_strands", "dcp_gpu_seqs_fetch", "dcp_seq_revcomp",
+    # windows: the resident batch cut into overlapping windows
+    "dcp_seq_window_count", "dcp_seq_window_start", "dcp_seq_window_plan", "dcp_gpu_seqs_cut_windows",
+    "dcp_gpu_seqs_windows", "dcp_gpu_seqs_window_map",
     # the decode of paths on the device
     "dcp_gpu_db_keep_dists", "dcp_gpu_db_has_dists", "dcp_gpu_decode_paths", "dcp_profile_codon_joint",
     "dcp_prod_format_row_codes",
@@ -231,6 +234,12 @@ def _load(path=None, hooks=False):
         "dcp_gpu_seqs_strands": (U, [P]),
         "dcp_gpu_seqs_fetch": (I, [P, U, P, U, C.POINTER(U)]),
         "dcp_seq_revcomp": (None, [P, U, P]),
+        "dcp_seq_window_count": (U, [U, U, U]),
+        "dcp_seq_window_start": (U, [U, U, U, U]),
+        "dcp_seq_window_plan": (I, [P, U, U, U, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+        "dcp_gpu_seqs_cut_windows": (I, [P, U, U]),
+        "dcp_gpu_seqs_windows": (I, [P, C.POINTER(U), C.POINTER(U)]),
+        "dcp_gpu_seqs_window_map": (I, [P, P, P, U]),
         "dcp_gpu_db_keep_dists": (I, [P, I]),
         "dcp_gpu_db_has_dists": (I, [P]),
         "dcp_gpu_decode_paths": (I, [P, P, P, U, P, P, P]),
@@ -622,6 +631,36 @@ def revcomp(ids):
     return out
 
 
+def _window_rule(window, step):
+    if not (1 <= window < 2 ** 32 and 1 <= step <= window):
+        raise DcpError(RC_EINVAL, f"bad window rule (window {window}, step {step}): window >= 1 and 1 <= step <= window")
+
+
+def window_count(L, window, step):
+    """Windows of a sequence of L bases (dcp_seq_window_count): 1 if L <= window, else 1 + ceil((L - window) / step)."""
+    _window_rule(window, step)
+    return lib.dcp_seq_window_count(L, window, step)
+
+
+def window_starts(L, window, step):
+    """First bases of the windows Scanner.cut_windows(window, step) cuts a sequence of L bases into
+    (dcp_seq_window_start): i * step, the last one anchored at L - window; [0] if L <= window.  A uint32 array."""
+    n = window_count(L, window, step)
+    return np.array([lib.dcp_seq_window_start(L, window, step, i) for i in range(n)], np.uint32)
+
+
+def window_plan(lens, window, step):
+    """(windows, words) of a batch with these lengths, cut by the rule (dcp_seq_window_plan): the totals as Python
+    ints; DcpError(RC_EINVAL) for a bad rule or when either passes 2^32 - 1 -- the refusal of Scanner.cut_windows."""
+    lens = np.ascontiguousarray(lens, np.uint32)
+    nwin, nwords = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.dcp_seq_window_plan(lens.ctypes.data, len(lens), min(window, 2 ** 32 - 1) if window >= 0 else 0,
+                                 min(step, 2 ** 32 - 1) if step >= 0 else 0, C.byref(nwin), C.byref(nwords))
+    if rc:
+        raise DcpError(rc, f"window plan refused: {nwin.value} windows, {nwords.value} words")
+    return nwin.value, nwords.value
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -731,6 +770,32 @@ class Scanner:
         scan(q_range=(n, 2 * n)) is the minus strand alone.  Until the next upload_seqs."""
         self._check(self._lib.dcp_gpu_seqs_add_revcomp(self._c))
         self._seq_lens = np.concatenate([self._seq_lens, self._seq_lens])
+
+    def cut_windows(self, window, step):
+        """Windows (dcp_gpu_seqs_cut_windows): the resident batch is replaced by its windows of `window` bases every
+        `step` bases (window_starts), in source order, then offset order, written on the device.  Scans, hits, scores and
+        traces then carry window indices; window_map() names each window's source and offset.  add_reverse_strand()
+        may follow (not precede) it.  Until the next upload_seqs."""
+        if not (0 <= window < 2 ** 32 and 0 <= step < 2 ** 32):
+            raise DcpError(RC_EINVAL, f"bad window rule (window {window}, step {step})")
+        self._check(self._lib.dcp_gpu_seqs_cut_windows(self._c, window, step))
+        self._seq_lens = np.concatenate([np.full(len(window_starts(int(L), window, step)), min(int(L), window), np.int64)
+                                         for L in self._seq_lens])
+
+    @property
+    def windows(self):
+        """None, or (window, step) while the resident batch is cut into windows."""
+        w, s = C.c_uint(0), C.c_uint(0)
+        return (w.value, s.value) if self._lib.dcp_gpu_seqs_windows(self._c, C.byref(w), C.byref(s)) else None
+
+    def window_map(self):
+        """(src, off), two uint32 arrays with one entry per window: its source's index in the uploaded batch and its
+        first base there (dcp_gpu_seqs_window_map).  After add_reverse_strand resident W + i is window i's reverse
+        complement; the map keeps W entries."""
+        n = self.nseqs // max(self.strands, 1)
+        src, off = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        self._check(self._lib.dcp_gpu_seqs_window_map(self._c, src.ctypes.data, off.ctypes.data, n))
+        return src, off
 
     @property
     def strands(self):

@@ -231,6 +231,15 @@ struct dcp_gpu_ctx
     unsigned strands = 0; // 0 no batch, 1 as uploaded, 2 after dcp_gpu_seqs_add_revcomp: [nseqs / 2, nseqs) is the reverse strand
     uint64_t total_len = 0;
     std::vector<uint32_t> seq_len;
+    // dcp_gpu_seqs_cut_windows: the rule in force (0 / 0: the batch is as uploaded) and the map of its windows, window ->
+    // (source index in the uploaded batch, offset); after dcp_gpu_seqs_add_revcomp still the forward half's entries
+    unsigned win_window = 0, win_step = 0;
+    std::vector<uint32_t> win_src, win_off;
+    void drop_windows()
+    {
+        win_window = win_step = 0;
+        win_src.clear(), win_off.clear();
+    }
     DevBuf<uint32_t> d_seq_words, d_seq_woff, d_seq_len;
     DevBuf<float> d_xtrans;
     int xt_multi = -1, xt_h3 = -1;
@@ -1589,6 +1598,7 @@ static int upload_seqs(dcp_gpu_ctx *c, uint8_t const *seqs, uint32_t const *seq_
     c->strands = 0;
     c->total_len = 0;
     c->seq_len.clear();
+    c->drop_windows(); // a new batch is uncut
     HIP_TRY(c, c->d_seq_words.alloc(nwords));
     HIP_TRY(c, c->d_seq_woff.alloc(nseqs));
     HIP_TRY(c, c->d_seq_len.alloc(nseqs));
@@ -1649,6 +1659,7 @@ int dcp_gpu_seqs_add_revcomp(dcp_gpu_ctx *c)
     auto drop = [&]() {
         c->nseqs = 0, c->strands = 0, c->total_len = 0;
         c->seq_len.clear();
+        c->drop_windows();
         c->xt_multi = c->xt_h3 = -1;
     };
 #define SEQS_TRY(call)                                                                                                  \
@@ -1682,6 +1693,118 @@ int dcp_gpu_seqs_add_revcomp(dcp_gpu_ctx *c)
     c->total_len = 2u * total;
     c->xt_multi = c->xt_h3 = -1; // the rows of the reverse half are derived with the next scan's flags
     c->xt64.clear();
+    return DCP_OK;
+}
+
+// Windows: the resident batch of n sequences is replaced by its W windows (dcp_seq_window_count / _start), in source
+// order, then offset order, written on the device from the resident words (dcp_seqs.hip).  Dependent state is
+// treated as dcp_gpu_seqs_add_revcomp treats it.
+int dcp_gpu_seqs_cut_windows(dcp_gpu_ctx *c, unsigned window, unsigned step)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: upload a batch before cutting it into windows");
+    if (window < 1u || step < 1u || step > window)
+        return c->fail(DCP_EINVAL, "bad window rule (window %u, step %u): window >= 1 and 1 <= step <= window", window, step);
+    if (c->strands != 1)
+        return c->fail(DCP_EINVAL, "the resident batch already holds both strands: cut the windows first, then add the reverse strand");
+    if (c->win_window) return c->fail(DCP_EINVAL, "the resident batch is already cut into windows (window %u, step %u)", c->win_window, c->win_step);
+    if (c->xt_explicit || !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "explicit special transitions are in force: they are per sequence -- set them after "
+                                   "dcp_gpu_seqs_cut_windows, one row per window");
+    unsigned const n = c->nseqs;
+    uint64_t W64 = 0, nwords64 = 0;
+    if (dcp_seq_window_plan(c->seq_len.data(), n, window, step, &W64, &nwords64))
+        return c->fail(DCP_EINVAL, "sequence batch too large for these windows (%llu windows, %llu words)",
+                       (unsigned long long)W64, (unsigned long long)nwords64);
+    unsigned const W = (unsigned)W64;
+    uint32_t const nwords = (uint32_t)nwords64;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a scan of the uncut batch may still be running on the stream: it reads the arrays that are replaced below
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void_last_scan(c);
+    c->qorder_q0 = c->qorder_q1 = ~0u; // the length order and the word planes belong to the batch that was resident
+    // the plan: each source's first window and that window's first word (what the index kernel searches), the
+    // windows' lengths and the map
+    std::vector<uint32_t> first(2u * (size_t)n), len(W), src(W), off(W);
+    uint64_t total = 0;
+    {
+        uint32_t w = 0, words = 0;
+        for (unsigned q = 0; q < n; ++q)
+        {
+            uint32_t const L = c->seq_len[q], wl = L < window ? L : window;
+            unsigned const cnt = dcp_seq_window_count(L, window, step);
+            first[q] = w, first[(size_t)n + q] = words;
+            for (unsigned i = 0; i < cnt; ++i, ++w)
+                len[w] = wl, src[w] = q, off[w] = dcp_seq_window_start(L, window, step, i);
+            words += cnt * (wl / 16u + 3u);
+            total += (uint64_t)cnt * wl;
+        }
+    }
+    DevBuf<uint32_t> words, woff, dlen, dfirst, dsrc, dofs;
+    DevBuf<float> xt;
+    // as in an upload: a failed allocation must not leave the old batch's size paired with new buffers
+    auto drop = [&]() {
+        c->nseqs = 0, c->strands = 0, c->total_len = 0;
+        c->seq_len.clear();
+        c->drop_windows();
+        c->xt_multi = c->xt_h3 = -1;
+    };
+#define SEQS_TRY(call)                                                                                                  \
+    do                                                                                                                  \
+    {                                                                                                                   \
+        hipError_t e_ = (call);                                                                                         \
+        if (e_ != hipSuccess)                                                                                           \
+        {                                                                                                               \
+            drop();                                                                                                     \
+            return c->fail(e_ == hipErrorOutOfMemory ? DCP_ENOMEM : DCP_EFAIL, "%s: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                                               \
+    } while (0)
+    SEQS_TRY(words.alloc(nwords));
+    SEQS_TRY(woff.alloc(W));
+    SEQS_TRY(dlen.alloc(W));
+    SEQS_TRY(dsrc.alloc(W));
+    SEQS_TRY(dofs.alloc(W));
+    SEQS_TRY(dfirst.alloc(2u * (size_t)n));
+    SEQS_TRY(xt.alloc((size_t)W * DCP_XSTRIDE));
+    SEQS_TRY(hipMemcpyAsync(dfirst.p, first.data(), first.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    dcp_window_args a{};
+    a.src_words = c->d_seq_words.p, a.src_woff = c->d_seq_woff.p, a.src_len = c->d_seq_len.p;
+    a.wfirst = dfirst.p, a.nwfirst = dfirst.p + n;
+    a.words = words.p, a.woff = woff.p, a.len = dlen.p, a.wsrc = dsrc.p, a.wofs = dofs.p;
+    a.nsrc = n, a.nwin = W, a.nwords = nwords, a.window = window, a.step = step;
+    SEQS_TRY((hipError_t)dcp_launch_windows(&a, c->stream));
+    SEQS_TRY(hipStreamSynchronize(c->stream)); // `first` and the old arrays are freed below
+#undef SEQS_TRY
+    std::swap(c->d_seq_words.p, words.p), std::swap(c->d_seq_words.n, words.n);
+    std::swap(c->d_seq_woff.p, woff.p), std::swap(c->d_seq_woff.n, woff.n);
+    std::swap(c->d_seq_len.p, dlen.p), std::swap(c->d_seq_len.n, dlen.n);
+    std::swap(c->d_xtrans.p, xt.p), std::swap(c->d_xtrans.n, xt.n);
+    c->seq_len.swap(len);
+    c->win_src.swap(src), c->win_off.swap(off);
+    c->win_window = window, c->win_step = step;
+    c->nseqs = W;
+    c->total_len = total;
+    c->xt_multi = c->xt_h3 = -1; // the windows' rows are derived with the next scan's flags
+    c->xt64.clear();
+    return DCP_OK;
+}
+
+int dcp_gpu_seqs_windows(dcp_gpu_ctx const *c, unsigned *window, unsigned *step)
+{
+    bool const cut = c && c->nseqs && c->win_window;
+    if (window) *window = cut ? c->win_window : 0u;
+    if (step) *step = cut ? c->win_step : 0u;
+    return cut ? 1 : 0;
+}
+
+int dcp_gpu_seqs_window_map(dcp_gpu_ctx *c, uint32_t *src, uint32_t *off, unsigned cap)
+{
+    if (!c) return DCP_EINVAL;
+    if (!c->nseqs || !c->win_window) return c->fail(DCP_EINVAL, "the resident batch is not cut into windows");
+    size_t const W = c->win_src.size();
+    if (cap < W || !src || !off) return c->fail(DCP_ENOMEM, "the batch has %zu windows: the buffers hold %u", W, cap);
+    std::memcpy(src, c->win_src.data(), W * sizeof(uint32_t));
+    std::memcpy(off, c->win_off.data(), W * sizeof(uint32_t));
     return DCP_OK;
 }
 

@@ -1499,5 +1499,46 @@ int dcp_db_read(dcp_db *db, unsigned begin, unsigned end, dcp_profile **out)
     return DCP_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The window rule (dcp_gpu_seqs_cut_windows): a sequence of L bases is cut into windows of `window` bases every
+// `step` bases, the last one anchored at the sequence's end.  Pure integer arithmetic, no device.
+// ---------------------------------------------------------------------------
+static bool window_rule_ok(unsigned window, unsigned step) { return window >= 1u && step >= 1u && step <= window; }
+
+unsigned dcp_seq_window_count(unsigned L, unsigned window, unsigned step)
+{
+    if (!window_rule_ok(window, step)) return 0;
+    if (L <= window) return 1;
+    uint64_t const rest = (uint64_t)L - window; // >= 1
+    return (unsigned)(1u + (rest + step - 1u) / step); // <= L - window + 1: fits
+}
+
+unsigned dcp_seq_window_start(unsigned L, unsigned window, unsigned step, unsigned i)
+{
+    if (!window_rule_ok(window, step) || L <= window) return 0;
+    uint64_t const at = (uint64_t)i * step, last = (uint64_t)L - window;
+    return (unsigned)(at < last ? at : last);
+}
+
+int dcp_seq_window_plan(uint32_t const *len, unsigned nseqs, unsigned window, unsigned step, uint64_t *nwindows,
+                        uint64_t *nwords)
+{
+    if (nwindows) *nwindows = 0;
+    if (nwords) *nwords = 0;
+    if (!window_rule_ok(window, step) || (!len && nseqs)) return DCP_EINVAL;
+    uint64_t W = 0, words = 0;
+    for (unsigned q = 0; q < nseqs; ++q)
+    {
+        uint64_t const cnt = dcp_seq_window_count(len[q], window, step);
+        uint64_t const wl = len[q] < window ? len[q] : window;
+        W += cnt; // cnt < 2^32, nseqs < 2^32: no wrap
+        // one term is below 2^32 * 2^29; 2^32 of them could pass 2^64: the total saturates there
+        if (__builtin_add_overflow(words, cnt * (wl / 16u + 3u), &words)) words = ~0ull;
+    }
+    if (nwindows) *nwindows = W;
+    if (nwords) *nwords = words;
+    return W > 0xffffffffull || words > 0xffffffffull ? DCP_EINVAL : DCP_OK;
+}
+
 } // extern "C"
 

@@ -1,4 +1,4 @@
-// dcp_seqs.h -- kernels on the resident sequence batch itself (dcp_seqs.hip): the reverse strand.
+// dcp_seqs.h -- kernels on the resident sequence batch itself (dcp_seqs.hip): the reverse strand, windows.
 #ifndef DCP_SEQS_H
 #define DCP_SEQS_H
 
@@ -11,6 +11,20 @@ extern "C" {
 // woff / len: the forward half ([nwords], [n] of [2n], [n] of [2n]).  Two launches on `stream`; HIP's error code.
 int dcp_launch_revcomp(uint32_t const *words_in, uint32_t *words_out, uint32_t *woff, uint32_t *len, unsigned nseqs,
                        uint32_t nwords, void *stream);
+// Windows: the batch of nwin windows that replaces a resident batch of nsrc sequences (dcp_gpu_seqs_cut_windows; the
+// rule is dcp_seq_window_count / _start).  Device pointers throughout.
+struct dcp_window_args
+{
+    uint32_t const *src_words, *src_woff, *src_len; // the resident batch: its words, [nsrc], [nsrc]
+    uint32_t const *wfirst, *nwfirst;               // [nsrc]: each source's first window and that window's first word
+    uint32_t *words;                                // [nwords]: the new batch's words (no overlap with src_words)
+    uint32_t *woff, *len;                           // [nwin]: the new batch's index
+    uint32_t *wsrc, *wofs;                          // [nwin]: the map, window -> (source, offset)
+    unsigned nsrc, nwin;
+    uint32_t nwords, window, step;
+};
+// Two launches on `stream` (index, then words); HIP's error code.
+int dcp_launch_windows(struct dcp_window_args const *, void *stream);
 #ifdef DCP_TEST_HOOKS
 // NOT in the shipped library (libdcp_hip_testhooks.so only; declared here, not in include/dcp_gpu.h).  The raw
 // L / 16 + 3 words of resident sequence q as the device holds them: *nwords receives their number, out the words if

@@ -443,6 +443,17 @@ struct strands
 };
 static bool both_strands(struct strands const *st) { return st && st->id; }
 
+/* scan_cfg.window / window_step / window_id: with window set a pass's sequences are uploaded whole and cut into
+ * overlapping windows on the device (dcp_gpu_seqs_cut_windows); from there on the pass is its windows -- the hits'
+ * seq_idx, the traceback, the rows.  NULL (thread_run / thread_run_batch) or window == 0: no cut. */
+struct windows
+{
+    unsigned window, step;
+    int64_t (*id)(int64_t seq_id, unsigned offset, void *arg);
+    void *arg;
+};
+static bool cut_windows(struct windows const *w) { return w && w->window; }
+
 static enum rc batch_check(struct scan_thread *t, struct imm_seq const *seqs, unsigned nseqs, unsigned *nprofiles)
 {
     struct profile_reader *reader = t->reader;
@@ -454,7 +465,7 @@ static enum rc batch_check(struct scan_thread *t, struct imm_seq const *seqs, un
 }
 
 static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const *seqs, unsigned nseqs,
-                            struct strands const *st)
+                            struct strands const *st, struct windows const *win, unsigned nwindows)
 {
     double const t_in = stat_now();
     enum rc rc = thread_prepare(t, tid);
@@ -492,6 +503,13 @@ static enum rc batch_submit(struct scan_thread *t, int tid, struct imm_seq const
     }
     int drc = 0;
     if (!rc && (drc = dcp_gpu_seqs_upload(t->gpu, ids, off, nseqs))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+    /* windows: the sources are replaced by their windows on the device, before the reverse strand is added (so that
+     * resident nwindows + i is the reverse complement of window i) */
+    if (!rc && cut_windows(win))
+    {
+        if ((drc = dcp_gpu_seqs_cut_windows(t->gpu, win->window, win->step))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
+        else if (dcp_gpu_nseqs(t->gpu) != nwindows) rc = fail(RC_EFAIL, "the device cut %u windows, the host %u", dcp_gpu_nseqs(t->gpu), nwindows);
+    }
     /* the minus strand never leaves the device: sequences nseqs .. 2 nseqs - 1 of the resident batch */
     if (!rc && both_strands(st) && (drc = dcp_gpu_seqs_add_revcomp(t->gpu))) rc = fail((enum rc)drc, "%s", dcp_gpu_last_error(t->gpu));
     free(ids);
@@ -764,7 +782,7 @@ enum rc thread_run_batch(struct scan_thread *t, int tid, struct imm_seq const *s
     enum rc rc = batch_check(t, seqs, nseqs, &n);
     if (rc || n == 0) return rc;
     struct batch_result res;
-    if ((rc = batch_submit(t, tid, seqs, nseqs, NULL))) return rc;
+    if ((rc = batch_submit(t, tid, seqs, nseqs, NULL, NULL, nseqs))) return rc;
     if ((rc = batch_trace(t, seqs, nseqs, n, NULL, &res))) return rc;
     return batch_rows(t, seqs, seq_ids, nseqs, NULL, &res);
 }
@@ -833,6 +851,12 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
      * and the progress units keep counting source sequences */
     struct strands const strands = {cfg.minus_strand_id, cfg.minus_strand_arg};
     unsigned long const bases_per_symbol = both_strands(&strands) ? 2u : 1u;
+    /* windows: a pass still holds whole source sequences (`batch` and the progress units count them); its size is
+     * compared with batch_symbols as its windows' bases.  Behind the cut the pass is its windows: wseq / wid below. */
+    if (cfg.window && !cfg.window_id) return fail(RC_EINVAL, "scan_cfg.window needs window_id: the rows of a window carry the caller's id for it");
+    if (cfg.window && cfg.window_step > cfg.window) return fail(RC_EINVAL, "scan_cfg.window_step exceeds window");
+    struct windows const windows = {cfg.window, cfg.window_step ? cfg.window_step : (cfg.window > 1u ? cfg.window / 2u : 1u),
+                                    cfg.window_id, cfg.window_arg};
     memset(&g_stats, 0, sizeof g_stats);
     /* the partitions' host threads (one per device) each fan out once more: unpacking a partition and formatting a
      * batch's product rows are many-core jobs of their own */
@@ -853,6 +877,8 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
     struct imm_seq *bseq[2] = {NULL, NULL};
     int64_t *bid[2] = {NULL, NULL};
     char **btext[2] = {NULL, NULL};
+    struct imm_seq *wseq[2] = {NULL, NULL}; /* windows of the passes in bseq: views into their texts */
+    int64_t *wid[2] = {NULL, NULL};
     char **qtext = NULL; /* look-ahead queue: sequences fetched from the source, not yet in a pass */
     int64_t *qid = NULL;
     unsigned long *qlen = NULL;
@@ -929,7 +955,9 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
      * batch i-1's product rows are formatted and written by the host while the device scans, then batch
      * i's hits and paths are collected.  Rows reach the product files in the same order as without the
      * overlap; with one batch in flight per partition a sequence buffer is reused two batches later. */
-    unsigned npend = 0;  /* sequences of the batch whose rows are still to be written */
+    unsigned npend = 0;  /* sequences (or windows) of the batch whose rows are still to be written */
+    struct imm_seq const *pseq = NULL; /* that batch as it was resident, and its ids */
+    int64_t const *pid = NULL;
     int cur = 0;         /* host copy the next batch is fetched into */
     /* Passes are cut from a look-ahead queue.  A pass's target is `batch` sequences or cfg.batch_symbols bases,
      * whichever comes first; the queue is filled until it exceeds one and a half targets or the source ends.  If the
@@ -961,7 +989,17 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
                 break;
             }
             qid[qn] = s.id;
-            qlen[qn] = (unsigned long)strlen(qtext[qn]) * bases_per_symbol;
+            qlen[qn] = (unsigned long)strlen(qtext[qn]);
+            if (cut_windows(&windows) && qlen[qn] > windows.window)
+            {
+                if (qlen[qn] > UINT32_MAX)
+                {
+                    rc = fail(RC_EINVAL, "sequence exceeds 2^32 - 1 symbols");
+                    break;
+                }
+                qlen[qn] = (unsigned long)dcp_seq_window_count((unsigned)qlen[qn], windows.window, windows.step) * windows.window;
+            }
+            qlen[qn] *= bases_per_symbol;
             qs += qlen[qn];
             ++qn;
         }
@@ -986,24 +1024,60 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
         memmove(qid, qid + nb, (size_t)(qn - nb) * sizeof *qid);
         memmove(qlen, qlen + nb, (size_t)(qn - nb) * sizeof *qlen);
         qn -= nb;
+        /* what the device holds per strand behind the upload: the pass's sequences, or their windows in source order,
+         * then offset order, each under the caller's id for it */
+        unsigned nres = nb;
+        struct imm_seq const *rseq = bseq[cur];
+        int64_t const *rid = bid[cur];
+        if (cut_windows(&windows))
+        {
+            uint64_t nw = 0;
+            for (unsigned i = 0; i < nb; ++i)
+                nw += dcp_seq_window_count(bseq[cur][i].size, windows.window, windows.step);
+            if (nw > UINT32_MAX)
+            {
+                rc = fail(RC_EINVAL, "a pass exceeds 2^32 - 1 windows: scan it in smaller batches");
+                break;
+            }
+            struct imm_seq *ws = realloc(wseq[cur], (size_t)nw * sizeof *ws);
+            if (ws) wseq[cur] = ws;
+            int64_t *wi = realloc(wid[cur], (size_t)nw * sizeof *wi);
+            if (wi) wid[cur] = wi;
+            if (!ws || !wi)
+            {
+                rc = fail(RC_ENOMEM, "alloc windows");
+                break;
+            }
+            unsigned w = 0;
+            for (unsigned i = 0; i < nb; ++i)
+            {
+                unsigned const L = bseq[cur][i].size, cnt = dcp_seq_window_count(L, windows.window, windows.step);
+                for (unsigned k = 0; k < cnt; ++k, ++w)
+                {
+                    unsigned const off = dcp_seq_window_start(L, windows.window, windows.step, k);
+                    ws[w] = imm_subseq(&bseq[cur][i], off, L < windows.window ? L : windows.window);
+                    wi[w] = windows.id(bid[cur][i], off, windows.arg);
+                }
+            }
+            nres = (unsigned)nw, rseq = ws, rid = wi;
+        }
         enum rc shared = RC_OK;
         ++g_stats.passes;
         if (nparts == 0) continue; /* an empty database: every sequence is consumed, nothing is scored */
-        int const prev = cur ^ 1;
 #pragma omp parallel for schedule(static, 1) num_threads(nparts)
         for (unsigned i = 0; i < nparts; ++i)
         {
             unsigned n = 0;
             enum rc r = batch_check(&th[i], bseq[cur], nb, &n);
             bool const work = !r && n != 0;
-            if (work) r = batch_submit(&th[i], (int)i, bseq[cur], nb, &strands);
+            if (work) r = batch_submit(&th[i], (int)i, bseq[cur], nb, &strands, &windows, nres);
             /* the device is busy with batch i: now the rows of batch i-1 */
             if (npend && pend[i].nhits)
             {
-                enum rc r2 = batch_rows(&th[i], bseq[prev], bid[prev], npend, &strands, &pend[i]);
+                enum rc r2 = batch_rows(&th[i], pseq, pid, npend, &strands, &pend[i]);
                 if (!r) r = r2;
             }
-            if (work && !r) r = batch_trace(&th[i], bseq[cur], nb, n, &strands, &pend[i]);
+            if (work && !r) r = batch_trace(&th[i], rseq, nres, n, &strands, &pend[i]);
             if (r)
             {
 #pragma omp atomic write
@@ -1013,18 +1087,17 @@ enum rc scan_run_source(char const *db_filename, struct scan_cfg cfg, unsigned n
                 cfg.progress((unsigned long)nb * reader->partition_size[i], cfg.progress_arg);
         }
         rc = shared;
-        npend = nb;
+        npend = nres, pseq = rseq, pid = rid;
         cur ^= 1;
     }
     /* the last batch's rows */
     if (!rc && npend && nparts)
     {
         enum rc shared = RC_OK;
-        int const prev = cur ^ 1;
 #pragma omp parallel for schedule(static, 1) num_threads(nparts)
         for (unsigned i = 0; i < nparts; ++i)
         {
-            enum rc r = pend[i].nhits ? batch_rows(&th[i], bseq[prev], bid[prev], npend, &strands, &pend[i]) : RC_OK;
+            enum rc r = pend[i].nhits ? batch_rows(&th[i], pseq, pid, npend, &strands, &pend[i]) : RC_OK;
             if (r)
             {
 #pragma omp atomic write
@@ -1067,6 +1140,7 @@ cleanup:
         for (unsigned i = 0; btext[k] && i < limit_n; ++i)
             free(btext[k][i]);
         free(btext[k]), free(bid[k]), free(bseq[k]);
+        free(wseq[k]), free(wid[k]);
     }
     for (unsigned i = 0; qtext && i < qn; ++i)
         free(qtext[i]);
@@ -1100,7 +1174,7 @@ enum rc scan_run_local(char const *db_filename, struct scan_seq const *seqs, uns
 {
     if (!seqs || !prods || batch == 0) return fail(RC_EINVAL, "bad scan arguments");
     struct list_source src = {seqs, nseqs, 0};
-    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0, NULL, NULL, false};
+    struct scan_cfg cfg = {scan_id, multi_hits, hmmer3_compat, lrt_threshold, batch, true, false, NULL, NULL, 0, NULL, NULL, false, 0, 0, NULL, NULL};
     enum rc rc = scan_run_source(db_filename, cfg, nthreads, list_next, &src);
     if (rc) return rc;
     char buf[1 << 16];

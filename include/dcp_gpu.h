@@ -339,6 +339,38 @@ int dcp_gpu_seqs_fetch(dcp_gpu_ctx *, unsigned q, uint8_t *ids, unsigned cap, un
 /* The reverse complement of n symbol ids 0..3 on the host: out[i] = 3 - ids[n - 1 - i] (out must not overlap ids).
  * The restatement of the device kernel that the tests and the host layer use. */
 void dcp_seq_revcomp(uint8_t const *ids, unsigned n, uint8_t *out);
+/* Windows.  A long sequence costs the traceback a work area over all its rows per hit, and a batch is as slow as its
+ * longest member: long targets are cut into overlapping windows and the windows scanned.  The rule, for window >= 1 and
+ * 1 <= step <= window: a sequence of L bases gives 1 window if L <= window, else 1 + ceil((L - window) / step); window
+ * i starts at min(i step, L - window) (0 if L <= window) and has min(L, window) bases -- the last one is anchored at
+ * the sequence's end, every window of a longer sequence has exactly `window` bases.  Pure host arithmetic:
+ * _count returns 0 and _start 0 for a bad rule; _plan sums over a batch's lengths, *nwindows the windows and *nwords
+ * their resident words (wl / 16 + 3 each), both in 64 bits (either may be NULL), and returns DCP_EINVAL for a bad
+ * rule or when either total exceeds 2^32 - 1. */
+unsigned dcp_seq_window_count(unsigned L, unsigned window, unsigned step);
+unsigned dcp_seq_window_start(unsigned L, unsigned window, unsigned step, unsigned i);
+int dcp_seq_window_plan(uint32_t const *len, unsigned nseqs, unsigned window, unsigned step, uint64_t *nwindows,
+                        uint64_t *nwords);
+/* The resident batch of n sequences is REPLACED by its W = sum of counts windows, in source order, then offset order,
+ * written on the device from the resident 2-bit words (csrc/dcp_seqs.hip: no base goes through the host again); the
+ * sources are no longer resident.  Everything downstream sees a batch of W sequences; a batch in which every L <=
+ * window comes out word for word as it was.  Dependent state is treated as dcp_gpu_seqs_add_revcomp treats it (the
+ * last scan is void); strands stays 1, and dcp_gpu_seqs_add_revcomp after the cut gives 2 W: resident W + i is the
+ * reverse complement of window i.  A window is scored as the sequence it now is: its Viterbi score is that of its
+ * bases alone, under special transitions for its own length -- not a share of the source's score -- and a gene in the
+ * overlap of two windows is reported from both (merging is the caller's).  DCP_EINVAL, with a message and the batch
+ * untouched: no batch resident; a bad window / step; both strands already resident (cut first, then add the reverse
+ * strand); the batch already cut; explicit special transitions in force (set them after the cut, one row per
+ * window); W or the windows' words would pass 2^32 - 1 (checked before any allocation).  A failed allocation
+ * leaves the context without a batch, as a failed upload does.  The next sequence upload returns the context to
+ * uncut.  Works on float and double DBs alike, and with no DB resident. */
+int dcp_gpu_seqs_cut_windows(dcp_gpu_ctx *, unsigned window, unsigned step);
+/* 1 if the resident batch is cut into windows, with the rule in *window / *step (either may be NULL); else 0 / 0 / 0. */
+int dcp_gpu_seqs_windows(dcp_gpu_ctx const *, unsigned *window, unsigned *step);
+/* For window i < W: src[i] its source's index in the uploaded batch, off[i] its first base there.  After
+ * dcp_gpu_seqs_add_revcomp the map still has W entries (resident W + i is window i's reverse complement).  DCP_ENOMEM if
+ * cap < W, DCP_EINVAL if the batch is not cut.  dcp_gpu_seqs_fetch serves a window's bases. */
+int dcp_gpu_seqs_window_map(dcp_gpu_ctx *, uint32_t *src, uint32_t *off, unsigned cap);
 /* Explicit special transitions for the resident sequences: xt [nseqs][13] in dcp_xtrans order.
  * By default a scan derives them from each sequence's length and the scan's flags (what
  * protein_profile_setup does per pair); imm_dp_viterbi on a profile whose transitions were set some

@@ -913,6 +913,24 @@ struct scan_cfg
      * Part of the key of keep_resident: a database left resident by a job with the other setting is uploaded again.
      * thread_run / thread_run_batch take no scan_cfg and decode on the host. */
     bool device_decode;
+    /* Windows: window != 0 -> a pass's sequences are uploaded whole and cut on the device into overlapping windows of
+     * `window` bases every window_step bases (0 = window / 2), the last window of a sequence anchored at its end
+     * (dcp_seq_window_count / _start; a sequence of at most `window` bases is one window, itself), and the windows are
+     * scanned instead of the sequences.  A hit's row is formatted from its window's bases under window_id(seq_id, offset,
+     * window_arg) -- the products format has no offset column, the caller owns the id space; required when window is
+     * set (RC_EINVAL without it, and for window_step > window); it is called once per window, on the calling thread,
+     * when a pass is cut from the source.  With
+     * minus_strand_id as well the reverse strand is added behind the cut: a minus-strand window's row carries
+     * minus_strand_id(window_id(seq_id, offset)).  The products are the bytes of a job whose source yields every window,
+     * in order, as a sequence of its own under that id: per source sequence its windows by offset, per window what
+     * the rules above say.  A gene in the overlap of two windows is reported from both, path coordinates count from
+     * the window's first base, and a window's scores are those of its bases alone (special transitions for the window's
+     * length): merging and mapping back are the caller's.  A pass still holds whole source sequences; its size is
+     * compared with batch_symbols as its windows' bases (doubled with both strands); `batch` and `progress` keep
+     * counting source sequences.  Not part of the key of keep_resident.  window = 0: exactly as before. */
+    unsigned window, window_step;
+    int64_t (*window_id)(int64_t seq_id, unsigned offset, void *arg);
+    void *window_arg;
 };
 /* Where the last scan_run_source spent its time (not in the reference; profiles/host_scan_probe.c prints it): host
  * seconds summed over the partitions' threads.  scan_wait_s is the wait for the device scans (the host has nothing

@@ -85,6 +85,9 @@ ABI_SYMBOLS = [
     # the decode of paths on the device
     "dcp_gpu_db_keep_dists", "dcp_gpu_db_has_dists", "dcp_gpu_decode_paths", "dcp_profile_codon_joint",
     "dcp_prod_format_row_codes",
+    # domains: hit paths split at B .. E on the device, located on their sources, merged
+    "dcp_gpu_path_domains", "dcp_gpu_path_domains64", "dcp_gpu_path_domains_kernel_ms", "dcp_domains_locate",
+    "dcp_gpu_domains_locate", "dcp_domains_merge",
 ]
 
 
@@ -132,6 +135,9 @@ HIT_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
                       ("null_loglik", np.float32), ("alt_loglik", np.float32)])
 HIT64_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
                         ("null_loglik", np.float64), ("alt_loglik", np.float64)])
+# struct dcp_domain: one B .. E stretch of an alt path (Scanner.path_domains)
+DOMAIN_DTYPE = np.dtype([(f, np.uint32) for f in ("path", "step_begin", "step_end", "seq_begin", "seq_end", "node_first",
+                                                   "node_last", "n_match", "n_insert", "n_delete", "n_shift", "reserved")])
 
 
 def _load(path=None, hooks=False):
@@ -246,6 +252,12 @@ def _load(path=None, hooks=False):
         "dcp_profile_codon_joint": (I, [P, P, U, U, P, C.POINTER(C.c_double)]),
         "dcp_prod_format_row_codes": (C.c_long, [C.c_char_p, C.c_size_t, C.c_int64, C.c_int64, C.c_char_p, C.c_char_p,
                                                  C.c_double, C.c_double, C.c_char_p, C.c_char_p, P, P, U, P, U, P]),
+        "dcp_gpu_path_domains": (I, [P, P, P, U, P, P, I, I, P, U, P, P, P, P]),
+        "dcp_gpu_path_domains64": (I, [P, P, P, U, P, P, I, I, P, U, P, P, P, P]),
+        "dcp_gpu_path_domains_kernel_ms": (F, [P]),
+        "dcp_domains_locate": (I, [P, P, U, P, U, U, P, P, P, P, P, P]),
+        "dcp_gpu_domains_locate": (I, [P, P, P, U, P, P, P, P]),
+        "dcp_domains_merge": (I, [P, P, P, P, P, P, U, P, C.POINTER(U)]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -661,6 +673,58 @@ def window_plan(lens, window, step):
     return nwin.value, nwords.value
 
 
+def _locate_outputs(n):
+    return np.zeros(n, np.uint32), np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros(n, np.uint8)
+
+
+def locate_domains(res_idx, domains, res_len, per_strand, strands=1, win_src=None, win_off=None):
+    """Where domains lie on their sources (dcp_domains_locate): (src uint32, begin uint64, end uint64, minus uint8).
+    res_idx[j]: the resident sequence domain j was found on (its hit's seq_idx); res_len: the resident lengths, strands
+    x per_strand of them; win_src / win_off: the window map of a cut batch (Scanner.window_map), None if uncut.  On the
+    minus strand [seq_begin, seq_end) becomes [len - seq_end, len - seq_begin) before the window's offset is added."""
+    res = np.ascontiguousarray(res_idx, np.uint32)
+    dom = np.ascontiguousarray(domains, DOMAIN_DTYPE)
+    if len(res) != len(dom):
+        raise DcpError(RC_EINVAL, "one resident index per domain")
+    lens = np.ascontiguousarray(res_len, np.uint32)
+    if len(lens) != per_strand * strands:
+        raise DcpError(RC_EINVAL, "res_len holds strands x per_strand lengths")
+    ws = wo = None
+    if win_src is not None:
+        ws, wo = np.ascontiguousarray(win_src, np.uint32), np.ascontiguousarray(win_off, np.uint32)
+        if len(ws) != per_strand or len(wo) != per_strand:
+            raise DcpError(RC_EINVAL, "the window map holds per_strand entries")
+    src, begin, end, minus = _locate_outputs(len(dom))
+    rc = lib.dcp_domains_locate(res.ctypes.data, dom.ctypes.data, len(dom), lens.ctypes.data, per_strand, strands,
+                                ws.ctypes.data if ws is not None else None, wo.ctypes.data if wo is not None else None,
+                                src.ctypes.data, begin.ctypes.data, end.ctypes.data, minus.ctypes.data)
+    if rc:
+        raise DcpError(rc, "a domain lies outside its resident sequence, or a bad batch shape")
+    return src, begin, end, minus
+
+
+def merge_domains(src, minus, profile, begin, end, odds):
+    """One representative per duplicated domain (dcp_domains_merge): a bool array, True for the domains kept.  Within
+    each (src, minus, profile) group the candidates go by odds = core - null descending (then longer first, then lower
+    index first), and one is dropped if a kept one overlaps it by more than half the shorter of the two.  The rank is
+    the odds, not the core score: core is a log-likelihood that falls with length, so a stump cut by a window's edge
+    would outrank the whole gene."""
+    src, profile = np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(profile, np.uint32)
+    minus = np.ascontiguousarray(minus, np.uint8)
+    begin, end = np.ascontiguousarray(begin, np.uint64), np.ascontiguousarray(end, np.uint64)
+    odds = np.ascontiguousarray(odds, np.float64)
+    n = len(src)
+    if not all(len(a) == n for a in (minus, profile, begin, end, odds)):
+        raise DcpError(RC_EINVAL, "arrays of one length")
+    keep, nkept = np.zeros(n, np.uint8), C.c_uint(0)
+    rc = lib.dcp_domains_merge(src.ctypes.data, minus.ctypes.data, profile.ctypes.data, begin.ctypes.data,
+                               end.ctypes.data, odds.ctypes.data, n, keep.ctypes.data, C.byref(nkept))
+    if rc:
+        raise DcpError(rc, "a NaN in odds, or an empty interval")
+    assert int(keep.sum()) == nkept.value
+    return keep.astype(bool)
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -1039,6 +1103,59 @@ class Scanner:
         self._check(self._lib.dcp_gpu_decode_paths(self._c, sq.ctypes.data, pr.ctypes.data, n, steps.ctypes.data,
                                                    off.ctypes.data, codes.ctypes.data))
         return [codes[off[i]:off[i + 1]].copy() for i in range(n)]
+
+    def path_domains(self, hits, paths, multi_hits=True, hmmer3_compat=False):
+        """The domains of the given paths -- one per B .. E stretch of an alt path -- split and scored on the device
+        (dcp_gpu_path_domains / ...64): (domains DOMAIN_DTYPE, dom_off uint32 [n + 1], core, null, total).  Path i's
+        domains are domains[dom_off[i]:dom_off[i + 1]] (none for a null path); core[d] is the domain's score from B to
+        E on the resident tables, null[d] the null emissions of the same fragments, total[i] the whole path's score, all
+        in the DB's precision and in step order.  hits, paths: as for decode_paths; the flags as for trace_paths.
+        Like hits(), it retries once at the true count when the first capacity is too small."""
+        if isinstance(paths, tuple):
+            paths = paths[0]
+        n = len(paths)
+        if len(hits) != n:
+            raise DcpError(RC_EINVAL, "one path per hit")
+        f64 = self.precision == 64
+        real = np.float64 if f64 else np.float32
+        call = self._lib.dcp_gpu_path_domains64 if f64 else self._lib.dcp_gpu_path_domains
+        sq = np.ascontiguousarray(hits["seq_idx"], np.uint32)
+        pr = np.ascontiguousarray(hits["profile_idx"], np.uint32)
+        off = np.zeros(n + 1, np.uint32)
+        if n:
+            off[1:] = np.cumsum([len(p) for p in paths])
+        steps = np.ascontiguousarray(np.concatenate(paths), STEP_DTYPE) if n and off[n] else np.zeros(1, STEP_DTYPE)
+        dom_off = np.zeros(n + 1, np.uint32)
+        total = np.zeros(n, real)
+        cap = max(2 * n, 1)
+        for _ in range(2):
+            dom = np.zeros(cap, DOMAIN_DTYPE)
+            core, null = np.zeros(cap, real), np.zeros(cap, real)
+            rc = call(self._c, sq.ctypes.data, pr.ctypes.data, n, steps.ctypes.data, off.ctypes.data, int(multi_hits),
+                      int(hmmer3_compat), dom.ctypes.data, cap, dom_off.ctypes.data, core.ctypes.data, null.ctypes.data,
+                      total.ctypes.data)
+            if rc != RC_ENOMEM or dom_off[n] <= cap:
+                break
+            cap = int(dom_off[n])
+        self._check(rc)
+        nd = int(dom_off[n])
+        return dom[:nd], dom_off, core[:nd], null[:nd], total
+
+    @property
+    def path_domains_kernel_ms(self):
+        """Milliseconds the kernel of the last path_domains call ran (dcp_gpu_path_domains_kernel_ms)."""
+        return self._lib.dcp_gpu_path_domains_kernel_ms(self._c)
+
+    def locate_domains(self, hits, domains):
+        """Where the domains of path_domains(hits, ...) lie on the uploaded sequences (dcp_gpu_domains_locate), through
+        the context's own strand and window maps: (src uint32, begin uint64, end uint64, minus uint8), the interval in
+        the source's plus-strand coordinates."""
+        dom = np.ascontiguousarray(domains, DOMAIN_DTYPE)
+        res = np.ascontiguousarray(np.asarray(hits["seq_idx"], np.uint32)[dom["path"]] if len(dom) else [], np.uint32)
+        src, begin, end, minus = _locate_outputs(len(dom))
+        self._check(self._lib.dcp_gpu_domains_locate(self._c, res.ctypes.data, dom.ctypes.data, len(dom), src.ctypes.data,
+                                                     begin.ctypes.data, end.ctypes.data, minus.ctypes.data))
+        return src, begin, end, minus
 
     def hits(self, cap=1 << 20):
         """Hit records of the last scan, sorted by (seq_idx, profile_idx): HIT64_DTYPE after a scan of a double DB."""

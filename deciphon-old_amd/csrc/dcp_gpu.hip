@@ -9,6 +9,7 @@
 #include "dcp_f64.h"
 #include "dcp_seqs.h"
 #include "dcp_decode.h"
+#include "dcp_domains.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -341,6 +342,15 @@ struct dcp_gpu_ctx
     } dec;
     DevBuf<dcp_decode_item> d_dec_items; // one round's work list and codes (kept between calls)
     DevBuf<uint8_t> d_dec_codes;
+    // dcp_gpu_path_domains (dcp_domains.hip): the call's steps, its path records, its special transitions (a double
+    // DB: one row per path), the domain records, and core / null / total sums with the error word in one buffer of
+    // 8-byte units; kept between calls, grown when a call needs more.  ev_dom: around the kernel of the last call.
+    DevBuf<dcp_step> d_dom_steps;
+    DevBuf<dcp_dom_path> d_dom_paths;
+    DevBuf<double> d_dom_xt, d_dom_sums;
+    DevBuf<uint32_t> d_dom_recs;
+    hipEvent_t ev_dom[2] = {nullptr, nullptr};
+    bool dom_timed = false;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -662,6 +672,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     if (c->h_qstage) (void)hipHostFree(c->h_qstage);
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
+    for (hipEvent_t e : c->ev_dom)
+        if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
     for (int k = 0; k <= kNumClasses; ++k)
@@ -1443,19 +1455,13 @@ static int decode_step_kind(unsigned id, unsigned core_size, unsigned *k)
     return msb == 0 ? DCP_DECODE_MATCH + 1 : msb == (1u << 14) ? DCP_DECODE_INSERT + 1 : 0;
 }
 
-int dcp_gpu_decode_paths(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
-                         struct dcp_step const *steps, uint32_t const *step_off, uint8_t *codes_out)
+// What dcp_gpu_decode_paths and dcp_gpu_path_domains check of the caller's paths before anything is launched or
+// written, from integers alone: the indices, the step offsets, every state id and seqlen, and the bases the steps emit
+// -- at most the sequence's length, or (whole) exactly that.  *nemit: the emitting steps of all paths.
+static int check_path_steps(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                            struct dcp_step const *steps, uint32_t const *step_off, bool whole, uint64_t *nemit)
 {
-    if (!c) return DCP_EINVAL;
-    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident: nothing to decode with");
-    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing to decode");
-    if (!c->dec.ready)
-        return c->fail(DCP_EINVAL, "the resident DB's compact distributions are not resident: switch them on with "
-                                   "dcp_gpu_db_keep_dists before the upload");
-    if (npaths == 0) return DCP_OK;
-    if (!seq_idx || !profile_idx || !step_off) return c->fail(DCP_EINVAL, "null index array");
-    // everything is checked before anything is launched or written
-    uint64_t nemit = 0;
+    *nemit = 0;
     for (unsigned h = 0; h < npaths; ++h)
     {
         if (step_off[h + 1] < step_off[h]) return c->fail(DCP_EINVAL, "path %u: step offsets decrease", h);
@@ -1477,12 +1483,30 @@ int dcp_gpu_decode_paths(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const
             if (kind > 0 && (len < 1u || len > 5u))
                 return c->fail(DCP_EINVAL, "path %u, step %u: an emitting state with seqlen %u (1..5)", h, i - step_off[h], len);
             pos += len;
-            nemit += kind > 0;
+            *nemit += kind > 0;
         }
-        if (pos > c->seq_len[seq_idx[h]])
+        uint32_t const L = c->seq_len[seq_idx[h]];
+        if (pos > L || (whole && pos != L))
             return c->fail(DCP_EINVAL, "path %u: its steps emit %llu bases, sequence %u has %u", h, (unsigned long long)pos,
-                           seq_idx[h], c->seq_len[seq_idx[h]]);
+                           seq_idx[h], L);
     }
+    return DCP_OK;
+}
+
+int dcp_gpu_decode_paths(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                         struct dcp_step const *steps, uint32_t const *step_off, uint8_t *codes_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident: nothing to decode with");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing to decode");
+    if (!c->dec.ready)
+        return c->fail(DCP_EINVAL, "the resident DB's compact distributions are not resident: switch them on with "
+                                   "dcp_gpu_db_keep_dists before the upload");
+    if (npaths == 0) return DCP_OK;
+    if (!seq_idx || !profile_idx || !step_off) return c->fail(DCP_EINVAL, "null index array");
+    // everything is checked before anything is launched or written
+    uint64_t nemit = 0;
+    if (int rc = check_path_steps(c, seq_idx, profile_idx, npaths, steps, step_off, false, &nemit)) return rc;
     uint32_t const first = step_off[0], total = step_off[npaths] - step_off[0];
     if (total == 0) return DCP_OK;
     if (!codes_out) return c->fail(DCP_EINVAL, "null output");
@@ -3385,6 +3409,219 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
     };
     return trace_rounds(c, hits, nhits, need, cap, grp, 4, true, budget, null_model ? "null" : "alt", steps_out, cap_steps, step_off,
                         alt_out, round);
+}
+
+// ---------------------------------------------------------------------------
+// Hit paths -> domains (dcp_domains.hip)
+// ---------------------------------------------------------------------------
+} // extern "C": one template serves the float and the double call
+
+namespace
+{
+char const *const kSpecialNames[8] = {"R", "S", "N", "B", "E", "J", "C", "T"};
+void step_name(unsigned id, char out[16])
+{
+    unsigned const kind = id >> 14, x = id & 0x3fffu;
+    if (kind == 3u) snprintf(out, 16, "%s", x < 8u ? kSpecialNames[x] : "?");
+    else snprintf(out, 16, "%c%u", "MID"[kind], x);
+}
+
+template <class Real>
+int path_domains(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                 struct dcp_step const *steps, uint32_t const *step_off, int multi_hits, int hmmer3_compat,
+                 struct dcp_domain *dom_out, unsigned cap_domains, uint32_t *dom_off, Real *core_out, Real *null_out,
+                 Real *total_out)
+{
+    constexpr bool f64 = std::is_same<Real, double>::value;
+    if (!c) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident: nothing to score the paths on");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing the paths emit");
+    if ((c->precision == 64) != f64)
+        return c->fail(DCP_EINVAL, f64 ? "dcp_gpu_path_domains64 works on a double DB: the resident DB is float (dcp_gpu_path_domains)"
+                                       : "dcp_gpu_path_domains works on a float DB: the resident DB is double (dcp_gpu_path_domains64)");
+    if (npaths == 0) return DCP_OK;
+    if (!seq_idx || !profile_idx || !step_off || !dom_off) return c->fail(DCP_EINVAL, "null index array");
+    if (!f64 && !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    if (f64 && c->xt_explicit)
+        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    // everything integers decide is checked before anything is launched or written
+    uint64_t nemit = 0;
+    if (int rc = check_path_steps(c, seq_idx, profile_idx, npaths, steps, step_off, true, &nemit)) return rc;
+    std::vector<uint32_t> doff(npaths + 1u, 0u);
+    uint64_t ndom = 0;
+    for (unsigned h = 0; h < npaths; ++h)
+    {
+        uint32_t const b = step_off[h], e = step_off[h + 1];
+        doff[h] = (uint32_t)ndom;
+        if (b == e) return c->fail(DCP_EINVAL, "path %u is empty", h);
+        unsigned const R = 3u << 14, S = R | 1u, B = R | 3u, E = R | 4u, T = R | 7u;
+        if (steps[b].state_id == R) // a null path: all R
+        {
+            for (uint32_t i = b; i < e; ++i)
+                if (steps[i].state_id != R)
+                    return c->fail(DCP_EINVAL, "path %u, step %u: a null path holds R steps only", h, i - b);
+            continue;
+        }
+        if (steps[b].state_id != S) return c->fail(DCP_EINVAL, "path %u: an alt path starts with S (a null path with R)", h);
+        if (steps[e - 1u].state_id != T) return c->fail(DCP_EINVAL, "path %u: an alt path ends with T", h);
+        bool open = false;
+        for (uint32_t i = b; i < e; ++i)
+        {
+            unsigned const id = steps[i].state_id;
+            if (id == R) return c->fail(DCP_EINVAL, "path %u, step %u: R in an alt path", h, i - b);
+            if (id == B)
+            {
+                if (open) return c->fail(DCP_EINVAL, "path %u, step %u: a B before the E of the B before it", h, i - b);
+                open = true;
+                ++ndom;
+            }
+            else if (id == E)
+            {
+                if (!open) return c->fail(DCP_EINVAL, "path %u, step %u: an E without a B", h, i - b);
+                open = false;
+            }
+        }
+        if (open) return c->fail(DCP_EINVAL, "path %u: a B without an E", h);
+        if (ndom > 0xffffffffull) return c->fail(DCP_EINVAL, "too many domains");
+    }
+    doff[npaths] = (uint32_t)ndom;
+    if (ndom > cap_domains)
+    {
+        dom_off[npaths] = (uint32_t)ndom; // the need; nothing else is written
+        return c->fail(DCP_ENOMEM, "the paths hold %llu domains: the buffers hold %u", (unsigned long long)ndom, cap_domains);
+    }
+    if (ndom && (!dom_out || !core_out || !null_out)) return c->fail(DCP_EINVAL, "null output");
+    uint32_t const first = step_off[0], total = step_off[npaths] - step_off[0];
+
+    HIP_TRY(c, hipSetDevice(c->device));
+    std::vector<dcp_dom_path> recs(npaths + 1u);
+    std::vector<Real> xt; // a double DB: one row per path
+    if (f64)
+    {
+        std::vector<uint32_t> seqs(seq_idx, seq_idx + npaths);
+        if (int rc = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
+        std::vector<uint32_t> slot(c->nprof);
+        for (unsigned i = 0; i < (unsigned)c->f64.profs.size(); ++i)
+            slot[c->f64.profs[i].pidx] = i;
+        for (unsigned h = 0; h < npaths; ++h)
+            recs[h] = dcp_dom_path{seq_idx[h], slot[profile_idx[h]], step_off[h] - first, doff[h]};
+    }
+    else
+    {
+        if (int rc = ensure_xtrans(c, multi_hits, hmmer3_compat)) return rc;
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+        for (unsigned h = 0; h < npaths; ++h)
+            recs[h] = dcp_dom_path{seq_idx[h], c->slot_of_pidx[profile_idx[h]], step_off[h] - first, doff[h]};
+    }
+    recs[npaths] = dcp_dom_path{0u, 0u, total, (uint32_t)ndom};
+
+    // sums: [ndom] core, [ndom] null, [npaths] total, then the error word, in 8-byte units
+    size_t const nsums = 2u * (size_t)ndom + npaths + 1u;
+    if (c->d_dom_steps.n < total) HIP_TRY(c, c->d_dom_steps.alloc(total));
+    if (c->d_dom_paths.n < recs.size()) HIP_TRY(c, c->d_dom_paths.alloc(recs.size()));
+    if (c->d_dom_sums.n < nsums) HIP_TRY(c, c->d_dom_sums.alloc(nsums));
+    if (ndom && c->d_dom_recs.n < 12u * (size_t)ndom) HIP_TRY(c, c->d_dom_recs.alloc(12u * (size_t)ndom));
+    if (f64 && c->d_dom_xt.n < xt.size()) HIP_TRY(c, c->d_dom_xt.alloc(xt.size()));
+    for (hipEvent_t &e : c->ev_dom)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    unsigned long long const none = ~0ull;
+    unsigned long long *const d_bad = (unsigned long long *)(c->d_dom_sums.p + nsums - 1u);
+    HIP_TRY(c, hipMemcpyAsync(c->d_dom_steps.p, steps + first, (size_t)total * sizeof(dcp_step), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_dom_paths.p, recs.data(), recs.size() * sizeof(dcp_dom_path), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_bad, &none, sizeof none, hipMemcpyHostToDevice, c->stream));
+    if (f64) HIP_TRY(c, hipMemcpyAsync(c->d_dom_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    dcp_domains_args a{};
+    a.paths = c->d_dom_paths.p, a.npaths = npaths, a.steps = c->d_dom_steps.p;
+    a.words = c->d_seq_words.p, a.woff = c->d_seq_woff.p;
+    if (f64)
+    {
+        a.profs = c->f64.d_profs.p, a.match = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.insert = c->f64.d_xe.p;
+        a.xtrans = c->d_dom_xt.p, a.xt_per_path = 1;
+    }
+    else
+    {
+        a.profs = c->d_metas.p, a.match = c->d_emis_match.p, a.trans = c->d_trans8.p;
+        a.insert = c->d_emis_insert.p, a.null_tab = c->d_emis_null.p;
+        a.xtrans = c->d_xtrans.p, a.xt_per_path = 0;
+    }
+    Real *const d_core = (Real *)c->d_dom_sums.p, *const d_null = (Real *)(c->d_dom_sums.p + ndom),
+               *const d_total = (Real *)(c->d_dom_sums.p + 2u * (size_t)ndom);
+    a.dom_out = c->d_dom_recs.p, a.core_out = d_core, a.null_out = d_null, a.total_out = d_total, a.bad = d_bad;
+    HIP_TRY(c, hipEventRecord(c->ev_dom[0], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_domains(&a, f64, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_dom[1], c->stream));
+    c->dom_timed = true;
+    std::vector<dcp_domain> h_dom(ndom);
+    std::vector<Real> h_core(ndom), h_null(ndom), h_total(npaths);
+    unsigned long long bad = none;
+    if (ndom)
+    {
+        static_assert(sizeof(dcp_domain) == 48, "a domain record is 12 words");
+        HIP_TRY(c, hipMemcpyAsync(h_dom.data(), c->d_dom_recs.p, ndom * sizeof(dcp_domain), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_core.data(), d_core, ndom * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(h_null.data(), d_null, ndom * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipMemcpyAsync(h_total.data(), d_total, npaths * sizeof(Real), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (bad != none)
+    {
+        unsigned const h = (unsigned)(bad >> 32), i = (unsigned)bad;
+        char from[16], to[16];
+        step_name(steps[step_off[h] + i - 1u].state_id, from);
+        step_name(steps[step_off[h] + i].state_id, to);
+        return c->fail(DCP_EINVAL, "path %u, step %u: %s -> %s is no edge of the model graph", h, i, from, to);
+    }
+    std::memcpy(dom_off, doff.data(), doff.size() * sizeof(uint32_t));
+    if (ndom)
+    {
+        std::memcpy(dom_out, h_dom.data(), ndom * sizeof(dcp_domain));
+        std::memcpy(core_out, h_core.data(), ndom * sizeof(Real));
+        std::memcpy(null_out, h_null.data(), ndom * sizeof(Real));
+    }
+    if (total_out) std::memcpy(total_out, h_total.data(), npaths * sizeof(Real));
+    return DCP_OK;
+}
+} // namespace
+
+extern "C" {
+
+int dcp_gpu_path_domains(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                         struct dcp_step const *steps, uint32_t const *step_off, int multi_hits, int hmmer3_compat,
+                         struct dcp_domain *dom_out, unsigned cap_domains, uint32_t *dom_off, float *core_out,
+                         float *null_out, float *total_out)
+{
+    return path_domains<float>(c, seq_idx, profile_idx, npaths, steps, step_off, multi_hits, hmmer3_compat, dom_out,
+                               cap_domains, dom_off, core_out, null_out, total_out);
+}
+
+int dcp_gpu_path_domains64(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                           struct dcp_step const *steps, uint32_t const *step_off, int multi_hits, int hmmer3_compat,
+                           struct dcp_domain *dom_out, unsigned cap_domains, uint32_t *dom_off, double *core_out,
+                           double *null_out, double *total_out)
+{
+    return path_domains<double>(c, seq_idx, profile_idx, npaths, steps, step_off, multi_hits, hmmer3_compat, dom_out,
+                                cap_domains, dom_off, core_out, null_out, total_out);
+}
+
+float dcp_gpu_path_domains_kernel_ms(dcp_gpu_ctx *c)
+{
+    float ms = 0.0f;
+    if (!c || !c->dom_timed || hipEventElapsedTime(&ms, c->ev_dom[0], c->ev_dom[1]) != hipSuccess) return 0.0f;
+    return ms;
+}
+
+int dcp_gpu_domains_locate(dcp_gpu_ctx *c, uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n,
+                           uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing to locate the domains on");
+    bool const cut = c->win_window != 0;
+    int const rc = dcp_domains_locate(res_idx, dom, n, c->seq_len.data(), c->nseqs / c->strands, c->strands,
+                                      cut ? c->win_src.data() : nullptr, cut ? c->win_off.data() : nullptr, src_out,
+                                      begin_out, end_out, minus_out);
+    return rc ? c->fail(rc, "a domain lies outside the resident batch (%u sequences), or a null pointer", c->nseqs) : DCP_OK;
 }
 
 static void last_range(dcp_gpu_ctx const *c, uint64_t *sumM, uint64_t *len, uint64_t *nq)

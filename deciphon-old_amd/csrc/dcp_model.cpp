@@ -13,6 +13,7 @@
 // in double in the probability domain and rounded once to float32 (imm_float).
 #include "dcp_host.h"
 
+#include <algorithm>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -20,6 +21,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <mutex>
 #include <vector>
 
@@ -1538,6 +1540,97 @@ int dcp_seq_window_plan(uint32_t const *len, unsigned nseqs, unsigned window, un
     if (nwindows) *nwindows = W;
     if (nwords) *nwords = words;
     return W > 0xffffffffull || words > 0xffffffffull ? DCP_EINVAL : DCP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Domains (dcp_gpu_path_domains) on their sources, and one representative per duplicate.  Pure arithmetic, no device.
+// ---------------------------------------------------------------------------
+int dcp_domains_locate(uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n, uint32_t const *res_len,
+                       unsigned per_strand, unsigned strands, uint32_t const *win_src, uint32_t const *win_off,
+                       uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out)
+{
+    if (n == 0) return DCP_OK;
+    if (!res_idx || !dom || !res_len || !src_out || !begin_out || !end_out || !minus_out) return DCP_EINVAL;
+    if (win_src && !win_off) return DCP_EINVAL;
+    if (strands < 1u || strands > 2u || per_strand == 0u) return DCP_EINVAL;
+    uint64_t const resident = (uint64_t)per_strand * strands;
+    // everything is checked before anything is written
+    for (unsigned j = 0; j < n; ++j)
+    {
+        if (res_idx[j] >= resident) return DCP_EINVAL;
+        if (dom[j].seq_begin > dom[j].seq_end || dom[j].seq_end > res_len[res_idx[j]]) return DCP_EINVAL;
+    }
+    for (unsigned j = 0; j < n; ++j)
+    {
+        uint32_t const r = res_idx[j], i = r % per_strand, len = res_len[r];
+        bool const minus = r >= per_strand;
+        uint64_t const b = minus ? len - dom[j].seq_end : dom[j].seq_begin;
+        uint64_t const e = minus ? len - dom[j].seq_begin : dom[j].seq_end;
+        uint64_t const off = win_src ? win_off[i] : 0u;
+        src_out[j] = win_src ? win_src[i] : i;
+        begin_out[j] = off + b;
+        end_out[j] = off + e;
+        minus_out[j] = minus ? 1u : 0u;
+    }
+    return DCP_OK;
+}
+
+int dcp_domains_merge(uint32_t const *src, uint8_t const *minus, uint32_t const *profile, uint64_t const *begin,
+                      uint64_t const *end, double const *odds, unsigned n, uint8_t *keep_out, unsigned *nkept_out)
+{
+    if (n == 0)
+    {
+        if (nkept_out) *nkept_out = 0;
+        return DCP_OK;
+    }
+    if (!src || !minus || !profile || !begin || !end || !odds || !keep_out) return DCP_EINVAL;
+    for (unsigned j = 0; j < n; ++j)
+        if (odds[j] != odds[j] || end[j] <= begin[j]) return DCP_EINVAL; // (this unit is built with -fhonor-nans)
+    auto same_group = [&](unsigned a, unsigned b) {
+        return src[a] == src[b] && (minus[a] != 0) == (minus[b] != 0) && profile[a] == profile[b];
+    };
+    // one sort: by group, then by the rank inside it
+    std::vector<unsigned> order(n);
+    for (unsigned j = 0; j < n; ++j)
+        order[j] = j;
+    std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) {
+        if (src[a] != src[b]) return src[a] < src[b];
+        if ((minus[a] != 0) != (minus[b] != 0)) return minus[a] == 0;
+        if (profile[a] != profile[b]) return profile[a] < profile[b];
+        if (odds[a] != odds[b]) return odds[a] > odds[b];
+        uint64_t const la = end[a] - begin[a], lb = end[b] - begin[b];
+        if (la != lb) return la > lb;
+        return a < b;
+    });
+    unsigned nkept = 0;
+    // the kept members of the group at hand by their first base, and the longest of them: a kept member that overlaps
+    // [b, e) begins after b - longest and before e, so only that stretch of the map is compared
+    std::multimap<uint64_t, unsigned> kept;
+    uint64_t longest = 0;
+    for (unsigned o = 0; o < n; ++o)
+    {
+        unsigned const j = order[o];
+        if (o > 0 && !same_group(order[o - 1], j)) kept.clear(), longest = 0;
+        uint64_t const b = begin[j], e = end[j], len = e - b;
+        bool keep = true;
+        for (auto it = b > longest ? kept.upper_bound(b - longest) : kept.begin(); keep && it != kept.end() && it->first < e; ++it)
+        {
+            unsigned const k = it->second;
+            uint64_t const lo = std::max(b, begin[k]), hi = std::min(e, end[k]);
+            if (hi <= lo) continue;
+            uint64_t const ov = hi - lo, shorter = std::min(len, end[k] - begin[k]);
+            if (ov > shorter - ov) keep = false; // 2 ov > shorter, with no doubling to overflow
+        }
+        keep_out[j] = keep ? 1u : 0u;
+        if (keep)
+        {
+            kept.emplace(b, j);
+            longest = std::max(longest, len);
+            ++nkept;
+        }
+    }
+    if (nkept_out) *nkept_out = nkept;
+    return DCP_OK;
 }
 
 } // extern "C"

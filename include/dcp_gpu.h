@@ -653,6 +653,84 @@ long dcp_prod_format_row_codes(char *buf, size_t cap, int64_t scan_id, int64_t s
                                dcp_profile const *prof, uint8_t const *seq, unsigned seq_len,
                                struct dcp_step const *steps, unsigned nsteps, uint8_t const *codes);
 
+/* ---- Domains: hit paths split at B .. E on the device, located on their sources, merged --------
+ * A domain is one B .. E stretch of an alt path: one pass through the core model.  A multi-hit path holds one per
+ * pass (joined through J), a window's edge can cut one short, and two overlapping windows report the same one. */
+struct dcp_domain              /* 48 bytes, 12 uint32 words, no padding */
+{
+    uint32_t path;             /* index into the call's paths */
+    uint32_t step_begin;       /* the B step, counted from the path's first step */
+    uint32_t step_end;         /* the E step */
+    uint32_t seq_begin, seq_end; /* bases of the resident sequence its steps emit, half open */
+    uint32_t node_first;       /* node (1-based) of the first core step: an M */
+    uint32_t node_last;        /* node of the last core step before E: an M or a D */
+    uint32_t n_match, n_insert, n_delete; /* core steps by kind */
+    uint32_t n_shift;          /* emitting core steps (M, I) whose seqlen != 3 */
+    uint32_t reserved;         /* 0 */
+};
+/* For npaths (resident sequence, resident profile) pairs and their paths, given as to dcp_gpu_decode_paths -- any
+ * valid path of the model graph, not only a Viterbi path -- the domains of every alt path, in path order then step
+ * order: path h's are dom_out[dom_off[h] .. dom_off[h + 1]).  A path that starts with R is a null path: no domains.
+ * Three sums per call, in the DB's precision and in step order with no reassociation (csrc/dcp_domains.hip), t_i the
+ * transition into step i, e_i the emission of its fragment, n_i the resident NULL table's value for the same word:
+ *   total_out[h] (may be NULL): s = 0; per step: if (i > 0) s = s + t_i; if (seqlen) s = s + e_i -- bit for bit the
+ *     traceback's alt_out and the hit's alt_loglik (null_loglik for a null path) when the path is the Viterbi path;
+ *   core_out[d]: from c = 0 at B, for every later step up to and including E: c = c + t_i; if (seqlen) c = c + e_i;
+ *   null_out[d]: from n = 0 at B, over the same steps: if (seqlen) n = n + n_i.
+ * A domain's sums do not depend on what lies before its B: the same domain seen from two windows gives the same bits.
+ * core - null is the domain's log-odds against the null emissions (dcp_domains_merge ranks by it).  Special
+ * transitions: the explicit rows while they are in force, else those of the two flags, as dcp_gpu_trace_paths takes
+ * them.
+ * Everything that integers decide is checked on the host before any launch -- indices, state ids, seqlen ranges, an
+ * alt path starts with S, ends with T and holds no R, a null path is all R, the steps emit exactly the sequence's
+ * length, every B is followed by an E before the next B and every E follows a B -- and the host counts the B steps:
+ * if cap_domains is too small the call returns DCP_ENOMEM with the need in dom_off[npaths] and writes nothing else.
+ * An edge that is not in the model graph (M3 -> M5, D1, B -> E ...) is found by the kernel, never scored, and the call
+ * returns DCP_EINVAL naming the first such (path, step).  DCP_EINVAL with a message also: no DB or no batch resident,
+ * a float call on a double DB or the reverse, a null pointer.  All outputs stay untouched on every error (but
+ * dom_off[npaths] of DCP_ENOMEM).  npaths == 0 is DCP_OK.  The call runs on the context's stream and returns
+ * synchronised; the last scan's results stay valid. */
+int dcp_gpu_path_domains(dcp_gpu_ctx *, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                         struct dcp_step const *steps, uint32_t const *step_off,
+                         int multi_hits, int hmmer3_compat,
+                         struct dcp_domain *dom_out, unsigned cap_domains, uint32_t *dom_off /* [npaths + 1] */,
+                         float *core_out, float *null_out /* [cap_domains] each */,
+                         float *total_out /* [npaths], may be NULL */);
+/* The same with double outputs, on a double DB. */
+int dcp_gpu_path_domains64(dcp_gpu_ctx *, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npaths,
+                           struct dcp_step const *steps, uint32_t const *step_off,
+                           int multi_hits, int hmmer3_compat,
+                           struct dcp_domain *dom_out, unsigned cap_domains, uint32_t *dom_off,
+                           double *core_out, double *null_out, double *total_out);
+/* Milliseconds the domain kernel of the context's last dcp_gpu_path_domains / ...64 call ran, between two events on
+ * the context's stream (copies excluded); 0 before the first call. */
+float dcp_gpu_path_domains_kernel_ms(dcp_gpu_ctx *);
+
+/* Where n domains lie on their sources.  Pure host arithmetic.  The resident batch holds `strands` x per_strand
+ * sequences of res_len[] bases (strands 1 or 2; resident per_strand + i is the reverse complement of resident i);
+ * resident i < per_strand is window win_src[i] + win_off[i] of its source, or source i itself if win_src is NULL (an
+ * uncut batch; win_off is then not read).  For domain j on resident r = res_idx[j], i = r % per_strand, minus =
+ * r >= per_strand: its interval in the window's plus coordinates is [seq_begin, seq_end), or [len - seq_end, len -
+ * seq_begin) on the minus strand; begin_out / end_out add the window's offset (64 bits), src_out is the source,
+ * minus_out 0 / 1.  DCP_EINVAL, nothing written: a null pointer with n > 0, strands outside 1..2, r >= strands x
+ * per_strand, seq_begin > seq_end or seq_end > len. */
+int dcp_domains_locate(uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n, uint32_t const *res_len,
+                       unsigned per_strand, unsigned strands, uint32_t const *win_src, uint32_t const *win_off,
+                       uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out);
+/* The same with the context's own lengths, strands and window map.  DCP_EINVAL with a message if no batch is
+ * resident. */
+int dcp_gpu_domains_locate(dcp_gpu_ctx *, uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n,
+                           uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out);
+/* One representative per duplicated domain.  Within each (src, minus, profile) group the candidates are taken by
+ * odds descending -- odds[j] = (double)core - (double)null: the raw core score is a log-likelihood, negative and
+ * growing with length, so a stump cut by a window's edge would outrank the whole gene -- then by
+ * end - begin descending, then by input index ascending; a candidate is kept unless an already kept one of its group
+ * overlaps it by more than half the shorter of the two (2 ov > min(len_a, len_b), in 64 bits).  keep_out[j] = 1 / 0,
+ * *nkept_out (may be NULL) the number kept.  One sort, then comparisons inside groups against kept members only.
+ * DCP_EINVAL, nothing written: a null pointer with n > 0, a NaN in odds, end <= begin. */
+int dcp_domains_merge(uint32_t const *src, uint8_t const *minus, uint32_t const *profile, uint64_t const *begin,
+                      uint64_t const *end, double const *odds, unsigned n, uint8_t *keep_out, unsigned *nkept_out);
+
 /* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */

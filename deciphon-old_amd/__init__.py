@@ -88,6 +88,9 @@ ABI_SYMBOLS = [
     # domains: hit paths split at B .. E on the device, located on their sources, merged
     "dcp_gpu_path_domains", "dcp_gpu_path_domains64", "dcp_gpu_path_domains_kernel_ms", "dcp_domains_locate",
     "dcp_gpu_domains_locate", "dcp_domains_merge",
+    # rescoring: located domains joined into regions, regions cut out of the resident batch, a pair list scored
+    "dcp_domains_regions", "dcp_domains_locate_regions", "dcp_gpu_seqs_cut_regions", "dcp_gpu_seqs_regions",
+    "dcp_gpu_seqs_region_map", "dcp_gpu_scan_pairs",
 ]
 
 
@@ -258,6 +261,12 @@ def _load(path=None, hooks=False):
         "dcp_domains_locate": (I, [P, P, U, P, U, U, P, P, P, P, P, P]),
         "dcp_gpu_domains_locate": (I, [P, P, P, U, P, P, P, P]),
         "dcp_domains_merge": (I, [P, P, P, P, P, P, U, P, C.POINTER(U)]),
+        "dcp_domains_regions": (I, [P, P, P, P, P, U, P, U, C.c_uint64, C.c_uint32, P, P, P, P, P, P, P, U, C.POINTER(U)]),
+        "dcp_domains_locate_regions": (I, [P, P, U, P, U, P, P, P, P, P, P, P]),
+        "dcp_gpu_seqs_cut_regions": (I, [P, P, P, P, P, U]),
+        "dcp_gpu_seqs_regions": (U, [P]),
+        "dcp_gpu_seqs_region_map": (I, [P, P, P, P, U]),
+        "dcp_gpu_scan_pairs": (I, [P, C.POINTER(ScanParams), P, P, U]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -725,6 +734,63 @@ def merge_domains(src, minus, profile, begin, end, odds):
     return keep.astype(bool)
 
 
+# one region of domain_regions: what Scanner.cut_regions cuts and Scanner.scan_pairs scores against `profile`
+REGION_DTYPE = np.dtype([("src", np.uint32), ("minus", np.uint8), ("profile", np.uint32), ("begin", np.uint32),
+                         ("len", np.uint32), ("nparts", np.uint32)])
+
+
+def domain_regions(src, minus, profile, begin, end, src_len, max_gap=0, flank=0):
+    """Located domains (locate_domains' output, BEFORE any merge) joined into the regions to score again
+    (dcp_domains_regions): (reg_of uint32 [n], regions REGION_DTYPE).  Within each (src, minus, profile) group a domain
+    joins the open cluster while it begins at most max_gap behind the cluster's largest end; a cluster [lo, hi) gives
+    the region [lo - flank, hi + flank) clipped to its source.  Regions come ordered by (src, minus, profile, begin);
+    reg_of[j] is domain j's region, nparts the domains of a region."""
+    src, profile = np.ascontiguousarray(src, np.uint32), np.ascontiguousarray(profile, np.uint32)
+    minus = np.ascontiguousarray(minus, np.uint8)
+    begin, end = np.ascontiguousarray(begin, np.uint64), np.ascontiguousarray(end, np.uint64)
+    lens = np.ascontiguousarray(src_len, np.uint32)
+    n = len(src)
+    if not all(len(a) == n for a in (minus, profile, begin, end)):
+        raise DcpError(RC_EINVAL, "arrays of one length")
+    if not (0 <= max_gap < 2 ** 64 and 0 <= flank < 2 ** 32):
+        raise DcpError(RC_EINVAL, f"max_gap {max_gap} / flank {flank} out of range")
+    reg_of, nreg = np.zeros(n, np.uint32), C.c_uint(0)
+    cap = 0
+    for _ in range(2):  # count, then fill
+        cols = [np.zeros(cap, t) for t in (np.uint32, np.uint8, np.uint32, np.uint32, np.uint32, np.uint32)]
+        rc = lib.dcp_domains_regions(src.ctypes.data, minus.ctypes.data, profile.ctypes.data, begin.ctypes.data,
+                                     end.ctypes.data, n, lens.ctypes.data, len(lens), int(max_gap), int(flank),
+                                     reg_of.ctypes.data, *[a.ctypes.data if cap else None for a in cols], cap, C.byref(nreg))
+        if rc != RC_ENOMEM:
+            break
+        cap = nreg.value
+    if rc:
+        raise DcpError(rc, "an empty interval, a domain outside its source, or a source that is not in src_len")
+    regions = np.zeros(nreg.value, REGION_DTYPE)
+    for name, a in zip(("src", "minus", "profile", "begin", "len", "nparts"), cols):
+        regions[name] = a[:nreg.value]
+    return reg_of, regions
+
+
+def locate_domains_regions(res_idx, domains, res_len, reg_src, reg_begin, reg_minus):
+    """locate_domains for a batch of regions (dcp_domains_locate_regions): resident r is the res_len[r] bases from
+    reg_begin[r] of source reg_src[r], reverse-complemented where reg_minus[r]."""
+    res = np.ascontiguousarray(res_idx, np.uint32)
+    dom = np.ascontiguousarray(domains, DOMAIN_DTYPE)
+    lens = np.ascontiguousarray(res_len, np.uint32)
+    rs, rb = np.ascontiguousarray(reg_src, np.uint32), np.ascontiguousarray(reg_begin, np.uint32)
+    rm = np.ascontiguousarray(reg_minus, np.uint8)
+    if len(res) != len(dom) or not len(lens) == len(rs) == len(rb) == len(rm):
+        raise DcpError(RC_EINVAL, "one resident index per domain, one map entry per region")
+    src, begin, end, minus = _locate_outputs(len(dom))
+    rc = lib.dcp_domains_locate_regions(res.ctypes.data, dom.ctypes.data, len(dom), lens.ctypes.data, len(lens),
+                                        rs.ctypes.data, rb.ctypes.data, rm.ctypes.data, src.ctypes.data,
+                                        begin.ctypes.data, end.ctypes.data, minus.ctypes.data)
+    if rc:
+        raise DcpError(rc, "a domain lies outside its region")
+    return src, begin, end, minus
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -861,6 +927,36 @@ class Scanner:
         self._check(self._lib.dcp_gpu_seqs_window_map(self._c, src.ctypes.data, off.ctypes.data, n))
         return src, off
 
+    def cut_regions(self, src, begin, length, minus):
+        """Regions (dcp_gpu_seqs_cut_regions): the resident batch is replaced by the stretches [begin[i], begin[i] +
+        length[i]) of its sequences src[i], reverse-complemented where minus[i], written on the device.  Regions may
+        overlap, repeat and come in any order.  Scans, hits and traces then carry region indices; region_map() names
+        each region's source, first base and strand, and locate_domains() maps through it.  Neither add_reverse_strand
+        nor cut_windows may follow.  Until the next upload_seqs."""
+        cols = [np.atleast_1d(np.asarray(a)) for a in (src, begin, length)]
+        if any(a.size and (a.min() < 0 or a.max() >= 2 ** 32) for a in cols):
+            raise DcpError(RC_EINVAL, "a region's source, first base or length does not fit 32 bits")
+        src, begin, length = (np.ascontiguousarray(a, np.uint32) for a in cols)
+        minus = np.ascontiguousarray(np.atleast_1d(np.asarray(minus)) != 0, np.uint8)
+        if not len(src) == len(begin) == len(length) == len(minus):
+            raise DcpError(RC_EINVAL, "arrays of one length")
+        self._check(self._lib.dcp_gpu_seqs_cut_regions(self._c, src.ctypes.data, begin.ctypes.data, length.ctypes.data,
+                                                       minus.ctypes.data, len(src)))
+        self._seq_lens = length.astype(np.int64)
+
+    @property
+    def regions(self):
+        """The number of regions while the resident batch is one of regions (cut_regions), else 0."""
+        return self._lib.dcp_gpu_seqs_regions(self._c)
+
+    def region_map(self):
+        """(src uint32, begin uint32, minus uint8), one entry per region: its source's index in the uploaded batch, its
+        first base there in plus-strand coordinates, its strand (dcp_gpu_seqs_region_map)."""
+        n = self.regions
+        src, begin, minus = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._check(self._lib.dcp_gpu_seqs_region_map(self._c, src.ctypes.data, begin.ctypes.data, minus.ctypes.data, n))
+        return src, begin, minus
+
     @property
     def strands(self):
         """0 (no batch resident), 1, or 2 after add_reverse_strand."""
@@ -913,6 +1009,21 @@ class Scanner:
             self._check(self._lib.dcp_gpu_scan(self._c, C.byref(prm)))
         else:
             self._check(self._lib.dcp_gpu_scan_range(self._c, C.byref(prm), q_range[0], q_range[1]))
+        if sync:
+            self.sync()
+
+    def scan_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False, lrt_threshold=10.0, sync=True):
+        """Score exactly the pairs (resident sequence seq_idx[i], resident profile profile_idx[i]) with the row-sweep
+        kernels over the list (dcp_gpu_scan_pairs), on a float or a double DB: hits() then holds the listed pairs that
+        pass the LRT filter, with the bits of a KERNEL_ROWSWEEP scan; lrt_threshold=-inf reports every pair whose scores
+        are finite.  A pair listed twice is reported twice.  No dense scores are kept: scores() fails afterwards."""
+        sq = np.ascontiguousarray(seq_idx, np.uint32)
+        pr = np.ascontiguousarray(profile_idx, np.uint32)
+        if sq.ndim != 1 or sq.shape != pr.shape:
+            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        prm = ScanParams(int(multi_hits), int(hmmer3_compat), float(lrt_threshold), 0, KERNEL_AUTO)
+        self._check(self._lib.dcp_gpu_set_lrt_threshold64(self._c, float(lrt_threshold)))
+        self._check(self._lib.dcp_gpu_scan_pairs(self._c, C.byref(prm), sq.ctypes.data, pr.ctypes.data, len(sq)))
         if sync:
             self.sync()
 

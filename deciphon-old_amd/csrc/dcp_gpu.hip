@@ -236,10 +236,15 @@ struct dcp_gpu_ctx
     // (source index in the uploaded batch, offset); after dcp_gpu_seqs_add_revcomp still the forward half's entries
     unsigned win_window = 0, win_step = 0;
     std::vector<uint32_t> win_src, win_off;
-    void drop_windows()
+    // dcp_gpu_seqs_cut_regions: the map of the resident regions, region -> (source index in the uploaded batch, first
+    // base there, strand); empty unless the batch is one of regions
+    std::vector<uint32_t> reg_src, reg_begin;
+    std::vector<uint8_t> reg_minus;
+    void drop_windows() // a batch as uploaded: neither windows nor regions
     {
         win_window = win_step = 0;
         win_src.clear(), win_off.clear();
+        reg_src.clear(), reg_begin.clear(), reg_minus.clear();
     }
     DevBuf<uint32_t> d_seq_words, d_seq_woff, d_seq_len;
     DevBuf<float> d_xtrans;
@@ -254,6 +259,13 @@ struct dcp_gpu_ctx
     unsigned last_launches = 0;
     bool scanned = false;
     unsigned last_q0 = 0, last_q1 = 0;
+    // dcp_gpu_scan_pairs: the float DB's lists, one per size class back to back, and their lengths; what the last scan
+    // scored if it was one of a pair list (the accounting of a scan is that of a range x the whole DB)
+    DevBuf<dcp_pair> d_pair_list;
+    DevBuf<unsigned> d_pair_n; // [DCP_MAX_CLASSES]
+    bool last_pair_scan = false;
+    uint64_t pair_cells = 0, pair_bytes = 0;
+    uint64_t pair_class_cells[DCP_MAX_CLASSES] = {0}, pair_class_bytes[DCP_MAX_CLASSES] = {0};
     // one HIP event after each size-class launch of the last scan
     static constexpr int kMaxLaunches = 2 * kNumClasses + 1; // a segmented class is two launches
     hipEvent_t ev_class[kMaxLaunches] = {nullptr};
@@ -312,8 +324,11 @@ struct dcp_gpu_ctx
         DevBuf<unsigned> d_task, d_redo_n;
         DevBuf<dcp_f64_pair> d_redo;
         bool redo_pending = false; // the last scan's redo counters have not been checked yet
+        DevBuf<dcp_f64_pair> d_pair_list; // dcp_gpu_scan_pairs: one list per launch group back to back, their lengths
+        DevBuf<unsigned> d_pair_n;        // [4]
         void release()
         {
+            d_pair_list.release(), d_pair_n.release();
             profs.clear();
             d_profs.release(), d_tab.release(), d_trans.release(), d_xe.release();
             d_xt.release(), d_col.release(), res.release();
@@ -1660,6 +1675,8 @@ int dcp_gpu_seqs_add_revcomp(dcp_gpu_ctx *c)
     if (!c) return DCP_EINVAL;
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: upload a batch before adding its reverse strand");
     if (c->strands != 1) return c->fail(DCP_EINVAL, "the resident batch already holds both strands");
+    if (!c->reg_src.empty())
+        return c->fail(DCP_EINVAL, "the resident batch is one of regions: a region carries its own strand (dcp_gpu_seqs_cut_regions)");
     if (c->xt_explicit || !c->xt64.empty())
         return c->fail(DCP_EINVAL, "explicit special transitions are in force: they are per sequence -- set them after "
                                    "dcp_gpu_seqs_add_revcomp, for %llu rows", 2ull * c->nseqs);
@@ -1732,6 +1749,8 @@ int dcp_gpu_seqs_cut_windows(dcp_gpu_ctx *c, unsigned window, unsigned step)
     if (c->strands != 1)
         return c->fail(DCP_EINVAL, "the resident batch already holds both strands: cut the windows first, then add the reverse strand");
     if (c->win_window) return c->fail(DCP_EINVAL, "the resident batch is already cut into windows (window %u, step %u)", c->win_window, c->win_step);
+    if (!c->reg_src.empty())
+        return c->fail(DCP_EINVAL, "the resident batch is one of regions (dcp_gpu_seqs_cut_regions): windows are cut from an uploaded batch");
     if (c->xt_explicit || !c->xt64.empty())
         return c->fail(DCP_EINVAL, "explicit special transitions are in force: they are per sequence -- set them after "
                                    "dcp_gpu_seqs_cut_windows, one row per window");
@@ -1829,6 +1848,114 @@ int dcp_gpu_seqs_window_map(dcp_gpu_ctx *c, uint32_t *src, uint32_t *off, unsign
     if (cap < W || !src || !off) return c->fail(DCP_ENOMEM, "the batch has %zu windows: the buffers hold %u", W, cap);
     std::memcpy(src, c->win_src.data(), W * sizeof(uint32_t));
     std::memcpy(off, c->win_off.data(), W * sizeof(uint32_t));
+    return DCP_OK;
+}
+
+// Regions: the resident batch is replaced by n stretches of its sequences, each on the strand the list names, written
+// on the device from the resident words (dcp_seqs.hip).  The host holds the list, so the new index is computed here
+// and uploaded with the map.  Dependent state is treated as dcp_gpu_seqs_cut_windows treats it.
+int dcp_gpu_seqs_cut_regions(dcp_gpu_ctx *c, uint32_t const *src, uint32_t const *begin, uint32_t const *len,
+                             uint8_t const *minus, unsigned n)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: upload a batch before cutting regions out of it");
+    if (c->win_window) return c->fail(DCP_EINVAL, "the resident batch is cut into windows (window %u, step %u): regions are cut from an uploaded batch", c->win_window, c->win_step);
+    if (c->strands != 1) return c->fail(DCP_EINVAL, "the resident batch holds both strands: regions are cut from an uploaded batch, each on the strand its list names");
+    if (!c->reg_src.empty()) return c->fail(DCP_EINVAL, "the resident batch is already one of regions (%zu of them)", c->reg_src.size());
+    if (c->xt_explicit || !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "explicit special transitions are in force: they are per sequence -- set them after "
+                                   "dcp_gpu_seqs_cut_regions, one row per region");
+    if (n == 0 || !src || !begin || !len || !minus) return c->fail(DCP_EINVAL, "an empty list of regions, or a null pointer");
+    uint64_t nwords64 = 0, total = 0;
+    for (unsigned i = 0; i < n; ++i)
+    {
+        if (src[i] >= c->nseqs || len[i] == 0 || (uint64_t)begin[i] + len[i] > c->seq_len[src[i]])
+            return c->fail(DCP_EINVAL, "region %u (source %u, bases %u + %u) is empty or lies outside its source (%u sequences resident, %u bases)",
+                           i, src[i], begin[i], len[i], c->nseqs, src[i] < c->nseqs ? c->seq_len[src[i]] : 0u);
+        nwords64 += len[i] / 16u + 3u; // n < 2^32 terms below 2^28 + 3: no wrap
+        total += len[i];
+    }
+    if (nwords64 > 0xffffffffull)
+        return c->fail(DCP_EINVAL, "sequence batch too large for these regions (%u regions, %llu words)", n, (unsigned long long)nwords64);
+    uint32_t const nwords = (uint32_t)nwords64;
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a scan of the uncut batch may still be running on the stream: it reads the arrays that are replaced below
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    void_last_scan(c);
+    c->qorder_q0 = c->qorder_q1 = ~0u; // the length order and the word planes belong to the batch that was resident
+    // the new index and the map, in one array: woff, len, source, first base, strand
+    std::vector<uint32_t> plan(5u * (size_t)n);
+    {
+        uint32_t at = 0;
+        for (unsigned i = 0; i < n; ++i)
+        {
+            plan[i] = at, plan[(size_t)n + i] = len[i], plan[2u * (size_t)n + i] = src[i];
+            plan[3u * (size_t)n + i] = begin[i], plan[4u * (size_t)n + i] = minus[i] ? 1u : 0u;
+            at += len[i] / 16u + 3u;
+        }
+    }
+    DevBuf<uint32_t> words, woff, dlen, dmap;
+    DevBuf<float> xt;
+    // as in an upload: a failed allocation must not leave the old batch's size paired with new buffers
+    auto drop = [&]() {
+        c->nseqs = 0, c->strands = 0, c->total_len = 0;
+        c->seq_len.clear();
+        c->drop_windows();
+        c->xt_multi = c->xt_h3 = -1;
+    };
+#define SEQS_TRY(call)                                                                                                  \
+    do                                                                                                                  \
+    {                                                                                                                   \
+        hipError_t e_ = (call);                                                                                         \
+        if (e_ != hipSuccess)                                                                                           \
+        {                                                                                                               \
+            drop();                                                                                                     \
+            return c->fail(e_ == hipErrorOutOfMemory ? DCP_ENOMEM : DCP_EFAIL, "%s: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                                               \
+    } while (0)
+    SEQS_TRY(words.alloc(nwords));
+    SEQS_TRY(woff.alloc(n));
+    SEQS_TRY(dlen.alloc(n));
+    SEQS_TRY(dmap.alloc(3u * (size_t)n));
+    SEQS_TRY(xt.alloc((size_t)n * DCP_XSTRIDE));
+    SEQS_TRY(hipMemcpyAsync(woff.p, plan.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SEQS_TRY(hipMemcpyAsync(dlen.p, plan.data() + n, n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SEQS_TRY(hipMemcpyAsync(dmap.p, plan.data() + 2u * (size_t)n, 3u * (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    dcp_region_args a{};
+    a.src_words = c->d_seq_words.p, a.src_woff = c->d_seq_woff.p;
+    a.words = words.p, a.woff = woff.p, a.len = dlen.p;
+    a.rsrc = dmap.p, a.rbegin = dmap.p + n, a.rminus = dmap.p + 2u * (size_t)n;
+    a.n = n, a.nwords = nwords;
+    SEQS_TRY((hipError_t)dcp_launch_regions(&a, c->stream));
+    SEQS_TRY(hipStreamSynchronize(c->stream)); // `plan`, the map and the old arrays are freed below
+#undef SEQS_TRY
+    std::swap(c->d_seq_words.p, words.p), std::swap(c->d_seq_words.n, words.n);
+    std::swap(c->d_seq_woff.p, woff.p), std::swap(c->d_seq_woff.n, woff.n);
+    std::swap(c->d_seq_len.p, dlen.p), std::swap(c->d_seq_len.n, dlen.n);
+    std::swap(c->d_xtrans.p, xt.p), std::swap(c->d_xtrans.n, xt.n);
+    c->seq_len.assign(len, len + n);
+    c->reg_src.assign(src, src + n), c->reg_begin.assign(begin, begin + n);
+    c->reg_minus.resize(n);
+    for (unsigned i = 0; i < n; ++i)
+        c->reg_minus[i] = minus[i] ? 1u : 0u;
+    c->nseqs = n;
+    c->total_len = total;
+    c->xt_multi = c->xt_h3 = -1; // the regions' rows are derived with the next scan's flags
+    c->xt64.clear();
+    return DCP_OK;
+}
+
+unsigned dcp_gpu_seqs_regions(dcp_gpu_ctx const *c) { return c && c->nseqs ? (unsigned)c->reg_src.size() : 0u; }
+
+int dcp_gpu_seqs_region_map(dcp_gpu_ctx *c, uint32_t *src, uint32_t *begin, uint8_t *minus, unsigned cap)
+{
+    if (!c) return DCP_EINVAL;
+    if (!c->nseqs || c->reg_src.empty()) return c->fail(DCP_EINVAL, "the resident batch is not one of regions");
+    size_t const n = c->reg_src.size();
+    if (cap < n || !src || !begin || !minus) return c->fail(DCP_ENOMEM, "the batch has %zu regions: the buffers hold %u", n, cap);
+    std::memcpy(src, c->reg_src.data(), n * sizeof(uint32_t));
+    std::memcpy(begin, c->reg_begin.data(), n * sizeof(uint32_t));
+    std::memcpy(minus, c->reg_minus.data(), n);
     return DCP_OK;
 }
 
@@ -2845,6 +2972,7 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
     if (q_begin >= q_end || q_end > c->nseqs) return c->fail(DCP_EINVAL, "bad sequence range");
     HIP_TRY(c, hipSetDevice(c->device));
+    c->last_pair_scan = false;
     if (c->precision == 64) return scan64(c, prm, q_begin, q_end);
     c->last_f64 = false;
     // One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST
@@ -2888,6 +3016,198 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     c->n_launched = 0;
     if (kernel == 2) return launch_qlane_scan(c, prm, a, ql_nt, ql_blocks_per_cu, two_stage, w3 && !two_stage);
     return launch_rowsweep_scan(c, a, q_begin, q_end);
+}
+
+// dcp_gpu_scan_pairs on a double DB: the lists by launch group, viterbi64_kernel<R, false, PAIRS> over each -- what
+// scan64 launches behind the query-lane kernel over its redo lists.
+static int scan_pairs64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32_t const *seq_idx, uint32_t const *profile_idx,
+                        unsigned npairs)
+{
+    if (c->xt_explicit)
+        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    auto &F = c->f64;
+    if (F.redo_pending)
+        if (int rc = finish_scan(c)) return rc;
+    c->scanned = false;
+    // entry of F.profs (group-sorted) of each caller's profile index
+    std::vector<uint32_t> slot(c->nprof);
+    for (unsigned i = 0; i < (unsigned)F.profs.size(); ++i)
+        slot[F.profs[i].pidx] = i;
+    unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0};
+    for (unsigned i = 0; i < npairs; ++i)
+        ++count[range_of(F.group_first, 4, slot[profile_idx[i]])];
+    for (int g = 0; g < 4; ++g)
+        first[g + 1] = first[g] + count[g];
+    std::vector<dcp_f64_pair> pairs(npairs);
+    uint32_t seg_lmax = 0;
+    uint64_t cells = 0, bytes = 0;
+    {
+        unsigned at[4] = {first[0], first[1], first[2], first[3]};
+        for (unsigned i = 0; i < npairs; ++i)
+        {
+            uint32_t const s = slot[profile_idx[i]];
+            int const g = range_of(F.group_first, 4, s);
+            pairs[at[g]++] = dcp_f64_pair{seq_idx[i], s};
+            uint64_t const M = F.profs[s].core_size, L = c->seq_len[seq_idx[i]];
+            if (g == 3) seg_lmax = std::max(seg_lmax, (uint32_t)L);
+            cells += M * L, bytes += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
+        }
+    }
+    // the kernel takes a pair's special transitions from its query's row: one row per resident sequence, as a scan's
+    std::vector<uint32_t> seqs(c->nseqs);
+    std::iota(seqs.begin(), seqs.end(), 0u);
+    std::vector<double> xt;
+    if (int rc = fill_xtrans(c, seqs, prm->multi_hits, prm->hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
+    if (F.d_xt.n < xt.size()) HIP_TRY(c, F.d_xt.alloc(xt.size()));
+    HIP_TRY(c, F.res.ensure(npairs, false));
+    uint64_t col_stride = 0, seg_waves = 0;
+    if (int rc = f64_seg_columns(c, seg_lmax, count[3], &col_stride, &seg_waves)) return rc;
+    if (F.d_pair_list.n < npairs) HIP_TRY(c, F.d_pair_list.alloc(npairs));
+    if (!F.d_pair_n.p) HIP_TRY(c, F.d_pair_n.alloc(4));
+    HIP_TRY(c, hipMemcpyAsync(F.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (npairs) HIP_TRY(c, hipMemcpyAsync(F.d_pair_list.p, pairs.data(), (size_t)npairs * sizeof(dcp_f64_pair), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(F.d_pair_n.p, count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists and xt leave scope (and an earlier scan has read its own)
+
+    dcp_f64_pairs_args pa{};
+    pa.profs = F.d_profs.p;
+    pa.nprof = c->nprof;
+    pa.nprof_total = c->nprof;
+    pa.tab = F.d_tab.p, pa.trans = F.d_trans.p, pa.xe = F.d_xe.p;
+    pa.seq_words = c->d_seq_words.p, pa.seq_woff = c->d_seq_woff.p, pa.seq_len = c->d_seq_len.p;
+    pa.xtrans = F.d_xt.p;
+    pa.nq = c->nseqs, pa.q_base = 0;
+    pa.out_null = pa.out_alt = nullptr;
+    pa.hits = F.res.hits(), pa.nhits = F.res.nhits(), pa.hit_cap = F.res.cap();
+    pa.lrt_threshold = is_nan(c->lrt_threshold64) ? (double)prm->lrt_threshold : c->lrt_threshold64; // NaN: not set
+    HIP_TRY(c, hipMemsetAsync(pa.nhits, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    unsigned launches = 0;
+    for (int g = 0; g < 4; ++g)
+    {
+        if (count[g] == 0) continue;
+        pa.pairs = F.d_pair_list.p + first[g];
+        pa.npairs_dev = F.d_pair_n.p + g;
+        pa.pair_cap = count[g];
+        // one wavefront per pair; the segmented group strides over its pairs with one boundary column per wavefront
+        uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(count[g], 1ull << 24);
+        pa.col = g == 3 ? F.d_col.p : nullptr;
+        pa.col_stride = g == 3 ? col_stride : 0;
+        if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, (unsigned)waves, c->stream))
+            return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
+        HIP_TRY(c, hipGetLastError());
+        ++launches;
+    }
+    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->last_q0 = 0, c->last_q1 = c->nseqs;
+    c->last_launches = launches;
+    c->n_launched = 0; // no per-launch records for the f64 kernels
+    c->last_kernel = c->last_kernel_variant = 1;
+    c->last_prm = *prm;
+    c->last_redo_pairs = 0;
+    F.redo_pending = false;
+    c->last_overlapped = false;
+    c->res.have_scores = false;
+    c->last_f64 = true;
+    c->last_pair_scan = true;
+    c->pair_cells = cells, c->pair_bytes = bytes;
+    c->scanned = true;
+    return DCP_OK;
+}
+
+// Score a list of pairs: bucketed by size class on the host, then the row-sweep kernels in pair mode over each
+// non-empty class's list -- what the query-lane scans launch over their redo lists, with lists the host wrote.
+int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32_t const *seq_idx, uint32_t const *profile_idx,
+                       unsigned npairs)
+{
+    if (!c || !prm) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
+    if (prm->keep_scores) return c->fail(DCP_EINVAL, "a scan of a pair list keeps no dense score matrix: keep_scores must be 0");
+    if (prm->kernel != 0 && prm->kernel != 1)
+        return c->fail(DCP_EINVAL, "a pair list is scored by the row sweep (kernel 0 or 1), not %d", prm->kernel);
+    if (npairs && (!seq_idx || !profile_idx)) return c->fail(DCP_EINVAL, "a pair list without its indices");
+    for (unsigned i = 0; i < npairs; ++i)
+        if (seq_idx[i] >= c->nseqs || profile_idx[i] >= c->nprof)
+            return c->fail(DCP_EINVAL, "pair %u (sequence %u, profile %u) is outside the resident batch (%u sequences) / DB (%u profiles)",
+                           i, seq_idx[i], profile_idx[i], c->nseqs, c->nprof);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->precision == 64) return scan_pairs64(c, prm, seq_idx, profile_idx, npairs);
+    // one scan is outstanding per context: an earlier query-lane scan is completed first (dcp_gpu_scan_range)
+    if (c->redo_pending || c->ring_check_pending)
+        if (int rc = finish_scan(c)) return rc;
+    if (!c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
+    if (int rc = ensure_rowsweep_layout(c)) return rc;
+    HIP_TRY(c, c->res.ensure(npairs, false));
+    c->last_f64 = false;
+    c->scanned = false;
+    unsigned first[kNumClasses + 1] = {0}, count[DCP_MAX_CLASSES] = {0};
+    for (unsigned i = 0; i < npairs; ++i)
+        ++count[range_of(c->class_first, kNumClasses, c->slot_of_pidx[profile_idx[i]])];
+    for (int k = 0; k < kNumClasses; ++k)
+        first[k + 1] = first[k] + count[k];
+    std::vector<dcp_pair> pairs(npairs);
+    c->pair_cells = c->pair_bytes = 0;
+    {
+        unsigned at[kNumClasses];
+        for (int k = 0; k < kNumClasses; ++k)
+            at[k] = first[k], c->pair_class_cells[k] = c->pair_class_bytes[k] = 0;
+        for (unsigned i = 0; i < npairs; ++i)
+        {
+            uint32_t const slot = c->slot_of_pidx[profile_idx[i]];
+            int const k = range_of(c->class_first, kNumClasses, slot);
+            pairs[at[k]++] = dcp_pair{seq_idx[i], slot}; // {q, slot}: the scan's first sequence is resident 0
+            uint64_t const M = c->metas[slot].core_size, L = c->seq_len[seq_idx[i]];
+            c->pair_class_cells[k] += M * L;
+            c->pair_class_bytes[k] += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
+        }
+        for (int k = 0; k < kNumClasses; ++k)
+            c->pair_cells += c->pair_class_cells[k], c->pair_bytes += c->pair_class_bytes[k];
+    }
+    if (c->d_pair_list.n < npairs) HIP_TRY(c, c->d_pair_list.alloc(npairs));
+    if (!c->d_pair_n.p) HIP_TRY(c, c->d_pair_n.alloc(DCP_MAX_CLASSES));
+    if (npairs) HIP_TRY(c, hipMemcpyAsync(c->d_pair_list.p, pairs.data(), (size_t)npairs * sizeof(dcp_pair), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_pair_n.p, count, sizeof count, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists leave scope (and an earlier scan has read its own)
+
+    dcp_scan_args a = scan_args(c, prm, 0, c->nseqs); // no score matrix: res.have_scores is false
+    a.emis_match = c->d_emis_match.p;
+    a.first_prof = 0;
+    a.nprof = c->nprof;
+    c->last_q0 = 0, c->last_q1 = c->nseqs;
+    c->last_kernel = c->last_kernel_variant = 1;
+    c->last_launches = 0;
+    c->n_launched = 0;
+    c->redo_pending = false;
+    c->last_redo_pairs = 0;
+    c->last_overlapped = false;
+    c->last_prm = *prm;
+#ifdef DCP_TEST_HOOKS
+    for (int k = 0; k < kNumClasses; ++k)
+        c->rs_plan[k] = {};
+#endif
+    HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
+    for (int k = 0; k < kNumClasses; ++k)
+    {
+        if (count[k] == 0) continue;
+        a.pairs = c->d_pair_list.p + first[k];
+        a.npairs = c->d_pair_n.p + k;
+        a.pair_cap = count[k];
+        SizeClass const sc = kClasses[k];
+        uint64_t const tpb = dcp_rowsweep_tasks_per_block(sc.W);
+        uint64_t const g = std::min<uint64_t>((count[k] + tpb - 1u) / tpb, 8ull * c->num_cus);
+        if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)((g + 7u) / 8u * 8u), c->stream))
+            return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
+        if (int rc = record_launch(c, k, false, c->stream, false)) return rc;
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
+    c->last_pair_scan = true;
+    c->scanned = true;
+    return DCP_OK;
 }
 
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
@@ -3104,6 +3424,12 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_
     out->nprofiles = (unsigned)np;
     out->cells = out->algorithmic_bytes = 0;
     if (c->last_kernel == 2 || c->launched_redo[i]) return DCP_OK; // a redo launch: its pairs are counted in the launch before it
+    if (c->last_pair_scan) // dcp_gpu_scan_pairs: the class's listed pairs
+    {
+        out->cells = c->pair_class_cells[k];
+        out->algorithmic_bytes = c->pair_class_bytes[k];
+        return DCP_OK;
+    }
     uint64_t sumM = 0, len = 0;
     for (unsigned j = c->class_first[k]; j < c->class_first[k + 1]; ++j)
         sumM += c->metas[j].core_size;
@@ -3617,6 +3943,12 @@ int dcp_gpu_domains_locate(dcp_gpu_ctx *c, uint32_t const *res_idx, struct dcp_d
 {
     if (!c) return DCP_EINVAL;
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident: nothing to locate the domains on");
+    if (!c->reg_src.empty()) // a batch of regions: through the region map
+    {
+        int const rrc = dcp_domains_locate_regions(res_idx, dom, n, c->seq_len.data(), c->nseqs, c->reg_src.data(), c->reg_begin.data(),
+                                                   c->reg_minus.data(), src_out, begin_out, end_out, minus_out);
+        return rrc ? c->fail(rrc, "a domain lies outside the resident batch (%u regions), or a null pointer", c->nseqs) : DCP_OK;
+    }
     bool const cut = c->win_window != 0;
     int const rc = dcp_domains_locate(res_idx, dom, n, c->seq_len.data(), c->nseqs / c->strands, c->strands,
                                       cut ? c->win_src.data() : nullptr, cut ? c->win_off.data() : nullptr, src_out,
@@ -3638,6 +3970,7 @@ static void last_range(dcp_gpu_ctx const *c, uint64_t *sumM, uint64_t *len, uint
 uint64_t dcp_gpu_scan_cells(dcp_gpu_ctx const *c)
 {
     if (!c) return 0;
+    if (c->scanned && c->last_pair_scan) return c->pair_cells; // dcp_gpu_scan_pairs: the listed pairs
     uint64_t sumM, len, nq;
     last_range(c, &sumM, &len, &nq);
     return sumM * len;
@@ -3647,6 +3980,7 @@ uint64_t dcp_gpu_scan_algorithmic_bytes(dcp_gpu_ctx const *c)
 {
     // per pair 20*M*L + 32*(M+1) + L + 8
     if (!c) return 0;
+    if (c->scanned && c->last_pair_scan) return c->pair_bytes;
     uint64_t sumM, len, Q, P = c->core_sizes.size();
     last_range(c, &sumM, &len, &Q);
     return 20ull * sumM * len + 32ull * (sumM + P) * Q + len * P + 8ull * P * Q;

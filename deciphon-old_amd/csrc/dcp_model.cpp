@@ -1633,5 +1633,105 @@ int dcp_domains_merge(uint32_t const *src, uint8_t const *minus, uint32_t const 
     return DCP_OK;
 }
 
+// Located domains -> the regions to score again (dcp_gpu_seqs_cut_regions): inside each (src, minus, profile) group
+// the domains by (begin, end, index); one joins the open cluster while it begins at most max_gap behind the cluster's
+// largest end; a cluster [lo, hi) becomes the region [lo - flank, hi + flank) clipped to its source.
+int dcp_domains_regions(uint32_t const *src, uint8_t const *minus, uint32_t const *profile, uint64_t const *begin,
+                        uint64_t const *end, unsigned n, uint32_t const *src_len, unsigned nsrc, uint64_t max_gap,
+                        uint32_t flank, uint32_t *reg_of, uint32_t *reg_src, uint8_t *reg_minus, uint32_t *reg_profile,
+                        uint32_t *reg_begin, uint32_t *reg_len, uint32_t *reg_nparts, unsigned cap, unsigned *nregions)
+{
+    if (!nregions) return DCP_EINVAL;
+    if (n == 0)
+    {
+        *nregions = 0;
+        return DCP_OK;
+    }
+    if (!src || !minus || !profile || !begin || !end || !src_len || !reg_of) return DCP_EINVAL;
+    for (unsigned j = 0; j < n; ++j)
+        if (src[j] >= nsrc || end[j] <= begin[j] || end[j] > src_len[src[j]]) return DCP_EINVAL;
+    std::vector<unsigned> order(n);
+    for (unsigned j = 0; j < n; ++j)
+        order[j] = j;
+    std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) {
+        if (src[a] != src[b]) return src[a] < src[b];
+        if ((minus[a] != 0) != (minus[b] != 0)) return minus[a] == 0;
+        if (profile[a] != profile[b]) return profile[a] < profile[b];
+        if (begin[a] != begin[b]) return begin[a] < begin[b];
+        if (end[a] != end[b]) return end[a] < end[b];
+        return a < b;
+    });
+    // a domain opens a cluster if it is the first of its group or begins more than max_gap behind the cluster's end
+    // (begin - hi > max_gap: hi + max_gap itself could pass 64 bits)
+    auto opens = [&](unsigned o, uint64_t hi) {
+        unsigned const j = order[o], p = order[o - 1];
+        bool const same = src[j] == src[p] && (minus[j] != 0) == (minus[p] != 0) && profile[j] == profile[p];
+        return !same || (begin[j] > hi && begin[j] - hi > max_gap);
+    };
+    uint64_t count = 1, hi = end[order[0]];
+    for (unsigned o = 1; o < n; ++o)
+    {
+        if (opens(o, hi)) ++count, hi = end[order[o]];
+        else hi = std::max(hi, end[order[o]]);
+    }
+    if (count > cap)
+    {
+        *nregions = (unsigned)count; // <= n
+        return DCP_ENOMEM;
+    }
+    if (!reg_src || !reg_minus || !reg_profile || !reg_begin || !reg_len || !reg_nparts) return DCP_EINVAL;
+    *nregions = (unsigned)count;
+    unsigned r = 0;
+    uint64_t lo = 0;
+    auto close = [&](unsigned j) { // the open cluster [lo, hi) of j's group: every end is within the source's 32 bits
+        uint64_t const b = lo - std::min<uint64_t>(lo, flank), e = std::min<uint64_t>(hi + flank, src_len[src[j]]);
+        reg_src[r] = src[j], reg_minus[r] = minus[j] ? 1u : 0u, reg_profile[r] = profile[j];
+        reg_begin[r] = (uint32_t)b, reg_len[r] = (uint32_t)(e - b);
+    };
+    for (unsigned o = 0; o < n; ++o)
+    {
+        unsigned const j = order[o];
+        if (o == 0 || opens(o, hi))
+        {
+            if (o > 0) close(order[o - 1]), ++r;
+            lo = begin[j], hi = end[j];
+            reg_nparts[r] = 0;
+        }
+        else hi = std::max(hi, end[j]);
+        reg_of[j] = r;
+        ++reg_nparts[r];
+    }
+    close(order[n - 1]);
+    return DCP_OK;
+}
+
+// dcp_domains_locate for a batch of regions (dcp_gpu_seqs_cut_regions): resident r is the bases [reg_begin[r],
+// reg_begin[r] + res_len[r]) of source reg_src[r], reverse-complemented where reg_minus[r].
+int dcp_domains_locate_regions(uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n, uint32_t const *res_len,
+                               unsigned nres, uint32_t const *reg_src, uint32_t const *reg_begin, uint8_t const *reg_minus,
+                               uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out)
+{
+    if (n == 0) return DCP_OK;
+    if (!res_idx || !dom || !res_len || !reg_src || !reg_begin || !reg_minus || !src_out || !begin_out || !end_out || !minus_out)
+        return DCP_EINVAL;
+    for (unsigned j = 0; j < n; ++j)
+    {
+        if (res_idx[j] >= nres) return DCP_EINVAL;
+        if (dom[j].seq_begin > dom[j].seq_end || dom[j].seq_end > res_len[res_idx[j]]) return DCP_EINVAL;
+    }
+    for (unsigned j = 0; j < n; ++j)
+    {
+        uint32_t const r = res_idx[j], len = res_len[r];
+        bool const minus = reg_minus[r] != 0;
+        uint64_t const b = minus ? len - dom[j].seq_end : dom[j].seq_begin;
+        uint64_t const e = minus ? len - dom[j].seq_begin : dom[j].seq_end;
+        src_out[j] = reg_src[r];
+        begin_out[j] = (uint64_t)reg_begin[r] + b;
+        end_out[j] = (uint64_t)reg_begin[r] + e;
+        minus_out[j] = minus ? 1u : 0u;
+    }
+    return DCP_OK;
+}
+
 } // extern "C"
 

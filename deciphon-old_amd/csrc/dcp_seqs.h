@@ -1,4 +1,4 @@
-// dcp_seqs.h -- kernels on the resident sequence batch itself (dcp_seqs.hip): the reverse strand, windows.
+// dcp_seqs.h -- kernels on the resident sequence batch itself (dcp_seqs.hip): the reverse strand, windows, regions.
 #ifndef DCP_SEQS_H
 #define DCP_SEQS_H
 
@@ -25,6 +25,21 @@ struct dcp_window_args
 };
 // Two launches on `stream` (index, then words); HIP's error code.
 int dcp_launch_windows(struct dcp_window_args const *, void *stream);
+// Regions: the batch of n regions that replaces a resident batch (dcp_gpu_seqs_cut_regions).  The host holds the list,
+// so it computes the new index too; device pointers throughout.  Region i is the len[i] bases from rbegin[i] of
+// source rsrc[i], reverse-complemented where rminus[i] != 0; the caller has checked rsrc[i] < the resident sequences,
+// len[i] >= 1 and rbegin[i] + len[i] <= the source's length.
+struct dcp_region_args
+{
+    uint32_t const *src_words, *src_woff; // the resident batch: its words, each source's first word
+    uint32_t *words;                      // [nwords]: the new batch's words (no overlap with src_words)
+    uint32_t const *woff, *len;           // [n]: the new batch's index, woff[0] = 0, woff[i + 1] = woff[i] + len[i] / 16 + 3
+    uint32_t const *rsrc, *rbegin, *rminus; // [n]: the map
+    unsigned n;
+    uint32_t nwords;
+};
+// One launch on `stream`; HIP's error code.
+int dcp_launch_regions(struct dcp_region_args const *, void *stream);
 #ifdef DCP_TEST_HOOKS
 // NOT in the shipped library (libdcp_hip_testhooks.so only; declared here, not in include/dcp_gpu.h).  The raw
 // L / 16 + 3 words of resident sequence q as the device holds them: *nwords receives their number, out the words if

@@ -1,5 +1,6 @@
 // dcp_seqs.hip -- the reverse strand of the resident batch (dcp_gpu_seqs_add_revcomp) with its host restatement, and
-// the cut of the resident batch into overlapping windows (dcp_gpu_seqs_cut_windows, further down).
+// the cut of the resident batch into overlapping windows (dcp_gpu_seqs_cut_windows, further down) and into arbitrary
+// regions of either strand (dcp_gpu_seqs_cut_regions, behind the windows).
 //
 // A resident sequence of L bases is L / 16 + 3 words, base i in bits 2 (i & 15) of word i >> 4 (A = 0, C = 1, G = 2,
 // T = 3), every bit behind base L - 1 zero.  Its reverse complement has base i = 3 - base(L - 1 - i): output word j
@@ -141,7 +142,68 @@ __global__ __launch_bounds__(kBlock) void window_words_kernel(uint32_t const *__
     words_out[g] = out;
 }
 
+// Regions (dcp_gpu_seqs_cut_regions): one lane per word of the new batch, as the two kernels above.  A plus region is a
+// window at an arbitrary offset: window_words_kernel's arithmetic.  Word j of a minus region holds the source's bases
+// [e - 16, e), e = begin + len - 16 j, in falling order and complemented: revcomp_words_kernel's arithmetic with the
+// source's word index -- e >> 4 <= L / 16 stays inside the source's words, the word below is read only if e >= 16 --
+// but unlike the whole sequence's reverse complement the bases BELOW `begin` are real bases of the source, not zeros:
+// the min(16, len - 16 j) groups of the word are masked after the complement, whatever lies below.
+__global__ __launch_bounds__(kBlock) void region_words_kernel(uint32_t const *__restrict__ words_in,
+                                                              uint32_t const *__restrict__ src_woff,
+                                                              uint32_t *__restrict__ words_out,
+                                                              uint32_t const *__restrict__ woff,
+                                                              uint32_t const *__restrict__ len,
+                                                              uint32_t const *__restrict__ rsrc,
+                                                              uint32_t const *__restrict__ rbegin,
+                                                              uint32_t const *__restrict__ rminus, unsigned n,
+                                                              uint32_t nwords)
+{
+    uint64_t const g64 = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (g64 >= nwords) return;
+    uint32_t const g = (uint32_t)g64;
+    unsigned lo = 0, hi = n; // the last region with woff <= g (woff[0] = 0)
+    while (hi - lo > 1u)
+    {
+        unsigned const mid = lo + (hi - lo) / 2u;
+        if (woff[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    uint32_t const rl = len[lo];
+    uint32_t const j = g - woff[lo]; // < rl / 16 + 3
+    uint32_t out = 0u;               // pad words stay zero
+    if ((uint64_t)j * 16u < rl)
+    {
+        uint32_t const *w = words_in + src_woff[rsrc[lo]];
+        uint32_t const cnt = rl - j * 16u < 16u ? rl - j * 16u : 16u; // bases of this output word
+        uint32_t const mask = cnt == 16u ? 0xffffffffu : (1u << (2u * cnt)) - 1u;
+        if (rminus[lo])
+        {
+            uint32_t const e = rbegin[lo] + rl - j * 16u; // 1 <= e <= L
+            uint32_t const we = e >> 4, r = e & 15u;
+            uint64_t const v = ((uint64_t)w[we] << 32) | (we ? w[we - 1u] : 0u);
+            uint32_t const x = (uint32_t)(v >> (2u * r)); // group k = source base e - 16 + k
+            out = ~reverse_groups(x) & mask;
+        }
+        else
+        {
+            uint32_t const b0 = rbegin[lo] + j * 16u; // < begin + len <= L: words b0 >> 4 and the next one exist
+            uint64_t const v = ((uint64_t)w[(b0 >> 4) + 1u] << 32) | w[b0 >> 4];
+            out = (uint32_t)(v >> (2u * (b0 & 15u))) & mask;
+        }
+    }
+    words_out[g] = out;
+}
+
 } // namespace
+
+extern "C" int dcp_launch_regions(dcp_region_args const *a, void *stream)
+{
+    if (!a || a->n == 0 || a->nwords == 0) return (int)hipErrorInvalidValue;
+    unsigned const wblocks = (unsigned)(((uint64_t)a->nwords + kBlock - 1u) / kBlock);
+    region_words_kernel<<<wblocks, kBlock, 0, (hipStream_t)stream>>>(a->src_words, a->src_woff, a->words, a->woff, a->len,
+                                                                     a->rsrc, a->rbegin, a->rminus, a->n, a->nwords);
+    return (int)hipGetLastError();
+}
 
 extern "C" int dcp_launch_windows(dcp_window_args const *a, void *stream)
 {

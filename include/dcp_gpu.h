@@ -371,6 +371,29 @@ int dcp_gpu_seqs_windows(dcp_gpu_ctx const *, unsigned *window, unsigned *step);
  * dcp_gpu_seqs_add_revcomp the map still has W entries (resident W + i is window i's reverse complement).  DCP_ENOMEM if
  * cap < W, DCP_EINVAL if the batch is not cut.  dcp_gpu_seqs_fetch serves a window's bases. */
 int dcp_gpu_seqs_window_map(dcp_gpu_ctx *, uint32_t *src, uint32_t *off, unsigned cap);
+/* Regions.  What windows report of a gene longer than their overlap is pieces: the finish is to cut the
+ * stretch the pieces cover out of the source and score it again.  The resident batch of uploaded sequences is REPLACED
+ * by n regions: resident i is the bases [begin[i], begin[i] + len[i]) of resident source src[i], and their reverse
+ * complement where minus[i] != 0 -- base k = 3 - base(begin + len - 1 - k) -- written on the device from the resident
+ * 2-bit words (csrc/dcp_seqs.hip, region_words_kernel); the sources are no longer resident.  Regions may overlap, repeat
+ * and come in any order.  Everything downstream sees a batch of n sequences in the resident layout (len / 16 + 3 words
+ * each, every bit behind the last base zero); dcp_gpu_seqs_strands stays 1, a region carries its own strand.
+ * Dependent state is treated as dcp_gpu_seqs_cut_windows treats it (the last scan is void).  A region is scored as the
+ * sequence it now is.  DCP_EINVAL, with a message and the batch untouched, all checked before any allocation: no
+ * batch resident; the batch is cut into windows, holds both strands or is already regions; explicit special
+ * transitions in force (set them after the cut, one row per region); n == 0 or a null pointer; src >= the resident
+ * sequences, len == 0 or begin + len > the source's length (in 64 bits), naming the first bad region; the regions'
+ * words would pass 2^32 - 1.  A failed allocation leaves the context without a batch.  After the cut
+ * dcp_gpu_seqs_add_revcomp and dcp_gpu_seqs_cut_windows are DCP_EINVAL; the next sequence upload returns the context
+ * to normal.  Works on float and double DBs alike, and with no DB resident. */
+int dcp_gpu_seqs_cut_regions(dcp_gpu_ctx *, uint32_t const *src, uint32_t const *begin, uint32_t const *len,
+                             uint8_t const *minus, unsigned n);
+/* The number of regions while the resident batch is one of regions, else 0. */
+unsigned dcp_gpu_seqs_regions(dcp_gpu_ctx const *);
+/* For region i < n: its source's index in the uploaded batch, its first base there (plus-strand coordinates) and its
+ * strand (0 / 1); its length is the resident sequence's.  DCP_ENOMEM if cap < n, DCP_EINVAL if the batch is not one of
+ * regions.  dcp_gpu_seqs_fetch serves a region's bases. */
+int dcp_gpu_seqs_region_map(dcp_gpu_ctx *, uint32_t *src, uint32_t *begin, uint8_t *minus, unsigned cap);
 /* Explicit special transitions for the resident sequences: xt [nseqs][13] in dcp_xtrans order.
  * By default a scan derives them from each sequence's length and the scan's flags (what
  * protein_profile_setup does per pair); imm_dp_viterbi on a profile whose transitions were set some
@@ -435,6 +458,23 @@ int dcp_gpu_scan(dcp_gpu_ctx *, struct dcp_scan_params const *);
  * of the resident batch. */
 int dcp_gpu_scan_range(dcp_gpu_ctx *, struct dcp_scan_params const *,
                        unsigned q_begin, unsigned q_end);
+/* Score exactly the npairs pairs (resident sequence seq_idx[i], resident profile profile_idx[i]), on a float or a
+ * double DB, without scanning the batch against the whole DB.  The host buckets the pairs by the row sweep's size
+ * class (a double DB: by launch group) and the row-sweep kernels run over the lists in their pair mode, as they do over
+ * a query-lane scan's redo lists: a pair's scores are the bits of a kernel-1 scan.  Results arrive as a scan's do:
+ * asynchronous on the context's stream, one scan outstanding, dcp_gpu_sync, dcp_gpu_fetch_hits / ...64, the caller's
+ * hit buffer and the gathers.  The LRT filter of params (dcp_gpu_set_lrt_threshold64 on a double DB) applies: a
+ * threshold of -inf reports every pair whose scores are finite.  A pair listed twice is reported twice; the
+ * context's own hit buffer holds min(npairs, 2^22) records.  There is no dense score matrix: keep_scores != 0 is
+ * DCP_EINVAL, and dcp_gpu_fetch_scores after the call fails as after any scan without keep_scores.  Accounting:
+ * dcp_gpu_last_scan_kernel is 1, the redo pairs 0, dcp_gpu_scan_cells the sum of core_size x length over the list
+ * (dcp_gpu_scan_algorithmic_bytes likewise), dcp_gpu_last_scan_launch_info one record per non-empty size class with
+ * that class's pairs' cells (a double DB keeps no launch records).  Explicit special transitions apply per sequence,
+ * as in a scan.  DCP_EINVAL with a message: keep_scores != 0; kernel other than 0 or 1; an index out of range, naming
+ * the first bad pair; no DB or no batch resident; explicit transitions of the other precision.  npairs == 0 is
+ * DCP_OK with zero hits. */
+int dcp_gpu_scan_pairs(dcp_gpu_ctx *, struct dcp_scan_params const *, uint32_t const *seq_idx,
+                       uint32_t const *profile_idx, unsigned npairs);
 /* Let the scan write its hit records and hit count into caller-owned DEVICE
  * memory (cap records of struct dcp_hit, one uint32 counter) -- e.g. a buffer
  * that RCCL then gathers. NULL, 0, NULL restores the internal
@@ -730,6 +770,30 @@ int dcp_gpu_domains_locate(dcp_gpu_ctx *, uint32_t const *res_idx, struct dcp_do
  * DCP_EINVAL, nothing written: a null pointer with n > 0, a NaN in odds, end <= begin. */
 int dcp_domains_merge(uint32_t const *src, uint8_t const *minus, uint32_t const *profile, uint64_t const *begin,
                       uint64_t const *end, double const *odds, unsigned n, uint8_t *keep_out, unsigned *nkept_out);
+/* Located domains (as dcp_domains_locate returns them, BEFORE any merge) -> the regions to cut and score again
+ * (dcp_gpu_seqs_cut_regions, dcp_gpu_scan_pairs).  Pure host arithmetic.  Within each (src, minus, profile) group the
+ * domains go by (begin, end, input index); a domain joins the open cluster if begin <= hi + max_gap (in 64 bits), hi
+ * the cluster's largest end so far, else it opens a new one.  There is no collinearity condition: tandem copies that
+ * fall into one cluster are separated again by the multi-hit rescan.  A cluster [lo, hi) gives the region
+ * [lo - min(lo, flank), min(hi + flank, src_len[src])).  Regions come out ordered by (src, minus, profile, begin):
+ * reg_of[j] is domain j's region; per region its source, strand (0 / 1), profile, first base, length and the number
+ * of domains in it.  DCP_ENOMEM with *nregions set and nothing else written if cap is too small (the region arrays
+ * may be NULL for such a counting call).  DCP_EINVAL, nothing written: end <= begin, end > src_len[src], src >= nsrc,
+ * a null pointer.  n == 0 is DCP_OK with 0 regions. */
+int dcp_domains_regions(uint32_t const *src, uint8_t const *minus, uint32_t const *profile, uint64_t const *begin,
+                        uint64_t const *end, unsigned n, uint32_t const *src_len, unsigned nsrc, uint64_t max_gap,
+                        uint32_t flank, uint32_t *reg_of /* [n] */, uint32_t *reg_src, uint8_t *reg_minus,
+                        uint32_t *reg_profile, uint32_t *reg_begin, uint32_t *reg_len, uint32_t *reg_nparts /* [cap] each */,
+                        unsigned cap, unsigned *nregions);
+/* dcp_domains_locate for a batch of regions: resident r < nres is the res_len[r] bases from reg_begin[r] of source
+ * reg_src[r], reverse-complemented where reg_minus[r] != 0.  A domain [b, e) on it lies at [reg_begin + b, reg_begin +
+ * e) of the source's plus strand, or at [reg_begin + len - e, reg_begin + len - b) where the region is a minus one;
+ * src_out is the region's source, minus_out its flag.  DCP_EINVAL, nothing written: a null pointer with n > 0,
+ * r >= nres, seq_begin > seq_end or seq_end > len.  dcp_gpu_domains_locate does this with the context's own region map
+ * while the resident batch is one of regions. */
+int dcp_domains_locate_regions(uint32_t const *res_idx, struct dcp_domain const *dom, unsigned n, uint32_t const *res_len,
+                               unsigned nres, uint32_t const *reg_src, uint32_t const *reg_begin, uint8_t const *reg_minus,
+                               uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out);
 
 /* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */

@@ -91,6 +91,9 @@ ABI_SYMBOLS = [
     # rescoring: located domains joined into regions, regions cut out of the resident batch, a pair list scored
     "dcp_domains_regions", "dcp_domains_locate_regions", "dcp_gpu_seqs_cut_regions", "dcp_gpu_seqs_regions",
     "dcp_gpu_seqs_region_map", "dcp_gpu_scan_pairs",
+    # calibration: a random batch and one Gumbel fit per profile on the device, their host twins, E-values
+    "dcp_seq_random_thresholds", "dcp_seq_random", "dcp_gpu_seqs_random", "dcp_gumbel_fit", "dcp_gpu_fit_gumbel",
+    "dcp_gpu_db_calibrate", "dcp_gpu_calib_kernel_ms", "dcp_gumbel_sf", "dcp_hits_evalues", "dcp_hits_evalues64",
 ]
 
 
@@ -267,6 +270,16 @@ def _load(path=None, hooks=False):
         "dcp_gpu_seqs_regions": (U, [P]),
         "dcp_gpu_seqs_region_map": (I, [P, P, P, P, U]),
         "dcp_gpu_scan_pairs": (I, [P, C.POINTER(ScanParams), P, P, U]),
+        "dcp_seq_random_thresholds": (I, [P, P]),
+        "dcp_seq_random": (None, [C.c_uint64, C.c_uint32, U, P, P]),
+        "dcp_gpu_seqs_random": (I, [P, U, U, C.c_uint64, P]),
+        "dcp_gumbel_fit": (I, [P, U, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "dcp_gpu_fit_gumbel": (I, [P, P, P, P]),
+        "dcp_gpu_db_calibrate": (I, [P, U, U, C.c_uint64, P, I, I, I, P, P, P]),
+        "dcp_gpu_calib_kernel_ms": (F, [P, I]),
+        "dcp_gumbel_sf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+        "dcp_hits_evalues": (I, [P, U, P, P, P, U, C.c_double, P]),
+        "dcp_hits_evalues64": (I, [P, U, P, P, P, U, C.c_double, P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -791,6 +804,82 @@ def locate_domains_regions(res_idx, domains, res_len, reg_src, reg_begin, reg_mi
     return src, begin, end, minus
 
 
+# enum dcp_fit_status (include/dcp_gpu.h): what a Gumbel fit can end with
+FIT_OK, FIT_FLAT, FIT_NONFINITE, FIT_DIVERGED = 0, 16, 17, 18
+
+
+def _probs(probs):
+    """None (uniform), or the four base probabilities as a float64 array for the C side to judge."""
+    if probs is None:
+        return None
+    probs = np.ascontiguousarray(probs, np.float64)
+    if probs.shape != (4,):
+        raise DcpError(RC_EINVAL, "base probabilities: four values, A C G T")
+    return probs
+
+
+def random_thresholds(probs=None):
+    """The generator's three thresholds in 0 .. 65 536 for base probabilities (A, C, G, T); None is uniform
+    (dcp_seq_random_thresholds).  c[k] = floor(65536 (p_0 + .. + p_k) + 0.5).  A uint32 array."""
+    probs = _probs(probs)
+    out = np.zeros(3, np.uint32)
+    rc = lib.dcp_seq_random_thresholds(None if probs is None else probs.ctypes.data, out.ctypes.data)
+    if rc:
+        raise DcpError(rc, "bad base probabilities: four finite values >= 0 that sum to 1")
+    return out
+
+
+def random_seq(seed, q, length, probs=None):
+    """Random sequence q of `length` bases under seed, as symbol ids (dcp_seq_random): what Scanner.random_seqs makes
+    resident as sequence q.  Integer arithmetic, the same bits on host and device."""
+    if not (0 <= seed < 2 ** 64 and 0 <= q < 2 ** 32 and 0 <= length < 2 ** 32):
+        raise DcpError(RC_EINVAL, "seed in 64 bits, q and length in 32")
+    c = random_thresholds(probs)
+    out = np.zeros(length, np.uint8)
+    lib.dcp_seq_random(seed, q, length, c.ctypes.data, out.ctypes.data)
+    return out
+
+
+def gumbel_fit(x):
+    """(mu, lambda, status) of the maximum-likelihood Gumbel fit of a 1-d sample (dcp_gumbel_fit; a strided view is
+    fitted in place).  status is FIT_OK, FIT_FLAT, FIT_NONFINITE or FIT_DIVERGED; mu and lambda are NaN unless FIT_OK.
+    Fewer than 2 values: DcpError(RC_EINVAL)."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or (len(x) > 1 and (x.strides[0] <= 0 or x.strides[0] % 8)):
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+    stride = x.strides[0] // 8 if len(x) > 1 else 1
+    mu, lam = C.c_double(0), C.c_double(0)
+    rc = lib.dcp_gumbel_fit(x.ctypes.data, len(x), stride, C.byref(mu), C.byref(lam))
+    if rc == RC_EINVAL:
+        raise DcpError(rc, "a fit needs at least 2 values")
+    return mu.value, lam.value, rc
+
+
+def gumbel_sf(mu, lam, s):
+    """P(X > s) under a Gumbel fit: -expm1(-exp(-lam (s - mu))) (dcp_gumbel_sf)."""
+    return lib.dcp_gumbel_sf(float(mu), float(lam), float(s))
+
+
+def hit_evalues(hits, mu, lam, status, nsearched):
+    """E-values of hit records (HIT_DTYPE or HIT64_DTYPE) under a calibration (mu, lam, status) of the resident DB:
+    nsearched * P(score >= alt - null) per hit, the number of sequences among nsearched random ones expected to score as
+    high against the hit's profile; NaN where the profile's fit is not FIT_OK (dcp_hits_evalues / ...64)."""
+    hits = np.ascontiguousarray(hits)
+    if hits.dtype not in (HIT_DTYPE, HIT64_DTYPE) or hits.ndim != 1:
+        raise DcpError(RC_EINVAL, "hit records: a 1-d array of HIT_DTYPE or HIT64_DTYPE")
+    mu, lam = _f64(mu), _f64(lam)
+    status = np.ascontiguousarray(status, np.uint8)
+    if not (mu.ndim == 1 and mu.shape == lam.shape == status.shape):
+        raise DcpError(RC_EINVAL, "mu, lam and status: one entry per profile")
+    out = np.zeros(len(hits), np.float64)
+    fn = lib.dcp_hits_evalues64 if hits.dtype == HIT64_DTYPE else lib.dcp_hits_evalues
+    rc = fn(hits.ctypes.data, len(hits), mu.ctypes.data, lam.ctypes.data, status.ctypes.data, len(mu), float(nsearched),
+            out.ctypes.data)
+    if rc:
+        raise DcpError(rc, "a profile index outside the calibration, or nsearched not finite or negative")
+    return out
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -893,6 +982,48 @@ class Scanner:
         off = np.ascontiguousarray(off, np.uint32)
         self._check(self._lib.dcp_gpu_seqs_upload(self._c, cat.ctypes.data, off.ctypes.data, len(off) - 1))
         self._seq_lens = np.diff(off.astype(np.int64))
+
+    def random_seqs(self, n, length, seed, probs=None):
+        """A random batch (dcp_gpu_seqs_random): the resident batch is replaced by n sequences of `length` bases,
+        sequence q the bases of random_seq(seed, q, length, probs), generated on the device.  Afterwards the context is
+        as after an upload: one strand, uncut; add_reverse_strand, cut_windows and cut_regions may follow."""
+        if not (0 <= n < 2 ** 32 and 0 <= length < 2 ** 32 and 0 <= seed < 2 ** 64):
+            raise DcpError(RC_EINVAL, "n and length in 32 bits, seed in 64")
+        probs = _probs(probs)
+        self._check(self._lib.dcp_gpu_seqs_random(self._c, n, length, seed, None if probs is None else probs.ctypes.data))
+        self._seq_lens = np.full(n, length, np.int64)
+
+    def _fit_outputs(self):
+        n = self.nprofiles
+        return np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint8)
+
+    def fit_gumbel(self):
+        """(mu, lam, status), one entry per resident profile: the Gumbel fit of alt - null over the dense scores of the
+        last scan, which must have covered the whole batch with keep_scores (dcp_gpu_fit_gumbel; one lane per profile
+        on the device).  status: FIT_OK, FIT_FLAT, FIT_NONFINITE, FIT_DIVERGED; mu and lam are NaN unless FIT_OK."""
+        mu, lam, status = self._fit_outputs()
+        self._check(self._lib.dcp_gpu_fit_gumbel(self._c, mu.ctypes.data, lam.ctypes.data, status.ctypes.data))
+        return mu, lam, status
+
+    def calibrate(self, n, length, seed, probs=None, multi_hits=True, hmmer3_compat=False, kernel=KERNEL_AUTO):
+        """random_seqs(n, length, seed, probs), one scan with these flags that keeps the dense scores and reports no
+        hits, fit_gumbel(): (mu, lam, status) for hit_evalues (dcp_gpu_db_calibrate).  The random batch and that scan
+        STAY resident: upload the real batch afterwards.  The fit holds for this length, these flags and this base
+        composition -- calibrate at the window length that cut_windows will cut."""
+        if not (0 <= n < 2 ** 32 and 0 <= length < 2 ** 32 and 0 <= seed < 2 ** 64):
+            raise DcpError(RC_EINVAL, "n and length in 32 bits, seed in 64")
+        probs = _probs(probs)
+        mu, lam, status = self._fit_outputs()
+        self._check(self._lib.dcp_gpu_db_calibrate(self._c, n, length, seed, None if probs is None else probs.ctypes.data,
+                                                   int(multi_hits), int(hmmer3_compat), int(kernel), mu.ctypes.data,
+                                                   lam.ctypes.data, status.ctypes.data))
+        self._seq_lens = np.full(n, length, np.int64)
+        return mu, lam, status
+
+    def calib_kernel_ms(self, which):
+        """Milliseconds of the last generator kernel (which = 0) or fit kernel (1) alone, by HIP events; negative if
+        none has run."""
+        return self._lib.dcp_gpu_calib_kernel_ms(self._c, which)
 
     def add_reverse_strand(self):
         """Both strands (dcp_gpu_seqs_add_revcomp): the resident batch of n sequences becomes 2n, sequence n + q the

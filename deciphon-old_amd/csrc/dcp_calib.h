@@ -1,0 +1,154 @@
+// dcp_calib.h -- calibration: the random batch and the per-profile Gumbel fit (dcp_calib.hip), and the two rules that
+// the kernels there and their host twins in dcp_model.cpp both evaluate.  One source for both sides, as
+// dcp_frame_word.h: the generator is integer arithmetic mod 2^64, equal in bits wherever it runs; the fit is double
+// arithmetic with every sum taken in index order and a fixed number of steps, so that with no contraction
+// (-ffp-contract=off in both units) host and device differ only in exp, log and sqrt.
+#ifndef DCP_CALIB_H
+#define DCP_CALIB_H
+
+#include <math.h>
+#include <stdint.h>
+
+#ifdef __HIP__
+#define DCP_HD __host__ __device__
+#else
+#define DCP_HD
+#endif
+
+// ---- the generator ------------------------------------------------------------------------------------------------
+// splitmix64's output function; key(q) = sm(seed ^ sm(q)), draw(q, i) = sm(key(q) + i): counter-based, any base of any
+// sequence is computed on its own.  One draw gives four bases, 16 bits each: base b of sequence q is
+//   u = (draw(q, b >> 2) >> (16 (b & 3))) & 0xffff,  id = (u >= c[0]) + (u >= c[1]) + (u >= c[2])   (A C G T = 0 1 2 3)
+// with thresholds c in 0 .. 65 536 (dcp_seq_random_thresholds).
+DCP_HD inline uint64_t dcp_rand_sm(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+DCP_HD inline uint64_t dcp_rand_key(uint64_t seed, uint32_t q) { return dcp_rand_sm(seed ^ dcp_rand_sm((uint64_t)q)); }
+DCP_HD inline uint64_t dcp_rand_draw(uint64_t key, uint64_t i) { return dcp_rand_sm(key + i); }
+// the four bases of one draw as four 2-bit groups, the first base lowest
+DCP_HD inline uint32_t dcp_rand_groups(uint64_t d, uint32_t c0, uint32_t c1, uint32_t c2)
+{
+    uint32_t out = 0;
+    for (unsigned t = 0; t < 4u; ++t)
+    {
+        uint32_t const u = (uint32_t)(d >> (16u * t)) & 0xffffu;
+        out |= ((uint32_t)(u >= c0) + (uint32_t)(u >= c1) + (uint32_t)(u >= c2)) << (2u * t);
+    }
+    return out;
+}
+
+// ---- the fit ------------------------------------------------------------------------------------------------------
+// Status of one fit (include/dcp_gpu.h: enum dcp_fit_status has the same values).
+enum
+{
+    DCP_FITR_OK = 0,
+    DCP_FITR_FLAT = 16,
+    DCP_FITR_NONFINITE = 17,
+    DCP_FITR_DIVERGED = 18,
+    DCP_FIT_STEPS = 12,
+};
+
+// by the encoding: right whatever the unit's NaN flags are
+DCP_HD inline bool dcp_fit_finite(double v)
+{
+    uint64_t b;
+    __builtin_memcpy(&b, &v, sizeof b);
+    return ((b >> 52) & 0x7ffu) != 0x7ffu;
+}
+DCP_HD inline double dcp_fit_nan()
+{
+    uint64_t const b = 0x7ff8000000000000ull;
+    double v;
+    __builtin_memcpy(&v, &b, sizeof v);
+    return v;
+}
+
+// One pass: f(x(0)), f(x(1)), .. f(x(n - 1)) in this order, the values fetched four at a time ahead of their use -- on the
+// device four rows' loads are in flight while f, whose sums stay in index order, takes the four before them.
+template <class X, class F> DCP_HD inline void dcp_fit_pass(X const &x, unsigned n, F const &f)
+{
+    unsigned i = 0;
+    for (; i + 4u <= n; i += 4u)
+    {
+        double const v0 = x(i), v1 = x(i + 1u), v2 = x(i + 2u), v3 = x(i + 3u);
+        f(v0), f(v1), f(v2), f(v3);
+    }
+    for (; i < n; ++i)
+        f(x(i));
+}
+
+// Maximum-likelihood Gumbel fit of x(0) .. x(n - 1), n >= 2 (the caller checks): 15 passes over the sample, each in
+// index order.  Pass 1: non-finite -> NONFINITE; the minimum m and the mean.  Pass 2: the variance; 0 -> FLAT, else
+// the moment estimate lambda = pi / sqrt(6 var).  Then exactly DCP_FIT_STEPS Newton steps on
+//   f(lambda) = 1 / lambda - (mean - m) + s1 / s0,  s_k = sum y^k exp(-lambda y),  y = x - m >= 0
+// (every term of every sum is non-negative).  A step to a lambda that is not finite or not positive sets a sticky
+// DIVERGED and keeps the lambda it came from, so every caller runs the same number of passes; so does a last step that
+// moved lambda by more than 2^-40 of itself.  Last pass: mu = m - log(s0 / n) / lambda.  Any status but OK gives
+// NaN in both outputs.  exp, log and sqrt are the side's own.
+template <class X> DCP_HD inline int dcp_gumbel_fit_rule(X const &x, unsigned n, double *mu, double *lambda)
+{
+    *mu = *lambda = dcp_fit_nan();
+    bool bad = false;
+    double m = 1.7976931348623157e308, sum = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        bad |= !dcp_fit_finite(v);
+        m = v < m ? v : m;
+        sum += v;
+    });
+    if (bad) return DCP_FITR_NONFINITE;
+    double const mean = sum / (double)n;
+    double ss = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        double const d = v - mean;
+        ss += d * d;
+    });
+    double const var = ss / (double)(n - 1u);
+    if (var == 0.0) return DCP_FITR_FLAT;
+    double lam = 3.14159265358979323846 / sqrt(6.0 * var);
+    double const gap = mean - m;
+    bool diverged = false, settled = false;
+    for (int step = 0; step < DCP_FIT_STEPS; ++step)
+    {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        dcp_fit_pass(x, n, [&](double v) {
+            double const y = v - m;
+            double const w = exp(-(lam * y));
+            s0 += w;
+            s1 += y * w;
+            s2 += (y * y) * w;
+        });
+        double const r = s1 / s0;
+        double const f = 1.0 / lam - gap + r;
+        double const df = -1.0 / (lam * lam) - s2 / s0 + r * r;
+        double next = lam - f / df;
+        if (!dcp_fit_finite(next) || !(next > 0.0)) diverged = true, next = lam;
+        double const moved = next > lam ? next - lam : lam - next;
+        settled = moved <= 0x1p-40 * next;
+        lam = next;
+    }
+    double s0 = 0.0;
+    dcp_fit_pass(x, n, [&](double v) { s0 += exp(-(lam * (v - m))); });
+    if (diverged || !settled) return DCP_FITR_DIVERGED;
+    *lambda = lam;
+    *mu = m - log(s0 / (double)n) / lam;
+    return DCP_FITR_OK;
+}
+
+// ---- the launches (dcp_calib.hip) -----------------------------------------------------------------------------------
+extern "C" {
+// A batch of nseqs sequences of len bases in the resident layout (dcp_seqs.hip: len / 16 + 3 words each, every bit
+// behind the last base and every pad word zero): words [nseqs (len / 16 + 3)], woff / len_out [nseqs].  Device
+// pointers; the caller has checked that the words and nseqs fit 32 bits.  One launch on `stream`; HIP's error code.
+int dcp_launch_random(uint32_t *words, uint32_t *woff, uint32_t *len_out, unsigned nseqs, uint32_t len, uint64_t seed,
+                      uint32_t const c[3], void *stream);
+// One fit per profile p < nprof of x_q = (double) alt[q nprof + p] - (double) null[q nprof + p], q < nseqs (>= 2):
+// mu / lambda [nprof] doubles, status [nprof] bytes.  real_bytes: 4 (float matrices) or 8.  One launch on `stream`.
+int dcp_launch_gumbel_fit(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof, int real_bytes,
+                          double *mu, double *lambda, uint8_t *status, void *stream);
+}
+
+#endif

@@ -10,6 +10,7 @@
 #include "dcp_seqs.h"
 #include "dcp_decode.h"
 #include "dcp_domains.h"
+#include "dcp_calib.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -366,6 +367,12 @@ struct dcp_gpu_ctx
     DevBuf<uint32_t> d_dom_recs;
     hipEvent_t ev_dom[2] = {nullptr, nullptr};
     bool dom_timed = false;
+    // calibration (dcp_calib.hip): the last fit's mu [nprof], lambda [nprof] and status bytes on the device (kept between
+    // calls), and events around the last random_words_kernel ([0], [1]) and the last gumbel_fit_kernel ([2], [3])
+    DevBuf<double> d_fit;
+    DevBuf<uint8_t> d_fit_status;
+    hipEvent_t ev_calib[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool calib_timed[2] = {false, false};
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -688,6 +695,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     if (c->ev_start) (void)hipEventDestroy(c->ev_start);
     if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
     for (hipEvent_t e : c->ev_dom)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_calib)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -1828,6 +1837,80 @@ int dcp_gpu_seqs_cut_windows(dcp_gpu_ctx *c, unsigned window, unsigned step)
     c->nseqs = W;
     c->total_len = total;
     c->xt_multi = c->xt_h3 = -1; // the windows' rows are derived with the next scan's flags
+    c->xt64.clear();
+    return DCP_OK;
+}
+
+// A random batch (dcp_calib.hip): nseqs sequences of len bases written on the device into new arrays, which then replace
+// the resident ones as in dcp_gpu_seqs_add_revcomp.  Every refusal comes before anything is touched.
+int dcp_gpu_seqs_random(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4])
+{
+    if (!c) return DCP_EINVAL;
+    if (nseqs == 0 || len == 0) return c->fail(DCP_EINVAL, "a random batch needs sequences and bases (%u sequences of %u)", nseqs, len);
+    uint32_t thr[3];
+    if (dcp_seq_random_thresholds(probs, thr))
+        return c->fail(DCP_EINVAL, "bad base probabilities: four finite values >= 0 that sum to 1");
+    uint64_t const nwords = (uint64_t)nseqs * (len / 16u + 3u);
+    if (nwords > 0xffffffffull)
+        return c->fail(DCP_EINVAL, "random batch too large (%u sequences, %llu words)", nseqs, (unsigned long long)nwords);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // a scan of the batch that is replaced may still be running on the stream: it reads the arrays freed below
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<uint32_t> lens;
+    try
+    {
+        lens.assign(nseqs, len);
+    }
+    catch (std::bad_alloc const &)
+    {
+        return c->fail(DCP_ENOMEM, "out of host memory for %u sequence lengths", nseqs);
+    }
+    for (hipEvent_t &e : c->ev_calib)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    void_last_scan(c);
+    c->qorder_q0 = c->qorder_q1 = ~0u; // the length order and the word planes belong to the batch that was resident
+    DevBuf<uint32_t> words, woff, dlen;
+    DevBuf<float> xt;
+    // as in an upload: a failed allocation must not leave the old batch's size paired with new buffers
+    auto drop = [&]() {
+        c->nseqs = 0, c->strands = 0, c->total_len = 0;
+        c->seq_len.clear();
+        c->drop_windows();
+        c->xt_multi = c->xt_h3 = -1;
+        c->xt_explicit = false;
+        c->xt64.clear();
+    };
+#define SEQS_TRY(call)                                                                                                  \
+    do                                                                                                                  \
+    {                                                                                                                   \
+        hipError_t e_ = (call);                                                                                         \
+        if (e_ != hipSuccess)                                                                                           \
+        {                                                                                                               \
+            drop();                                                                                                     \
+            return c->fail(e_ == hipErrorOutOfMemory ? DCP_ENOMEM : DCP_EFAIL, "%s: %s", #call, hipGetErrorString(e_)); \
+        }                                                                                                               \
+    } while (0)
+    SEQS_TRY(words.alloc((size_t)nwords));
+    SEQS_TRY(woff.alloc(nseqs));
+    SEQS_TRY(dlen.alloc(nseqs));
+    SEQS_TRY(xt.alloc((size_t)nseqs * DCP_XSTRIDE));
+    SEQS_TRY(hipEventRecord(c->ev_calib[0], c->stream));
+    SEQS_TRY((hipError_t)dcp_launch_random(words.p, woff.p, dlen.p, nseqs, len, seed, thr, c->stream));
+    SEQS_TRY(hipEventRecord(c->ev_calib[1], c->stream));
+    SEQS_TRY(hipStreamSynchronize(c->stream)); // the old arrays are freed below
+#undef SEQS_TRY
+    c->calib_timed[0] = true;
+    std::swap(c->d_seq_words.p, words.p), std::swap(c->d_seq_words.n, words.n);
+    std::swap(c->d_seq_woff.p, woff.p), std::swap(c->d_seq_woff.n, woff.n);
+    std::swap(c->d_seq_len.p, dlen.p), std::swap(c->d_seq_len.n, dlen.n);
+    std::swap(c->d_xtrans.p, xt.p), std::swap(c->d_xtrans.n, xt.n);
+    c->seq_len.swap(lens);
+    c->drop_windows(); // a new batch is uncut
+    c->nseqs = nseqs;
+    c->strands = 1;
+    c->total_len = (uint64_t)nseqs * len;
+    c->xt_multi = c->xt_h3 = -1;
+    c->xt_explicit = false;
     c->xt64.clear();
     return DCP_OK;
 }
@@ -3464,6 +3547,73 @@ int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
     if (c->scanned && !c->last_f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its scores with dcp_gpu_fetch_scores");
     return fetch_scores(c, c->f64.res, null_out, alt_out);
+}
+
+// One Gumbel fit per resident profile over the last scan's dense scores (dcp_calib.hip).
+int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8_t *status_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out) return c->fail(DCP_EINVAL, "dcp_gpu_fit_gumbel: a null output");
+    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet: the fit is over the last scan's dense scores");
+    bool const have = c->last_f64 ? c->f64.res.have_scores : c->res.have_scores;
+    if (c->last_pair_scan || !have)
+        return c->fail(DCP_EINVAL, "no dense scores kept by the last scan (keep_scores = 0, or a scan of a pair list)");
+    if (c->last_q0 != 0 || c->last_q1 != c->nseqs)
+        return c->fail(DCP_EINVAL, "the last scan covered sequences [%u, %u) of %u: the fit is over the whole batch", c->last_q0,
+                       c->last_q1, c->nseqs);
+    if (c->nseqs < 2u) return c->fail(DCP_EINVAL, "a fit needs at least 2 sequences: %u resident", c->nseqs);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (int rc = finish_scan(c)) return rc; // a query-lane scan completes its redo pairs there
+    unsigned const np = c->nprof;
+    if (c->d_fit.n < 2u * (size_t)np) HIP_TRY(c, c->d_fit.alloc(2u * (size_t)np));
+    if (c->d_fit_status.n < np) HIP_TRY(c, c->d_fit_status.alloc(np));
+    for (hipEvent_t &e : c->ev_calib)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    void const *nl = c->last_f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
+    void const *al = c->last_f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
+    HIP_TRY(c, hipEventRecord(c->ev_calib[2], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_gumbel_fit(nl, al, c->nseqs, np, c->last_f64 ? 8 : 4, c->d_fit.p, c->d_fit.p + np,
+                                                  c->d_fit_status.p, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_calib[3], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->calib_timed[1] = true;
+    // into buffers of the call's own first: the caller's arrays stay untouched if a copy fails
+    std::vector<double> fit(2u * (size_t)np);
+    std::vector<uint8_t> st(np);
+    HIP_TRY(c, hipMemcpy(fit.data(), c->d_fit.p, fit.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(st.data(), c->d_fit_status.p, np, hipMemcpyDeviceToHost));
+    std::memcpy(mu_out, fit.data(), np * sizeof(double));
+    std::memcpy(lambda_out, fit.data() + np, np * sizeof(double));
+    std::memcpy(status_out, st.data(), np);
+    return DCP_OK;
+}
+
+int dcp_gpu_db_calibrate(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4], int multi_hits,
+                         int hmmer3_compat, int kernel, double *mu_out, double *lambda_out, uint8_t *status_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = dcp_gpu_seqs_random(c, nseqs, len, seed, probs)) return rc;
+    struct dcp_scan_params prm = {};
+    prm.multi_hits = multi_hits, prm.hmmer3_compat = hmmer3_compat;
+    prm.lrt_threshold = std::numeric_limits<float>::infinity(); // no hit records
+    prm.keep_scores = 1, prm.kernel = kernel;
+    // a double DB filters by its own threshold: +inf for this scan -- to its end, the re-run of an overflowed
+    // query-lane scan included -- then the caller's again
+    double const thr64 = c->lrt_threshold64;
+    c->lrt_threshold64 = std::numeric_limits<double>::infinity();
+    int rc = dcp_gpu_scan(c, &prm);
+    if (!rc) rc = dcp_gpu_sync(c);
+    c->lrt_threshold64 = thr64;
+    if (rc) return rc;
+    return dcp_gpu_fit_gumbel(c, mu_out, lambda_out, status_out);
+}
+
+float dcp_gpu_calib_kernel_ms(dcp_gpu_ctx *c, int which)
+{
+    float ms = -1.0f;
+    if (!c || which < 0 || which > 1 || !c->calib_timed[which]) return -1.0f;
+    if (hipEventElapsedTime(&ms, c->ev_calib[2 * which], c->ev_calib[2 * which + 1]) != hipSuccess) return -1.0f;
+    return ms;
 }
 
 int dcp_gpu_fetch_hits64(dcp_gpu_ctx *c, struct dcp_hit64 *hits, unsigned cap, unsigned *nhits)

@@ -1735,3 +1735,97 @@ int dcp_domains_locate_regions(uint32_t const *res_idx, struct dcp_domain const 
 
 } // extern "C"
 
+// ---------------------------------------------------------------------------
+// Calibration on the host: the generator's and the fit's twins (the rules are dcp_calib.h, which dcp_calib.hip compiles
+// for the device), the Gumbel tail and E-values.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_calib.h"
+
+static_assert(DCP_FIT_OK == DCP_FITR_OK && DCP_FIT_FLAT == DCP_FITR_FLAT && DCP_FIT_NONFINITE == DCP_FITR_NONFINITE &&
+                  DCP_FIT_DIVERGED == DCP_FITR_DIVERGED,
+              "dcp_calib.h restates enum dcp_fit_status");
+
+extern "C" {
+
+int dcp_seq_random_thresholds(double const probs[4], uint32_t c_out[3])
+{
+    if (!c_out) return DCP_EINVAL;
+    uint32_t c[3] = {16384u, 32768u, 49152u};
+    if (probs)
+    {
+        double sum = 0.0, cum[4];
+        for (int k = 0; k < 4; ++k)
+        {
+            if (!std::isfinite(probs[k]) || probs[k] < 0.0) return DCP_EINVAL;
+            cum[k] = sum += probs[k];
+        }
+        if (!(std::fabs(sum - 1.0) <= 1e-6)) return DCP_EINVAL;
+        for (int k = 0; k < 3; ++k)
+        {
+            double const t = std::floor(65536.0 * cum[k] + 0.5);
+            c[k] = t >= 65536.0 ? 65536u : (uint32_t)t;
+        }
+    }
+    std::memcpy(c_out, c, sizeof c);
+    return DCP_OK;
+}
+
+void dcp_seq_random(uint64_t seed, uint32_t q, unsigned len, uint32_t const c[3], uint8_t *ids_out)
+{
+    if (!c || !ids_out) return;
+    uint64_t const key = dcp_rand_key(seed, q);
+    for (unsigned b = 0; b < len; b += 4u)
+    {
+        uint32_t g = dcp_rand_groups(dcp_rand_draw(key, b >> 2), c[0], c[1], c[2]);
+        for (unsigned t = 0; t < 4u && b + t < len; ++t, g >>= 2)
+            ids_out[b + t] = (uint8_t)(g & 3u);
+    }
+}
+
+int dcp_gumbel_fit(double const *x, unsigned n, size_t stride, double *mu, double *lambda)
+{
+    if (!x || !mu || !lambda || n < 2u || stride == 0) return DCP_EINVAL;
+    return dcp_gumbel_fit_rule([=](unsigned i) { return x[(size_t)i * stride]; }, n, mu, lambda);
+}
+
+double dcp_gumbel_sf(double mu, double lambda, double s) { return -std::expm1(-std::exp(-lambda * (s - mu))); }
+
+} // extern "C"
+
+namespace
+{
+template <class Hit>
+int hits_evalues(Hit const *hits, unsigned n, double const *mu, double const *lambda, uint8_t const *status, unsigned nprofiles,
+                 double nsearched, double *evalue_out)
+{
+    if (!std::isfinite(nsearched) || nsearched < 0.0) return DCP_EINVAL;
+    if (n == 0) return DCP_OK;
+    if (!hits || !mu || !lambda || !status || !evalue_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < n; ++i) // everything is checked before anything is written
+        if (hits[i].profile_idx >= nprofiles) return DCP_EINVAL;
+    for (unsigned i = 0; i < n; ++i)
+    {
+        uint32_t const p = hits[i].profile_idx;
+        double const s = (double)hits[i].alt_loglik - (double)hits[i].null_loglik;
+        evalue_out[i] = status[p] == DCP_FIT_OK ? nsearched * dcp_gumbel_sf(mu[p], lambda[p], s) : dcp_fit_nan();
+    }
+    return DCP_OK;
+}
+} // namespace
+
+extern "C" {
+
+int dcp_hits_evalues(struct dcp_hit const *hits, unsigned n, double const *mu, double const *lambda, uint8_t const *status,
+                     unsigned nprofiles, double nsearched, double *evalue_out)
+{
+    return hits_evalues(hits, n, mu, lambda, status, nprofiles, nsearched, evalue_out);
+}
+
+int dcp_hits_evalues64(struct dcp_hit64 const *hits, unsigned n, double const *mu, double const *lambda, uint8_t const *status,
+                       unsigned nprofiles, double nsearched, double *evalue_out)
+{
+    return hits_evalues(hits, n, mu, lambda, status, nprofiles, nsearched, evalue_out);
+}
+
+} // extern "C"
+

@@ -796,6 +796,83 @@ int dcp_domains_locate_regions(uint32_t const *res_idx, struct dcp_domain const 
                                uint32_t *src_out, uint64_t *begin_out, uint64_t *end_out, uint8_t *minus_out);
 
 /* ------------------------------------------------------------------------ */
+/* Calibration: a random batch, one Gumbel fit per profile, E-values */
+/* ------------------------------------------------------------------------ */
+/* How often does a profile reach a score on sequence that holds no gene?  Score it against random sequences, fit an
+ * extreme-value (Gumbel) distribution to the scores x = alt - null, read tail probabilities off the fit.  The
+ * answer holds for the sequence length, the scan flags and the base composition it was computed with, and nothing
+ * else: calibrate at the window's length what dcp_gpu_seqs_cut_windows will cut.
+ *
+ * The generator.  Integers only, counter-based, the same on host and device; all arithmetic mod 2^64.
+ *   sm(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *          return z ^ (z >> 31)
+ *   key(q) = sm(seed ^ sm(q)),  draw(q, i) = sm(key(q) + i)
+ *   base b of sequence q: u = (draw(q, b >> 2) >> (16 (b & 3))) & 0xffff, id = (u >= c[0]) + (u >= c[1]) + (u >= c[2])
+ * (A C G T = 0 1 2 3).  c_out[k] = floor(65536 (p_0 + .. + p_k) + 0.5) in double, at most 65 536; probs == NULL is
+ * uniform: 16 384, 32 768, 49 152.  DCP_EINVAL, nothing written: a non-finite or negative entry, a sum further than
+ * 1e-6 from 1, c_out NULL. */
+int dcp_seq_random_thresholds(double const probs[4], uint32_t c_out[3]);
+/* The len symbol ids of random sequence q under (seed, c) on the host: what dcp_gpu_seqs_random makes resident. */
+void dcp_seq_random(uint64_t seed, uint32_t q, unsigned len, uint32_t const c[3], uint8_t *ids_out);
+/* The resident batch is REPLACED, as by an upload, with nseqs sequences of len bases, sequence q the bases of
+ * dcp_seq_random(seed, q, len, thresholds of probs), written on the device into the resident layout
+ * (csrc/dcp_calib.hip, random_words_kernel): no base crosses the host.  The context is back to one strand, uncut,
+ * with no regions and no explicit transitions; dcp_gpu_seqs_add_revcomp, _cut_windows and _cut_regions work afterwards
+ * as after an upload, and the last scan is void.  DCP_EINVAL, with a message and the batch untouched, all checked
+ * before any allocation: nseqs == 0 or len == 0; bad probs (NULL is uniform); nseqs (len / 16 + 3) past 2^32 - 1.  A
+ * failed allocation leaves the context without a batch, as a failed upload does.  Works on float and double DBs
+ * alike, and with no DB resident. */
+int dcp_gpu_seqs_random(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4]);
+/* What a fit can end with.  Distinct from enum dcp_rc, so that dcp_gumbel_fit can return either. */
+enum dcp_fit_status
+{
+    DCP_FIT_OK = 0,
+    DCP_FIT_FLAT = 16,      /* every score the same: no variance, nothing to fit */
+    DCP_FIT_NONFINITE = 17, /* a score is +-inf or NaN (an epsilon = 0 profile on a sequence it cannot emit) */
+    DCP_FIT_DIVERGED = 18,  /* a step gave a lambda not finite or not positive, or the twelfth still moved it by > 2^-40 of itself */
+};
+/* The maximum-likelihood Gumbel fit of x[0], x[stride], .. x[(n - 1) stride] on the host: P(X > s) = 1 - exp(-exp(
+ * -lambda (s - mu))).  Double arithmetic, every sum sequential in index order (csrc/dcp_calib.h, which the device
+ * kernel compiles too).  n < 2, stride == 0 or a null pointer is DCP_EINVAL, nothing written.  Pass 1: a non-finite
+ * x is DCP_FIT_NONFINITE; m = min x, mean.  Pass 2: var = sum (x - mean)^2 / (n - 1); 0 is DCP_FIT_FLAT; lambda = pi /
+ * sqrt(6 var).  Then exactly 12 Newton steps on the likelihood equation with y = x - m >= 0, w = exp(-lambda y), s0 =
+ * sum w, s1 = sum y w, s2 = sum (y y) w, r = s1 / s0: f = 1 / lambda - (mean - m) + r, df = -1 / (lambda lambda) - s2 /
+ * s0 + r r, lambda' = lambda - f / df; a lambda' that is not finite or not positive is a sticky DCP_FIT_DIVERGED, and so
+ * is a last step with |lambda' - lambda| > 2^-40 lambda'.  mu = m - log(sum exp(-lambda y) / n) / lambda.  Any status
+ * but DCP_FIT_OK (which is returned as it is) writes NaN to both outputs. */
+int dcp_gumbel_fit(double const *x, unsigned n, size_t stride, double *mu, double *lambda);
+/* The same fit, one lane per resident profile p, of x_q = (double) alt[q][p] - (double) null[q][p] over the dense
+ * matrices the last scan left on the device (csrc/dcp_calib.hip, gumbel_fit_kernel): mu_out / lambda_out [nprofiles]
+ * doubles, status_out [nprofiles] of enum dcp_fit_status.  Float and double DBs alike.  Host and device differ in exp,
+ * log and sqrt only (DESIGN.md §17 has the bound).  The call completes the scan first (dcp_gpu_sync) and returns
+ * synchronised; the scan's results stay valid.  DCP_EINVAL with a message, outputs untouched: no scan has run; the
+ * last scan kept no dense scores (keep_scores == 0, or dcp_gpu_scan_pairs); it was a dcp_gpu_scan_range that did not
+ * cover the whole batch; the batch holds fewer than 2 sequences; a null pointer. */
+int dcp_gpu_fit_gumbel(dcp_gpu_ctx *, double *mu_out, double *lambda_out, uint8_t *status_out);
+/* Exactly these three steps: dcp_gpu_seqs_random(nseqs, len, seed, probs); one dcp_gpu_scan with these flags and
+ * kernel, keep_scores = 1 and lrt_threshold = +inf (no hit records; on a double DB the threshold of
+ * dcp_gpu_set_lrt_threshold64 is +inf for that scan and restored behind it); dcp_gpu_fit_gumbel.  The first failing
+ * step's code is returned.  The call LEAVES the random batch and that scan resident: whatever batch was there before
+ * is gone, dcp_gpu_fetch_scores[64] serves the calibration's scores, and the next upload starts afresh.  Nothing is
+ * kept with the DB: the caller holds mu / lambda / status and passes them to dcp_hits_evalues. */
+int dcp_gpu_db_calibrate(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4], int multi_hits,
+                         int hmmer3_compat, int kernel, double *mu_out, double *lambda_out, uint8_t *status_out);
+/* Milliseconds, by HIP events around the kernel alone, of the context's last random_words_kernel (which = 0) or
+ * gumbel_fit_kernel (1); negative if none has run. */
+float dcp_gpu_calib_kernel_ms(dcp_gpu_ctx *, int which);
+/* P(X > s) under the fit: -expm1(-exp(-lambda (s - mu))) -- expm1 keeps the relative precision far in the tail, where
+ * the probability is exp(-lambda (s - mu)) itself. */
+double dcp_gumbel_sf(double mu, double lambda, double s);
+/* evalue_out[i] = nsearched * dcp_gumbel_sf(mu[p], lambda[p], (double) alt - (double) null) of hit i, p its
+ * profile_idx: the number of sequences among nsearched random ones expected to score as high against profile p.  NaN
+ * where status[p] != DCP_FIT_OK.  DCP_EINVAL, nothing written: a profile_idx >= nprofiles, a null pointer with n > 0,
+ * nsearched not finite or negative.  ...64 takes the hits of a double DB. */
+int dcp_hits_evalues(struct dcp_hit const *, unsigned n, double const *mu, double const *lambda, uint8_t const *status,
+                     unsigned nprofiles, double nsearched, double *evalue_out);
+int dcp_hits_evalues64(struct dcp_hit64 const *, unsigned n, double const *mu, double const *lambda, uint8_t const *status,
+                       unsigned nprofiles, double nsearched, double *evalue_out);
+
+/* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum

@@ -94,6 +94,8 @@ ABI_SYMBOLS = [
     # calibration: a random batch and one Gumbel fit per profile on the device, their host twins, E-values
     "dcp_seq_random_thresholds", "dcp_seq_random", "dcp_gpu_seqs_random", "dcp_gumbel_fit", "dcp_gpu_fit_gumbel",
     "dcp_gpu_db_calibrate", "dcp_gpu_calib_kernel_ms", "dcp_gumbel_sf", "dcp_hits_evalues", "dcp_hits_evalues64",
+    # the tail fit: the k-th largest score per profile, a censored Gumbel fit over the scores from it up
+    "dcp_gumbel_fit_tail", "dcp_gpu_fit_gumbel_tail", "dcp_gpu_db_calibrate_tail", "dcp_gpu_calib_tail_kernel_ms",
 ]
 
 
@@ -277,6 +279,11 @@ def _load(path=None, hooks=False):
         "dcp_gpu_fit_gumbel": (I, [P, P, P, P]),
         "dcp_gpu_db_calibrate": (I, [P, U, U, C.c_uint64, P, I, I, I, P, P, P]),
         "dcp_gpu_calib_kernel_ms": (F, [P, I]),
+        "dcp_gumbel_fit_tail": (I, [P, U, C.c_size_t, U, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                    C.POINTER(C.c_double), C.POINTER(C.c_uint)]),
+        "dcp_gpu_fit_gumbel_tail": (I, [P, U, P, P, P, P, P]),
+        "dcp_gpu_db_calibrate_tail": (I, [P, U, U, C.c_uint64, P, I, I, I, U, P, P, P, P, P]),
+        "dcp_gpu_calib_tail_kernel_ms": (F, [P, I]),
         "dcp_gumbel_sf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
         "dcp_hits_evalues": (I, [P, U, P, P, P, U, C.c_double, P]),
         "dcp_hits_evalues64": (I, [P, U, P, P, P, U, C.c_double, P]),
@@ -855,6 +862,24 @@ def gumbel_fit(x):
     return mu.value, lam.value, rc
 
 
+def gumbel_fit_tail(x, k):
+    """(mu, lambda, status, tau, k_eff) of the censored Gumbel fit of a 1-d sample (dcp_gumbel_fit_tail; a strided view
+    is fitted in place): tau is the k-th largest value, the k_eff >= k values >= tau enter with their values, the
+    others only as "below tau".  k = len(x) is gumbel_fit in bits.  tau is NaN and k_eff 0 with FIT_NONFINITE.  Fewer
+    than 2 values, k < 2 or k > len(x): DcpError(RC_EINVAL).  The law holds for scores >= tau only."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or (len(x) > 1 and (x.strides[0] <= 0 or x.strides[0] % 8)):
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+    stride = x.strides[0] // 8 if len(x) > 1 else 1
+    if not 0 <= k < 2 ** 32:
+        raise DcpError(RC_EINVAL, "the tail count: 2 .. len(x)")
+    mu, lam, tau, k_eff = C.c_double(0), C.c_double(0), C.c_double(0), C.c_uint(0)
+    rc = lib.dcp_gumbel_fit_tail(x.ctypes.data, len(x), stride, int(k), C.byref(mu), C.byref(lam), C.byref(tau), C.byref(k_eff))
+    if rc == RC_EINVAL:
+        raise DcpError(rc, "a tail fit needs at least 2 values and a tail count in 2 .. len(x)")
+    return mu.value, lam.value, rc, tau.value, k_eff.value
+
+
 def gumbel_sf(mu, lam, s):
     """P(X > s) under a Gumbel fit: -expm1(-exp(-lam (s - mu))) (dcp_gumbel_sf)."""
     return lib.dcp_gumbel_sf(float(mu), float(lam), float(s))
@@ -1019,6 +1044,39 @@ class Scanner:
                                                    lam.ctypes.data, status.ctypes.data))
         self._seq_lens = np.full(n, length, np.int64)
         return mu, lam, status
+
+    def fit_gumbel_tail(self, k):
+        """(mu, lam, status, tau, k_eff), one entry per resident profile: the censored Gumbel fit of alt - null over the
+        dense scores of the last scan, as fit_gumbel (dcp_gpu_fit_gumbel_tail; two launches: the k-th largest score tau
+        per profile by comparisons alone, then the fit over the k_eff scores >= tau).  k in 2 .. nseqs.  The law holds
+        for scores >= tau[p]: below it a hit's E-value is at least about nsearched k_eff / nseqs, and not calibrated."""
+        if not 0 <= k < 2 ** 32:
+            raise DcpError(RC_EINVAL, "the tail count: 2 .. nseqs")
+        mu, lam, status = self._fit_outputs()
+        tau, k_eff = np.zeros(len(mu), np.float64), np.zeros(len(mu), np.uint32)
+        self._check(self._lib.dcp_gpu_fit_gumbel_tail(self._c, int(k), mu.ctypes.data, lam.ctypes.data, status.ctypes.data,
+                                                      tau.ctypes.data, k_eff.ctypes.data))
+        return mu, lam, status, tau, k_eff
+
+    def calibrate_tail(self, n, length, seed, k, probs=None, multi_hits=True, hmmer3_compat=False, kernel=KERNEL_AUTO):
+        """calibrate() with fit_gumbel_tail(k) as its third step: (mu, lam, status, tau, k_eff)
+        (dcp_gpu_db_calibrate_tail).  A k outside 2 .. n is refused before the batch is replaced."""
+        if not (0 <= n < 2 ** 32 and 0 <= length < 2 ** 32 and 0 <= seed < 2 ** 64 and 0 <= k < 2 ** 32):
+            raise DcpError(RC_EINVAL, "n, length and k in 32 bits, seed in 64")
+        probs = _probs(probs)
+        mu, lam, status = self._fit_outputs()
+        tau, k_eff = np.zeros(len(mu), np.float64), np.zeros(len(mu), np.uint32)
+        self._check(self._lib.dcp_gpu_db_calibrate_tail(self._c, n, length, seed, None if probs is None else probs.ctypes.data,
+                                                        int(multi_hits), int(hmmer3_compat), int(kernel), int(k),
+                                                        mu.ctypes.data, lam.ctypes.data, status.ctypes.data, tau.ctypes.data,
+                                                        k_eff.ctypes.data))
+        self._seq_lens = np.full(n, length, np.int64)
+        return mu, lam, status, tau, k_eff
+
+    def calib_tail_kernel_ms(self, which):
+        """Milliseconds of the last tail selection kernel (which = 0) or tail fit kernel (1) alone, by HIP events;
+        negative if none has run."""
+        return self._lib.dcp_gpu_calib_tail_kernel_ms(self._c, which)
 
     def calib_kernel_ms(self, which):
         """Milliseconds of the last generator kernel (which = 0) or fit kernel (1) alone, by HIP events; negative if

@@ -138,6 +138,121 @@ template <class X> DCP_HD inline int dcp_gumbel_fit_rule(X const &x, unsigned n,
     return DCP_FITR_OK;
 }
 
+// ---- the tail fit -------------------------------------------------------------------------------------------------
+// A censored fit: only the scores >= tau, the k-th largest, enter with their values; the z others enter as "below
+// tau".  Two rules, each one launch on the device: the selection, which only compares and is exact, and the fit.
+
+// An order-preserving key: a < b <=> key(a) < key(b) for finite a, b, and zeros of either sign share one key (v + 0.0
+// is +0.0 for both), so that key order is value order.
+DCP_HD inline uint64_t dcp_fit_key(double v)
+{
+    v += 0.0;
+    uint64_t b;
+    __builtin_memcpy(&b, &v, sizeof b);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+
+// tau = the k-th largest of x(0) .. x(n - 1) by value, 2 <= k <= n (the caller checks), and k_eff = #{x >= tau} >= k:
+// 66 passes.  Pass 1: non-finite -> NONFINITE, tau = NaN, k_eff = 0.  Then the key of the k-th largest, bit by bit from
+// the top: the largest K with #{key >= K} >= k, one counting pass per bit.  Last pass: k_eff, and tau as the minimum of
+// the values that have key >= K, taken as pass 1 of dcp_gumbel_fit_rule takes its minimum (with k = n: its bits).
+template <class X> DCP_HD inline int dcp_tail_select_rule(X const &x, unsigned n, unsigned k, double *tau, unsigned *k_eff)
+{
+    *tau = dcp_fit_nan();
+    *k_eff = 0u;
+    bool bad = false;
+    dcp_fit_pass(x, n, [&](double v) { bad |= !dcp_fit_finite(v); });
+    if (bad) return DCP_FITR_NONFINITE;
+    uint64_t key = 0u;
+    for (int bit = 63; bit >= 0; --bit)
+    {
+        uint64_t const cand = key | (1ull << bit);
+        unsigned cnt = 0u;
+        dcp_fit_pass(x, n, [&](double v) { cnt += dcp_fit_key(v) >= cand ? 1u : 0u; });
+        key = cnt >= k ? cand : key;
+    }
+    double m = 1.7976931348623157e308;
+    unsigned ke = 0u;
+    dcp_fit_pass(x, n, [&](double v) {
+        bool const in = dcp_fit_key(v) >= key;
+        m = in && v < m ? v : m;
+        ke += in ? 1u : 0u;
+    });
+    *tau = m;
+    *k_eff = ke;
+    return DCP_FITR_OK;
+}
+
+// The censored maximum-likelihood fit, given tau and k_eff = #{x >= tau} of dcp_tail_select_rule: 16 passes, the
+// steps and statuses of dcp_gumbel_fit_rule.  log L = k_eff ln lambda - lambda sum_obs (x - mu) - sum_obs exp(-lambda
+// (x - mu)) - z exp(-lambda (tau - mu)), z = n - k_eff, the observed set {x >= tau} summed in index order.  Pass 1 and 2
+// over all n: NONFINITE; the whole sample's variance, 0 -> FLAT, else lambda = pi / sqrt(6 var).  Pass 3: gap = (sum_obs
+// x) / k_eff - tau; 0 -> FLAT (the whole observed set sits at tau).  Newton on
+//   f(lambda) = 1 / lambda - gap + s1 / s0,  s0 = sum_obs exp(-lambda y) + z,  s_k = sum_obs y^k exp(-lambda y),  y = x - tau >= 0
+// and mu = tau - log(s0 / k_eff) / lambda.  With k_eff = n (tau the minimum, z = 0) these are the sums of
+// dcp_gumbel_fit_rule in its order: the same bits.
+template <class X>
+DCP_HD inline int dcp_gumbel_fit_tail_rule(X const &x, unsigned n, double tau, unsigned k_eff, double *mu, double *lambda)
+{
+    *mu = *lambda = dcp_fit_nan();
+    bool bad = false;
+    double sum = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        bad |= !dcp_fit_finite(v);
+        sum += v;
+    });
+    if (bad) return DCP_FITR_NONFINITE;
+    double const mean = sum / (double)n;
+    double ss = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        double const d = v - mean;
+        ss += d * d;
+    });
+    double const var = ss / (double)(n - 1u);
+    if (var == 0.0) return DCP_FITR_FLAT;
+    double lam = 3.14159265358979323846 / sqrt(6.0 * var);
+    double so = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        if (v >= tau) so += v;
+    });
+    double const ke = (double)k_eff, z = (double)(n - k_eff);
+    double const gap = so / ke - tau;
+    if (gap == 0.0) return DCP_FITR_FLAT;
+    bool diverged = false, settled = false;
+    for (int step = 0; step < DCP_FIT_STEPS; ++step)
+    {
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        dcp_fit_pass(x, n, [&](double v) {
+            if (v >= tau)
+            {
+                double const y = v - tau;
+                double const w = exp(-(lam * y));
+                s0 += w;
+                s1 += y * w;
+                s2 += (y * y) * w;
+            }
+        });
+        s0 += z;
+        double const r = s1 / s0;
+        double const f = 1.0 / lam - gap + r;
+        double const df = -1.0 / (lam * lam) - s2 / s0 + r * r;
+        double next = lam - f / df;
+        if (!dcp_fit_finite(next) || !(next > 0.0)) diverged = true, next = lam;
+        double const moved = next > lam ? next - lam : lam - next;
+        settled = moved <= 0x1p-40 * next;
+        lam = next;
+    }
+    double s0 = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        if (v >= tau) s0 += exp(-(lam * (v - tau)));
+    });
+    s0 += z;
+    if (diverged || !settled) return DCP_FITR_DIVERGED;
+    *lambda = lam;
+    *mu = tau - log(s0 / ke) / lam;
+    return DCP_FITR_OK;
+}
+
 // ---- the launches (dcp_calib.hip) -----------------------------------------------------------------------------------
 extern "C" {
 // A batch of nseqs sequences of len bases in the resident layout (dcp_seqs.hip: len / 16 + 3 words each, every bit
@@ -149,6 +264,13 @@ int dcp_launch_random(uint32_t *words, uint32_t *woff, uint32_t *len_out, unsign
 // mu / lambda [nprof] doubles, status [nprof] bytes.  real_bytes: 4 (float matrices) or 8.  One launch on `stream`.
 int dcp_launch_gumbel_fit(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof, int real_bytes,
                           double *mu, double *lambda, uint8_t *status, void *stream);
+// The tail fit of the same x, 2 <= k <= nseqs (the caller checks), as two launches on `stream`.  The selection writes
+// tau / k_eff [nprof] (NaN and 0 in a lane with a non-finite score); the fit reads them and writes mu / lambda / status.
+int dcp_launch_tail_select(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof, int real_bytes,
+                           unsigned k, double *tau, uint32_t *k_eff, void *stream);
+int dcp_launch_gumbel_fit_tail(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof,
+                               int real_bytes, double const *tau, uint32_t const *k_eff, double *mu, double *lambda,
+                               uint8_t *status, void *stream);
 }
 
 #endif

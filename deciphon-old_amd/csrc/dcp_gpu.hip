@@ -373,6 +373,12 @@ struct dcp_gpu_ctx
     DevBuf<uint8_t> d_fit_status;
     hipEvent_t ev_calib[4] = {nullptr, nullptr, nullptr, nullptr};
     bool calib_timed[2] = {false, false};
+    // the tail fit: tau [nprof] and k_eff [nprof] of the last selection (mu, lambda and status go through d_fit and
+    // d_fit_status), and events around the last tail_select_kernel ([0], [1]) and gumbel_fit_tail_kernel ([2], [3])
+    DevBuf<double> d_tail_tau;
+    DevBuf<uint32_t> d_tail_keff;
+    hipEvent_t ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool tail_timed = false;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -697,6 +703,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     for (hipEvent_t e : c->ev_dom)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_calib)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_tail)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -3549,11 +3557,9 @@ int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
     return fetch_scores(c, c->f64.res, null_out, alt_out);
 }
 
-// One Gumbel fit per resident profile over the last scan's dense scores (dcp_calib.hip).
-int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8_t *status_out)
+// What either fit needs: a scan of the whole batch that kept its dense scores, completed.
+static int fit_ready(dcp_gpu_ctx *c)
 {
-    if (!c) return DCP_EINVAL;
-    if (!mu_out || !lambda_out || !status_out) return c->fail(DCP_EINVAL, "dcp_gpu_fit_gumbel: a null output");
     if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet: the fit is over the last scan's dense scores");
     bool const have = c->last_f64 ? c->f64.res.have_scores : c->res.have_scores;
     if (c->last_pair_scan || !have)
@@ -3563,7 +3569,15 @@ int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8
                        c->last_q1, c->nseqs);
     if (c->nseqs < 2u) return c->fail(DCP_EINVAL, "a fit needs at least 2 sequences: %u resident", c->nseqs);
     HIP_TRY(c, hipSetDevice(c->device));
-    if (int rc = finish_scan(c)) return rc; // a query-lane scan completes its redo pairs there
+    return finish_scan(c); // a query-lane scan completes its redo pairs there
+}
+
+// One Gumbel fit per resident profile over the last scan's dense scores (dcp_calib.hip).
+int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8_t *status_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out) return c->fail(DCP_EINVAL, "dcp_gpu_fit_gumbel: a null output");
+    if (int rc = fit_ready(c)) return rc;
     unsigned const np = c->nprof;
     if (c->d_fit.n < 2u * (size_t)np) HIP_TRY(c, c->d_fit.alloc(2u * (size_t)np));
     if (c->d_fit_status.n < np) HIP_TRY(c, c->d_fit_status.alloc(np));
@@ -3588,10 +3602,10 @@ int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8
     return DCP_OK;
 }
 
-int dcp_gpu_db_calibrate(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4], int multi_hits,
-                         int hmmer3_compat, int kernel, double *mu_out, double *lambda_out, uint8_t *status_out)
+// The first two steps of a calibration: the random batch, and its scan with dense scores and no hit records.
+static int calibration_scan(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4], int multi_hits,
+                            int hmmer3_compat, int kernel)
 {
-    if (!c) return DCP_EINVAL;
     if (int rc = dcp_gpu_seqs_random(c, nseqs, len, seed, probs)) return rc;
     struct dcp_scan_params prm = {};
     prm.multi_hits = multi_hits, prm.hmmer3_compat = hmmer3_compat;
@@ -3604,8 +3618,82 @@ int dcp_gpu_db_calibrate(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t 
     int rc = dcp_gpu_scan(c, &prm);
     if (!rc) rc = dcp_gpu_sync(c);
     c->lrt_threshold64 = thr64;
-    if (rc) return rc;
+    return rc;
+}
+
+int dcp_gpu_db_calibrate(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4], int multi_hits,
+                         int hmmer3_compat, int kernel, double *mu_out, double *lambda_out, uint8_t *status_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = calibration_scan(c, nseqs, len, seed, probs, multi_hits, hmmer3_compat, kernel)) return rc;
     return dcp_gpu_fit_gumbel(c, mu_out, lambda_out, status_out);
+}
+
+// The tail fit: the k-th largest score per profile, then the censored fit over the scores from it up (dcp_calib.hip).
+int dcp_gpu_fit_gumbel_tail(dcp_gpu_ctx *c, unsigned k, double *mu_out, double *lambda_out, uint8_t *status_out,
+                            double *tau_out, uint32_t *k_eff_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out || !tau_out || !k_eff_out)
+        return c->fail(DCP_EINVAL, "dcp_gpu_fit_gumbel_tail: a null output");
+    if (int rc = fit_ready(c)) return rc;
+    if (k < 2u || k > c->nseqs)
+        return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the resident sequences", k, c->nseqs);
+    unsigned const np = c->nprof;
+    if (c->d_fit.n < 2u * (size_t)np) HIP_TRY(c, c->d_fit.alloc(2u * (size_t)np));
+    if (c->d_fit_status.n < np) HIP_TRY(c, c->d_fit_status.alloc(np));
+    if (c->d_tail_tau.n < np) HIP_TRY(c, c->d_tail_tau.alloc(np));
+    if (c->d_tail_keff.n < np) HIP_TRY(c, c->d_tail_keff.alloc(np));
+    for (hipEvent_t &e : c->ev_tail)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    void const *nl = c->last_f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
+    void const *al = c->last_f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
+    int const real_bytes = c->last_f64 ? 8 : 4;
+    HIP_TRY(c, hipEventRecord(c->ev_tail[0], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_tail_select(nl, al, c->nseqs, np, real_bytes, k, c->d_tail_tau.p, c->d_tail_keff.p,
+                                                   c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_tail[1], c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_tail[2], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_gumbel_fit_tail(nl, al, c->nseqs, np, real_bytes, c->d_tail_tau.p, c->d_tail_keff.p,
+                                                       c->d_fit.p, c->d_fit.p + np, c->d_fit_status.p, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_tail[3], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->tail_timed = true;
+    // into buffers of the call's own first: the caller's arrays stay untouched if a copy fails
+    std::vector<double> fit(3u * (size_t)np);
+    std::vector<uint32_t> ke(np);
+    std::vector<uint8_t> st(np);
+    HIP_TRY(c, hipMemcpy(fit.data(), c->d_fit.p, 2u * (size_t)np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(fit.data() + 2u * (size_t)np, c->d_tail_tau.p, np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ke.data(), c->d_tail_keff.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(st.data(), c->d_fit_status.p, np, hipMemcpyDeviceToHost));
+    std::memcpy(mu_out, fit.data(), np * sizeof(double));
+    std::memcpy(lambda_out, fit.data() + np, np * sizeof(double));
+    std::memcpy(tau_out, fit.data() + 2u * (size_t)np, np * sizeof(double));
+    std::memcpy(k_eff_out, ke.data(), np * sizeof(uint32_t));
+    std::memcpy(status_out, st.data(), np);
+    return DCP_OK;
+}
+
+int dcp_gpu_db_calibrate_tail(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4],
+                              int multi_hits, int hmmer3_compat, int kernel, unsigned k, double *mu_out, double *lambda_out,
+                              uint8_t *status_out, double *tau_out, uint32_t *k_eff_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out || !tau_out || !k_eff_out)
+        return c->fail(DCP_EINVAL, "dcp_gpu_db_calibrate_tail: a null output");
+    if (nseqs != 0 && (k < 2u || k > nseqs)) // before the batch is replaced (nseqs == 0 is the generator's refusal)
+        return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the sequences asked for", k, nseqs);
+    if (int rc = calibration_scan(c, nseqs, len, seed, probs, multi_hits, hmmer3_compat, kernel)) return rc;
+    return dcp_gpu_fit_gumbel_tail(c, k, mu_out, lambda_out, status_out, tau_out, k_eff_out);
+}
+
+float dcp_gpu_calib_tail_kernel_ms(dcp_gpu_ctx *c, int which)
+{
+    float ms = -1.0f;
+    if (!c || which < 0 || which > 1 || !c->tail_timed) return -1.0f;
+    if (hipEventElapsedTime(&ms, c->ev_tail[2 * which], c->ev_tail[2 * which + 1]) != hipSuccess) return -1.0f;
+    return ms;
 }
 
 float dcp_gpu_calib_kernel_ms(dcp_gpu_ctx *c, int which)

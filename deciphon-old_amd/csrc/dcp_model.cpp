@@ -1788,6 +1788,16 @@ int dcp_gumbel_fit(double const *x, unsigned n, size_t stride, double *mu, doubl
     return dcp_gumbel_fit_rule([=](unsigned i) { return x[(size_t)i * stride]; }, n, mu, lambda);
 }
 
+int dcp_gumbel_fit_tail(double const *x, unsigned n, size_t stride, unsigned k, double *mu, double *lambda, double *tau,
+                        unsigned *k_eff)
+{
+    if (!x || !mu || !lambda || !tau || !k_eff || n < 2u || stride == 0 || k < 2u || k > n) return DCP_EINVAL;
+    auto const at = [=](unsigned i) { return x[(size_t)i * stride]; };
+    *mu = *lambda = dcp_fit_nan();
+    if (int st = dcp_tail_select_rule(at, n, k, tau, k_eff)) return st;
+    return dcp_gumbel_fit_tail_rule(at, n, *tau, *k_eff, mu, lambda);
+}
+
 double dcp_gumbel_sf(double mu, double lambda, double s) { return -std::expm1(-std::exp(-lambda * (s - mu))); }
 
 } // extern "C"

@@ -827,7 +827,7 @@ int dcp_gpu_seqs_random(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t se
 enum dcp_fit_status
 {
     DCP_FIT_OK = 0,
-    DCP_FIT_FLAT = 16,      /* every score the same: no variance, nothing to fit */
+    DCP_FIT_FLAT = 16,      /* every score the same (the tail fit: or every score of the tail): nothing to fit */
     DCP_FIT_NONFINITE = 17, /* a score is +-inf or NaN (an epsilon = 0 profile on a sequence it cannot emit) */
     DCP_FIT_DIVERGED = 18,  /* a step gave a lambda not finite or not positive, or the twelfth still moved it by > 2^-40 of itself */
 };
@@ -860,6 +860,41 @@ int dcp_gpu_db_calibrate(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t s
 /* Milliseconds, by HIP events around the kernel alone, of the context's last random_words_kernel (which = 0) or
  * gumbel_fit_kernel (1); negative if none has run. */
 float dcp_gpu_calib_kernel_ms(dcp_gpu_ctx *, int which);
+/* The tail fit: a censored maximum-likelihood fit, for an E-value is only ever read in the upper tail.
+ * tau = the k-th largest of the n values, compared by value (zeros of either sign are one value); the observed set is
+ * every x >= tau, k_eff >= k of them (more where values tie at tau), taken in index order wherever it is summed; the
+ * other z = n - k_eff enter only as "below tau": log L = k_eff ln lambda - lambda sum_obs (x - mu) - sum_obs exp(-lambda
+ * (x - mu)) - z exp(-lambda (tau - mu)).  The steps and statuses are dcp_gumbel_fit's: pass 1 over all n (a non-finite
+ * x is DCP_FIT_NONFINITE); the whole sample's variance (0 is DCP_FIT_FLAT) and lambda = pi / sqrt(6 var); gap = (sum_obs
+ * x) / k_eff - tau, and gap == 0 -- the whole observed set sits at tau -- is DCP_FIT_FLAT too; then exactly 12 Newton
+ * steps with y = x - tau >= 0 over the observed set, w = exp(-lambda y), s0 = sum w + z, s1 = sum y w, s2 = sum (y y) w, r =
+ * s1 / s0: f = 1 / lambda - gap + r, df = -1 / (lambda lambda) - s2 / s0 + r r, and DCP_FIT_DIVERGED as there; mu = tau -
+ * log(s0 / k_eff) / lambda.  With k = n this is dcp_gumbel_fit in bits: tau the minimum, z = 0, the same sums in the same
+ * order.  tau and k_eff are written with every status but DCP_FIT_NONFINITE, which writes NaN and 0; mu and lambda are
+ * NaN with every status but DCP_FIT_OK.  DCP_EINVAL, nothing written: n < 2, stride == 0, k < 2, k > n, a null
+ * pointer.
+ *
+ * The fitted law is still Gumbel(mu, lambda): dcp_gumbel_sf and dcp_hits_evalues[64] take the arrays unchanged.  But it is
+ * fitted to scores >= tau[p] only.  For a hit that scores below tau[p] the E-value is at least about nsearched
+ * k_eff / n -- such a hit is not significant, and its E-value is not calibrated. */
+int dcp_gumbel_fit_tail(double const *x, unsigned n, size_t stride, unsigned k, double *mu, double *lambda, double *tau,
+                        unsigned *k_eff);
+/* The same fit, one lane per resident profile, over the dense matrices the last scan left on the device: two launches
+ * (csrc/dcp_calib.hip: tail_select_kernel finds tau and k_eff by comparisons alone -- the host's bits; gumbel_fit_tail_kernel
+ * differs from the host in exp, log and sqrt only).  mu_out / lambda_out / tau_out [nprofiles] doubles, status_out
+ * [nprofiles] of enum dcp_fit_status, k_eff_out [nprofiles].  The preconditions, the messages and the synchronisation
+ * of dcp_gpu_fit_gumbel, and the scan's results stay valid; k < 2 or k > the resident sequences is DCP_EINVAL with a
+ * message too.  The outputs are untouched on every error. */
+int dcp_gpu_fit_gumbel_tail(dcp_gpu_ctx *, unsigned k, double *mu_out, double *lambda_out, uint8_t *status_out,
+                            double *tau_out, uint32_t *k_eff_out);
+/* dcp_gpu_db_calibrate's three steps with dcp_gpu_fit_gumbel_tail(k) as the third; what it leaves resident and what it
+ * restores are the same.  A null output, or k < 2 or k > nseqs, is refused before the batch is replaced. */
+int dcp_gpu_db_calibrate_tail(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4],
+                              int multi_hits, int hmmer3_compat, int kernel, unsigned k, double *mu_out, double *lambda_out,
+                              uint8_t *status_out, double *tau_out, uint32_t *k_eff_out);
+/* Milliseconds, by HIP events around the kernel alone, of the context's last tail_select_kernel (which = 0) or
+ * gumbel_fit_tail_kernel (1); negative if none has run. */
+float dcp_gpu_calib_tail_kernel_ms(dcp_gpu_ctx *, int which);
 /* P(X > s) under the fit: -expm1(-exp(-lambda (s - mu))) -- expm1 keeps the relative precision far in the tail, where
  * the probability is exp(-lambda (s - mu)) itself. */
 double dcp_gumbel_sf(double mu, double lambda, double s);

@@ -297,6 +297,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_fetch_table_span"] = (I, [P, U, P, C.c_ulonglong, C.POINTER(U), C.POINTER(U), C.POINTER(U)])
         sig["dcp_gpu_test_fetch_seq_words"] = (I, [P, U, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_last_rowsweep_plan"] = (I, [P, P, U, C.POINTER(U)])
+        sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -1295,6 +1296,27 @@ class Scanner:
                 classes[(R, W)] = dict(path=("plain", "mp", "segmented")[path - 1], stage=stage, waves=waves, prefetch=pf,
                                        chunk=chunk, seg_redo=redo, flagged_rest=bool(rest))
         return dict(forked=bool(w[0]), classes=classes)
+
+    def test_pair_launches(self):
+        """TEST-ONLY (test-hooks build, read-only): the pair-mode launches of the last scan or scan_pairs call, in launch
+        order (dcp_gpu_test_last_pair_launches): a list of {"kind": "scan_pairs" | "qlane_redo" | "seg_redo",
+        "precision": 32 | 64, "cls": (R, W) of the float size class, or "group": 0 .. 3 of the double launch group and
+        "R" its nodes per lane, "units": blocks (float) or wavefronts (double) launched, "tpb": tasks per block,
+        "cap": the list capacity the kernel was given}.  Waits for the stream and completes nothing: after a scan
+        whose redo lists overflowed, ask before anything that repeats it (hits, scores, last_scan_redo_pairs)."""
+        n = C.c_uint(0)
+        rc = self._lib.dcp_gpu_test_last_pair_launches(self._c, None, 0, C.byref(n))
+        if rc != RC_ENOMEM:
+            self._check(rc or RC_EFAIL)
+        w = np.zeros(n.value, np.uint32)
+        self._check(self._lib.dcp_gpu_test_last_pair_launches(self._c, w.ctypes.data, len(w), C.byref(n)))
+        out = []
+        for i in range(int(w[0])):
+            kind, prec, a, b, units, tpb, cap = (int(v) for v in w[1 + 7 * i:8 + 7 * i])
+            rec = dict(kind=("scan_pairs", "qlane_redo", "seg_redo")[kind - 1], precision=prec, units=units, tpb=tpb, cap=cap)
+            rec.update(dict(cls=(a, b)) if prec == 32 else dict(group=a, R=b))
+            out.append(rec)
+        return out
 
     def test_set_rowsweep_variant(self, stage_rows, block_waves=0):
         """TEST-ONLY (test-hooks build): force the grid-mode row-sweep kernel variant; stage_rows < 0: automatic."""

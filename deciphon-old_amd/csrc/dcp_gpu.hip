@@ -298,6 +298,12 @@ struct dcp_gpu_ctx
         unsigned chunk = 0;        // segmented: queries per pass
         unsigned flagged_rest = 0; // K profiles per wavefront: the flagged profiles got a launch of their own
     } rs_plan[kNumClasses];
+    // test hook (dcp_gpu_test_last_pair_launches): the pair-mode launches of the last scan or pair scan, in launch order
+    struct PairLaunch
+    {
+        unsigned kind, precision, a, b, units, tpb, cap;
+    };
+    std::vector<PairLaunch> pair_launches;
 #endif
 
     // The resident DB is float (dcp_gpu_db_upload) or double (dcp_gpu_db_upload64): 32 / 64, 0 while none is.
@@ -2528,6 +2534,9 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     unsigned launches = 0;
+#ifdef DCP_TEST_HOOKS
+    c->pair_launches.clear();
+#endif
     if (qlane)
     {
         dcp_f64_launch_qlane(&qa, ql_blocks, c->stream);
@@ -2551,6 +2560,9 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
                 return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
             HIP_TRY(c, hipGetLastError());
             ++launches;
+#ifdef DCP_TEST_HOOKS
+            c->pair_launches.push_back({DCP_PL_QLANE_REDO, 64u, (unsigned)g, (unsigned)kF64R[g], (unsigned)waves, 1u, pa.pair_cap});
+#endif
         }
     }
     for (int g = 0; g < 4 && !qlane; ++g)
@@ -2849,6 +2861,9 @@ static int launch_qlane_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, 
         if (dcp_launch_rowsweep(sc.R, sc.W, &a, redo_grid[k], c->stream))
             return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
         if (int rc = record_launch(c, k, true, c->stream, false)) return rc;
+#ifdef DCP_TEST_HOOKS
+        c->pair_launches.push_back({DCP_PL_QLANE_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, redo_grid[k], dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap});
+#endif
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
@@ -2945,6 +2960,9 @@ static int launch_segsweep_class(dcp_gpu_ctx *c, dcp_scan_args &a, int k, SegSwe
     g = (g + 7u) / 8u * 8u;
     if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)g, ls))
         return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
+#ifdef DCP_TEST_HOOKS
+    c->pair_launches.push_back({DCP_PL_SEG_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, (unsigned)g, dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap});
+#endif
     return record_launch(c, k, true, ls, overlap);
 }
 
@@ -3105,6 +3123,9 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     c->last_launches = 0;
     c->n_launched = 0;
+#ifdef DCP_TEST_HOOKS
+    c->pair_launches.clear();
+#endif
     if (kernel == 2) return launch_qlane_scan(c, prm, a, ql_nt, ql_blocks_per_cu, two_stage, w3 && !two_stage);
     return launch_rowsweep_scan(c, a, q_begin, q_end);
 }
@@ -3174,6 +3195,9 @@ static int scan_pairs64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint3
     HIP_TRY(c, hipMemsetAsync(pa.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     unsigned launches = 0;
+#ifdef DCP_TEST_HOOKS
+    c->pair_launches.clear();
+#endif
     for (int g = 0; g < 4; ++g)
     {
         if (count[g] == 0) continue;
@@ -3188,6 +3212,9 @@ static int scan_pairs64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint3
             return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
         HIP_TRY(c, hipGetLastError());
         ++launches;
+#ifdef DCP_TEST_HOOKS
+        c->pair_launches.push_back({DCP_PL_SCAN_PAIRS, 64u, (unsigned)g, (unsigned)kF64R[g], (unsigned)waves, 1u, pa.pair_cap});
+#endif
     }
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
     c->last_q0 = 0, c->last_q1 = c->nseqs;
@@ -3278,6 +3305,7 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
 #ifdef DCP_TEST_HOOKS
     for (int k = 0; k < kNumClasses; ++k)
         c->rs_plan[k] = {};
+    c->pair_launches.clear();
 #endif
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
@@ -3293,6 +3321,9 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
         if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)((g + 7u) / 8u * 8u), c->stream))
             return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
         if (int rc = record_launch(c, k, false, c->stream, false)) return rc;
+#ifdef DCP_TEST_HOOKS
+        c->pair_launches.push_back({DCP_PL_SCAN_PAIRS, 32u, (unsigned)sc.R, (unsigned)sc.W, (unsigned)((g + 7u) / 8u * 8u), (unsigned)tpb, a.pair_cap});
+#endif
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
@@ -3388,6 +3419,23 @@ int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *c, unsigned *out, unsigned cap,
         dcp_gpu_ctx::RowsweepClassPlan const &r = c->rs_plan[k];
         w[0] = (unsigned)kClasses[k].R, w[1] = (unsigned)kClasses[k].W, w[2] = r.path, w[3] = r.stage, w[4] = r.waves;
         w[5] = r.prefetch, w[6] = r.chunk, w[7] = r.path == DCP_RS_PATH_SEGMENTED ? redo[k] : 0u, w[8] = r.flagged_rest;
+    }
+    return DCP_OK;
+}
+int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *c, unsigned *out, unsigned cap, unsigned *nwords)
+{
+    if (!c || !nwords) return DCP_EINVAL;
+    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    *nwords = 1u + DCP_PL_WORDS * (unsigned)c->pair_launches.size();
+    if (!out || cap < *nwords) return DCP_ENOMEM;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    out[0] = (unsigned)c->pair_launches.size();
+    unsigned *w = out + 1u;
+    for (dcp_gpu_ctx::PairLaunch const &l : c->pair_launches)
+    {
+        w[0] = l.kind, w[1] = l.precision, w[2] = l.a, w[3] = l.b, w[4] = l.units, w[5] = l.tpb, w[6] = l.cap;
+        w += DCP_PL_WORDS;
     }
     return DCP_OK;
 }

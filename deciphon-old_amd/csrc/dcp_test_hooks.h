@@ -12,6 +12,11 @@
 #define DCP_RS_PATH_MP 2u        // K profiles per wavefront (viterbi_mp_kernel)
 #define DCP_RS_PATH_SEGMENTED 3u // one segment per launch (viterbi_segment_kernel), the exact kernel behind it
 #define DCP_RS_PLAN_WORDS 9u
+// which driver launched a row-sweep kernel in pair mode
+#define DCP_PL_SCAN_PAIRS 1u // dcp_gpu_scan_pairs: the host's list of a size class / launch group
+#define DCP_PL_QLANE_REDO 2u // a query-lane scan's redo list (launch_qlane_scan; scan64 with kernel 4)
+#define DCP_PL_SEG_REDO 3u   // the segmented sweep's seg_redo list (launch_segsweep_class)
+#define DCP_PL_WORDS 7u
 
 extern "C" {
 // What the last scan did, if it was a float row-sweep scan (else DCP_EINVAL); waits for it.  *nwords receives
@@ -22,6 +27,14 @@ extern "C" {
 //   not part of dcp_gpu_last_scan_redo_pairs); K profiles per wavefront: 1 if the flagged profiles of the class got
 //   a launch of the one-profile kernel}.  Changes nothing.
 int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *, unsigned *out, unsigned cap, unsigned *nwords);
+// The pair-mode launches of the last scan or dcp_gpu_scan_pairs call, in launch order; waits for the stream, looks at
+// no redo counter (a scan whose lists overflowed is repeated by the next call that completes it -- the repeat is a
+// dense row sweep: no pair-mode launch).  *nwords receives 1 + DCP_PL_WORDS x launches, out -- if cap holds them, else
+// DCP_ENOMEM -- the words [0] the number of launches, then per launch {DCP_PL_*, 32 | 64 the DB's precision,
+//   float: nodes per lane and wavefronts per pair of the size class; double: the launch group 0 .. 3 and its nodes per lane,
+//   blocks (float) / wavefronts (double) launched, tasks per block (double: 1 per wavefront), the list capacity the
+//   kernel was given (pair_cap)}.  Changes nothing.
+int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *, unsigned *out, unsigned cap, unsigned *nwords);
 }
 #endif
 

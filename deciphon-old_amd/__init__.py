@@ -96,6 +96,8 @@ ABI_SYMBOLS = [
     "dcp_gpu_db_calibrate", "dcp_gpu_calib_kernel_ms", "dcp_gumbel_sf", "dcp_hits_evalues", "dcp_hits_evalues64",
     # the tail fit: the k-th largest score per profile, a censored Gumbel fit over the scores from it up
     "dcp_gumbel_fit_tail", "dcp_gpu_fit_gumbel_tail", "dcp_gpu_db_calibrate_tail", "dcp_gpu_calib_tail_kernel_ms",
+    # Forward scores of a pair list: a log-sum-exp sweep on the device, and its host twin
+    "dcp_forward_tables", "dcp_gpu_forward_pairs", "dcp_gpu_forward_kernel_ms",
 ]
 
 
@@ -287,6 +289,9 @@ def _load(path=None, hooks=False):
         "dcp_gumbel_sf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
         "dcp_hits_evalues": (I, [P, U, P, P, P, U, C.c_double, P]),
         "dcp_hits_evalues64": (I, [P, U, P, P, P, U, C.c_double, P]),
+        "dcp_forward_tables": (I, [U, U, P, P, P, P, P, P, U, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "dcp_gpu_forward_pairs": (I, [P, I, I, P, P, U, P, P]),
+        "dcp_gpu_forward_kernel_ms": (F, [P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -298,6 +303,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_fetch_seq_words"] = (I, [P, U, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_last_rowsweep_plan"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
+        sig["dcp_gpu_test_set_forward_waves"] = (I, [P, U])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -632,6 +638,23 @@ def xtrans64(seq_size, multi_hits=True, hmmer3_compat=False):
     if rc:
         raise DcpError(rc, "sequence cannot be empty")
     return out
+
+
+def forward_tables(t8, em, ei, en, xt, seq):
+    """(null, alt) Forward scores of one sequence against one profile on the host (dcp_forward_tables): the scan's
+    recursion with every max replaced by log-sum-exp, in double.  t8 [8, ldk], em [1364, ldk], ei [1364], en [1364],
+    xt [13], seq base ids 0..3; the arrays are converted to float64, so float tables go in as they are."""
+    t8, em, ei, en, xt = _f64(t8), _f64(em), _f64(ei), _f64(en), _f64(xt)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if t8.ndim != 2 or em.ndim != 2 or t8.shape != (8, em.shape[1]) or em.shape[0] != NCODES or \
+            ei.shape != (NCODES,) or en.shape != (NCODES,) or xt.shape != (NXTRANS,) or seq.ndim != 1:
+        raise DcpError(RC_EINVAL, "tables of shapes [8, ldk], [1364, ldk], [1364], [1364], [13]")
+    null, alt = C.c_double(0.0), C.c_double(0.0)
+    rc = lib.dcp_forward_tables(em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data,
+                                xt.ctypes.data, seq.ctypes.data, len(seq), C.byref(null), C.byref(alt))
+    if rc:
+        raise DcpError(rc, "dcp_forward_tables")
+    return null.value, alt.value
 
 
 def lrt(null_loglik, alt_loglik):
@@ -1216,6 +1239,29 @@ class Scanner:
         self._check(self._lib.dcp_gpu_scan_pairs(self._c, C.byref(prm), sq.ctypes.data, pr.ctypes.data, len(sq)))
         if sync:
             self.sync()
+
+    def forward_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
+        """(null, alt) Forward scores, float64 arrays in list order, of the pairs (resident sequence seq_idx[i],
+        resident profile profile_idx[i]) on a float or a double DB (dcp_gpu_forward_pairs): the log of the summed
+        weight of all paths, where a scan's score is the weight of the best one.  Returns synchronised; the last scan's
+        results stay what they were.  A pair listed twice is scored twice."""
+        sq = np.ascontiguousarray(seq_idx, np.uint32)
+        pr = np.ascontiguousarray(profile_idx, np.uint32)
+        if sq.ndim != 1 or sq.shape != pr.shape:
+            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        null, alt = np.zeros(len(sq), np.float64), np.zeros(len(sq), np.float64)
+        self._check(self._lib.dcp_gpu_forward_pairs(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data,
+                                                    pr.ctypes.data, len(sq), null.ctypes.data, alt.ctypes.data))
+        return null, alt
+
+    @property
+    def forward_kernel_ms(self):
+        """Milliseconds of the last forward_pairs call's kernel launches, by HIP events; negative before any."""
+        return self._lib.dcp_gpu_forward_kernel_ms(self._c)
+
+    def test_set_forward_waves(self, nwaves):
+        """TEST-ONLY (test-hooks build): cap the wavefronts of the following forward_pairs launches (0: default)."""
+        self._check(self._lib.dcp_gpu_test_set_forward_waves(self._c, int(nwaves)))
 
     def set_hit_buffer(self, hits_dev_ptr, cap, nhits_dev_ptr):
         """Route hit records into caller-owned device memory (e.g. a torch tensor for RCCL)."""

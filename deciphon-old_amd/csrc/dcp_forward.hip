@@ -1,0 +1,511 @@
+// dcp_forward.hip -- gfx950 kernels of the Forward scores of a pair list (dcp_gpu_forward_pairs).
+//
+//  forward_kernel<Real, R>   null + alt Forward score of one (sequence, profile) pair per wavefront, R = 1, 2 or 4
+//                            consecutive nodes per lane, the whole profile (at most 64 R nodes) and its history rings
+//                            in registers.
+//  forward_wide_kernel<Real> the same for wider profiles, row-major: for each row the wavefront sweeps all chunks of
+//                            256 columns in order, with the rings of P and Q and the row's M, I, D in a per-wavefront
+//                            work area in global memory (13 x ldk doubles; a lane reads back only what it wrote
+//                            itself), the edge values (M, I, D of the chunk's last node, the running E) carried from
+//                            chunk to chunk in registers.  B(j) follows after the row's last chunk; a second pass over
+//                            the chunks forms P(j) and Q(j) into slot j mod 5.
+//
+// Real is the tables' scalar (a float DB's values are promoted to double, which is exact); the arithmetic is double.
+// The recursion is the Viterbi one of dcp_f64.hip with every max replaced by lse (dcp_forward.h), every candidate
+// (predecessor + transition) or (predecessor + emission) formed once.  Two things max allowed there do not carry over:
+//  * the delete chain D_k = lse(M_{k-1} + MD_k, D_{k-1} + DD_k) is a linear recurrence, not a fixed point: a lane's R
+//    nodes compose to d_out = lse(c, d_in + s), pairs combine as (s1, c1) (+) (s2, c2) = (s1 + s2, lse(c2, c1 + s2)),
+//    an inclusive scan over the 64 lanes (six steps) and the carry of the chunk before give every lane its true d_in,
+//    and the lane's chain is run again from it;
+//  * E(j) over the lanes is a sum: the wave's maximum, every lane's terms scaled by it and added, the lanes' sums added
+//    by a butterfly (the same tree in every lane), chunks merged in the running form.
+// The four special states that emit (N, J, C, R) are one state per lane: lane l & 3 keeps the ring of its own one,
+// and the row's values are read from lanes 0 .. 3.
+//
+// A column at or past core_size is never loaded: its transitions and emissions are -inf by construction here, so the
+// padding columns carry -inf and stay -inf, whatever the DB's own padding is (a float DB's small profiles share rows).
+#include "dcp_forward.h"
+#include "dcp_host.h"
+
+#include <hip/hip_runtime.h>
+
+namespace
+{
+
+__device__ __forceinline__ double ninf() { return -__builtin_inf(); }
+
+// gfx950's DPP moves 32-bit lanes: a double crosses lanes as its two halves (dcp_f64.hip)
+__device__ __forceinline__ double shr1(double v, double first) // value of lane - 1; lane 0 receives `first`
+{
+    unsigned long long const vb = __builtin_bit_cast(unsigned long long, v);
+    unsigned long long const fb = __builtin_bit_cast(unsigned long long, first);
+    int const lo = __builtin_amdgcn_update_dpp((int)(unsigned)fb, (int)(unsigned)vb, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
+    int const hi = __builtin_amdgcn_update_dpp((int)(unsigned)(fb >> 32), (int)(unsigned)(vb >> 32), 0x138, 0xf, 0xf, false);
+    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ double readlane(double v, int lane)
+{
+    unsigned long long const b = __builtin_bit_cast(unsigned long long, v);
+    unsigned const lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
+    unsigned const hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        v = dcp_fwd_max(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+__device__ __forceinline__ double wave_sum(double v) // lane i and lane i ^ o add the same two values: one tree for all
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1)
+        v = v + __shfl_xor(v, o, 64);
+    return v;
+}
+
+struct XF // the pair's special transitions as the rows use them
+{
+    double NB, EB, JB, ET, CT;
+    double xa, xb; // this lane's own special state X of N, J, C, R: PX(j) = lse(E(j) + xa, X(j) + xb)
+};
+
+template <class Real> struct Tabs
+{
+    Real const *tab, *trans, *ei, *en;
+    uint64_t ld;
+    unsigned M;
+    uint32_t const *words;
+};
+
+template <class Real> __device__ __forceinline__ double load_col(Real const *row, unsigned k, unsigned M)
+{
+    return k < M ? (double)row[k] : ninf();
+}
+
+// the last five bases' word codes, the shortest word first
+__device__ __forceinline__ void word_codes(unsigned w, unsigned (&code)[5])
+{
+    constexpr unsigned off[5] = {0u, 4u, 20u, 84u, 340u};
+#pragma unroll
+    for (int l = 0; l < 5; ++l)
+        code[l] = off[l] + (w & ((4u << (2 * l)) - 1u));
+}
+
+// D of the lane's R nodes: a[r] = M_{k-1} + MD_k, dd[r] = DD_k, carry = D of the node before lane 0's first
+template <int R>
+__device__ __forceinline__ void delete_chain(double const (&a)[R], double const (&dd)[R], double carry, double (&d)[R],
+                                             unsigned lane)
+{
+    double c = a[0], s = dd[0]; // the lane's chain from d_in = -inf, and the sum of its DD
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+    {
+        c = dcp_lse2(a[r], c + dd[r]);
+        s = s + dd[r];
+    }
+#pragma unroll
+    for (unsigned o = 1; o < 64u; o <<= 1)
+    {
+        double const sp = __shfl_up(s, o, 64), cp = __shfl_up(c, o, 64);
+        if (lane >= o)
+        {
+            c = dcp_lse2(c, cp + s);
+            s = sp + s;
+        }
+    }
+    // lanes 0 .. l - 1 composed, applied to the carry: lane 0 receives (0, -inf), the identity
+    double const cb = shr1(c, ninf()), sb = shr1(s, 0.0);
+    double const d_in = dcp_lse2(cb, carry + sb);
+    d[0] = dcp_lse2(a[0], d_in + dd[0]);
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+        d[r] = dcp_lse2(a[r], d[r - 1] + dd[r]);
+}
+
+// the lanes' M and D of one chunk as one term of E(j) in the running form
+template <int R> __device__ __forceinline__ dcp_lse_acc exit_terms(double const (&m)[R], double const (&d)[R])
+{
+    double mx = dcp_fwd_max(m[0], d[0]);
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+        mx = dcp_fwd_max(mx, dcp_fwd_max(m[r], d[r]));
+    mx = readlane(wave_max(mx), 0);
+    double const mm = dcp_fwd_shift(mx);
+    double sum = exp(m[0] - mm) + exp(d[0] - mm);
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+        sum = sum + exp(m[r] - mm) + exp(d[r] - mm);
+    return dcp_lse_acc{mx, readlane(wave_sum(sum), 0)};
+}
+
+__device__ __forceinline__ XF special_transitions(double const *xt, unsigned lane)
+{
+    XF x;
+    x.NB = xt[DCP_X_NB], x.EB = xt[DCP_X_EB], x.JB = xt[DCP_X_JB], x.ET = xt[DCP_X_ET], x.CT = xt[DCP_X_CT];
+    unsigned const sp = lane & 3u;
+    x.xa = sp == 1u ? xt[DCP_X_EJ] : sp == 2u ? xt[DCP_X_EC] : ninf(); // N and R have no edge from E
+    x.xb = sp == 0u ? xt[DCP_X_NN] : sp == 1u ? xt[DCP_X_JJ] : sp == 2u ? xt[DCP_X_CC] : xt[DCP_X_RR];
+    return x;
+}
+
+// row 0 of the lane's special state: N = S + SN, R starts at 0, J and C are -inf
+__device__ __forceinline__ double special_row0(double const *xt, unsigned lane)
+{
+    unsigned const sp = lane & 3u;
+    return sp == 0u ? 0.0 + xt[DCP_X_SN] : sp == 3u ? 0.0 : ninf();
+}
+
+// ---- profiles of at most 64 R nodes: everything in registers -------------------------------------------------------
+template <int R> struct Trans
+{
+    double ent[R], mm[R], im[R], dm[R], md[R], dd[R], mi[R], ii[R];
+};
+
+// history rings (State64's shape, dcp_f64.hip): row j's predecessors j - 1 .. j - 5 live in slots (j - l) % 5
+template <int R> struct State
+{
+    double P[5][R], Q[5][R];
+    double PX[5]; // the lane's own special state
+    double E, Cc, Rr;
+    unsigned w;
+};
+
+template <class Real, int R, int PH>
+__device__ __forceinline__ void forward_row(State<R> &s, Trans<R> const &t, XF const &x, Tabs<Real> const &g, unsigned j,
+                                            unsigned lane)
+{
+    constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH}; // slot of row j - l
+    unsigned const i = j - 1u;
+    s.w = ((s.w << 2) | ((g.words[i >> 4] >> ((i & 15u) * 2u)) & 3u)) & 1023u;
+    unsigned code[5];
+    word_codes(s.w, code);
+    unsigned const k0 = lane * R;
+
+    double cm[5][R], ci[5][R], cx[5];
+#pragma unroll
+    for (int l = 0; l < 5; ++l)
+    {
+        double const eI = (double)g.ei[code[l]], eN = (double)g.en[code[l]];
+        Real const *em = g.tab + (uint64_t)code[l] * g.ld;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+        {
+            cm[l][r] = s.P[sl[l]][r] + load_col(em, k0 + r, g.M);
+            ci[l][r] = s.Q[sl[l]][r] + eI;
+        }
+        cx[l] = s.PX[sl[l]] + eN;
+    }
+    double m[R], ins[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+        m[r] = dcp_lse5(cm[0][r], cm[1][r], cm[2][r], cm[3][r], cm[4][r]);
+        ins[r] = dcp_lse5(ci[0][r], ci[1][r], ci[2][r], ci[3][r], ci[4][r]);
+    }
+    double const X = dcp_lse5(cx[0], cx[1], cx[2], cx[3], cx[4]);
+
+    double a[R], d[R];
+    a[0] = shr1(m[R - 1], ninf()) + t.md[0];
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+        a[r] = m[r - 1] + t.md[r];
+    delete_chain<R>(a, t.dd, ninf(), d, lane);
+
+    double const E = dcp_lse_acc_value(exit_terms<R>(m, d));
+    double const N = readlane(X, 0), J = readlane(X, 1), Cc = readlane(X, 2), Rr = readlane(X, 3);
+    double const B = dcp_lse3(N + x.NB, E + x.EB, J + x.JB);
+
+    double const mp = shr1(m[R - 1], ninf()), ip = shr1(ins[R - 1], ninf()), dp = shr1(d[R - 1], ninf());
+    s.P[PH][0] = dcp_lse4(B + t.ent[0], mp + t.mm[0], ip + t.im[0], dp + t.dm[0]);
+#pragma unroll
+    for (int r = 1; r < R; ++r)
+        s.P[PH][r] = dcp_lse4(B + t.ent[r], m[r - 1] + t.mm[r], ins[r - 1] + t.im[r], d[r - 1] + t.dm[r]);
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        s.Q[PH][r] = dcp_lse2(m[r] + t.mi[r], ins[r] + t.ii[r]);
+    s.PX[PH] = dcp_lse2(E + x.xa, X + x.xb);
+    s.E = E, s.Cc = Cc, s.Rr = Rr;
+}
+
+template <class Real> __device__ __forceinline__ Tabs<Real> tables_of(dcp_fwd_args const &a, dcp_fwd_prof const &pr, unsigned q)
+{
+    Tabs<Real> g;
+    g.tab = (Real const *)a.tab + pr.tab_off;
+    g.trans = (Real const *)a.trans + pr.trans_off;
+    g.ei = (Real const *)a.ei + pr.ei_off;
+    g.en = (Real const *)a.en + pr.en_off;
+    g.ld = pr.ld;
+    g.M = pr.core_size;
+    g.words = a.seq_words + a.seq_woff[q];
+    return g;
+}
+
+template <class Real, int R> __global__ __launch_bounds__(256) void forward_kernel(dcp_fwd_args a)
+{
+    unsigned const lane = threadIdx.x & 63u;
+    uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    uint64_t const nw = a.nwaves;
+    if (gw >= nw) return; // the grid's last block may hold wavefronts past nwaves
+    for (uint64_t pair = gw; pair < a.npairs; pair += nw)
+    {
+        dcp_fwd_pair const pp = a.pairs[pair];
+        dcp_fwd_prof const pr = a.profs[pp.prof];
+        unsigned const L = a.seq_len[pp.q];
+        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        XF const x = special_transitions(xt, lane);
+        Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
+        unsigned const k0 = lane * R;
+        Trans<R> t;
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+        {
+            t.ent[r] = load_col(g.trans + DCP_T_ENTRY * g.ld, k0 + r, g.M);
+            t.mm[r] = load_col(g.trans + DCP_T_MM * g.ld, k0 + r, g.M);
+            t.im[r] = load_col(g.trans + DCP_T_IM * g.ld, k0 + r, g.M);
+            t.dm[r] = load_col(g.trans + DCP_T_DM * g.ld, k0 + r, g.M);
+            t.md[r] = load_col(g.trans + DCP_T_MD * g.ld, k0 + r, g.M);
+            t.dd[r] = load_col(g.trans + DCP_T_DD * g.ld, k0 + r, g.M);
+            t.mi[r] = load_col(g.trans + DCP_T_MI * g.ld, k0 + r, g.M);
+            t.ii[r] = load_col(g.trans + DCP_T_II * g.ld, k0 + r, g.M);
+        }
+        // row 0, anew for every pair: S = 0, B = S + SB; the rings are -inf but for row 0's slot
+        State<R> s;
+#pragma unroll
+        for (int h = 0; h < 5; ++h)
+        {
+#pragma unroll
+            for (int r = 0; r < R; ++r)
+                s.P[h][r] = s.Q[h][r] = ninf();
+            s.PX[h] = ninf();
+        }
+        double const B0 = 0.0 + xt[DCP_X_SB];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+            s.P[0][r] = B0 + t.ent[r];
+        s.PX[0] = special_row0(xt, lane);
+        s.E = s.Cc = s.Rr = ninf();
+        s.w = 0u;
+        unsigned j = 1u;
+#define DCP_FWD_ROW(PH)                                                                                                \
+    forward_row<Real, R, PH>(s, t, x, g, j, lane);                                                                     \
+    if (j == L) break;                                                                                                 \
+    ++j;
+        for (;;)
+        {
+            DCP_FWD_ROW(1)
+            DCP_FWD_ROW(2)
+            DCP_FWD_ROW(3)
+            DCP_FWD_ROW(4)
+            DCP_FWD_ROW(0)
+        }
+#undef DCP_FWD_ROW
+        if (lane == 0u)
+        {
+            a.out_null[pp.pos] = s.Rr;
+            a.out_alt[pp.pos] = dcp_lse2(s.E + x.ET, s.Cc + x.CT);
+        }
+    }
+}
+
+// ---- wider profiles: row-major over chunks of 256 columns, the rings in the wavefront's work area ------------------
+constexpr int WR = 4; // nodes per lane of a chunk
+
+struct WideState
+{
+    double PX[5];
+    double E, Cc, Rr;
+    unsigned w;
+};
+
+struct WideArea // rows of ldk doubles: P and Q slots, then the row's M, I, D
+{
+    double *base;
+    uint64_t ldk;
+    unsigned nchunks;
+    __device__ __forceinline__ double *P(int slot) const { return base + (uint64_t)slot * ldk; }
+    __device__ __forceinline__ double *Q(int slot) const { return base + (uint64_t)(5 + slot) * ldk; }
+    __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
+};
+
+template <class Real, int PH>
+__device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs<Real> const &g, WideArea const &wa, unsigned j,
+                                                 unsigned lane)
+{
+    constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
+    unsigned const i = j - 1u;
+    s.w = ((s.w << 2) | ((g.words[i >> 4] >> ((i & 15u) * 2u)) & 3u)) & 1023u;
+    unsigned code[5];
+    word_codes(s.w, code);
+    double eI[5], cx[5];
+#pragma unroll
+    for (int l = 0; l < 5; ++l)
+    {
+        eI[l] = (double)g.ei[code[l]];
+        cx[l] = s.PX[sl[l]] + (double)g.en[code[l]];
+    }
+    double const X = dcp_lse5(cx[0], cx[1], cx[2], cx[3], cx[4]);
+
+    // first pass: M, I, D of the row, chunk after chunk, and E over all of them
+    dcp_lse_acc acc = dcp_lse_acc_empty();
+    double em_ = ninf(), ed_ = ninf(); // M, D of the chunk's last node
+    for (unsigned ch = 0; ch < wa.nchunks; ++ch)
+    {
+        unsigned const k0 = ch * (unsigned)DCP_FWD_CHUNK + lane * WR;
+        double cm[5][WR], ci[5][WR];
+#pragma unroll
+        for (int l = 0; l < 5; ++l)
+        {
+            Real const *em = g.tab + (uint64_t)code[l] * g.ld;
+            double const *p = wa.P(sl[l]) + k0, *q = wa.Q(sl[l]) + k0;
+#pragma unroll
+            for (int r = 0; r < WR; ++r)
+            {
+                cm[l][r] = p[r] + load_col(em, k0 + r, g.M);
+                ci[l][r] = q[r] + eI[l];
+            }
+        }
+        double m[WR], ins[WR], a[WR], dd[WR], d[WR];
+#pragma unroll
+        for (int r = 0; r < WR; ++r)
+        {
+            m[r] = dcp_lse5(cm[0][r], cm[1][r], cm[2][r], cm[3][r], cm[4][r]);
+            ins[r] = dcp_lse5(ci[0][r], ci[1][r], ci[2][r], ci[3][r], ci[4][r]);
+            dd[r] = load_col(g.trans + DCP_T_DD * g.ld, k0 + r, g.M);
+        }
+        a[0] = shr1(m[WR - 1], em_) + load_col(g.trans + DCP_T_MD * g.ld, k0, g.M);
+#pragma unroll
+        for (int r = 1; r < WR; ++r)
+            a[r] = m[r - 1] + load_col(g.trans + DCP_T_MD * g.ld, k0 + r, g.M);
+        delete_chain<WR>(a, dd, ed_, d, lane);
+        double *const wm = wa.row(0) + k0, *const wi = wa.row(1) + k0, *const wd = wa.row(2) + k0;
+#pragma unroll
+        for (int r = 0; r < WR; ++r)
+            wm[r] = m[r], wi[r] = ins[r], wd[r] = d[r];
+        acc = dcp_lse_acc_merge(acc, exit_terms<WR>(m, d));
+        em_ = readlane(m[WR - 1], 63), ed_ = readlane(d[WR - 1], 63);
+    }
+    double const E = dcp_lse_acc_value(acc);
+    double const N = readlane(X, 0), J = readlane(X, 1), Cc = readlane(X, 2), Rr = readlane(X, 3);
+    double const B = dcp_lse3(N + x.NB, E + x.EB, J + x.JB);
+
+    // second pass: row j's edges into the next rows, into slot j mod 5
+    double bm = ninf(), bi = ninf(), bd = ninf();
+    for (unsigned ch = 0; ch < wa.nchunks; ++ch)
+    {
+        unsigned const k0 = ch * (unsigned)DCP_FWD_CHUNK + lane * WR;
+        double const *wm = wa.row(0) + k0, *wi = wa.row(1) + k0, *wd = wa.row(2) + k0;
+        double m[WR], ins[WR], d[WR];
+#pragma unroll
+        for (int r = 0; r < WR; ++r)
+            m[r] = wm[r], ins[r] = wi[r], d[r] = wd[r];
+        double pm[WR], pi[WR], pd[WR]; // node k - 1's values
+        pm[0] = shr1(m[WR - 1], bm), pi[0] = shr1(ins[WR - 1], bi), pd[0] = shr1(d[WR - 1], bd);
+#pragma unroll
+        for (int r = 1; r < WR; ++r)
+            pm[r] = m[r - 1], pi[r] = ins[r - 1], pd[r] = d[r - 1];
+        double *const p = wa.P(PH) + k0, *const q = wa.Q(PH) + k0;
+#pragma unroll
+        for (int r = 0; r < WR; ++r)
+        {
+            unsigned const k = k0 + r;
+            p[r] = dcp_lse4(B + load_col(g.trans + DCP_T_ENTRY * g.ld, k, g.M), pm[r] + load_col(g.trans + DCP_T_MM * g.ld, k, g.M),
+                            pi[r] + load_col(g.trans + DCP_T_IM * g.ld, k, g.M), pd[r] + load_col(g.trans + DCP_T_DM * g.ld, k, g.M));
+            q[r] = dcp_lse2(m[r] + load_col(g.trans + DCP_T_MI * g.ld, k, g.M), ins[r] + load_col(g.trans + DCP_T_II * g.ld, k, g.M));
+        }
+        bm = readlane(m[WR - 1], 63), bi = readlane(ins[WR - 1], 63), bd = readlane(d[WR - 1], 63);
+    }
+    s.PX[PH] = dcp_lse2(E + x.xa, X + x.xb);
+    s.E = E, s.Cc = Cc, s.Rr = Rr;
+}
+
+template <class Real> __global__ __launch_bounds__(256) void forward_wide_kernel(dcp_fwd_args a)
+{
+    unsigned const lane = threadIdx.x & 63u;
+    uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
+    uint64_t const nw = a.nwaves;
+    if (gw >= nw) return; // wavefronts past nwaves have no work area
+    for (uint64_t pair = gw; pair < a.npairs; pair += nw)
+    {
+        dcp_fwd_pair const pp = a.pairs[pair];
+        dcp_fwd_prof const pr = a.profs[pp.prof];
+        unsigned const L = a.seq_len[pp.q];
+        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        XF const x = special_transitions(xt, lane);
+        Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
+        WideArea wa;
+        wa.nchunks = (pr.core_size + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
+        wa.ldk = (uint64_t)wa.nchunks * DCP_FWD_CHUNK; // <= work_stride / DCP_FWD_WORK_ROWS: the host sized it by the widest
+        wa.base = a.work + gw * a.work_stride;
+        // row 0, anew for every pair (the pair before may have been of another width): the rings' own columns
+        double const B0 = 0.0 + xt[DCP_X_SB];
+        for (unsigned ch = 0; ch < wa.nchunks; ++ch)
+        {
+            unsigned const k0 = ch * (unsigned)DCP_FWD_CHUNK + lane * WR;
+#pragma unroll
+            for (int r = 0; r < WR; ++r)
+            {
+                wa.P(0)[k0 + r] = B0 + load_col(g.trans + DCP_T_ENTRY * g.ld, k0 + r, g.M);
+                wa.Q(0)[k0 + r] = ninf();
+#pragma unroll
+                for (int h = 1; h < 5; ++h)
+                    wa.P(h)[k0 + r] = wa.Q(h)[k0 + r] = ninf();
+            }
+        }
+        WideState s;
+#pragma unroll
+        for (int h = 0; h < 5; ++h)
+            s.PX[h] = ninf();
+        s.PX[0] = special_row0(xt, lane);
+        s.E = s.Cc = s.Rr = ninf();
+        s.w = 0u;
+        unsigned j = 1u;
+#define DCP_FWD_ROW(PH)                                                                                                \
+    forward_wide_row<Real, PH>(s, x, g, wa, j, lane);                                                                  \
+    if (j == L) break;                                                                                                 \
+    ++j;
+        for (;;)
+        {
+            DCP_FWD_ROW(1)
+            DCP_FWD_ROW(2)
+            DCP_FWD_ROW(3)
+            DCP_FWD_ROW(4)
+            DCP_FWD_ROW(0)
+        }
+#undef DCP_FWD_ROW
+        if (lane == 0u)
+        {
+            a.out_null[pp.pos] = s.Rr;
+            a.out_alt[pp.pos] = dcp_lse2(s.E + x.ET, s.Cc + x.CT);
+        }
+    }
+}
+
+template <class Real> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
+{
+    dim3 const grid((a.nwaves + 3u) / 4u), block(256);
+    switch (R)
+    {
+    case 0: hipLaunchKernelGGL((forward_wide_kernel<Real>), grid, block, 0, st, a); return 0;
+    case 1: hipLaunchKernelGGL((forward_kernel<Real, 1>), grid, block, 0, st, a); return 0;
+    case 2: hipLaunchKernelGGL((forward_kernel<Real, 2>), grid, block, 0, st, a); return 0;
+    case 4: hipLaunchKernelGGL((forward_kernel<Real, 4>), grid, block, 0, st, a); return 0;
+    default: return 1;
+    }
+}
+
+} // namespace
+
+extern "C" int dcp_forward_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+{
+    if (!a || a->nwaves == 0 || a->npairs == 0) return 1;
+    if (R == 0 && !a->work) return 1;
+    hipStream_t const st = (hipStream_t)stream;
+    if (precision == 32) return launch<float>(R, *a, st);
+    if (precision == 64) return launch<double>(R, *a, st);
+    return 1;
+}

@@ -11,6 +11,7 @@
 #include "dcp_decode.h"
 #include "dcp_domains.h"
 #include "dcp_calib.h"
+#include "dcp_forward.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -385,6 +386,26 @@ struct dcp_gpu_ctx
     DevBuf<uint32_t> d_tail_keff;
     hipEvent_t ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
     bool tail_timed = false;
+    // Forward scores of a pair list (dcp_gpu_forward_pairs, dcp_forward.hip): the resident DB's profiles as that kernel
+    // addresses them, by caller index (built on first use, void with the DB), and the call's own buffers -- the bucketed
+    // list, the special transitions, the two score arrays, the wide sweep's work areas -- kept between calls and grown
+    // when a call needs more; nothing of a scan's is written.  ev_fwd: around the launches of the last call that
+    // launched any.  waves_cap: the hooks build's cap on a launch's wavefronts (0: none).
+    struct ForwardState
+    {
+        bool profs_ready = false;
+        DevBuf<dcp_fwd_prof> d_profs;
+        DevBuf<dcp_fwd_pair> d_pairs;
+        DevBuf<double> d_xt, d_out, d_work;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        bool timed = false;
+        unsigned waves_cap = 0;
+        void release() // a new DB
+        {
+            profs_ready = false;
+            d_profs.release();
+        }
+    } fwd;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -712,6 +733,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_tail)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->fwd.ev)
+        if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
     for (int k = 0; k <= kNumClasses; ++k)
@@ -825,6 +848,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
     HIP_TRY(c, hipSetDevice(c->device));
     void_last_scan(c);
     c->dec.release();
+    c->fwd.release();
     if (c->precision == 64) // one resident DB per context: the double one goes
     {
         c->f64.release();
@@ -1352,6 +1376,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     // one resident DB per context: whatever was there goes, also if this upload fails half way
     void_last_scan(c);
     c->dec.release();
+    c->fwd.release();
     c->precision = 0;
     c->nprof = 0;
     c->f64.release();
@@ -3332,6 +3357,163 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
     return DCP_OK;
 }
 
+// ---- Forward scores of a pair list (dcp_forward.hip) ---------------------------------------------------------------
+// The kernel's classes: nodes per lane with the whole profile in registers (core sizes up to 64 R), or 0: the wide
+// sweep through a work area per wavefront.
+static constexpr int kFwdR[4] = {1, 2, 4, 0};
+static int fwd_class(unsigned M) { return M <= 64u ? 0 : M <= 128u ? 1 : M <= (unsigned)DCP_FWD_CHUNK ? 2 : 3; }
+
+// The resident DB's profiles as the Forward kernel addresses them, by caller index: base, row stride and core size.  A
+// float DB's small profiles share their rows (dcp_mp_group): a member's meta is already a column view of them.
+static int forward_profiles(dcp_gpu_ctx *c)
+{
+    auto &W = c->fwd;
+    if (W.profs_ready) return DCP_OK;
+    std::vector<dcp_fwd_prof> profs(c->nprof);
+    if (c->precision == 64)
+        for (dcp_f64_prof const &m : c->f64.profs)
+            profs[m.pidx] = dcp_fwd_prof{m.tab_off, m.trans_off, m.xe_off, m.xe_off + DCP_NCODES, m.core_size, m.ldk};
+    else
+        for (dcp_prof_meta const &m : c->metas)
+            profs[m.pidx] = dcp_fwd_prof{m.emis_off, m.trans_off, (uint64_t)m.pidx * DCP_NCODES, (uint64_t)m.pidx * DCP_NCODES,
+                                         m.core_size, m.ldk};
+    HIP_TRY(c, W.d_profs.alloc(profs.size()));
+    HIP_TRY(c, hipMemcpy(W.d_profs.p, profs.data(), profs.size() * sizeof(dcp_fwd_prof), hipMemcpyHostToDevice));
+    W.profs_ready = true;
+    return DCP_OK;
+}
+
+int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                          uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
+    if (npairs && (!seq_idx || !profile_idx)) return c->fail(DCP_EINVAL, "a pair list without its indices");
+    if (npairs && (!null_out || !alt_out)) return c->fail(DCP_EINVAL, "a pair list without its score arrays");
+    for (unsigned i = 0; i < npairs; ++i)
+        if (seq_idx[i] >= c->nseqs || profile_idx[i] >= c->nprof)
+            return c->fail(DCP_EINVAL, "pair %u (sequence %u, profile %u) is outside the resident batch (%u sequences) / DB (%u profiles)",
+                           i, seq_idx[i], profile_idx[i], c->nseqs, c->nprof);
+    bool const f64 = c->precision == 64;
+    if (f64 && c->xt_explicit)
+        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    if (!f64 && !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    if (npairs == 0) return DCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->fwd;
+    if (!f64)
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+    if (int rc = forward_profiles(c)) return rc;
+
+    // the special transitions a scan would use, one row per resident sequence, in double: a float DB's are the float
+    // ones (derived, or the caller's resident rows) promoted
+    std::vector<double> xt;
+    {
+        std::vector<uint32_t> seqs(c->nseqs);
+        std::iota(seqs.begin(), seqs.end(), 0u);
+        if (f64)
+        {
+            if (int rc = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_FWD_XSTRIDE, xt)) return rc;
+        }
+        else
+        {
+            static_assert((int)DCP_XSTRIDE == (int)DCP_FWD_XSTRIDE, "one row layout in both precisions");
+            std::vector<float> xf;
+            if (c->xt_explicit)
+            {
+                xf.resize((size_t)c->nseqs * DCP_XSTRIDE);
+                HIP_TRY(c, hipMemcpy(xf.data(), c->d_xtrans.p, xf.size() * sizeof(float), hipMemcpyDeviceToHost));
+            }
+            else if (int rc = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_XSTRIDE, xf)) return rc;
+            xt.assign(xf.begin(), xf.end());
+        }
+    }
+
+    // the list by class, each class in list order; a pair remembers its position
+    unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0};
+    for (unsigned i = 0; i < npairs; ++i)
+        ++count[fwd_class(c->core_sizes[profile_idx[i]])];
+    for (int k = 0; k < 4; ++k)
+        first[k + 1] = first[k] + count[k];
+    std::vector<dcp_fwd_pair> pairs(npairs);
+    unsigned wide_chunks = 0;
+    {
+        unsigned at[4] = {first[0], first[1], first[2], first[3]};
+        for (unsigned i = 0; i < npairs; ++i)
+        {
+            unsigned const M = c->core_sizes[profile_idx[i]];
+            int const k = fwd_class(M);
+            pairs[at[k]++] = dcp_fwd_pair{seq_idx[i], profile_idx[i], i};
+            if (k == 3) wide_chunks = std::max(wide_chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
+        }
+        // a pair costs its rows times its chunks: the dearest first, so that the wavefronts striding over a class's
+        // list end together (pairs of one cost keep their list order)
+        auto const cost = [&](dcp_fwd_pair const &p) {
+            return (uint64_t)c->seq_len[p.q] * ((c->core_sizes[p.prof] + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
+        };
+        for (int k = 0; k < 4; ++k)
+            std::stable_sort(pairs.begin() + first[k], pairs.begin() + first[k + 1],
+                             [&](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return cost(x) > cost(y); });
+    }
+    // wavefronts per launch: a grid's worth (the register-resident classes hold one or two wavefronts per SIMD and
+    // leave some waiting, the wide sweep one), striding over the class's list
+    unsigned waves[4];
+    for (int k = 0; k < 4; ++k)
+    {
+        waves[k] = (unsigned)std::min<uint64_t>(count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
+        if (W.waves_cap) waves[k] = std::min(waves[k], W.waves_cap);
+    }
+    uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK;
+    if (W.d_work.n < work_stride * waves[3]) HIP_TRY(c, W.d_work.alloc(work_stride * waves[3]));
+    if (W.d_pairs.n < npairs) HIP_TRY(c, W.d_pairs.alloc(npairs));
+    if (W.d_xt.n < xt.size()) HIP_TRY(c, W.d_xt.alloc(xt.size()));
+    if (W.d_out.n < 2u * (size_t)npairs) HIP_TRY(c, W.d_out.alloc(2u * (size_t)npairs));
+    for (hipEvent_t &e : W.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipMemcpyAsync(W.d_pairs.p, pairs.data(), (size_t)npairs * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below (and whatever was outstanding is done)
+
+    dcp_fwd_args a{};
+    a.profs = W.d_profs.p;
+    if (f64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
+    else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
+    a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
+    a.xtrans = W.d_xt.p;
+    a.work = W.d_work.p, a.work_stride = work_stride;
+    a.out_null = W.d_out.p, a.out_alt = W.d_out.p + npairs;
+    HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+    for (int k = 0; k < 4; ++k)
+    {
+        if (count[k] == 0) continue;
+        a.pairs = W.d_pairs.p + first[k];
+        a.npairs = count[k];
+        a.nwaves = waves[k];
+        if (dcp_forward_launch(c->precision, kFwdR[k], &a, c->stream))
+            return c->fail(DCP_EFAIL, "no Forward kernel for %d nodes per lane", kFwdR[k]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+    // into a buffer of the call's own first: the caller's arrays stay untouched if the copy fails
+    std::vector<double> out(2u * (size_t)npairs);
+    HIP_TRY(c, hipMemcpyAsync(out.data(), W.d_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    W.timed = true;
+    std::memcpy(null_out, out.data(), (size_t)npairs * sizeof(double));
+    std::memcpy(alt_out, out.data() + npairs, (size_t)npairs * sizeof(double));
+    return DCP_OK;
+}
+
+float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c)
+{
+    float ms = -1.0f;
+    if (!c || !c->fwd.timed) return -1.0f;
+    if (hipEventElapsedTime(&ms, c->fwd.ev[0], c->fwd.ev[1]) != hipSuccess) return -1.0f;
+    return ms;
+}
+
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
 static int rerun_with_rowsweep(dcp_gpu_ctx *c)
 {
@@ -3458,6 +3640,13 @@ int dcp_gpu_test_set_trace_mode(dcp_gpu_ctx *c, int own_forward, unsigned long l
     c->trace_budget = budget_floats;
     return DCP_OK;
 }
+int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *c, unsigned nwaves)
+{
+    if (!c) return DCP_EINVAL;
+    c->fwd.waves_cap = nwaves;
+    return DCP_OK;
+}
+
 int dcp_gpu_test_set_redo_cap(dcp_gpu_ctx *c, unsigned cap)
 {
     if (!c) return DCP_EINVAL;

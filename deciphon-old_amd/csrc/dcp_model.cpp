@@ -1839,3 +1839,108 @@ int dcp_hits_evalues64(struct dcp_hit64 const *hits, unsigned n, double const *m
 
 } // extern "C"
 
+
+// ---------------------------------------------------------------------------
+// Forward on the host: the twin of dcp_forward.hip.  The end-indexed recursion of the scan with
+// every max replaced by lse (dcp_forward.h), sequential in k, every lse in the order written; tables as the device
+// holds them ([8][ldk], [1364][ldk], [1364], [1364]) in double.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_forward.h"
+
+extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                  double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                  unsigned char const *seq, unsigned L, double *null_out, double *alt_out)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq || !null_out || !alt_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
+                 *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
+                 *MD = trans8 + (size_t)DCP_T_MD * ldk, *DD = trans8 + (size_t)DCP_T_DD * ldk,
+                 *MI = trans8 + (size_t)DCP_T_MI * ldk, *II = trans8 + (size_t)DCP_T_II * ldk;
+    double const *x = xtrans;
+    double const ninf = dcp_fwd_ninf();
+    // rows j - 1 .. j - 5 of P and Q in slots (j - l) % 5, then the row's M, I, D: DCP_FWD_WORK_ROWS rows of M
+    double *const rows = (double *)std::malloc(sizeof(double) * DCP_FWD_WORK_ROWS * (size_t)M);
+    if (!rows) return DCP_ENOMEM;
+    double *const P = rows, *const Q = rows + 5 * (size_t)M, *const Mr = rows + 10 * (size_t)M, *const Ir = Mr + M,
+                 *const Dr = Ir + M;
+    double PN[5], PJ[5], PC[5], PR[5];
+    for (size_t i = 0; i < 10 * (size_t)M; ++i)
+        rows[i] = ninf;
+    for (int h = 0; h < 5; ++h)
+        PN[h] = PJ[h] = PC[h] = PR[h] = ninf;
+    // row 0: S = 0, B = S + SB; N = S + SN; R starts at 0
+    double const B0 = 0.0 + x[DCP_X_SB];
+    for (unsigned k = 0; k < M; ++k)
+        P[k] = B0 + ENT[k];
+    PN[0] = 0.0 + x[DCP_X_SN];
+    PR[0] = 0.0;
+
+    static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
+    double E = ninf, Cc = ninf, Rr = ninf;
+    unsigned w = 0;
+    for (unsigned j = 1; j <= L; ++j)
+    {
+        w = ((w << 2) | seq[j - 1]) & 1023u;
+        // words that would start before row 0 meet -inf predecessors: they add exp(-inf) = 0
+        unsigned code[5], slot[5];
+        for (unsigned l = 1; l <= 5u; ++l)
+        {
+            code[l - 1] = code_off[l - 1] + (w & ((1u << (2 * l)) - 1u));
+            slot[l - 1] = (j + 5u - l) % 5u;
+        }
+        double cn[5], cj[5], cc[5], cr[5];
+        for (int l = 0; l < 5; ++l)
+        {
+            double const eN = emis_null[code[l]];
+            cn[l] = PN[slot[l]] + eN, cj[l] = PJ[slot[l]] + eN, cc[l] = PC[slot[l]] + eN, cr[l] = PR[slot[l]] + eN;
+        }
+        double const N = dcp_lse5(cn[0], cn[1], cn[2], cn[3], cn[4]), J = dcp_lse5(cj[0], cj[1], cj[2], cj[3], cj[4]);
+        Cc = dcp_lse5(cc[0], cc[1], cc[2], cc[3], cc[4]);
+        Rr = dcp_lse5(cr[0], cr[1], cr[2], cr[3], cr[4]);
+        for (unsigned k = 0; k < M; ++k)
+        {
+            double cm[5], ci[5];
+            for (int l = 0; l < 5; ++l)
+            {
+                cm[l] = P[(size_t)slot[l] * M + k] + emis_match[(size_t)code[l] * ldk + k];
+                ci[l] = Q[(size_t)slot[l] * M + k] + emis_insert[code[l]];
+            }
+            Mr[k] = dcp_lse5(cm[0], cm[1], cm[2], cm[3], cm[4]);
+            Ir[k] = dcp_lse5(ci[0], ci[1], ci[2], ci[3], ci[4]);
+        }
+        Dr[0] = ninf;
+        for (unsigned k = 1; k < M; ++k)
+            Dr[k] = dcp_lse2(Mr[k - 1] + MD[k], Dr[k - 1] + DD[k]);
+        // E = lse(M_0, M_1, D_1, M_2, D_2, ..): the maximum, then the terms in this order
+        double mx = ninf;
+        for (unsigned k = 0; k < M; ++k)
+            mx = dcp_fwd_max(mx, dcp_fwd_max(Mr[k], Dr[k]));
+        double const mm = dcp_fwd_shift(mx);
+        double sum = 0.0;
+        for (unsigned k = 0; k < M; ++k)
+        {
+            sum += std::exp(Mr[k] - mm);
+            if (k) sum += std::exp(Dr[k] - mm);
+        }
+        E = mm + std::log(sum);
+        double const B = dcp_lse3(N + x[DCP_X_NB], E + x[DCP_X_EB], J + x[DCP_X_JB]);
+        unsigned const r = j % 5u; // row j - 5's slot: M(j) and I(j) are formed, nothing reads it any more
+        double *const pm = P + (size_t)r * M, *const qi = Q + (size_t)r * M;
+        for (unsigned k = 0; k < M; ++k)
+        {
+            pm[k] = k ? dcp_lse4(B + ENT[k], Mr[k - 1] + MM[k], Ir[k - 1] + IM[k], Dr[k - 1] + DM[k]) : B + ENT[0];
+            qi[k] = dcp_lse2(Mr[k] + MI[k], Ir[k] + II[k]);
+        }
+        PN[r] = N + x[DCP_X_NN];
+        PJ[r] = dcp_lse2(E + x[DCP_X_EJ], J + x[DCP_X_JJ]);
+        PC[r] = dcp_lse2(E + x[DCP_X_EC], Cc + x[DCP_X_CC]);
+        PR[r] = Rr + x[DCP_X_RR];
+    }
+    *null_out = Rr;
+    *alt_out = dcp_lse2(E + x[DCP_X_ET], Cc + x[DCP_X_CT]);
+    std::free(rows);
+    return DCP_OK;
+}

@@ -1,5 +1,6 @@
-// dcp_test_hooks.h -- read-only hooks of the tests' own -DDCP_TEST_HOOKS build (libdcp_hip_testhooks.so) that
-// include/dcp_gpu.h does not list.  Only dcp_gpu.hip includes it: the DP kernels' objects do not change with it.
+// dcp_test_hooks.h -- hooks of the tests' own -DDCP_TEST_HOOKS build (libdcp_hip_testhooks.so) that include/dcp_gpu.h
+// does not list: read-only ones, and a cap on the Forward launches' wavefronts that must change no result.  Only
+// dcp_gpu.hip includes it: the DP kernels' objects do not change with it.
 #ifndef DCP_TEST_HOOKS_H
 #define DCP_TEST_HOOKS_H
 
@@ -35,6 +36,10 @@ int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *, unsigned *out, unsigned cap, 
 //   blocks (float) / wavefronts (double) launched, tasks per block (double: 1 per wavefront), the list capacity the
 //   kernel was given (pair_cap)}.  Changes nothing.
 int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *, unsigned *out, unsigned cap, unsigned *nwords);
+// Cap on the wavefronts of each of the following dcp_gpu_forward_pairs launches (the stride loop then takes several
+// pairs per wavefront, of whatever widths follow each other in the class's list); 0 restores the default.  Results
+// must not change with it.
+int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *, unsigned nwaves);
 }
 #endif
 

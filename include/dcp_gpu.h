@@ -908,6 +908,39 @@ int dcp_hits_evalues64(struct dcp_hit64 const *, unsigned n, double const *mu, d
                        unsigned nprofiles, double nsearched, double *evalue_out);
 
 /* ------------------------------------------------------------------------ */
+/* Forward scores: the summed weight of all paths, for a list of pairs         */
+/* ------------------------------------------------------------------------ */
+/* Every score above is a Viterbi score, the weight of one best path.  Forward is the same recursion with every max
+ * replaced by lse(c_1 .. c_n) = mm + log(sum_i exp(c_i - mm)), mm the largest c_i (0 if that is -inf), the terms added
+ * in index order: the log of the summed weight of all paths.  It is computed in double whatever the tables'
+ * precision (float tables are promoted, which is exact).
+ *
+ * The host twin, on tables of the shapes the device holds: trans8 [8][ldk] (DCP_T_* rows), emis_match [1364][ldk],
+ * emis_insert [1364], emis_null [1364], xtrans as dcp_xtrans64 writes them, seq of L base ids 0..3.  Sequential in the
+ * node index, every lse in the order the recursion is written.  DCP_EINVAL, nothing written: M == 0, M > 4096,
+ * ldk < M, L == 0, a base id above 3, a null pointer.  DCP_ENOMEM if its rows cannot be allocated.  No device. */
+int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                       double const *emis_insert, double const *emis_null, double const xtrans[13],
+                       unsigned char const *seq, unsigned L, double *null_out, double *alt_out);
+/* The Forward scores, null and alt, of the npairs pairs (resident sequence seq_idx[i], resident profile
+ * profile_idx[i]) on a float or a double DB, in list order: null_out / alt_out [npairs] doubles.  One wavefront per
+ * pair (csrc/dcp_forward.hip); the host buckets the list by the kernel's classes.  The special transitions are those a
+ * scan would use for the sequence: from its length and the two flags, or the explicit ones of dcp_gpu_seqs_set_xtrans /
+ * ...64 while they hold (those of the other precision are refused, as a scan refuses them).  Whatever batch is
+ * resident serves: uploaded, random, both strands, windows, regions.  A float DB's row-sweep tables are expanded on
+ * first use, as a row-sweep scan expands them.  The call runs on the context's stream behind whatever is outstanding
+ * and returns synchronised; the last scan's hits, dense scores, hit buffer and accounting stay what they were.
+ * Device and host twin differ in exp and log and in the association of the delete chain and of E(j).  A pair listed
+ * twice is scored twice; npairs == 0 is DCP_OK.  DCP_EINVAL with a message, outputs untouched: no DB or no batch
+ * resident, a null pointer with npairs > 0, an index out of range (naming the first bad pair), explicit transitions of
+ * the other precision. */
+int dcp_gpu_forward_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                          uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out);
+/* Milliseconds, by HIP events around the kernel launches of the context's last dcp_gpu_forward_pairs that launched
+ * any; negative before. */
+float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *);
+
+/* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum

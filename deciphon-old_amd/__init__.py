@@ -98,6 +98,8 @@ ABI_SYMBOLS = [
     "dcp_gumbel_fit_tail", "dcp_gpu_fit_gumbel_tail", "dcp_gpu_db_calibrate_tail", "dcp_gpu_calib_tail_kernel_ms",
     # Forward scores of a pair list: a log-sum-exp sweep on the device, and its host twin
     "dcp_forward_tables", "dcp_gpu_forward_pairs", "dcp_gpu_forward_kernel_ms",
+    # Backward sweep and posterior decoding of a pair list, the host twin, envelopes from the core row
+    "dcp_posterior_tables", "dcp_posterior_envelopes", "dcp_gpu_posterior_pairs", "dcp_gpu_posterior_kernel_ms",
 ]
 
 
@@ -292,6 +294,10 @@ def _load(path=None, hooks=False):
         "dcp_forward_tables": (I, [U, U, P, P, P, P, P, P, U, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "dcp_gpu_forward_pairs": (I, [P, I, I, P, P, U, P, P]),
         "dcp_gpu_forward_kernel_ms": (F, [P]),
+        "dcp_posterior_tables": (I, [U, U, P, P, P, P, P, P, U, P, P, P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "dcp_posterior_envelopes": (I, [P, U, C.c_double, U, P, P, U, C.POINTER(U)]),
+        "dcp_gpu_posterior_pairs": (I, [P, I, I, P, P, U, P, P, P, P, C.c_uint64, P, P]),
+        "dcp_gpu_posterior_kernel_ms": (F, [P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -304,6 +310,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_last_rowsweep_plan"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_set_forward_waves"] = (I, [P, U])
+        sig["dcp_gpu_test_set_posterior_budget"] = (I, [P, C.c_ulonglong])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -655,6 +662,45 @@ def forward_tables(t8, em, ei, en, xt, seq):
     if rc:
         raise DcpError(rc, "dcp_forward_tables")
     return null.value, alt.value
+
+
+def posterior_tables(t8, em, ei, en, xt, seq):
+    """(begin, end, core, alt_fwd, alt_bwd) of one sequence against one profile on the host (dcp_posterior_tables):
+    three float64 rows of len(seq) + 1 -- the posteriors that a domain begins at row j, that one ends there, and that
+    base j - 1 is emitted by a core state -- and the alt score by the Forward and by the Backward sweep.  The tables
+    are forward_tables' ones."""
+    t8, em, ei, en, xt = _f64(t8), _f64(em), _f64(ei), _f64(en), _f64(xt)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if t8.ndim != 2 or em.ndim != 2 or t8.shape != (8, em.shape[1]) or em.shape[0] != NCODES or \
+            ei.shape != (NCODES,) or en.shape != (NCODES,) or xt.shape != (NXTRANS,) or seq.ndim != 1:
+        raise DcpError(RC_EINVAL, "tables of shapes [8, ldk], [1364, ldk], [1364], [1364], [13]")
+    begin, end, core = (np.zeros(len(seq) + 1, np.float64) for _ in range(3))
+    fwd, bwd = C.c_double(0.0), C.c_double(0.0)
+    rc = lib.dcp_posterior_tables(em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data,
+                                  xt.ctypes.data, seq.ctypes.data, len(seq), begin.ctypes.data, end.ctypes.data,
+                                  core.ctypes.data, C.byref(fwd), C.byref(bwd))
+    if rc:
+        raise DcpError(rc, "dcp_posterior_tables")
+    return begin, end, core, fwd.value, bwd.value
+
+
+def posterior_envelopes(core, threshold=0.5, min_len=1):
+    """[(begin, end), ..]: the maximal runs of bases whose core posterior is at least `threshold` and that are at least
+    min_len bases long, as half-open base intervals in order (dcp_posterior_envelopes).  core is a row of
+    posterior_tables / Scanner.posterior_pairs: len(seq) + 1 values, base i at core[i + 1]."""
+    core = _f64(core)
+    if core.ndim != 1 or len(core) == 0 or not 0 <= min_len < 2 ** 32:
+        raise DcpError(RC_EINVAL, "a core row of L + 1 values; min_len in 32 bits")
+    L, n = len(core) - 1, C.c_uint(0)
+    rc = lib.dcp_posterior_envelopes(core.ctypes.data, L, float(threshold), int(min_len), None, None, 0, C.byref(n))
+    if rc:
+        raise DcpError(rc, "dcp_posterior_envelopes")
+    b, e = np.zeros(n.value, np.uint32), np.zeros(n.value, np.uint32)
+    rc = lib.dcp_posterior_envelopes(core.ctypes.data, L, float(threshold), int(min_len), b.ctypes.data, e.ctypes.data,
+                                     n.value, C.byref(n))
+    if rc:
+        raise DcpError(rc, "dcp_posterior_envelopes")
+    return [(int(x), int(y)) for x, y in zip(b, e)]
 
 
 def lrt(null_loglik, alt_loglik):
@@ -1262,6 +1308,39 @@ class Scanner:
     def test_set_forward_waves(self, nwaves):
         """TEST-ONLY (test-hooks build): cap the wavefronts of the following forward_pairs launches (0: default)."""
         self._check(self._lib.dcp_gpu_test_set_forward_waves(self._c, int(nwaves)))
+
+    def posterior_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
+        """(row_off, begin, end, core, alt_fwd, alt_bwd) of the pairs (resident sequence seq_idx[i], resident profile
+        profile_idx[i]) on a float or a double DB (dcp_gpu_posterior_pairs): pair i's rows are
+        [row_off[i], row_off[i + 1]) of the three float64 arrays, one per row j = 0 .. L_i -- the posteriors that a
+        domain begins at row j, that one ends there, and that base j - 1 is emitted by a core state -- and the alt score
+        by the Forward sweep (forward_pairs' bits) and by the Backward sweep.  Returns synchronised; the last scan's
+        results stay what they were."""
+        sq = np.ascontiguousarray(seq_idx, np.uint32)
+        pr = np.ascontiguousarray(profile_idx, np.uint32)
+        if sq.ndim != 1 or sq.shape != pr.shape:
+            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        lens = getattr(self, "_seq_lens", np.zeros(0, np.int64))
+        ok = sq < len(lens)  # an index out of range is the call's to refuse, with its message
+        cap = int(np.sum(lens[sq[ok]] + 1)) if len(sq) else 0
+        row_off = np.zeros(len(sq) + 1, np.uint64)
+        begin, end, core = (np.zeros(cap, np.float64) for _ in range(3))
+        fwd, bwd = np.zeros(len(sq), np.float64), np.zeros(len(sq), np.float64)
+        self._check(self._lib.dcp_gpu_posterior_pairs(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data,
+                                                      pr.ctypes.data, len(sq), row_off.ctypes.data, begin.ctypes.data,
+                                                      end.ctypes.data, core.ctypes.data, cap, fwd.ctypes.data,
+                                                      bwd.ctypes.data))
+        return row_off, begin, end, core, fwd, bwd
+
+    @property
+    def posterior_kernel_ms(self):
+        """Milliseconds of the last posterior_pairs call's kernel launches, by HIP events; negative before any."""
+        return self._lib.dcp_gpu_posterior_kernel_ms(self._c)
+
+    def test_set_posterior_budget(self, nbytes):
+        """TEST-ONLY (test-hooks build): the device memory the following posterior_pairs calls give their row records
+        (0: the default, 1 GiB)."""
+        self._check(self._lib.dcp_gpu_test_set_posterior_budget(self._c, int(nbytes)))
 
     def set_hit_buffer(self, hits_dev_ptr, cap, nhits_dev_ptr):
         """Route hit records into caller-owned device memory (e.g. a torch tensor for RCCL)."""

@@ -117,6 +117,11 @@ struct dcp_fwd_args
     double *work;         // the wide sweep: work_stride doubles per wavefront
     uint64_t work_stride; // DCP_FWD_WORK_ROWS x the widest listed profile's padded columns
     double *out_null, *out_alt; // [the caller's list]
+    // the row-storing Forward variant and the Backward sweep only (dcp_posterior.h): pair `pos` has its DCP_POST_REC
+    // doubles per row j = 0 .. L from rows + (row_off[pos] - row_base) * DCP_POST_REC on
+    double *rows;
+    uint64_t const *row_off; // [the caller's list + 1]
+    uint64_t row_base;       // row_off of the round's first pair
 };
 
 #ifdef __cplusplus

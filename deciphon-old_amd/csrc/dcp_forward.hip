@@ -10,6 +10,10 @@
 //                            chunk to chunk in registers.  B(j) follows after the row's last chunk; a second pass over
 //                            the chunks forms P(j) and Q(j) into slot j mod 5.
 //
+// Both take a compile-time flag ROWS: the same sweep that also stores, per row j = 0 .. L, the five values the posterior
+// rows are built from -- PN(j), PJ(j), PC(j), B(j), E(j), dcp_posterior.h -- from lane 0 (dcp_gpu_posterior_pairs' first
+// half).  ROWS = false is dcp_gpu_forward_pairs' kernel, with the registers it had before the flag.
+//
 // Real is the tables' scalar (a float DB's values are promoted to double, which is exact); the arithmetic is double.
 // The recursion is the Viterbi one of dcp_f64.hip with every max replaced by lse (dcp_forward.h), every candidate
 // (predecessor + transition) or (predecessor + emission) formed once.  Two things max allowed there do not carry over:
@@ -26,139 +30,14 @@
 // padding columns carry -inf and stay -inf, whatever the DB's own padding is (a float DB's small profiles share rows).
 #include "dcp_forward.h"
 #include "dcp_host.h"
+#include "dcp_posterior.h"
 
 #include <hip/hip_runtime.h>
 
+#include "dcp_forward_dev.h"
+
 namespace
 {
-
-__device__ __forceinline__ double ninf() { return -__builtin_inf(); }
-
-// gfx950's DPP moves 32-bit lanes: a double crosses lanes as its two halves (dcp_f64.hip)
-__device__ __forceinline__ double shr1(double v, double first) // value of lane - 1; lane 0 receives `first`
-{
-    unsigned long long const vb = __builtin_bit_cast(unsigned long long, v);
-    unsigned long long const fb = __builtin_bit_cast(unsigned long long, first);
-    int const lo = __builtin_amdgcn_update_dpp((int)(unsigned)fb, (int)(unsigned)vb, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
-    int const hi = __builtin_amdgcn_update_dpp((int)(unsigned)(fb >> 32), (int)(unsigned)(vb >> 32), 0x138, 0xf, 0xf, false);
-    return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-__device__ __forceinline__ double readlane(double v, int lane)
-{
-    unsigned long long const b = __builtin_bit_cast(unsigned long long, v);
-    unsigned const lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, lane);
-    unsigned const hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), lane);
-    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ double wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-        v = dcp_fwd_max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) // lane i and lane i ^ o add the same two values: one tree for all
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1)
-        v = v + __shfl_xor(v, o, 64);
-    return v;
-}
-
-struct XF // the pair's special transitions as the rows use them
-{
-    double NB, EB, JB, ET, CT;
-    double xa, xb; // this lane's own special state X of N, J, C, R: PX(j) = lse(E(j) + xa, X(j) + xb)
-};
-
-template <class Real> struct Tabs
-{
-    Real const *tab, *trans, *ei, *en;
-    uint64_t ld;
-    unsigned M;
-    uint32_t const *words;
-};
-
-template <class Real> __device__ __forceinline__ double load_col(Real const *row, unsigned k, unsigned M)
-{
-    return k < M ? (double)row[k] : ninf();
-}
-
-// the last five bases' word codes, the shortest word first
-__device__ __forceinline__ void word_codes(unsigned w, unsigned (&code)[5])
-{
-    constexpr unsigned off[5] = {0u, 4u, 20u, 84u, 340u};
-#pragma unroll
-    for (int l = 0; l < 5; ++l)
-        code[l] = off[l] + (w & ((4u << (2 * l)) - 1u));
-}
-
-// D of the lane's R nodes: a[r] = M_{k-1} + MD_k, dd[r] = DD_k, carry = D of the node before lane 0's first
-template <int R>
-__device__ __forceinline__ void delete_chain(double const (&a)[R], double const (&dd)[R], double carry, double (&d)[R],
-                                             unsigned lane)
-{
-    double c = a[0], s = dd[0]; // the lane's chain from d_in = -inf, and the sum of its DD
-#pragma unroll
-    for (int r = 1; r < R; ++r)
-    {
-        c = dcp_lse2(a[r], c + dd[r]);
-        s = s + dd[r];
-    }
-#pragma unroll
-    for (unsigned o = 1; o < 64u; o <<= 1)
-    {
-        double const sp = __shfl_up(s, o, 64), cp = __shfl_up(c, o, 64);
-        if (lane >= o)
-        {
-            c = dcp_lse2(c, cp + s);
-            s = sp + s;
-        }
-    }
-    // lanes 0 .. l - 1 composed, applied to the carry: lane 0 receives (0, -inf), the identity
-    double const cb = shr1(c, ninf()), sb = shr1(s, 0.0);
-    double const d_in = dcp_lse2(cb, carry + sb);
-    d[0] = dcp_lse2(a[0], d_in + dd[0]);
-#pragma unroll
-    for (int r = 1; r < R; ++r)
-        d[r] = dcp_lse2(a[r], d[r - 1] + dd[r]);
-}
-
-// the lanes' M and D of one chunk as one term of E(j) in the running form
-template <int R> __device__ __forceinline__ dcp_lse_acc exit_terms(double const (&m)[R], double const (&d)[R])
-{
-    double mx = dcp_fwd_max(m[0], d[0]);
-#pragma unroll
-    for (int r = 1; r < R; ++r)
-        mx = dcp_fwd_max(mx, dcp_fwd_max(m[r], d[r]));
-    mx = readlane(wave_max(mx), 0);
-    double const mm = dcp_fwd_shift(mx);
-    double sum = exp(m[0] - mm) + exp(d[0] - mm);
-#pragma unroll
-    for (int r = 1; r < R; ++r)
-        sum = sum + exp(m[r] - mm) + exp(d[r] - mm);
-    return dcp_lse_acc{mx, readlane(wave_sum(sum), 0)};
-}
-
-__device__ __forceinline__ XF special_transitions(double const *xt, unsigned lane)
-{
-    XF x;
-    x.NB = xt[DCP_X_NB], x.EB = xt[DCP_X_EB], x.JB = xt[DCP_X_JB], x.ET = xt[DCP_X_ET], x.CT = xt[DCP_X_CT];
-    unsigned const sp = lane & 3u;
-    x.xa = sp == 1u ? xt[DCP_X_EJ] : sp == 2u ? xt[DCP_X_EC] : ninf(); // N and R have no edge from E
-    x.xb = sp == 0u ? xt[DCP_X_NN] : sp == 1u ? xt[DCP_X_JJ] : sp == 2u ? xt[DCP_X_CC] : xt[DCP_X_RR];
-    return x;
-}
-
-// row 0 of the lane's special state: N = S + SN, R starts at 0, J and C are -inf
-__device__ __forceinline__ double special_row0(double const *xt, unsigned lane)
-{
-    unsigned const sp = lane & 3u;
-    return sp == 0u ? 0.0 + xt[DCP_X_SN] : sp == 3u ? 0.0 : ninf();
-}
 
 // ---- profiles of at most 64 R nodes: everything in registers -------------------------------------------------------
 template <int R> struct Trans
@@ -175,9 +54,16 @@ template <int R> struct State
     unsigned w;
 };
 
-template <class Real, int R, int PH>
+// ROWS: the row's record for the posteriors (dcp_posterior.h) -- PN(j), PJ(j), PC(j), B(j), E(j) -- goes to rec from lane 0
+template <int PH> __device__ __forceinline__ void store_record(double const (&PX)[5], double B, double E, double *rec, unsigned lane)
+{
+    double const pn = readlane(PX[PH], 0), pj = readlane(PX[PH], 1), pc = readlane(PX[PH], 2);
+    if (lane == 0u) rec[0] = pn, rec[1] = pj, rec[2] = pc, rec[3] = B, rec[4] = E;
+}
+
+template <class Real, int R, int PH, bool ROWS>
 __device__ __forceinline__ void forward_row(State<R> &s, Trans<R> const &t, XF const &x, Tabs<Real> const &g, unsigned j,
-                                            unsigned lane)
+                                            unsigned lane, double *rec)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH}; // slot of row j - l
     unsigned const i = j - 1u;
@@ -230,22 +116,10 @@ __device__ __forceinline__ void forward_row(State<R> &s, Trans<R> const &t, XF c
         s.Q[PH][r] = dcp_lse2(m[r] + t.mi[r], ins[r] + t.ii[r]);
     s.PX[PH] = dcp_lse2(E + x.xa, X + x.xb);
     s.E = E, s.Cc = Cc, s.Rr = Rr;
+    if constexpr (ROWS) store_record<PH>(s.PX, B, E, rec + (uint64_t)DCP_POST_REC * j, lane);
 }
 
-template <class Real> __device__ __forceinline__ Tabs<Real> tables_of(dcp_fwd_args const &a, dcp_fwd_prof const &pr, unsigned q)
-{
-    Tabs<Real> g;
-    g.tab = (Real const *)a.tab + pr.tab_off;
-    g.trans = (Real const *)a.trans + pr.trans_off;
-    g.ei = (Real const *)a.ei + pr.ei_off;
-    g.en = (Real const *)a.en + pr.en_off;
-    g.ld = pr.ld;
-    g.M = pr.core_size;
-    g.words = a.seq_words + a.seq_woff[q];
-    return g;
-}
-
-template <class Real, int R> __global__ __launch_bounds__(256) void forward_kernel(dcp_fwd_args a)
+template <class Real, int R, bool ROWS> __global__ __launch_bounds__(256) void forward_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -290,9 +164,15 @@ template <class Real, int R> __global__ __launch_bounds__(256) void forward_kern
         s.PX[0] = special_row0(xt, lane);
         s.E = s.Cc = s.Rr = ninf();
         s.w = 0u;
+        double *rec = nullptr;
+        if constexpr (ROWS)
+        {
+            rec = a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
+            store_record<0>(s.PX, B0, ninf(), rec, lane); // row 0: PN = SN, B = SB, no J, C, E yet
+        }
         unsigned j = 1u;
 #define DCP_FWD_ROW(PH)                                                                                                \
-    forward_row<Real, R, PH>(s, t, x, g, j, lane);                                                                     \
+    forward_row<Real, R, PH, ROWS>(s, t, x, g, j, lane, rec);                                                          \
     if (j == L) break;                                                                                                 \
     ++j;
         for (;;)
@@ -332,9 +212,9 @@ struct WideArea // rows of ldk doubles: P and Q slots, then the row's M, I, D
     __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
 };
 
-template <class Real, int PH>
+template <class Real, int PH, bool ROWS>
 __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs<Real> const &g, WideArea const &wa, unsigned j,
-                                                 unsigned lane)
+                                                 unsigned lane, double *rec)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
     unsigned const i = j - 1u;
@@ -421,9 +301,10 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
     }
     s.PX[PH] = dcp_lse2(E + x.xa, X + x.xb);
     s.E = E, s.Cc = Cc, s.Rr = Rr;
+    if constexpr (ROWS) store_record<PH>(s.PX, B, E, rec + (uint64_t)DCP_POST_REC * j, lane);
 }
 
-template <class Real> __global__ __launch_bounds__(256) void forward_wide_kernel(dcp_fwd_args a)
+template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_wide_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -463,9 +344,15 @@ template <class Real> __global__ __launch_bounds__(256) void forward_wide_kernel
         s.PX[0] = special_row0(xt, lane);
         s.E = s.Cc = s.Rr = ninf();
         s.w = 0u;
+        double *rec = nullptr;
+        if constexpr (ROWS)
+        {
+            rec = a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
+            store_record<0>(s.PX, B0, ninf(), rec, lane);
+        }
         unsigned j = 1u;
 #define DCP_FWD_ROW(PH)                                                                                                \
-    forward_wide_row<Real, PH>(s, x, g, wa, j, lane);                                                                  \
+    forward_wide_row<Real, PH, ROWS>(s, x, g, wa, j, lane, rec);                                                       \
     if (j == L) break;                                                                                                 \
     ++j;
         for (;;)
@@ -485,15 +372,15 @@ template <class Real> __global__ __launch_bounds__(256) void forward_wide_kernel
     }
 }
 
-template <class Real> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
+template <class Real, bool ROWS> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
     {
-    case 0: hipLaunchKernelGGL((forward_wide_kernel<Real>), grid, block, 0, st, a); return 0;
-    case 1: hipLaunchKernelGGL((forward_kernel<Real, 1>), grid, block, 0, st, a); return 0;
-    case 2: hipLaunchKernelGGL((forward_kernel<Real, 2>), grid, block, 0, st, a); return 0;
-    case 4: hipLaunchKernelGGL((forward_kernel<Real, 4>), grid, block, 0, st, a); return 0;
+    case 0: hipLaunchKernelGGL((forward_wide_kernel<Real, ROWS>), grid, block, 0, st, a); return 0;
+    case 1: hipLaunchKernelGGL((forward_kernel<Real, 1, ROWS>), grid, block, 0, st, a); return 0;
+    case 2: hipLaunchKernelGGL((forward_kernel<Real, 2, ROWS>), grid, block, 0, st, a); return 0;
+    case 4: hipLaunchKernelGGL((forward_kernel<Real, 4, ROWS>), grid, block, 0, st, a); return 0;
     default: return 1;
     }
 }
@@ -505,7 +392,18 @@ extern "C" int dcp_forward_launch(int precision, int R, struct dcp_fwd_args cons
     if (!a || a->nwaves == 0 || a->npairs == 0) return 1;
     if (R == 0 && !a->work) return 1;
     hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch<float>(R, *a, st);
-    if (precision == 64) return launch<double>(R, *a, st);
+    if (precision == 32) return launch<float, false>(R, *a, st);
+    if (precision == 64) return launch<double, false>(R, *a, st);
+    return 1;
+}
+
+// the same sweeps, every row's record stored as well (a->rows, a->row_off, a->row_base): dcp_gpu_posterior_pairs' first half
+extern "C" int dcp_forward_rows_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+{
+    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off) return 1;
+    if (R == 0 && !a->work) return 1;
+    hipStream_t const st = (hipStream_t)stream;
+    if (precision == 32) return launch<float, true>(R, *a, st);
+    if (precision == 64) return launch<double, true>(R, *a, st);
     return 1;
 }

@@ -12,6 +12,7 @@
 #include "dcp_domains.h"
 #include "dcp_calib.h"
 #include "dcp_forward.h"
+#include "dcp_posterior.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -406,6 +407,20 @@ struct dcp_gpu_ctx
             d_profs.release();
         }
     } fwd;
+    // Backward sweep and posterior rows of a pair list (dcp_gpu_posterior_pairs, dcp_posterior.hip): the call's own
+    // buffers, kept between calls and grown when a call needs more -- the list's row offsets, the special transitions,
+    // the scores (null, alt by Forward, alt by Backward), a round's bucketed and listed pairs, its two sweeps' row records
+    // and its three output rows.  The profiles, the wide sweep's work areas and the wavefront cap are fwd's.  budget: the
+    // hooks build's bound on the row records' bytes (0: 1 GiB).  ms: the last call's kernel time, summed over its rounds.
+    struct PosteriorState
+    {
+        DevBuf<uint64_t> d_row_off;
+        DevBuf<dcp_fwd_pair> d_pairs;
+        DevBuf<double> d_xt, d_score, d_rec, d_rows;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint64_t budget = 0;
+        float ms = -1.0f;
+    } post;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -734,6 +749,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     for (hipEvent_t e : c->ev_tail)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->fwd.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->post.ev)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -3383,14 +3400,13 @@ static int forward_profiles(dcp_gpu_ctx *c)
     return DCP_OK;
 }
 
-int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
-                          uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out)
+// What dcp_gpu_forward_pairs and dcp_gpu_posterior_pairs refuse alike, on the host, before anything runs.
+static int forward_check_list(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npairs, bool outputs)
 {
-    if (!c) return DCP_EINVAL;
     if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
     if (npairs && (!seq_idx || !profile_idx)) return c->fail(DCP_EINVAL, "a pair list without its indices");
-    if (npairs && (!null_out || !alt_out)) return c->fail(DCP_EINVAL, "a pair list without its score arrays");
+    if (npairs && !outputs) return c->fail(DCP_EINVAL, "a pair list without its score arrays");
     for (unsigned i = 0; i < npairs; ++i)
         if (seq_idx[i] >= c->nseqs || profile_idx[i] >= c->nprof)
             return c->fail(DCP_EINVAL, "pair %u (sequence %u, profile %u) is outside the resident batch (%u sequences) / DB (%u profiles)",
@@ -3400,16 +3416,14 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
         return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
     if (!f64 && !c->xt64.empty())
         return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
-    if (npairs == 0) return DCP_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto &W = c->fwd;
-    if (!f64)
-        if (int rc = ensure_rowsweep_layout(c)) return rc;
-    if (int rc = forward_profiles(c)) return rc;
+    return DCP_OK;
+}
 
-    // the special transitions a scan would use, one row per resident sequence, in double: a float DB's are the float
-    // ones (derived, or the caller's resident rows) promoted
-    std::vector<double> xt;
+// The special transitions a scan would use, one row per resident sequence, in double: a float DB's are the float ones
+// (derived, or the caller's resident rows) promoted.
+static int forward_special_transitions(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, std::vector<double> &xt)
+{
+    bool const f64 = c->precision == 64;
     {
         std::vector<uint32_t> seqs(c->nseqs);
         std::iota(seqs.begin(), seqs.end(), 0u);
@@ -3430,22 +3444,36 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
             xt.assign(xf.begin(), xf.end());
         }
     }
+    return DCP_OK;
+}
 
-    // the list by class, each class in list order; a pair remembers its position
-    unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0};
+// The list by class, each class in list order, the dearest pairs of a class first; a pair remembers its position pos0 + i
+// in the caller's list.  waves: the wavefronts of each class's launch.
+struct ForwardBuckets
+{
+    unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0}, waves[4] = {0, 0, 0, 0};
+    unsigned wide_chunks = 0;
+    std::vector<dcp_fwd_pair> pairs;
+};
+
+static void forward_bucket(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npairs, unsigned pos0,
+                           ForwardBuckets &b)
+{
+    unsigned(&first)[5] = b.first, (&count)[4] = b.count, (&waves)[4] = b.waves;
+    unsigned &wide_chunks = b.wide_chunks;
+    std::vector<dcp_fwd_pair> &pairs = b.pairs;
     for (unsigned i = 0; i < npairs; ++i)
         ++count[fwd_class(c->core_sizes[profile_idx[i]])];
     for (int k = 0; k < 4; ++k)
         first[k + 1] = first[k] + count[k];
-    std::vector<dcp_fwd_pair> pairs(npairs);
-    unsigned wide_chunks = 0;
+    pairs.resize(npairs);
     {
         unsigned at[4] = {first[0], first[1], first[2], first[3]};
         for (unsigned i = 0; i < npairs; ++i)
         {
             unsigned const M = c->core_sizes[profile_idx[i]];
             int const k = fwd_class(M);
-            pairs[at[k]++] = dcp_fwd_pair{seq_idx[i], profile_idx[i], i};
+            pairs[at[k]++] = dcp_fwd_pair{seq_idx[i], profile_idx[i], pos0 + i};
             if (k == 3) wide_chunks = std::max(wide_chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
         }
         // a pair costs its rows times its chunks: the dearest first, so that the wavefronts striding over a class's
@@ -3459,12 +3487,32 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
     }
     // wavefronts per launch: a grid's worth (the register-resident classes hold one or two wavefronts per SIMD and
     // leave some waiting, the wide sweep one), striding over the class's list
-    unsigned waves[4];
     for (int k = 0; k < 4; ++k)
     {
         waves[k] = (unsigned)std::min<uint64_t>(count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
-        if (W.waves_cap) waves[k] = std::min(waves[k], W.waves_cap);
+        if (c->fwd.waves_cap) waves[k] = std::min(waves[k], c->fwd.waves_cap);
     }
+}
+
+int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                          uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, null_out && alt_out)) return rc;
+    if (npairs == 0) return DCP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->fwd;
+    bool const f64 = c->precision == 64;
+    if (!f64)
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+    if (int rc = forward_profiles(c)) return rc;
+    std::vector<double> xt;
+    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
+    ForwardBuckets b;
+    forward_bucket(c, seq_idx, profile_idx, npairs, 0u, b);
+    unsigned const(&first)[5] = b.first, (&count)[4] = b.count, (&waves)[4] = b.waves;
+    unsigned const wide_chunks = b.wide_chunks;
+    std::vector<dcp_fwd_pair> const &pairs = b.pairs;
     uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK;
     if (W.d_work.n < work_stride * waves[3]) HIP_TRY(c, W.d_work.alloc(work_stride * waves[3]));
     if (W.d_pairs.n < npairs) HIP_TRY(c, W.d_pairs.alloc(npairs));
@@ -3513,6 +3561,139 @@ float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c)
     if (hipEventElapsedTime(&ms, c->fwd.ev[0], c->fwd.ev[1]) != hipSuccess) return -1.0f;
     return ms;
 }
+
+// ---- Backward sweep and posterior rows of a pair list (dcp_posterior.hip) -------------------------------------------
+// The list runs in rounds of consecutive pairs whose row records -- 2 x DCP_POST_REC doubles a row -- fit the budget (a
+// single pair that exceeds it gets a round of its own).  A round: the row-storing Forward launches by class, the
+// Backward launches by class, the combining kernel, the round's rows copied out; then the next.
+int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                            uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                            double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, alt_fwd_out && alt_bwd_out)) return rc;
+    if (!row_off) return c->fail(DCP_EINVAL, "a pair list without its row offsets");
+    std::vector<uint64_t> off((size_t)npairs + 1u, 0u);
+    for (unsigned i = 0; i < npairs; ++i)
+        off[i + 1u] = off[i] + c->seq_len[seq_idx[i]] + 1u;
+    uint64_t const need = off[npairs];
+    if (need > cap_rows)
+        return c->fail(DCP_EINVAL, "the list needs %llu rows, the arrays hold %llu", (unsigned long long)need, (unsigned long long)cap_rows);
+    if (npairs && (!begin_out || !end_out || !core_out)) return c->fail(DCP_EINVAL, "a pair list without its row arrays");
+    if (npairs == 0)
+    {
+        row_off[0] = 0u;
+        return DCP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->post;
+    bool const f64 = c->precision == 64;
+    if (!f64)
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+    if (int rc = forward_profiles(c)) return rc;
+    std::vector<double> xt;
+    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
+
+    uint64_t const budget = W.budget ? W.budget : (uint64_t)1u << 30;
+    uint64_t const rows_cap = std::max<uint64_t>(1u, budget / (2u * DCP_POST_REC * sizeof(double)));
+    uint64_t round_rows = 0; // the largest round's
+    for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
+    {
+        for (i1 = i0 + 1u; i1 < npairs && off[i1 + 1u] - off[i0] <= rows_cap; ++i1) {}
+        round_rows = std::max(round_rows, off[i1] - off[i0]);
+    }
+    if (W.d_row_off.n < off.size()) HIP_TRY(c, W.d_row_off.alloc(off.size()));
+    if (W.d_xt.n < xt.size()) HIP_TRY(c, W.d_xt.alloc(xt.size()));
+    if (W.d_score.n < 3u * (size_t)npairs) HIP_TRY(c, W.d_score.alloc(3u * (size_t)npairs));
+    if (W.d_rec.n < 2u * DCP_POST_REC * round_rows) HIP_TRY(c, W.d_rec.alloc(2u * DCP_POST_REC * round_rows));
+    if (W.d_rows.n < 3u * round_rows) HIP_TRY(c, W.d_rows.alloc(3u * round_rows));
+    for (hipEvent_t &e : W.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipMemcpyAsync(W.d_row_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+
+    dcp_fwd_args a{};
+    a.profs = c->fwd.d_profs.p;
+    if (f64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
+    else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
+    a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
+    a.xtrans = W.d_xt.p;
+    a.row_off = W.d_row_off.p;
+    double *const d_null = W.d_score.p, *const d_fwd = d_null + npairs, *const d_bwd = d_fwd + npairs;
+    dcp_post_args pa{};
+    pa.profs = a.profs, pa.en = a.en;
+    pa.seq_words = a.seq_words, pa.seq_woff = a.seq_woff, pa.seq_len = a.seq_len;
+    pa.alt_fwd = d_fwd;
+
+    std::vector<double> rows;
+    std::vector<dcp_fwd_pair> list;
+    float ms_total = 0.0f;
+    for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
+    {
+        for (i1 = i0 + 1u; i1 < npairs && off[i1 + 1u] - off[i0] <= rows_cap; ++i1) {}
+        unsigned const n = i1 - i0;
+        uint64_t const nrows = off[i1] - off[i0];
+        ForwardBuckets b;
+        forward_bucket(c, seq_idx + i0, profile_idx + i0, n, i0, b);
+        list.resize(n);
+        for (unsigned i = 0; i < n; ++i)
+            list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
+        uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
+        if (c->fwd.d_work.n < work_stride * b.waves[3]) HIP_TRY(c, c->fwd.d_work.alloc(work_stride * b.waves[3]));
+        if (W.d_pairs.n < 2u * (size_t)n) HIP_TRY(c, W.d_pairs.alloc(2u * (size_t)n));
+        dcp_fwd_pair *const d_bucketed = W.d_pairs.p, *const d_list = W.d_pairs.p + n;
+        HIP_TRY(c, hipMemcpyAsync(d_bucketed, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below
+
+        a.work = c->fwd.d_work.p, a.work_stride = work_stride;
+        a.row_base = off[i0];
+        a.out_null = d_null;
+        HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+        for (int sweep = 0; sweep < 2; ++sweep)
+        {
+            a.rows = W.d_rec.p + (sweep ? (size_t)DCP_POST_REC * nrows : 0u);
+            a.out_alt = sweep ? d_bwd : d_fwd;
+            for (int k = 0; k < 4; ++k)
+            {
+                if (b.count[k] == 0) continue;
+                a.pairs = d_bucketed + b.first[k];
+                a.npairs = b.count[k];
+                a.nwaves = b.waves[k];
+                if ((sweep ? dcp_backward_launch : dcp_forward_rows_launch)(c->precision, kFwdR[k], &a, c->stream))
+                    return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
+                HIP_TRY(c, hipGetLastError());
+            }
+        }
+        pa.list = d_list, pa.nlist = n, pa.row_off = W.d_row_off.p + i0;
+        pa.rows_f = W.d_rec.p, pa.rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
+        pa.begin = W.d_rows.p, pa.end = pa.begin + nrows, pa.core = pa.end + nrows;
+        if (dcp_posterior_combine_launch(c->precision, &pa, nrows, c->stream))
+            return c->fail(DCP_EFAIL, "no combining kernel for a round of %llu rows", (unsigned long long)nrows);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+        // into a buffer of the call's own first: the caller's arrays stay untouched if this round's copy fails
+        rows.resize(3u * (size_t)nrows);
+        HIP_TRY(c, hipMemcpyAsync(rows.data(), W.d_rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        float ms = 0.0f;
+        HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+        ms_total += ms;
+        std::memcpy(begin_out + off[i0], rows.data(), (size_t)nrows * sizeof(double));
+        std::memcpy(end_out + off[i0], rows.data() + nrows, (size_t)nrows * sizeof(double));
+        std::memcpy(core_out + off[i0], rows.data() + 2u * nrows, (size_t)nrows * sizeof(double));
+    }
+    std::vector<double> score(2u * (size_t)npairs);
+    HIP_TRY(c, hipMemcpy(score.data(), d_fwd, score.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
+    std::memcpy(alt_bwd_out, score.data() + npairs, (size_t)npairs * sizeof(double));
+    std::memcpy(row_off, off.data(), off.size() * sizeof(uint64_t));
+    W.ms = ms_total;
+    return DCP_OK;
+}
+
+float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->post.ms : -1.0f; }
 
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
 static int rerun_with_rowsweep(dcp_gpu_ctx *c)
@@ -3640,6 +3821,13 @@ int dcp_gpu_test_set_trace_mode(dcp_gpu_ctx *c, int own_forward, unsigned long l
     c->trace_budget = budget_floats;
     return DCP_OK;
 }
+int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *c, unsigned long long bytes)
+{
+    if (!c) return DCP_EINVAL;
+    c->post.budget = bytes;
+    return DCP_OK;
+}
+
 int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *c, unsigned nwaves)
 {
     if (!c) return DCP_EINVAL;

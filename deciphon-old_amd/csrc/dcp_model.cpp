@@ -1846,15 +1846,14 @@ int dcp_hits_evalues64(struct dcp_hit64 const *hits, unsigned n, double const *m
 // holds them ([8][ldk], [1364][ldk], [1364], [1364]) in double.  No device.
 // ---------------------------------------------------------------------------
 #include "dcp_forward.h"
+#include "dcp_posterior.h"
 
-extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
-                                  double const *emis_insert, double const *emis_null, double const xtrans[13],
-                                  unsigned char const *seq, unsigned L, double *null_out, double *alt_out)
+// The sweep itself, arguments checked.  rec, if given, receives per row j = 0 .. L the five values a word starting
+// after row j, or a domain beginning or ending there, leaves from: PN(j), PJ(j), PC(j), B(j), E(j) (dcp_posterior.h).
+static int forward_sweep(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+                         double const *emis_null, double const *xtrans, unsigned char const *seq, unsigned L, double *rec,
+                         double *null_out, double *alt_out)
 {
-    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
-    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq || !null_out || !alt_out) return DCP_EINVAL;
-    for (unsigned i = 0; i < L; ++i)
-        if (seq[i] > 3) return DCP_EINVAL;
     double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
                  *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
                  *MD = trans8 + (size_t)DCP_T_MD * ldk, *DD = trans8 + (size_t)DCP_T_DD * ldk,
@@ -1877,6 +1876,7 @@ extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8
         P[k] = B0 + ENT[k];
     PN[0] = 0.0 + x[DCP_X_SN];
     PR[0] = 0.0;
+    if (rec) rec[0] = PN[0], rec[1] = ninf, rec[2] = ninf, rec[3] = B0, rec[4] = ninf;
 
     static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
     double E = ninf, Cc = ninf, Rr = ninf;
@@ -1938,9 +1938,168 @@ extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8
         PJ[r] = dcp_lse2(E + x[DCP_X_EJ], J + x[DCP_X_JJ]);
         PC[r] = dcp_lse2(E + x[DCP_X_EC], Cc + x[DCP_X_CC]);
         PR[r] = Rr + x[DCP_X_RR];
+        if (rec)
+        {
+            double *const o = rec + (size_t)DCP_POST_REC * j;
+            o[0] = PN[r], o[1] = PJ[r], o[2] = PC[r], o[3] = B, o[4] = E;
+        }
     }
     *null_out = Rr;
     *alt_out = dcp_lse2(E + x[DCP_X_ET], Cc + x[DCP_X_CT]);
     std::free(rows);
+    return DCP_OK;
+}
+
+extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                  double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                  unsigned char const *seq, unsigned L, double *null_out, double *alt_out)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq || !null_out || !alt_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    return forward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, nullptr, null_out, alt_out);
+}
+
+// ---------------------------------------------------------------------------
+// Backward and the posterior rows on the host: the twin of dcp_posterior.hip and the tests' yardstick.  The rule is
+// dcp_posterior.h's; sequential in k, every lse in the order written, bB and E summed in k order from the maximum.  It
+// holds the full matrices of bM and bI: it is no hot path.  No device.
+// ---------------------------------------------------------------------------
+extern "C" int dcp_posterior_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                    double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                    unsigned char const *seq, unsigned L, double *begin_out, double *end_out,
+                                    double *core_out, double *alt_fwd_out, double *alt_bwd_out)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq) return DCP_EINVAL;
+    if (!begin_out || !end_out || !core_out || !alt_fwd_out || !alt_bwd_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
+                 *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
+                 *MD = trans8 + (size_t)DCP_T_MD * ldk, *DD = trans8 + (size_t)DCP_T_DD * ldk,
+                 *MI = trans8 + (size_t)DCP_T_MI * ldk, *II = trans8 + (size_t)DCP_T_II * ldk;
+    double const *x = xtrans;
+    double const ninf = dcp_fwd_ninf();
+    size_t const rows = (size_t)L + 6u; // rows L + 1 .. L + 5 stay -inf: words that would end past L
+    size_t const nrec = 2u * (size_t)DCP_POST_REC * rows, nmat = 2u * rows * M, nrow = 3u * (size_t)M;
+    double *const mem = (double *)std::malloc(sizeof(double) * (nrec + nmat + nrow));
+    if (!mem) return DCP_ENOMEM;
+    double *const fr = mem, *const br = fr + DCP_POST_REC * rows, *const bM = mem + nrec, *const bI = bM + rows * M,
+                 *const bP = mem + nrec + nmat, *const bQ = bP + M, *const bD = bQ + M;
+    for (size_t i = 0; i < nrec + nmat; ++i)
+        mem[i] = ninf;
+    double null_fwd, alt_fwd;
+    if (int rc = forward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, fr, &null_fwd, &alt_fwd))
+    {
+        std::free(mem);
+        return rc;
+    }
+    static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
+    double bPN0 = ninf;
+    for (unsigned j = L;; --j)
+    {
+        // x[j .. j+l), first base most significant; a word past L meets the -inf rows, whatever its code
+        unsigned code[5], v = 0;
+        for (unsigned l = 1; l <= 5u; ++l)
+        {
+            v = (v << 2) | (j + l - 1u < L ? seq[j + l - 1u] : 0u);
+            code[l - 1] = code_off[l - 1] + v;
+        }
+        double cn[5], cj[5], cc[5];
+        for (unsigned l = 1; l <= 5u; ++l)
+        {
+            double const eN = emis_null[code[l - 1]];
+            double const *b = br + (size_t)DCP_POST_REC * (j + l);
+            cn[l - 1] = eN + b[0], cj[l - 1] = eN + b[1], cc[l - 1] = eN + b[2];
+        }
+        double const bPN = dcp_lse5(cn[0], cn[1], cn[2], cn[3], cn[4]), bPJ = dcp_lse5(cj[0], cj[1], cj[2], cj[3], cj[4]),
+                     bPC = dcp_lse5(cc[0], cc[1], cc[2], cc[3], cc[4]);
+        for (unsigned k = 0; k < M; ++k)
+        {
+            double cm[5], ci[5];
+            for (unsigned l = 1; l <= 5u; ++l)
+            {
+                cm[l - 1] = emis_match[(size_t)code[l - 1] * ldk + k] + bM[(size_t)(j + l) * M + k];
+                ci[l - 1] = emis_insert[code[l - 1]] + bI[(size_t)(j + l) * M + k];
+            }
+            bP[k] = dcp_lse5(cm[0], cm[1], cm[2], cm[3], cm[4]);
+            bQ[k] = dcp_lse5(ci[0], ci[1], ci[2], ci[3], ci[4]);
+        }
+        // bB = lse_k entry_k + bP_k: the maximum, then the terms in k order
+        double mx = ninf;
+        for (unsigned k = 0; k < M; ++k)
+            mx = dcp_fwd_max(mx, ENT[k] + bP[k]);
+        double const mm = dcp_fwd_shift(mx);
+        double sum = 0.0;
+        for (unsigned k = 0; k < M; ++k)
+            sum += std::exp((ENT[k] + bP[k]) - mm);
+        double const bB = mm + std::log(sum);
+        bool const last = j == L;
+        double *const o = br + (size_t)DCP_POST_REC * j;
+        double const bE = dcp_lse4(last ? x[DCP_X_ET] : ninf, x[DCP_X_EB] + bB, x[DCP_X_EJ] + bPJ, x[DCP_X_EC] + bPC);
+        o[0] = dcp_lse2(x[DCP_X_NB] + bB, x[DCP_X_NN] + bPN);
+        o[1] = dcp_lse2(x[DCP_X_JB] + bB, x[DCP_X_JJ] + bPJ);
+        o[2] = dcp_lse2(last ? x[DCP_X_CT] : ninf, x[DCP_X_CC] + bPC);
+        o[3] = bB, o[4] = bE;
+        double *const m = bM + (size_t)j * M, *const ins = bI + (size_t)j * M;
+        for (unsigned k = M; k-- > 0;)
+        {
+            bool const nx = k + 1u < M; // node k + 1 exists
+            double const dn = nx ? bD[k + 1] : ninf, pn = nx ? bP[k + 1] : ninf;
+            bD[k] = dcp_lse3(bE, nx ? DD[k + 1] + dn : ninf, nx ? DM[k + 1] + pn : ninf);
+            m[k] = dcp_lse4(bE, nx ? MD[k + 1] + dn : ninf, nx ? MM[k + 1] + pn : ninf, MI[k] + bQ[k]);
+            ins[k] = dcp_lse2(nx ? IM[k + 1] + pn : ninf, II[k] + bQ[k]);
+        }
+        if (j == 0)
+        {
+            bPN0 = bPN;
+            break;
+        }
+    }
+    double const alt_bwd = dcp_lse2(x[DCP_X_SB] + br[3], x[DCP_X_SN] + bPN0);
+    for (unsigned j = 0; j <= L; ++j)
+    {
+        unsigned win = 0; // bases j - 5 .. j + 3, first most significant; outside the sequence 0
+        for (unsigned i = 0; i < 9u; ++i)
+        {
+            long const t = (long)j - 5 + (long)i;
+            win = (win << 2) | (t >= 0 && t < (long)L ? seq[t] : 0u);
+        }
+        dcp_posterior_row<double>(fr, br, emis_null, win, j, L, alt_fwd, begin_out + j, end_out + j, core_out + j);
+    }
+    *alt_fwd_out = alt_fwd;
+    *alt_bwd_out = alt_bwd;
+    std::free(mem);
+    return DCP_OK;
+}
+
+// Envelopes: the maximal runs of bases with core >= threshold that are at least min_len bases long, as half-open base
+// intervals in order.  core is dcp_posterior_tables' row [L + 1]: base i is core[i + 1].  *n_out is the true count, of
+// which the first cap are written.  Plain C++, no device.
+extern "C" int dcp_posterior_envelopes(double const *core, unsigned L, double threshold, unsigned min_len,
+                                       unsigned *begin_out, unsigned *end_out, unsigned cap, unsigned *n_out)
+{
+    if (!n_out || (L && !core) || (cap && (!begin_out || !end_out)) || !(threshold == threshold)) return DCP_EINVAL;
+    unsigned n = 0;
+    for (unsigned i = 0; i < L;)
+    {
+        if (!(core[i + 1u] >= threshold))
+        {
+            ++i;
+            continue;
+        }
+        unsigned e = i + 1u;
+        while (e < L && core[e + 1u] >= threshold)
+            ++e;
+        if (e - i >= min_len)
+        {
+            if (n < cap) begin_out[n] = i, end_out[n] = e;
+            ++n;
+        }
+        i = e;
+    }
+    *n_out = n;
     return DCP_OK;
 }

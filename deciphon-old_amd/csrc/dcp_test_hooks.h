@@ -1,5 +1,6 @@
 // dcp_test_hooks.h -- hooks of the tests' own -DDCP_TEST_HOOKS build (libdcp_hip_testhooks.so) that include/dcp_gpu.h
-// does not list: read-only ones, and a cap on the Forward launches' wavefronts that must change no result.  Only
+// does not list: read-only ones, and a cap on the Forward launches' wavefronts and a bound on the posterior rounds' memory that must
+// change no result.  Only
 // dcp_gpu.hip includes it: the DP kernels' objects do not change with it.
 #ifndef DCP_TEST_HOOKS_H
 #define DCP_TEST_HOOKS_H
@@ -39,7 +40,11 @@ int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *, unsigned *out, unsigned cap, 
 // Cap on the wavefronts of each of the following dcp_gpu_forward_pairs launches (the stride loop then takes several
 // pairs per wavefront, of whatever widths follow each other in the class's list); 0 restores the default.  Results
 // must not change with it.
+// (dcp_gpu_posterior_pairs' launches take the same cap.)
 int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *, unsigned nwaves);
+// Bound, in bytes, on the device memory of the row records of each of the following dcp_gpu_posterior_pairs calls: a
+// small one makes the list run in several rounds; 0 restores the default (1 GiB).  Results must not change with it.
+int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *, unsigned long long bytes);
 }
 #endif
 

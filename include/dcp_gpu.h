@@ -941,6 +941,48 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint
 float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *);
 
 /* ------------------------------------------------------------------------ */
+/* Backward sweep and posterior decoding for a list of pairs                   */
+/* ------------------------------------------------------------------------ */
+/* With the Backward value of a state at row j -- the log of the summed weight of all path suffixes from it to the end
+ * (csrc/dcp_posterior.h has the recursion) -- every pair gets three rows of L + 1 doubles, j = 0 .. L:
+ *   begin[j]  the posterior that a domain begins at row j:  exp(B(j) + bB(j) - a), a the Forward alt score;
+ *   end[j]    the posterior that a domain ends at row j:    exp(E(j) + bE(j) - a); end[0] = 0;
+ *   core[j]   the posterior that base j - 1 is emitted by a core state (M or I): 1 minus the posteriors of the at most
+ *             15 words of each of N, J, C that cover the base; core[0] = 0.
+ * sum(begin) = sum(end) is the expected number of domains.  When a is -inf the three rows are 0, never NaN.  The alt
+ * score comes back by both sweeps: alt_fwd (the bits of dcp_forward_tables / dcp_gpu_forward_pairs) and alt_bwd, which
+ * agree within the scores' allowance.
+ *
+ * The host twin takes dcp_forward_tables' tables and refuses as it does (a null output too), nothing written.  It holds
+ * the full matrices of the Backward sweep: the tests' yardstick, no hot path.  No device. */
+int dcp_posterior_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                         double const *emis_insert, double const *emis_null, double const xtrans[13],
+                         unsigned char const *seq, unsigned L, double *begin_out, double *end_out, double *core_out,
+                         double *alt_fwd_out, double *alt_bwd_out);
+/* Envelopes from a core row [L + 1]: the maximal runs of bases with core >= threshold that are at least min_len bases
+ * long, as half-open base intervals [begin_out[i], end_out[i]) in order.  *n_out receives the true count, of which the
+ * first cap are written.  DCP_EINVAL: n_out null, core null with L > 0, an output null with cap > 0, threshold NaN.
+ * No device. */
+int dcp_posterior_envelopes(double const *core, unsigned L, double threshold, unsigned min_len, unsigned *begin_out,
+                            unsigned *end_out, unsigned cap, unsigned *n_out);
+/* The three rows and the two alt scores of the npairs pairs (resident sequence seq_idx[i], resident profile
+ * profile_idx[i]), in list order: pair i's rows are [row_off[i], row_off[i + 1]) of begin_out / end_out / core_out
+ * [cap_rows], L_i + 1 of them; row_off [npairs + 1] is written by the call; alt_fwd_out / alt_bwd_out [npairs].
+ * Device work: the Forward kernels in a variant that also stores five doubles a row, a Backward sweep of the same
+ * shape (one wavefront per pair, csrc/dcp_posterior.hip) and a combining kernel, one thread per row.  The two sweeps'
+ * row records live in device memory of the call's own, bounded by a budget (1 GiB): a longer list runs in rounds, a
+ * single pair that exceeds it in a round of its own.  Checks, messages, special transitions, batches, precisions,
+ * stream and what is left untouched: all as dcp_gpu_forward_pairs.  DCP_EINVAL, outputs untouched, also when cap_rows
+ * is smaller than the rows the list needs (the message names the need).  After a device failure in a later round the
+ * rows of the rounds before are written. */
+int dcp_gpu_posterior_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                            uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                            double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out);
+/* Milliseconds, by HIP events, summed over the rounds' kernel launches of the context's last dcp_gpu_posterior_pairs
+ * that launched any; negative before. */
+float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *);
+
+/* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum

@@ -91,6 +91,8 @@ template <class T> struct DevBuf
         else p = nullptr;
         return e;
     }
+    // room for at least `count`: a buffer kept between calls grows, and never shrinks
+    hipError_t reserve(size_t count) { return n < count ? alloc(count) : hipSuccess; }
     void release()
     {
         if (p) (void)hipFree(p);
@@ -154,6 +156,53 @@ bool is_nan(double v)
     return (bits & 0x7fffffffffffffffull) > 0x7ff0000000000000ull;
 }
 
+constexpr int kMaxLaunches = 2 * kNumClasses + 1; // a segmented class is two launches
+
+// What the last scan was, and what of it has not been looked at yet: every default means "no scan".  The four scan
+// drivers (dcp_gpu_scan_range with its launch functions, scan64, dcp_gpu_scan_pairs, scan_pairs64) each begin with a
+// fresh record -- once the call's refusals are past and the scan before it is complete -- and fill in what they know,
+// `scanned` last: a scan that fails on the way leaves "no scan".  finish_scan settles the pending flags; a new DB or a
+// new batch puts the empty record back (void_last_scan).  Nothing else writes a member: Forward, posterior, traceback,
+// decode and domains do not mention it.
+struct LastScan
+{
+    bool scanned = false;
+    bool f64 = false;       // it ran on a double DB: its results are the context's f64 ones
+    bool pair_scan = false; // dcp_gpu_scan_pairs: the accounting is that of the list, not of a range x the whole DB
+    unsigned q0 = 0, q1 = 0;
+    int kernel = 0;         // 1 row sweep, 2 query lane
+    int kernel_variant = 0; // as dcp_scan_params.kernel names it: 1, 2, 3 (two-stage query lane) or 4 (f64 query lane)
+    struct dcp_scan_params prm = {};
+    unsigned launches = 0;
+    // the float kernels' launches, one HIP event (ev_class) behind each; the f64 kernels keep no such records
+    unsigned n_launched = 0;
+    int launched_class[kMaxLaunches] = {0};      // -1: the query-lane launch
+    bool launched_redo[kMaxLaunches] = {false}; // the exact kernel behind a segmented sweep: its cells are counted there
+    bool overlapped = false; // the row sweep's class launches ran side by side on their own streams
+    unsigned redo_pairs = 0;
+    // a pair list's cells and bytes, and (a float DB's) their parts per size class
+    uint64_t pair_cells = 0, pair_bytes = 0;
+    uint64_t pair_class_cells[DCP_MAX_CLASSES] = {0}, pair_class_bytes[DCP_MAX_CLASSES] = {0};
+    // not looked at yet: the redo counters of a float / an f64 query-lane scan, a two-stage scan's error word
+    bool redo_pending = false, redo_pending64 = false, ring_check_pending = false;
+#ifdef DCP_TEST_HOOKS
+    // test hook (dcp_gpu_test_last_rowsweep_plan): what launch_rowsweep_scan did with each size class
+    struct RowsweepClassPlan
+    {
+        unsigned path = 0;         // DCP_RS_PATH_*: 0 = the class is empty
+        unsigned stage = 0, waves = 0, prefetch = 0; // plain grid: rowsweep_variant's answer
+        unsigned chunk = 0;        // segmented: queries per pass
+        unsigned flagged_rest = 0; // K profiles per wavefront: the flagged profiles got a launch of their own
+    } rs_plan[kNumClasses];
+    // test hook (dcp_gpu_test_last_pair_launches): the pair-mode launches, in launch order
+    struct PairLaunch
+    {
+        unsigned kind, precision, a, b, units, tpb, cap;
+    };
+    std::vector<PairLaunch> pair_launches;
+#endif
+};
+
 } // namespace
 
 struct dcp_gpu_ctx
@@ -202,7 +251,6 @@ struct dcp_gpu_ctx
     DevBuf<uint32_t> d_slot_first;
     unsigned ql_nqb = 0, ql_plane_rows = 0; // the cached plan: blocks of slots, rows of a block's scratch planes
     unsigned ring_stall = 0;                // test hook: dcp_qlane_args::ring_stall
-    bool ring_check_pending = false;        // a two-stage scan's error word has not been looked at yet
     // the length-sorted query order and the plane offsets travel through pinned host memory: the copies are
     // truly asynchronous and dcp_gpu_scan_range returns without waiting for the stream
     uint32_t *h_qstage = nullptr;
@@ -219,14 +267,9 @@ struct dcp_gpu_ctx
     // d_redo_n = [DCP_MAX_CLASSES counters][overflow flag][ring hand-shake error word]
     DevBuf<dcp_pair> d_redo;
     DevBuf<unsigned> d_redo_n;
-    bool redo_pending = false;      // the last scan's redo counters have not been checked yet
-    unsigned last_redo_pairs = 0;
-    struct dcp_scan_params last_prm = {};
     unsigned qorder_q0 = ~0u, qorder_q1 = ~0u, qorder_lmax = 0;
     unsigned num_cus = 0;
-    int last_kernel = 0; // 1 row sweep, 2 query lane
     unsigned qorder_nt = 0;         // block size the cached query order / transposed words were built for
-    int last_kernel_variant = 0; // as dcp_scan_params.kernel names it: 1, 2 or 3 (two-stage query lane)
     unsigned redo_cap_limit = 1u << 26; // only the -DDCP_TEST_HOOKS build can change it
     float last_ql_ms = 0;
 
@@ -259,26 +302,16 @@ struct dcp_gpu_ctx
 
     // results
     ScanResults<float, dcp_hit> res;
-    unsigned last_launches = 0;
-    bool scanned = false;
-    unsigned last_q0 = 0, last_q1 = 0;
-    // dcp_gpu_scan_pairs: the float DB's lists, one per size class back to back, and their lengths; what the last scan
-    // scored if it was one of a pair list (the accounting of a scan is that of a range x the whole DB)
+    LastScan last;
+    // dcp_gpu_scan_pairs: the float DB's lists, one per size class back to back, and their lengths
     DevBuf<dcp_pair> d_pair_list;
     DevBuf<unsigned> d_pair_n; // [DCP_MAX_CLASSES]
-    bool last_pair_scan = false;
-    uint64_t pair_cells = 0, pair_bytes = 0;
-    uint64_t pair_class_cells[DCP_MAX_CLASSES] = {0}, pair_class_bytes[DCP_MAX_CLASSES] = {0};
     // one HIP event after each size-class launch of the last scan
-    static constexpr int kMaxLaunches = 2 * kNumClasses + 1; // a segmented class is two launches
     hipEvent_t ev_class[kMaxLaunches] = {nullptr};
     // small row-sweep scans (the reference's one-sequence-at-a-time mode) are bound by the latency
     // of one pair's row chain, not by throughput: their size-class launches run side by side
     hipStream_t class_stream[kNumClasses] = {nullptr};
     hipEvent_t ev_trace[kNumClasses + 1] = {nullptr}; // traceback: the fork point and one event per class's forward launch
-    bool last_overlapped = false;
-    int launched_class[kMaxLaunches] = {0};
-    bool launched_redo[kMaxLaunches] = {false}; // the exact kernel behind a segmented sweep: its cells are counted there
     // segmented sweep of the multi-wavefront classes (grid mode): per-class scratch columns and redo lists
     DevBuf<float> d_trace_work;   // the traceback's work areas (kept between calls, grows to the largest round): floats, or
                                   // the double traceback's values in the same bytes (one work area per context)
@@ -290,31 +323,14 @@ struct dcp_gpu_ctx
     int seg_mode = -1;             // test hook: 0 never, 1 always where a kernel exists, -1 automatic
     int mp_mode = -1;              // test hook: 0 never K profiles per wavefront, 1 always, -1 automatic
     uint64_t seg_col_bytes = (uint64_t)6 << 30; // cap on one class's boundary columns (test hook: shrink it to reach the chunked path)
-    unsigned n_launched = 0;
-#ifdef DCP_TEST_HOOKS
-    // test hook (dcp_gpu_test_last_rowsweep_plan): what launch_rowsweep_scan last did with each size class
-    struct RowsweepClassPlan
-    {
-        unsigned path = 0;         // DCP_RS_PATH_*: 0 = the class is empty
-        unsigned stage = 0, waves = 0, prefetch = 0; // plain grid: rowsweep_variant's answer
-        unsigned chunk = 0;        // segmented: queries per pass
-        unsigned flagged_rest = 0; // K profiles per wavefront: the flagged profiles got a launch of their own
-    } rs_plan[kNumClasses];
-    // test hook (dcp_gpu_test_last_pair_launches): the pair-mode launches of the last scan or pair scan, in launch order
-    struct PairLaunch
-    {
-        unsigned kind, precision, a, b, units, tpb, cap;
-    };
-    std::vector<PairLaunch> pair_launches;
-#endif
 
     // The resident DB is float (dcp_gpu_db_upload) or double (dcp_gpu_db_upload64): 32 / 64, 0 while none is.
     int precision = 0;
-    bool last_f64 = false; // the last scan ran on a double DB: its results are the f64 ones below
     double lrt_threshold64 = std::numeric_limits<double>::quiet_NaN(); // NaN: the scan's float threshold
     struct F64Db
     {
         std::vector<dcp_f64_prof> profs;   // by launch group (kF64Groups), then by caller index
+        std::vector<uint32_t> slot_of_pidx; // the entry of profs of each caller's profile index
         unsigned group_first[5] = {0, 0, 0, 0, 0};
         DevBuf<dcp_f64_prof> d_profs;
         DevBuf<double> d_tab, d_trans, d_xe; // match tables, trans8 rows, insert + null tables
@@ -332,7 +348,6 @@ struct dcp_gpu_ctx
         DevBuf<double> d_planes;
         DevBuf<unsigned> d_task, d_redo_n;
         DevBuf<dcp_f64_pair> d_redo;
-        bool redo_pending = false; // the last scan's redo counters have not been checked yet
         DevBuf<dcp_f64_pair> d_pair_list; // dcp_gpu_scan_pairs: one list per launch group back to back, their lengths
         DevBuf<unsigned> d_pair_n;        // [4]
         void release()
@@ -343,7 +358,7 @@ struct dcp_gpu_ctx
             d_xt.release(), d_col.release(), res.release();
             d_order.release(), d_qorder.release(), d_planes.release(), d_task.release(), d_redo_n.release();
             d_redo.release(), d_slot_first.release(), d_groups.release();
-            redo_pending = false;
+            slot_of_pidx.clear();
         }
     } f64;
 
@@ -445,13 +460,7 @@ struct dcp_gpu_ctx
     } while (0)
 
 // A new DB or a new batch: the last scan is void, and so is whatever of it has not been looked at yet.
-static void void_last_scan(dcp_gpu_ctx *c)
-{
-    c->scanned = false;
-    c->redo_pending = false;
-    c->f64.redo_pending = false;
-    c->ring_check_pending = false;
-}
+static void void_last_scan(dcp_gpu_ctx *c) { c->last = LastScan{}; }
 
 // What the float and the double path share (templates: outside the extern "C" block)
 extern "C" { static int finish_scan(dcp_gpu_ctx *c); } // defined behind dcp_gpu_scan_range
@@ -466,6 +475,21 @@ int range_of(unsigned const *first, int n, unsigned slot)
     while (k + 1 < n && slot >= first[k + 1])
         ++k;
     return k;
+}
+
+// A stable counting sort of n items into nclasses classes.  first[k] .. first[k + 1] are then the places of the items of
+// class k = class_of(item), in the order they came in (first: [nclasses + 1]); returns the item at each place.
+template <class ClassOf> std::vector<unsigned> sort_into_classes(unsigned n, int nclasses, unsigned *first, ClassOf class_of)
+{
+    std::fill(first, first + nclasses + 1, 0u);
+    for (unsigned i = 0; i < n; ++i)
+        ++first[class_of(i) + 1];
+    for (int k = 0; k < nclasses; ++k)
+        first[k + 1] += first[k];
+    std::vector<unsigned> at(first, first + nclasses), order(n);
+    for (unsigned i = 0; i < n; ++i)
+        order[at[class_of(i)]++] = i;
+    return order;
 }
 
 template <class Real> int fetch_table_rows(dcp_gpu_ctx *c, Real const *src, unsigned ldk, unsigned core_size, Real *out)
@@ -515,7 +539,7 @@ int fill_xtrans(dcp_gpu_ctx *c, std::vector<uint32_t> const &seqs, int multi_hit
 // dcp_gpu_fetch_scores[64] / dcp_gpu_fetch_hits[64] once the last scan is known to be of the precision asked for
 template <class Real, class Hit> int fetch_scores(dcp_gpu_ctx *c, ScanResults<Real, Hit> const &r, Real *null_out, Real *alt_out)
 {
-    if (!c->scanned || !r.have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
+    if (!c->last.scanned || !r.have_scores) return c->fail(DCP_EINVAL, "no dense scores kept by the last scan");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc;
     size_t const bytes = (size_t)c->nseqs * c->nprof * sizeof(Real);
@@ -625,7 +649,7 @@ int trace_rounds(dcp_gpu_ctx *c, Hit const *hits, unsigned nhits, std::vector<ui
                 if (first[k] < first[k - 1]) first[k] = first[k - 1];
             // one work area per context, kept between calls: floats, or the double traceback's values in the same bytes
             size_t const work_floats = (size_t)(work * (sizeof(Real) / sizeof(float)));
-            if (c->d_trace_work.n < work_floats) HIP_TRY(c, c->d_trace_work.alloc(work_floats));
+            HIP_TRY(c, c->d_trace_work.reserve(work_floats));
             r.work = reinterpret_cast<Real *>(c->d_trace_work.p);
             HIP_TRY(c, r.alt.alloc(n));
             HIP_TRY(c, r.woff.alloc(n));
@@ -720,7 +744,7 @@ dcp_gpu_ctx *dcp_gpu_ctx_new(int device)
         c->ql_G = (int)dcp_qlane_tile_nodes() / 4;
     }
     bool ok = true;
-    for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
+    for (int k = 0; k < kMaxLaunches; ++k)
         ok = ok && hipEventCreate(&c->ev_class[k]) == hipSuccess;
     for (int k = 0; k < kNumClasses; ++k)
         ok = ok && hipStreamCreateWithFlags(&c->class_stream[k], hipStreamNonBlocking) == hipSuccess;
@@ -752,7 +776,7 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->post.ev)
         if (e) (void)hipEventDestroy(e);
-    for (int k = 0; k < dcp_gpu_ctx::kMaxLaunches; ++k)
+    for (int k = 0; k < kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
     for (int k = 0; k <= kNumClasses; ++k)
         if (c->ev_trace[k]) (void)hipEventDestroy(c->ev_trace[k]);
@@ -1436,6 +1460,9 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     }
     for (int g = 1; g < 5; ++g) // empty groups start where the one before ends
         F.group_first[g] = std::max(F.group_first[g], F.group_first[g - 1]);
+    F.slot_of_pidx.assign(nprofiles, 0);
+    for (unsigned i = 0; i < nprofiles; ++i)
+        F.slot_of_pidx[F.profs[i].pidx] = i;
 
     // transitions padded with -inf; one expansion job per table column
     std::vector<double> h_trans(trans, -std::numeric_limits<double>::infinity());
@@ -1595,11 +1622,8 @@ int dcp_gpu_decode_paths(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const
     {
         HIP_TRY(c, hipSetDevice(c->device));
         size_t const cap = (size_t)std::min<uint64_t>(nemit, (uint64_t)DCP_DECODE_MAX_ITEMS);
-        if (c->d_dec_items.n < cap || c->d_dec_codes.n < cap) // both or neither: a failed second allocation is tried again
-        {
-            HIP_TRY(c, c->d_dec_items.alloc(cap));
-            HIP_TRY(c, c->d_dec_codes.alloc(cap));
-        }
+        HIP_TRY(c, c->d_dec_items.reserve(cap)); // (the two grow together: a failed second allocation is tried again)
+        HIP_TRY(c, c->d_dec_codes.reserve(cap));
         // rounds of at most DCP_DECODE_MAX_ITEMS emitting steps, cut wherever the list is full: the work list (path,
         // fragment start, length, state) holds integers only
         std::vector<dcp_decode_item> items;
@@ -2213,8 +2237,8 @@ int dcp_gpu_set_hit_buffer(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void *n
 int dcp_gpu_hit_buffer(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsigned *cap)
 {
     if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
-    if (c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a double DB: its hits are struct dcp_hit64 (dcp_gpu_fetch_hits64)");
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (c->last.f64) return c->fail(DCP_EINVAL, "the last scan ran on a double DB: its hits are struct dcp_hit64 (dcp_gpu_fetch_hits64)");
     return hit_buffer(c->res, hits_dev, nhits_dev, cap);
 }
 
@@ -2227,8 +2251,8 @@ int dcp_gpu_set_hit_buffer64(dcp_gpu_ctx *c, void *hits_dev, unsigned cap, void 
 int dcp_gpu_hit_buffer64(dcp_gpu_ctx *c, void **hits_dev, void **nhits_dev, unsigned *cap)
 {
     if (!c || !hits_dev || !nhits_dev || !cap) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
-    if (!c->last_f64) return c->fail(DCP_EINVAL, "the last scan ran on a float DB: its hits are struct dcp_hit (dcp_gpu_hit_buffer)");
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (!c->last.f64) return c->fail(DCP_EINVAL, "the last scan ran on a float DB: its hits are struct dcp_hit (dcp_gpu_hit_buffer)");
     return hit_buffer(c->f64.res, hits_dev, nhits_dev, cap);
 }
 
@@ -2445,12 +2469,89 @@ static void rowsweep_variant(dcp_gpu_ctx const *c, int R, int W, unsigned nchunk
 
 // Boundary columns of the f64 DB's segmented launch group, for the npairs pairs of it that a scan or a traceback round
 // sweeps: 5 doubles per row and wavefront, at most 1 GiB of them; the wavefronts stride over the pairs.
-static int f64_seg_columns(dcp_gpu_ctx *c, uint32_t lmax, uint64_t npairs, uint64_t *col_stride, uint64_t *seg_waves)
+struct F64Seg
 {
-    *col_stride = 5ull * ((uint64_t)lmax + 1u);
-    *seg_waves = npairs ? std::min<uint64_t>(npairs, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / *col_stride)) : 0;
-    if (c->f64.d_col.n < *seg_waves * *col_stride) HIP_TRY(c, c->f64.d_col.alloc(*seg_waves * *col_stride));
+    uint64_t col_stride = 0, waves = 0;
+};
+static int f64_seg_columns(dcp_gpu_ctx *c, uint32_t lmax, uint64_t npairs, F64Seg *seg)
+{
+    seg->col_stride = 5ull * ((uint64_t)lmax + 1u);
+    seg->waves = npairs ? std::min<uint64_t>(npairs, std::max<uint64_t>(1u, ((uint64_t)1 << 27) / seg->col_stride)) : 0;
+    HIP_TRY(c, c->f64.d_col.reserve(seg->waves * seg->col_stride));
     return DCP_OK;
+}
+
+// The geometry of launch group g of an f64 DB over `count` pairs: one wavefront per pair, at most `cap` (2^24: 2^22
+// blocks of 256); the segmented group strides over its pairs with one boundary column per wavefront (seg:
+// f64_seg_columns' answer for those pairs, never more wavefronts than pairs or than 2^24).  Returns the wavefronts.
+static unsigned f64_group_geometry(dcp_gpu_ctx const *c, int g, uint64_t count, F64Seg const &seg, dcp_f64_scan_args &a,
+                                   uint64_t cap = 1ull << 24)
+{
+    a.col = g == 3 ? c->f64.d_col.p : nullptr;
+    a.col_stride = g == 3 ? seg.col_stride : 0;
+    uint64_t const waves = std::min(count, cap);
+    return (unsigned)(g == 3 ? std::min(waves, seg.waves) : waves);
+}
+
+// What every driver that takes explicit special transitions refuses: the set of the other precision.
+static int check_xtrans_precision(dcp_gpu_ctx *c)
+{
+    if (c->precision == 64 && c->xt_explicit)
+        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    if (c->precision != 64 && !c->xt64.empty())
+        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    return DCP_OK;
+}
+
+// The bounds of a list of n (sequence, profile) pairs, `stride` words from one pair's indices to the next's (1: two
+// arrays; a traceback's hit records: the record's words).  `hit`: the tracebacks' short message.
+static_assert(sizeof(dcp_hit) % sizeof(uint32_t) == 0 && sizeof(dcp_hit64) % sizeof(uint32_t) == 0, "hit records are whole words");
+static int check_pairs(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, size_t stride, unsigned n, bool hit)
+{
+    for (unsigned i = 0; i < n; ++i)
+    {
+        uint32_t const s = seq_idx[i * stride], p = profile_idx[i * stride];
+        if (s < c->nseqs && p < c->nprof) continue;
+        char who[64] = "", batch[32] = "", db[32] = "";
+        if (!hit)
+        {
+            snprintf(who, sizeof who, " (sequence %u, profile %u)", s, p);
+            snprintf(batch, sizeof batch, " (%u sequences)", c->nseqs);
+            snprintf(db, sizeof db, " (%u profiles)", c->nprof);
+        }
+        return c->fail(DCP_EINVAL, "%s %u%s is outside the resident batch%s / DB%s", hit ? "hit" : "pair", i, who, batch, db);
+    }
+    return DCP_OK;
+}
+
+// One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST scan.  A scan enqueued
+// while the one before it still has unchecked redo lists or ring word first completes that one (its overflow re-run
+// included), so nothing of it is silently half done.
+static int complete_pending_scan(dcp_gpu_ctx *c)
+{
+    bool const pending = c->last.redo_pending || c->last.redo_pending64 || c->last.ring_check_pending;
+    return pending ? finish_scan(c) : DCP_OK;
+}
+
+// The hooks build's records of what launch_rowsweep_scan did with size class k (dcp_gpu_test_last_rowsweep_plan) and of
+// a pair-mode launch (dcp_gpu_test_last_pair_launches); nothing in the shipped library.
+static inline void note_rowsweep_plan(dcp_gpu_ctx *c, int k, unsigned path, int stage, unsigned waves, int prefetch, unsigned chunk,
+                                      bool flagged_rest)
+{
+#ifdef DCP_TEST_HOOKS
+    c->last.rs_plan[k] = {path, (unsigned)stage, waves, (unsigned)prefetch, chunk, flagged_rest ? 1u : 0u};
+#else
+    (void)c, (void)k, (void)path, (void)stage, (void)waves, (void)prefetch, (void)chunk, (void)flagged_rest;
+#endif
+}
+static inline void note_pair_launch(dcp_gpu_ctx *c, unsigned kind, unsigned precision, unsigned a, unsigned b, unsigned units,
+                                    unsigned tpb, unsigned cap)
+{
+#ifdef DCP_TEST_HOOKS
+    c->last.pair_launches.push_back({kind, precision, a, b, units, tpb, cap});
+#else
+    (void)c, (void)kind, (void)precision, (void)a, (void)b, (void)units, (void)tpb, (void)cap;
+#endif
 }
 
 // A scan of the resident double DB: viterbi64_kernel<R> per launch group (dcp_f64.hip), or -- kernel 4 -- the
@@ -2460,14 +2561,17 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
 {
     if (prm->kernel != 0 && prm->kernel != 1 && prm->kernel != 4)
         return c->fail(DCP_EINVAL, "a double DB is scanned by the f64 row sweep (kernel 0 or 1) or the f64 query-lane kernel (4), not %d", prm->kernel);
-    if (c->xt_explicit)
-        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    if (int rc = check_xtrans_precision(c)) return rc;
     auto &F = c->f64;
     // one scan is outstanding per context: a query-lane scan whose redo counters have not been looked at is
     // completed first (its overflow re-run included)
-    if (F.redo_pending)
-        if (int rc = finish_scan(c)) return rc;
-    c->scanned = false;
+    if (int rc = complete_pending_scan(c)) return rc;
+    bool const qlane = prm->kernel == 4;
+    c->last = LastScan{};
+    c->last.f64 = true;
+    c->last.prm = *prm;
+    c->last.q0 = q_begin, c->last.q1 = q_end;
+    c->last.kernel = qlane ? 2 : 1, c->last.kernel_variant = qlane ? 4 : 1;
     unsigned const nq = q_end - q_begin;
     bool const xt_given = !c->xt64.empty(); // dcp_gpu_seqs_set_xtrans64: the flags are ignored
     std::vector<uint32_t> seqs(nq);
@@ -2475,12 +2579,12 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     std::vector<double> xt;
     if (int rc = fill_xtrans(c, seqs, prm->multi_hits, prm->hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
     uint32_t const lmax = *std::max_element(c->seq_len.begin() + q_begin, c->seq_len.begin() + q_end);
-    if (F.d_xt.n < xt.size()) HIP_TRY(c, F.d_xt.alloc(xt.size()));
+    HIP_TRY(c, F.d_xt.reserve(xt.size()));
     HIP_TRY(c, hipMemcpyAsync(F.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
 
     HIP_TRY(c, F.res.ensure((size_t)c->nseqs * c->nprof, prm->keep_scores != 0));
-    uint64_t col_stride = 0, seg_waves = 0;
-    if (int rc = f64_seg_columns(c, lmax, (uint64_t)(F.group_first[4] - F.group_first[3]) * nq, &col_stride, &seg_waves)) return rc;
+    F64Seg seg;
+    if (int rc = f64_seg_columns(c, lmax, (uint64_t)(F.group_first[4] - F.group_first[3]) * nq, &seg)) return rc;
 
     dcp_f64_scan_args a{};
     a.nprof_total = c->nprof;
@@ -2499,7 +2603,6 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     a.nhits = F.res.nhits();
     a.hit_cap = F.res.cap();
     a.lrt_threshold = is_nan(c->lrt_threshold64) ? (double)prm->lrt_threshold : c->lrt_threshold64; // NaN: not set
-    bool const qlane = prm->kernel == 4;
     bool const redo = prm->multi_hits != 0 || xt_given;
     dcp_f64_qlane_args qa{};
     unsigned ql_blocks = 0;
@@ -2524,10 +2627,10 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         ql_blocks = (unsigned)std::min<uint64_t>(std::min<uint64_t>(2ull * c->num_cus, ntasks), budget / (plane_stride * sizeof(double)));
         if (ql_blocks == 0)
             return c->fail(DCP_ENOMEM, "sequences too long for the f64 query-lane kernel (%u rows of boundary planes do not fit the device): use kernel = 1", lmax);
-        if (F.d_planes.n < ql_blocks * plane_stride) HIP_TRY(c, F.d_planes.alloc(ql_blocks * plane_stride));
-        if (F.d_qorder.n < nq) HIP_TRY(c, F.d_qorder.alloc(nq));
-        if (F.d_slot_first.n < plan.slot_first.size()) HIP_TRY(c, F.d_slot_first.alloc(plan.slot_first.size()));
-        if (F.d_groups.n < plan.groups.size()) HIP_TRY(c, F.d_groups.alloc(plan.groups.size()));
+        HIP_TRY(c, F.d_planes.reserve(ql_blocks * plane_stride));
+        HIP_TRY(c, F.d_qorder.reserve(nq));
+        HIP_TRY(c, F.d_slot_first.reserve(plan.slot_first.size()));
+        HIP_TRY(c, F.d_groups.reserve(plan.groups.size()));
         HIP_TRY(c, hipMemcpyAsync(F.d_qorder.p, qorder.data(), nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(F.d_slot_first.p, plan.slot_first.data(), plan.slot_first.size() * sizeof(uint32_t),
                                   hipMemcpyHostToDevice, c->stream));
@@ -2538,8 +2641,8 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         F.plan_max_groups = 0;
         for (size_t i = 0; i + 1u < plan.slot_first.size(); ++i)
             F.plan_max_groups = std::max<unsigned>(F.plan_max_groups, plan.slot_first[i + 1u] - plan.slot_first[i]);
-        if (!F.d_task.p) HIP_TRY(c, F.d_task.alloc(1));
-        if (!F.d_redo_n.p) HIP_TRY(c, F.d_redo_n.alloc(5));
+        HIP_TRY(c, F.d_task.reserve(1));
+        HIP_TRY(c, F.d_redo_n.reserve(5));
         // a redo list per launch group; uni-hit scans have no feedback and no lists (explicit transitions may carry
         // E -> B / J -> B feedback whatever the flag says)
         uint64_t redo_total = 0;
@@ -2552,7 +2655,7 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         }
         if (redo_total > 0xffffffffull)
             return c->fail(DCP_ENOMEM, "batch too large for the f64 query-lane kernel's redo lists: use kernel = 1");
-        if (F.d_redo.n < redo_total) HIP_TRY(c, F.d_redo.alloc(redo_total));
+        HIP_TRY(c, F.d_redo.reserve(redo_total));
         qa.profs = F.d_profs.p;
         qa.order = F.d_order.p;
         qa.nprof_total = c->nprof;
@@ -2575,15 +2678,11 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
     }
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    unsigned launches = 0;
-#ifdef DCP_TEST_HOOKS
-    c->pair_launches.clear();
-#endif
     if (qlane)
     {
         dcp_f64_launch_qlane(&qa, ql_blocks, c->stream);
         HIP_TRY(c, hipGetLastError());
-        ++launches;
+        ++c->last.launches;
         // the pairs whose B(j) was not B0(j): the row sweep over each group's list, right behind
         for (int g = 0; g < 4 && redo; ++g)
         {
@@ -2595,16 +2694,12 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
             pa.pairs = F.d_redo.p + qa.redo_first[g];
             pa.npairs_dev = F.d_redo_n.p + g;
             pa.pair_cap = qa.redo_cap[g];
-            uint64_t const waves = std::min<uint64_t>(g == 3 ? seg_waves : 4096u, std::min<uint64_t>(qa.redo_cap[g], 4096u));
-            pa.col = g == 3 ? F.d_col.p : nullptr;
-            pa.col_stride = g == 3 ? col_stride : 0;
-            if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, (unsigned)waves, c->stream))
+            unsigned const waves = f64_group_geometry(c, g, qa.redo_cap[g], seg, pa, 4096u); // (these launches' own cap)
+            if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, waves, c->stream))
                 return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
             HIP_TRY(c, hipGetLastError());
-            ++launches;
-#ifdef DCP_TEST_HOOKS
-            c->pair_launches.push_back({DCP_PL_QLANE_REDO, 64u, (unsigned)g, (unsigned)kF64R[g], (unsigned)waves, 1u, pa.pair_cap});
-#endif
+            ++c->last.launches;
+            note_pair_launch(c, DCP_PL_QLANE_REDO, 64u, (unsigned)g, (unsigned)kF64R[g], waves, 1u, pa.pair_cap);
         }
     }
     for (int g = 0; g < 4 && !qlane; ++g)
@@ -2613,35 +2708,20 @@ static int scan64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsigned q_
         if (n == 0) continue;
         a.profs = F.d_profs.p + F.group_first[g];
         a.nprof = n;
-        uint64_t const pairs = (uint64_t)n * nq;
-        // one wavefront per pair; the segmented group strides over its pairs with one boundary column per wavefront
-        uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(pairs, 1ull << 24); // 2^22 blocks of 256
-        a.col = g == 3 ? F.d_col.p : nullptr;
-        a.col_stride = g == 3 ? col_stride : 0;
-        if (dcp_f64_launch_scan(kF64R[g], &a, (unsigned)waves, c->stream))
+        if (dcp_f64_launch_scan(kF64R[g], &a, f64_group_geometry(c, g, (uint64_t)n * nq, seg, a), c->stream))
             return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
         HIP_TRY(c, hipGetLastError());
-        ++launches;
+        ++c->last.launches;
     }
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->last_q0 = q_begin;
-    c->last_q1 = q_end;
-    c->last_launches = launches;
-    c->n_launched = 0; // no per-launch records (dcp_gpu_last_scan_launch_info) for the f64 kernels
-    c->last_kernel = qlane ? 2 : 1;
-    c->last_kernel_variant = qlane ? 4 : 1;
-    c->last_prm = *prm;
-    c->last_redo_pairs = 0;
-    F.redo_pending = qlane && redo;
-    c->last_overlapped = false;
-    c->res.have_scores = false;
-    c->last_f64 = true;
-    c->scanned = true;
+    c->last.redo_pending64 = qlane && redo;
+    c->last.scanned = true;
     return DCP_OK;
 }
 
-// The row-sweep kernels' argument block for the queries [q_begin, q_end) of the resident batch.
-static dcp_scan_args scan_args(dcp_gpu_ctx const *c, struct dcp_scan_params const *prm, unsigned q_begin, unsigned q_end)
+// What a row-sweep kernel reads of the resident DB and of the queries [q_begin, q_end) of the resident batch, and the
+// geometry of the range; no outputs (the traceback's forward pass has none of a scan's).
+static dcp_scan_args scan_inputs(dcp_gpu_ctx const *c, unsigned q_begin, unsigned q_end)
 {
     dcp_scan_args a{};
     a.profs = c->d_metas.p;
@@ -2655,12 +2735,6 @@ static dcp_scan_args scan_args(dcp_gpu_ctx const *c, struct dcp_scan_params cons
     a.seq_woff = c->d_seq_woff.p + q_begin;
     a.seq_len = c->d_seq_len.p + q_begin;
     a.xtrans = c->d_xtrans.p + (size_t)q_begin * DCP_XSTRIDE;
-    a.out_null = c->res.have_scores ? c->res.d_null.p + (size_t)q_begin * c->nprof : nullptr;
-    a.out_alt = c->res.have_scores ? c->res.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
-    a.hits = c->res.hits();
-    a.nhits = c->res.nhits();
-    a.hit_cap = c->res.cap();
-    a.lrt_threshold = prm->lrt_threshold;
     a.nprof_total = c->nprof;
     a.nseqs = nq;
     a.q_base = q_begin;
@@ -2670,6 +2744,19 @@ static dcp_scan_args scan_args(dcp_gpu_ctx const *c, struct dcp_scan_params cons
     // 4 MB L2 holds tables of (C3 step: 848 -> 879 Gcell/s from 8 to 1; 25 profiles x 256 queries: 8.8 -> 1.8 ms).
     a.qchunk = 1u;
     a.nchunks = (nq + a.qchunk - 1) / a.qchunk;
+    return a;
+}
+
+// The row-sweep kernels' argument block for a scan of those queries: the inputs, and the float results as its outputs.
+static dcp_scan_args scan_args(dcp_gpu_ctx const *c, struct dcp_scan_params const *prm, unsigned q_begin, unsigned q_end)
+{
+    dcp_scan_args a = scan_inputs(c, q_begin, q_end);
+    a.out_null = c->res.have_scores ? c->res.d_null.p + (size_t)q_begin * c->nprof : nullptr;
+    a.out_alt = c->res.have_scores ? c->res.d_alt.p + (size_t)q_begin * c->nprof : nullptr;
+    a.hits = c->res.hits();
+    a.nhits = c->res.nhits();
+    a.hit_cap = c->res.cap();
+    a.lrt_threshold = prm->lrt_threshold;
     return a;
 }
 
@@ -2729,7 +2816,7 @@ static int choose_kernel(dcp_gpu_ctx const *c, unsigned q_begin, unsigned q_end,
 // between scans of the same range and block size.
 static int ensure_qlane_layout(dcp_gpu_ctx *c, dcp_scan_args const &a, unsigned q_begin, unsigned q_end, unsigned ql_nt)
 {
-    if (!c->d_task_counter.p) HIP_TRY(c, c->d_task_counter.alloc(1));
+    HIP_TRY(c, c->d_task_counter.reserve(1));
     if (c->qorder_q0 == q_begin && c->qorder_q1 == q_end && c->qorder_nt == ql_nt) return DCP_OK;
     unsigned const nq = q_end - q_begin, NTq = ql_nt, slots = NTq / 64u;
     SortedQueries const sorted = sorted_query_plan(c, q_begin, q_end, slots);
@@ -2765,11 +2852,11 @@ static int ensure_qlane_layout(dcp_gpu_ctx *c, dcp_scan_args const &a, unsigned 
         if (tot > 0xffffffffull) return c->fail(DCP_EINVAL, "sequence batch too large");
         wt_off[b + 1u] = (uint32_t)tot;
     }
-    if (c->d_qorder.n < nq) HIP_TRY(c, c->d_qorder.alloc(nq));
-    if (c->d_wt_off.n < nqb + 1u) HIP_TRY(c, c->d_wt_off.alloc(nqb + 1u));
-    if (c->d_slot_first.n < nslot_words) HIP_TRY(c, c->d_slot_first.alloc(nslot_words));
-    if (c->d_ql_groups.n < plan.groups.size()) HIP_TRY(c, c->d_ql_groups.alloc(plan.groups.size()));
-    if (c->d_words_t.n < tot) HIP_TRY(c, c->d_words_t.alloc((size_t)tot));
+    HIP_TRY(c, c->d_qorder.reserve(nq));
+    HIP_TRY(c, c->d_wt_off.reserve(nqb + 1u));
+    HIP_TRY(c, c->d_slot_first.reserve(nslot_words));
+    HIP_TRY(c, c->d_ql_groups.reserve(plan.groups.size()));
+    HIP_TRY(c, c->d_words_t.reserve((size_t)tot));
     HIP_TRY(c, hipMemcpyAsync(c->d_qorder.p, h_ord, nq * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_wt_off.p, wt_off, (nqb + 1u) * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_slot_first.p, h_slots, nslot_words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -2791,11 +2878,11 @@ static int ensure_qlane_layout(dcp_gpu_ctx *c, dcp_scan_args const &a, unsigned 
 // launches by them), the context stream's join on it when the launch ran on a forked stream, and the launch's record.
 static int record_launch(dcp_gpu_ctx *c, int k, bool is_redo, hipStream_t stream, bool join)
 {
-    HIP_TRY(c, hipEventRecord(c->ev_class[c->n_launched], stream));
-    if (join) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->n_launched], 0));
-    c->launched_redo[c->n_launched] = is_redo; // the exact kernel behind a segmented sweep
-    c->launched_class[c->n_launched++] = k;    // -1: the query-lane launch
-    c->last_launches++;
+    HIP_TRY(c, hipEventRecord(c->ev_class[c->last.n_launched], stream));
+    if (join) HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_class[c->last.n_launched], 0));
+    c->last.launched_redo[c->last.n_launched] = is_redo; // the exact kernel behind a segmented sweep
+    c->last.launched_class[c->last.n_launched++] = k;    // -1: the query-lane launch
+    c->last.launches++;
     return DCP_OK;
 }
 
@@ -2859,11 +2946,11 @@ static int launch_qlane_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, 
             uint64_t g = std::min<uint64_t>((cap + tpb - 1) / tpb, 8ull * c->num_cus);
             redo_grid[k] = (unsigned)((g + 7) / 8 * 8);
         }
-        if (c->d_redo.n < tot) HIP_TRY(c, c->d_redo.alloc((size_t)tot));
+        HIP_TRY(c, c->d_redo.reserve((size_t)tot));
     }
     // counters, overflow flag and the ring's error word start every query-lane scan at zero (without redo the
     // lists' capacities are 0: the counters are never written)
-    if (!c->d_redo_n.p) HIP_TRY(c, c->d_redo_n.alloc(DCP_MAX_CLASSES + 2));
+    HIP_TRY(c, c->d_redo_n.reserve(DCP_MAX_CLASSES + 2));
     HIP_TRY(c, hipMemsetAsync(c->d_redo_n.p, 0, (DCP_MAX_CLASSES + 2) * sizeof(unsigned), c->stream));
     qa.redo = c->d_redo.p;
     qa.redo_n = c->d_redo_n.p;
@@ -2881,7 +2968,7 @@ static int launch_qlane_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, 
     if (nblocks == 0)
         return c->fail(DCP_ENOMEM, "sequences too long for the query-lane kernel (%u plane rows): use kernel = 1", qa.plane_rows);
     size_t const need = (size_t)nblocks * per_block;
-    if (c->d_scratch.n < need) HIP_TRY(c, c->d_scratch.alloc(need));
+    HIP_TRY(c, c->d_scratch.reserve(need));
     qa.scratch = c->d_scratch.p;
     HIP_TRY(c, hipMemsetAsync(c->d_task_counter.p, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
@@ -2903,17 +2990,13 @@ static int launch_qlane_scan(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, 
         if (dcp_launch_rowsweep(sc.R, sc.W, &a, redo_grid[k], c->stream))
             return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
         if (int rc = record_launch(c, k, true, c->stream, false)) return rc;
-#ifdef DCP_TEST_HOOKS
-        c->pair_launches.push_back({DCP_PL_QLANE_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, redo_grid[k], dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap});
-#endif
+        note_pair_launch(c, DCP_PL_QLANE_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, redo_grid[k], dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap);
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->scanned = true;
-    c->redo_pending = redo;
-    c->ring_check_pending = two_stage;
-    c->last_redo_pairs = 0;
-    c->last_prm = *prm;
+    c->last.redo_pending = redo;
+    c->last.ring_check_pending = two_stage;
+    c->last.scanned = true;
     return DCP_OK;
 }
 
@@ -3002,9 +3085,7 @@ static int launch_segsweep_class(dcp_gpu_ctx *c, dcp_scan_args &a, int k, SegSwe
     g = (g + 7u) / 8u * 8u;
     if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)g, ls))
         return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
-#ifdef DCP_TEST_HOOKS
-    c->pair_launches.push_back({DCP_PL_SEG_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, (unsigned)g, dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap});
-#endif
+    note_pair_launch(c, DCP_PL_SEG_REDO, 32u, (unsigned)sc.R, (unsigned)sc.W, (unsigned)g, dcp_rowsweep_tasks_per_block(sc.W), a.pair_cap);
     return record_launch(c, k, true, ls, overlap);
 }
 
@@ -3015,24 +3096,18 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
     unsigned const nq = q_end - q_begin;
     if (int rc = ensure_rowsweep_layout(c)) return rc;
     a.emis_match = c->d_emis_match.p;
-    c->redo_pending = false;
-    c->last_redo_pairs = 0;
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     // fork / join around the class launches when no single one fills the chip for long (2^22 pairs: 20 000 profiles x 209
     // queries, i.e. every batch the automatic choice gives the row sweep; 112 .. 160 queries: 1 % faster than one launch
     // after the other, profiles/r04/class_launch_order.txt)
     bool const overlap = (uint64_t)nq * c->nprof < ((uint64_t)1 << 22);
-    c->last_overlapped = overlap;
+    c->last.overlapped = overlap;
     SegSweepPlan const sp = plan_segsweep(c, q_begin, q_end);
-#ifdef DCP_TEST_HOOKS
-    for (int k = 0; k < kNumClasses; ++k)
-        c->rs_plan[k] = {};
-#endif
     if (sp.col_rows)
     {
-        if (c->d_seg_scratch.n < sp.col_rows * 4u) HIP_TRY(c, c->d_seg_scratch.alloc((size_t)sp.col_rows * 4u));
-        if (c->d_seg_redo.n < sp.redo_tot) HIP_TRY(c, c->d_seg_redo.alloc((size_t)sp.redo_tot));
-        if (!c->d_seg_redo_n.p) HIP_TRY(c, c->d_seg_redo_n.alloc(DCP_MAX_CLASSES));
+        HIP_TRY(c, c->d_seg_scratch.reserve((size_t)sp.col_rows * 4u));
+        HIP_TRY(c, c->d_seg_redo.reserve((size_t)sp.redo_tot));
+        HIP_TRY(c, c->d_seg_redo_n.reserve(DCP_MAX_CLASSES));
         HIP_TRY(c, hipMemsetAsync(c->d_seg_redo_n.p, 0, DCP_MAX_CLASSES * sizeof(unsigned), c->stream));
         HIP_TRY(c, hipEventRecord(c->ev_start, c->stream)); // the forked streams wait for the counters' reset too
     }
@@ -3059,9 +3134,7 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
         {
             float *const col_base = c->d_seg_scratch.p + seg_col_at;
             seg_col_at += (uint64_t)a.nprof * sp.chunk[k] * 2u * sp.stride * 4u;
-#ifdef DCP_TEST_HOOKS
-            c->rs_plan[k].path = DCP_RS_PATH_SEGMENTED, c->rs_plan[k].chunk = sp.chunk[k];
-#endif
+            note_rowsweep_plan(c, k, DCP_RS_PATH_SEGMENTED, 0, 0u, 0, sp.chunk[k], false);
             if (int rc = launch_segsweep_class(c, a, k, sp, col_base, ls, overlap)) return rc;
             continue;
         }
@@ -3090,19 +3163,14 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
                     return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch") : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
             }
             a.first_prof = first, a.nprof = last - first;
-#ifdef DCP_TEST_HOOKS
-            c->rs_plan[k].path = DCP_RS_PATH_MP, c->rs_plan[k].flagged_rest = c->mp_flagged_first[k] != 0u;
-#endif
+            note_rowsweep_plan(c, k, DCP_RS_PATH_MP, 0, 0u, 0, 0u, c->mp_flagged_first[k] != 0u);
         }
         else
         {
             int stg, pf;
             unsigned bw;
             rowsweep_variant(c, sc.R, sc.W, a.nchunks, &stg, &bw, &pf);
-#ifdef DCP_TEST_HOOKS
-            c->rs_plan[k].path = DCP_RS_PATH_PLAIN;
-            c->rs_plan[k].stage = (unsigned)stg, c->rs_plan[k].waves = bw, c->rs_plan[k].prefetch = (unsigned)pf;
-#endif
+            note_rowsweep_plan(c, k, DCP_RS_PATH_PLAIN, stg, bw, pf, 0u, false);
             if (int lrc = dcp_launch_rowsweep_grid(sc.R, sc.W, &a, stg, bw, ls, c->rs_pad_lds, pf))
                 return lrc == -2 ? c->fail(DCP_EINVAL, "scan too large for one launch")
                                  : c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d (stage %d, %u wavefronts)", sc.R, sc.W, stg, bw);
@@ -3111,7 +3179,7 @@ static int launch_rowsweep_scan(dcp_gpu_ctx *c, dcp_scan_args &a, unsigned q_beg
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->scanned = true;
+    c->last.scanned = true;
     return DCP_OK;
 }
 
@@ -3123,23 +3191,18 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
     if (q_begin >= q_end || q_end > c->nseqs) return c->fail(DCP_EINVAL, "bad sequence range");
     HIP_TRY(c, hipSetDevice(c->device));
-    c->last_pair_scan = false;
     if (c->precision == 64) return scan64(c, prm, q_begin, q_end);
-    c->last_f64 = false;
-    // One scan is outstanding per context: results (hits, scores, redo lists) are those of the LAST
-    // scan.  A scan enqueued while the previous one still has unchecked redo lists first completes
-    // that one (its overflow re-run included), so nothing of it is silently half done.
-    if (c->redo_pending || c->ring_check_pending)
-        if (int rc = finish_scan(c)) return rc;
-    if (!c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    if (int rc = complete_pending_scan(c)) return rc;
+    if (int rc = check_xtrans_precision(c)) return rc;
+    if (prm->kernel < 0 || prm->kernel > 3) return c->fail(DCP_EINVAL, "unknown kernel %d", prm->kernel);
+    c->last = LastScan{};
+    c->last.prm = *prm;
+    c->last.q0 = q_begin, c->last.q1 = q_end;
 
     if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
     HIP_TRY(c, c->res.ensure((size_t)c->nseqs * c->nprof, prm->keep_scores != 0));
     dcp_scan_args a = scan_args(c, prm, q_begin, q_end);
     unsigned const nq = q_end - q_begin;
-    c->last_q0 = q_begin;
-    c->last_q1 = q_end;
 
     // Queries per block of the single-stage query-lane kernel.  (Narrow 64- / 128-query blocks were tried for
     // small batches: hipOccupancyMaxActiveBlocksPerMultiprocessor reports three 54.5 KB blocks per CU, the
@@ -3153,21 +3216,15 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
     // kernel choice: the query-lane kernel needs enough queries to fill its lanes
     int kernel = prm->kernel;
     if (kernel == 0) kernel = choose_kernel(c, q_begin, q_end, a.qchunk, ql_nt, ql_blocks_per_cu, w3);
-    if (kernel < 1 || kernel > 3) return c->fail(DCP_EINVAL, "unknown kernel %d", kernel);
     bool const two_stage = kernel == 3; // the query-lane kernel's two-stage variant (dcp_qlane.hip)
-    c->last_kernel_variant = kernel;
+    c->last.kernel_variant = kernel;
     if (two_stage) kernel = 2;
-    c->last_kernel = kernel;
+    c->last.kernel = kernel;
     if (two_stage) ql_nt = dcp_qlane_block_size(), ql_blocks_per_cu = 1; // 2 x 256 queries' wavefronts, one block per CU
     if (kernel == 2)
         if (int rc = ensure_qlane_layout(c, a, q_begin, q_end, ql_nt)) return rc;
 
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
-    c->last_launches = 0;
-    c->n_launched = 0;
-#ifdef DCP_TEST_HOOKS
-    c->pair_launches.clear();
-#endif
     if (kernel == 2) return launch_qlane_scan(c, prm, a, ql_nt, ql_blocks_per_cu, two_stage, w3 && !two_stage);
     return launch_rowsweep_scan(c, a, q_begin, q_end);
 }
@@ -3177,47 +3234,41 @@ int dcp_gpu_scan_range(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, unsign
 static int scan_pairs64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32_t const *seq_idx, uint32_t const *profile_idx,
                         unsigned npairs)
 {
-    if (c->xt_explicit)
-        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    if (int rc = check_xtrans_precision(c)) return rc;
     auto &F = c->f64;
-    if (F.redo_pending)
-        if (int rc = finish_scan(c)) return rc;
-    c->scanned = false;
-    // entry of F.profs (group-sorted) of each caller's profile index
-    std::vector<uint32_t> slot(c->nprof);
-    for (unsigned i = 0; i < (unsigned)F.profs.size(); ++i)
-        slot[F.profs[i].pidx] = i;
-    unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0};
-    for (unsigned i = 0; i < npairs; ++i)
-        ++count[range_of(F.group_first, 4, slot[profile_idx[i]])];
+    if (int rc = complete_pending_scan(c)) return rc;
+    c->last = LastScan{};
+    c->last.f64 = c->last.pair_scan = true;
+    c->last.prm = *prm;
+    c->last.q0 = 0, c->last.q1 = c->nseqs;
+    c->last.kernel = c->last.kernel_variant = 1;
+    unsigned first[5], count[4];
+    std::vector<unsigned> const order = sort_into_classes(
+        npairs, 4, first, [&](unsigned i) { return range_of(F.group_first, 4, F.slot_of_pidx[profile_idx[i]]); });
     for (int g = 0; g < 4; ++g)
-        first[g + 1] = first[g] + count[g];
+        count[g] = first[g + 1] - first[g];
     std::vector<dcp_f64_pair> pairs(npairs);
     uint32_t seg_lmax = 0;
-    uint64_t cells = 0, bytes = 0;
+    for (unsigned j = 0; j < npairs; ++j)
     {
-        unsigned at[4] = {first[0], first[1], first[2], first[3]};
-        for (unsigned i = 0; i < npairs; ++i)
-        {
-            uint32_t const s = slot[profile_idx[i]];
-            int const g = range_of(F.group_first, 4, s);
-            pairs[at[g]++] = dcp_f64_pair{seq_idx[i], s};
-            uint64_t const M = F.profs[s].core_size, L = c->seq_len[seq_idx[i]];
-            if (g == 3) seg_lmax = std::max(seg_lmax, (uint32_t)L);
-            cells += M * L, bytes += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
-        }
+        unsigned const i = order[j];
+        uint32_t const slot = F.slot_of_pidx[profile_idx[i]];
+        pairs[j] = dcp_f64_pair{seq_idx[i], slot};
+        uint64_t const M = F.profs[slot].core_size, L = c->seq_len[seq_idx[i]];
+        if (j >= first[3]) seg_lmax = std::max(seg_lmax, (uint32_t)L); // the segmented group's pairs
+        c->last.pair_cells += M * L, c->last.pair_bytes += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
     }
     // the kernel takes a pair's special transitions from its query's row: one row per resident sequence, as a scan's
     std::vector<uint32_t> seqs(c->nseqs);
     std::iota(seqs.begin(), seqs.end(), 0u);
     std::vector<double> xt;
     if (int rc = fill_xtrans(c, seqs, prm->multi_hits, prm->hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
-    if (F.d_xt.n < xt.size()) HIP_TRY(c, F.d_xt.alloc(xt.size()));
+    HIP_TRY(c, F.d_xt.reserve(xt.size()));
     HIP_TRY(c, F.res.ensure(npairs, false));
-    uint64_t col_stride = 0, seg_waves = 0;
-    if (int rc = f64_seg_columns(c, seg_lmax, count[3], &col_stride, &seg_waves)) return rc;
-    if (F.d_pair_list.n < npairs) HIP_TRY(c, F.d_pair_list.alloc(npairs));
-    if (!F.d_pair_n.p) HIP_TRY(c, F.d_pair_n.alloc(4));
+    F64Seg seg;
+    if (int rc = f64_seg_columns(c, seg_lmax, count[3], &seg)) return rc;
+    HIP_TRY(c, F.d_pair_list.reserve(npairs));
+    HIP_TRY(c, F.d_pair_n.reserve(4));
     HIP_TRY(c, hipMemcpyAsync(F.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (npairs) HIP_TRY(c, hipMemcpyAsync(F.d_pair_list.p, pairs.data(), (size_t)npairs * sizeof(dcp_f64_pair), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(F.d_pair_n.p, count, sizeof count, hipMemcpyHostToDevice, c->stream));
@@ -3236,42 +3287,21 @@ static int scan_pairs64(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint3
     pa.lrt_threshold = is_nan(c->lrt_threshold64) ? (double)prm->lrt_threshold : c->lrt_threshold64; // NaN: not set
     HIP_TRY(c, hipMemsetAsync(pa.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
-    unsigned launches = 0;
-#ifdef DCP_TEST_HOOKS
-    c->pair_launches.clear();
-#endif
     for (int g = 0; g < 4; ++g)
     {
         if (count[g] == 0) continue;
         pa.pairs = F.d_pair_list.p + first[g];
         pa.npairs_dev = F.d_pair_n.p + g;
         pa.pair_cap = count[g];
-        // one wavefront per pair; the segmented group strides over its pairs with one boundary column per wavefront
-        uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(count[g], 1ull << 24);
-        pa.col = g == 3 ? F.d_col.p : nullptr;
-        pa.col_stride = g == 3 ? col_stride : 0;
-        if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, (unsigned)waves, c->stream))
+        unsigned const waves = f64_group_geometry(c, g, count[g], seg, pa);
+        if (dcp_f64_launch_scan_pairs(kF64R[g], &pa, waves, c->stream))
             return c->fail(DCP_EFAIL, "no f64 kernel for %d nodes per lane", kF64R[g]);
         HIP_TRY(c, hipGetLastError());
-        ++launches;
-#ifdef DCP_TEST_HOOKS
-        c->pair_launches.push_back({DCP_PL_SCAN_PAIRS, 64u, (unsigned)g, (unsigned)kF64R[g], (unsigned)waves, 1u, pa.pair_cap});
-#endif
+        ++c->last.launches;
+        note_pair_launch(c, DCP_PL_SCAN_PAIRS, 64u, (unsigned)g, (unsigned)kF64R[g], waves, 1u, pa.pair_cap);
     }
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->last_q0 = 0, c->last_q1 = c->nseqs;
-    c->last_launches = launches;
-    c->n_launched = 0; // no per-launch records for the f64 kernels
-    c->last_kernel = c->last_kernel_variant = 1;
-    c->last_prm = *prm;
-    c->last_redo_pairs = 0;
-    F.redo_pending = false;
-    c->last_overlapped = false;
-    c->res.have_scores = false;
-    c->last_f64 = true;
-    c->last_pair_scan = true;
-    c->pair_cells = cells, c->pair_bytes = bytes;
-    c->scanned = true;
+    c->last.scanned = true;
     return DCP_OK;
 }
 
@@ -3287,47 +3317,40 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
     if (prm->kernel != 0 && prm->kernel != 1)
         return c->fail(DCP_EINVAL, "a pair list is scored by the row sweep (kernel 0 or 1), not %d", prm->kernel);
     if (npairs && (!seq_idx || !profile_idx)) return c->fail(DCP_EINVAL, "a pair list without its indices");
-    for (unsigned i = 0; i < npairs; ++i)
-        if (seq_idx[i] >= c->nseqs || profile_idx[i] >= c->nprof)
-            return c->fail(DCP_EINVAL, "pair %u (sequence %u, profile %u) is outside the resident batch (%u sequences) / DB (%u profiles)",
-                           i, seq_idx[i], profile_idx[i], c->nseqs, c->nprof);
+    if (int rc = check_pairs(c, seq_idx, profile_idx, 1u, npairs, false)) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->precision == 64) return scan_pairs64(c, prm, seq_idx, profile_idx, npairs);
-    // one scan is outstanding per context: an earlier query-lane scan is completed first (dcp_gpu_scan_range)
-    if (c->redo_pending || c->ring_check_pending)
-        if (int rc = finish_scan(c)) return rc;
-    if (!c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    // one scan is outstanding per context: an earlier query-lane scan is completed first
+    if (int rc = complete_pending_scan(c)) return rc;
+    if (int rc = check_xtrans_precision(c)) return rc;
+    c->last = LastScan{};
+    c->last.pair_scan = true;
+    c->last.prm = *prm;
+    c->last.q0 = 0, c->last.q1 = c->nseqs;
+    c->last.kernel = c->last.kernel_variant = 1;
     if (int rc = ensure_xtrans(c, prm->multi_hits, prm->hmmer3_compat)) return rc;
     if (int rc = ensure_rowsweep_layout(c)) return rc;
     HIP_TRY(c, c->res.ensure(npairs, false));
-    c->last_f64 = false;
-    c->scanned = false;
-    unsigned first[kNumClasses + 1] = {0}, count[DCP_MAX_CLASSES] = {0};
-    for (unsigned i = 0; i < npairs; ++i)
-        ++count[range_of(c->class_first, kNumClasses, c->slot_of_pidx[profile_idx[i]])];
+    unsigned first[kNumClasses + 1], count[DCP_MAX_CLASSES] = {0};
+    std::vector<unsigned> const order = sort_into_classes(
+        npairs, kNumClasses, first, [&](unsigned i) { return range_of(c->class_first, kNumClasses, c->slot_of_pidx[profile_idx[i]]); });
     for (int k = 0; k < kNumClasses; ++k)
-        first[k + 1] = first[k] + count[k];
+        count[k] = first[k + 1] - first[k];
     std::vector<dcp_pair> pairs(npairs);
-    c->pair_cells = c->pair_bytes = 0;
-    {
-        unsigned at[kNumClasses];
-        for (int k = 0; k < kNumClasses; ++k)
-            at[k] = first[k], c->pair_class_cells[k] = c->pair_class_bytes[k] = 0;
-        for (unsigned i = 0; i < npairs; ++i)
+    for (int k = 0; k < kNumClasses; ++k)
+        for (unsigned j = first[k]; j < first[k + 1]; ++j)
         {
+            unsigned const i = order[j];
             uint32_t const slot = c->slot_of_pidx[profile_idx[i]];
-            int const k = range_of(c->class_first, kNumClasses, slot);
-            pairs[at[k]++] = dcp_pair{seq_idx[i], slot}; // {q, slot}: the scan's first sequence is resident 0
+            pairs[j] = dcp_pair{seq_idx[i], slot}; // {q, slot}: the scan's first sequence is resident 0
             uint64_t const M = c->metas[slot].core_size, L = c->seq_len[seq_idx[i]];
-            c->pair_class_cells[k] += M * L;
-            c->pair_class_bytes[k] += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
+            c->last.pair_class_cells[k] += M * L;
+            c->last.pair_class_bytes[k] += 20ull * M * L + 32ull * (M + 1u) + L + 8u;
         }
-        for (int k = 0; k < kNumClasses; ++k)
-            c->pair_cells += c->pair_class_cells[k], c->pair_bytes += c->pair_class_bytes[k];
-    }
-    if (c->d_pair_list.n < npairs) HIP_TRY(c, c->d_pair_list.alloc(npairs));
-    if (!c->d_pair_n.p) HIP_TRY(c, c->d_pair_n.alloc(DCP_MAX_CLASSES));
+    for (int k = 0; k < kNumClasses; ++k)
+        c->last.pair_cells += c->last.pair_class_cells[k], c->last.pair_bytes += c->last.pair_class_bytes[k];
+    HIP_TRY(c, c->d_pair_list.reserve(npairs));
+    HIP_TRY(c, c->d_pair_n.reserve(DCP_MAX_CLASSES));
     if (npairs) HIP_TRY(c, hipMemcpyAsync(c->d_pair_list.p, pairs.data(), (size_t)npairs * sizeof(dcp_pair), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(c->d_pair_n.p, count, sizeof count, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists leave scope (and an earlier scan has read its own)
@@ -3336,19 +3359,6 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
     a.emis_match = c->d_emis_match.p;
     a.first_prof = 0;
     a.nprof = c->nprof;
-    c->last_q0 = 0, c->last_q1 = c->nseqs;
-    c->last_kernel = c->last_kernel_variant = 1;
-    c->last_launches = 0;
-    c->n_launched = 0;
-    c->redo_pending = false;
-    c->last_redo_pairs = 0;
-    c->last_overlapped = false;
-    c->last_prm = *prm;
-#ifdef DCP_TEST_HOOKS
-    for (int k = 0; k < kNumClasses; ++k)
-        c->rs_plan[k] = {};
-    c->pair_launches.clear();
-#endif
     HIP_TRY(c, hipMemsetAsync(a.nhits, 0, sizeof(unsigned), c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     for (int k = 0; k < kNumClasses; ++k)
@@ -3359,18 +3369,15 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
         a.pair_cap = count[k];
         SizeClass const sc = kClasses[k];
         uint64_t const tpb = dcp_rowsweep_tasks_per_block(sc.W);
-        uint64_t const g = std::min<uint64_t>((count[k] + tpb - 1u) / tpb, 8ull * c->num_cus);
-        if (dcp_launch_rowsweep(sc.R, sc.W, &a, (unsigned)((g + 7u) / 8u * 8u), c->stream))
+        unsigned const grid = (unsigned)((std::min<uint64_t>((count[k] + tpb - 1u) / tpb, 8ull * c->num_cus) + 7u) / 8u * 8u);
+        if (dcp_launch_rowsweep(sc.R, sc.W, &a, grid, c->stream))
             return c->fail(DCP_EFAIL, "no kernel for class R=%d W=%d", sc.R, sc.W);
         if (int rc = record_launch(c, k, false, c->stream, false)) return rc;
-#ifdef DCP_TEST_HOOKS
-        c->pair_launches.push_back({DCP_PL_SCAN_PAIRS, 32u, (unsigned)sc.R, (unsigned)sc.W, (unsigned)((g + 7u) / 8u * 8u), (unsigned)tpb, a.pair_cap});
-#endif
+        note_pair_launch(c, DCP_PL_SCAN_PAIRS, 32u, (unsigned)sc.R, (unsigned)sc.W, grid, (unsigned)tpb, a.pair_cap);
     }
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventRecord(c->ev_stop, c->stream));
-    c->last_pair_scan = true;
-    c->scanned = true;
+    c->last.scanned = true;
     return DCP_OK;
 }
 
@@ -3407,16 +3414,8 @@ static int forward_check_list(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t 
     if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
     if (npairs && (!seq_idx || !profile_idx)) return c->fail(DCP_EINVAL, "a pair list without its indices");
     if (npairs && !outputs) return c->fail(DCP_EINVAL, "a pair list without its score arrays");
-    for (unsigned i = 0; i < npairs; ++i)
-        if (seq_idx[i] >= c->nseqs || profile_idx[i] >= c->nprof)
-            return c->fail(DCP_EINVAL, "pair %u (sequence %u, profile %u) is outside the resident batch (%u sequences) / DB (%u profiles)",
-                           i, seq_idx[i], profile_idx[i], c->nseqs, c->nprof);
-    bool const f64 = c->precision == 64;
-    if (f64 && c->xt_explicit)
-        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
-    if (!f64 && !c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
-    return DCP_OK;
+    if (int rc = check_pairs(c, seq_idx, profile_idx, 1u, npairs, false)) return rc;
+    return check_xtrans_precision(c);
 }
 
 // The special transitions a scan would use, one row per resident sequence, in double: a float DB's are the float ones
@@ -3447,6 +3446,19 @@ static int forward_special_transitions(dcp_gpu_ctx *c, int multi_hits, int hmmer
     return DCP_OK;
 }
 
+// What the Forward and Backward launches read of the resident DB (forward_profiles, and the tables of its precision) and
+// batch; xt: the call's special transitions on the device.
+static dcp_fwd_args forward_args(dcp_gpu_ctx const *c, double const *xt)
+{
+    dcp_fwd_args a{};
+    a.profs = c->fwd.d_profs.p;
+    if (c->precision == 64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
+    else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
+    a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
+    a.xtrans = xt;
+    return a;
+}
+
 // The list by class, each class in list order, the dearest pairs of a class first; a pair remembers its position pos0 + i
 // in the caller's list.  waves: the wavefronts of each class's launch.
 struct ForwardBuckets
@@ -3462,19 +3474,17 @@ static void forward_bucket(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t con
     unsigned(&first)[5] = b.first, (&count)[4] = b.count, (&waves)[4] = b.waves;
     unsigned &wide_chunks = b.wide_chunks;
     std::vector<dcp_fwd_pair> &pairs = b.pairs;
-    for (unsigned i = 0; i < npairs; ++i)
-        ++count[fwd_class(c->core_sizes[profile_idx[i]])];
-    for (int k = 0; k < 4; ++k)
-        first[k + 1] = first[k] + count[k];
+    std::vector<unsigned> const order =
+        sort_into_classes(npairs, 4, first, [&](unsigned i) { return fwd_class(c->core_sizes[profile_idx[i]]); });
     pairs.resize(npairs);
     {
-        unsigned at[4] = {first[0], first[1], first[2], first[3]};
-        for (unsigned i = 0; i < npairs; ++i)
+        for (int k = 0; k < 4; ++k)
+            count[k] = first[k + 1] - first[k];
+        for (unsigned j = 0; j < npairs; ++j)
         {
-            unsigned const M = c->core_sizes[profile_idx[i]];
-            int const k = fwd_class(M);
-            pairs[at[k]++] = dcp_fwd_pair{seq_idx[i], profile_idx[i], pos0 + i};
-            if (k == 3) wide_chunks = std::max(wide_chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
+            unsigned const i = order[j], M = c->core_sizes[profile_idx[i]];
+            pairs[j] = dcp_fwd_pair{seq_idx[i], profile_idx[i], pos0 + i};
+            if (j >= first[3]) wide_chunks = std::max(wide_chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
         }
         // a pair costs its rows times its chunks: the dearest first, so that the wavefronts striding over a class's
         // list end together (pairs of one cost keep their list order)
@@ -3514,22 +3524,17 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
     unsigned const wide_chunks = b.wide_chunks;
     std::vector<dcp_fwd_pair> const &pairs = b.pairs;
     uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK;
-    if (W.d_work.n < work_stride * waves[3]) HIP_TRY(c, W.d_work.alloc(work_stride * waves[3]));
-    if (W.d_pairs.n < npairs) HIP_TRY(c, W.d_pairs.alloc(npairs));
-    if (W.d_xt.n < xt.size()) HIP_TRY(c, W.d_xt.alloc(xt.size()));
-    if (W.d_out.n < 2u * (size_t)npairs) HIP_TRY(c, W.d_out.alloc(2u * (size_t)npairs));
+    HIP_TRY(c, W.d_work.reserve(work_stride * waves[3]));
+    HIP_TRY(c, W.d_pairs.reserve(npairs));
+    HIP_TRY(c, W.d_xt.reserve(xt.size()));
+    HIP_TRY(c, W.d_out.reserve(2u * (size_t)npairs));
     for (hipEvent_t &e : W.ev)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
     HIP_TRY(c, hipMemcpyAsync(W.d_pairs.p, pairs.data(), (size_t)npairs * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below (and whatever was outstanding is done)
 
-    dcp_fwd_args a{};
-    a.profs = W.d_profs.p;
-    if (f64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
-    else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
-    a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
-    a.xtrans = W.d_xt.p;
+    dcp_fwd_args a = forward_args(c, W.d_xt.p);
     a.work = W.d_work.p, a.work_stride = work_stride;
     a.out_null = W.d_out.p, a.out_alt = W.d_out.p + npairs;
     HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
@@ -3602,23 +3607,18 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
         for (i1 = i0 + 1u; i1 < npairs && off[i1 + 1u] - off[i0] <= rows_cap; ++i1) {}
         round_rows = std::max(round_rows, off[i1] - off[i0]);
     }
-    if (W.d_row_off.n < off.size()) HIP_TRY(c, W.d_row_off.alloc(off.size()));
-    if (W.d_xt.n < xt.size()) HIP_TRY(c, W.d_xt.alloc(xt.size()));
-    if (W.d_score.n < 3u * (size_t)npairs) HIP_TRY(c, W.d_score.alloc(3u * (size_t)npairs));
-    if (W.d_rec.n < 2u * DCP_POST_REC * round_rows) HIP_TRY(c, W.d_rec.alloc(2u * DCP_POST_REC * round_rows));
-    if (W.d_rows.n < 3u * round_rows) HIP_TRY(c, W.d_rows.alloc(3u * round_rows));
+    HIP_TRY(c, W.d_row_off.reserve(off.size()));
+    HIP_TRY(c, W.d_xt.reserve(xt.size()));
+    HIP_TRY(c, W.d_score.reserve(3u * (size_t)npairs));
+    HIP_TRY(c, W.d_rec.reserve(2u * DCP_POST_REC * round_rows));
+    HIP_TRY(c, W.d_rows.reserve(3u * round_rows));
     for (hipEvent_t &e : W.ev)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
     HIP_TRY(c, hipMemcpyAsync(W.d_row_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
 
-    dcp_fwd_args a{};
-    a.profs = c->fwd.d_profs.p;
-    if (f64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
-    else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
-    a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
-    a.xtrans = W.d_xt.p;
+    dcp_fwd_args a = forward_args(c, W.d_xt.p);
     a.row_off = W.d_row_off.p;
     double *const d_null = W.d_score.p, *const d_fwd = d_null + npairs, *const d_bwd = d_fwd + npairs;
     dcp_post_args pa{};
@@ -3640,8 +3640,8 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
         for (unsigned i = 0; i < n; ++i)
             list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
         uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
-        if (c->fwd.d_work.n < work_stride * b.waves[3]) HIP_TRY(c, c->fwd.d_work.alloc(work_stride * b.waves[3]));
-        if (W.d_pairs.n < 2u * (size_t)n) HIP_TRY(c, W.d_pairs.alloc(2u * (size_t)n));
+        HIP_TRY(c, c->fwd.d_work.reserve(work_stride * b.waves[3]));
+        HIP_TRY(c, W.d_pairs.reserve(2u * (size_t)n));
         dcp_fwd_pair *const d_bucketed = W.d_pairs.p, *const d_list = W.d_pairs.p + n;
         HIP_TRY(c, hipMemcpyAsync(d_bucketed, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
@@ -3698,9 +3698,11 @@ float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->post.ms : -1.0
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
 static int rerun_with_rowsweep(dcp_gpu_ctx *c)
 {
-    struct dcp_scan_params prm = c->last_prm;
+    // (copies: the new scan begins with a fresh record)
+    struct dcp_scan_params prm = c->last.prm;
+    unsigned const q0 = c->last.q0, q1 = c->last.q1;
     prm.kernel = 1;
-    if (int rc = dcp_gpu_scan_range(c, &prm, c->last_q0, c->last_q1)) return rc;
+    if (int rc = dcp_gpu_scan_range(c, &prm, q0, q1)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return DCP_OK;
 }
@@ -3712,38 +3714,38 @@ static int rerun_with_rowsweep(dcp_gpu_ctx *c)
 static int finish_scan(dcp_gpu_ctx *c)
 {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (c->f64.redo_pending) // the f64 query-lane kernel's lists: [4] pairs appended, [1] overflow flag
+    if (c->last.redo_pending64) // the f64 query-lane kernel's lists: [4] pairs appended, [1] overflow flag
     {
-        c->f64.redo_pending = false;
+        c->last.redo_pending64 = false;
         unsigned n[5];
         HIP_TRY(c, hipMemcpy(n, c->f64.d_redo_n.p, sizeof n, hipMemcpyDeviceToHost));
-        c->last_redo_pairs = (unsigned)std::min<uint64_t>((uint64_t)n[0] + n[1] + n[2] + n[3], 0xffffffffull);
+        c->last.redo_pairs = (unsigned)std::min<uint64_t>((uint64_t)n[0] + n[1] + n[2] + n[3], 0xffffffffull);
         if (n[4] == 0) return DCP_OK;
-        // the double scan's rerun sets the count to 0 (scan64): what the lists took stays the figure reported.  (The
-        // float row sweep's does the same, and there 0 is what is reported.)
-        unsigned const redone = c->last_redo_pairs;
+        // the double scan's rerun begins with a fresh record, the count 0 (scan64): what the lists took stays the figure
+        // reported.  (The float row sweep's does the same, and there 0 is what is reported.)
+        unsigned const redone = c->last.redo_pairs;
         if (int rc = rerun_with_rowsweep(c)) return rc;
-        c->last_redo_pairs = redone;
+        c->last.redo_pairs = redone;
         return DCP_OK;
     }
-    if (!c->redo_pending && !c->ring_check_pending) return DCP_OK;
-    bool const redo = c->redo_pending;
-    c->redo_pending = false;
-    c->ring_check_pending = false;
+    if (!c->last.redo_pending && !c->last.ring_check_pending) return DCP_OK;
+    bool const redo = c->last.redo_pending;
+    c->last.redo_pending = false;
+    c->last.ring_check_pending = false;
     unsigned n[DCP_MAX_CLASSES + 2];
     HIP_TRY(c, hipMemcpy(n, c->d_redo_n.p, sizeof n, hipMemcpyDeviceToHost));
     // the two-stage kernel's ring hand-shake ran into its poll bound (dcp_qlane.hip, ring_wait): the stages drained,
     // but rows were computed from values their partner never wrote -- nothing of this scan can be used
     if (n[DCP_MAX_CLASSES + 1])
     {
-        c->scanned = false;
+        c->last.scanned = false;
         return c->fail(DCP_EFAIL, "query-lane kernel: the LDS ring hand-shake between the two stages timed out; the scan's results are invalid");
     }
     if (!redo) return DCP_OK;
     uint64_t tot = 0;
     for (int k = 0; k < kNumClasses; ++k)
         tot += n[k];
-    c->last_redo_pairs = (unsigned)std::min<uint64_t>(tot, 0xffffffffull);
+    c->last.redo_pairs = (unsigned)std::min<uint64_t>(tot, 0xffffffffull);
     if (n[DCP_MAX_CLASSES] == 0) return DCP_OK;
     return rerun_with_rowsweep(c);
 }
@@ -3764,7 +3766,7 @@ int dcp_gpu_test_set_rowsweep_variant(dcp_gpu_ctx *c, int stg, unsigned bw)
 int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *c, unsigned *out, unsigned cap, unsigned *nwords)
 {
     if (!c || !nwords) return DCP_EINVAL;
-    if (!c->scanned || c->last_kernel != 1 || c->last_f64) return c->fail(DCP_EINVAL, "the last scan was no float row sweep");
+    if (!c->last.scanned || c->last.kernel != 1 || c->last.f64) return c->fail(DCP_EINVAL, "the last scan was no float row sweep");
     *nwords = 2u + DCP_RS_PLAN_WORDS * (unsigned)kNumClasses;
     if (!out || cap < *nwords) return DCP_ENOMEM;
     HIP_TRY(c, hipSetDevice(c->device));
@@ -3772,14 +3774,14 @@ int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *c, unsigned *out, unsigned cap,
     unsigned redo[DCP_MAX_CLASSES] = {0};
     bool segmented = false;
     for (int k = 0; k < kNumClasses; ++k)
-        segmented = segmented || c->rs_plan[k].path == DCP_RS_PATH_SEGMENTED;
+        segmented = segmented || c->last.rs_plan[k].path == DCP_RS_PATH_SEGMENTED;
     if (segmented) HIP_TRY(c, hipMemcpy(redo, c->d_seg_redo_n.p, sizeof redo, hipMemcpyDeviceToHost));
-    out[0] = c->last_overlapped ? 1u : 0u;
+    out[0] = c->last.overlapped ? 1u : 0u;
     out[1] = (unsigned)kNumClasses;
     for (int k = 0; k < kNumClasses; ++k)
     {
         unsigned *w = out + 2u + DCP_RS_PLAN_WORDS * (unsigned)k;
-        dcp_gpu_ctx::RowsweepClassPlan const &r = c->rs_plan[k];
+        LastScan::RowsweepClassPlan const &r = c->last.rs_plan[k];
         w[0] = (unsigned)kClasses[k].R, w[1] = (unsigned)kClasses[k].W, w[2] = r.path, w[3] = r.stage, w[4] = r.waves;
         w[5] = r.prefetch, w[6] = r.chunk, w[7] = r.path == DCP_RS_PATH_SEGMENTED ? redo[k] : 0u, w[8] = r.flagged_rest;
     }
@@ -3788,14 +3790,14 @@ int dcp_gpu_test_last_rowsweep_plan(dcp_gpu_ctx *c, unsigned *out, unsigned cap,
 int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *c, unsigned *out, unsigned cap, unsigned *nwords)
 {
     if (!c || !nwords) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
-    *nwords = 1u + DCP_PL_WORDS * (unsigned)c->pair_launches.size();
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    *nwords = 1u + DCP_PL_WORDS * (unsigned)c->last.pair_launches.size();
     if (!out || cap < *nwords) return DCP_ENOMEM;
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    out[0] = (unsigned)c->pair_launches.size();
+    out[0] = (unsigned)c->last.pair_launches.size();
     unsigned *w = out + 1u;
-    for (dcp_gpu_ctx::PairLaunch const &l : c->pair_launches)
+    for (LastScan::PairLaunch const &l : c->last.pair_launches)
     {
         w[0] = l.kind, w[1] = l.precision, w[2] = l.a, w[3] = l.b, w[4] = l.units, w[5] = l.tpb, w[6] = l.cap;
         w += DCP_PL_WORDS;
@@ -3879,10 +3881,10 @@ int dcp_gpu_sync(dcp_gpu_ctx *c)
 int dcp_gpu_last_scan_redo_pairs(dcp_gpu_ctx *c, unsigned *npairs)
 {
     if (!c || !npairs) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc;
-    *npairs = c->last_redo_pairs;
+    *npairs = c->last.redo_pairs;
     return DCP_OK;
 }
 
@@ -3890,10 +3892,10 @@ int dcp_gpu_last_scan_query_plan(dcp_gpu_ctx *c, unsigned *nblocks, unsigned lon
                                  unsigned *plane_rows, unsigned *max_groups_per_slot)
 {
     if (!c) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet");
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet");
     HIP_TRY(c, hipSetDevice(c->device));
     if (int rc = finish_scan(c)) return rc; // an overflowed kernel-4 scan is repeated with the row sweep
-    if (!c->last_f64 || c->last_kernel_variant != 4)
+    if (!c->last.f64 || c->last.kernel_variant != 4)
         return c->fail(DCP_EINVAL, "the last scan did not run the f64 query-lane kernel (kernel = 4): it has no batch plan");
     if (nblocks) *nblocks = c->f64.plan_blocks;
     if (sum_block_rows) *sum_block_rows = c->f64.plan_sum_rows;
@@ -3904,23 +3906,23 @@ int dcp_gpu_last_scan_query_plan(dcp_gpu_ctx *c, unsigned *nblocks, unsigned lon
 
 float dcp_gpu_last_scan_ms(dcp_gpu_ctx *c)
 {
-    if (!c || !c->scanned) return -1.0f;
+    if (!c || !c->last.scanned) return -1.0f;
     float ms = -1.0f;
     if (hipEventSynchronize(c->ev_stop) != hipSuccess) return -1.0f;
     if (hipEventElapsedTime(&ms, c->ev_start, c->ev_stop) != hipSuccess) return -1.0f;
     return ms;
 }
 
-unsigned dcp_gpu_last_scan_launches(dcp_gpu_ctx const *c) { return c ? c->last_launches : 0; }
-int dcp_gpu_last_scan_kernel(dcp_gpu_ctx const *c) { return c && c->scanned ? c->last_kernel_variant : 0; }
+unsigned dcp_gpu_last_scan_launches(dcp_gpu_ctx const *c) { return c ? c->last.launches : 0; }
+int dcp_gpu_last_scan_kernel(dcp_gpu_ctx const *c) { return c && c->last.scanned ? c->last.kernel_variant : 0; }
 
 int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_info *out)
 {
-    if (!c || !out || !c->scanned) return DCP_EINVAL;
-    if (i >= c->n_launched) return DCP_EINVAL;
-    int const k = c->launched_class[i];
+    if (!c || !out || !c->last.scanned) return DCP_EINVAL;
+    if (i >= c->last.n_launched) return DCP_EINVAL;
+    int const k = c->last.launched_class[i];
     // overlapped row-sweep launches all start at ev_start
-    hipEvent_t const before = i == 0 || (c->last_kernel == 1 && c->last_overlapped) ? c->ev_start : c->ev_class[i - 1];
+    hipEvent_t const before = i == 0 || (c->last.kernel == 1 && c->last.overlapped) ? c->ev_start : c->ev_class[i - 1];
     if (hipEventSynchronize(c->ev_class[i]) != hipSuccess) return DCP_EFAIL;
     float ms = 0;
     if (hipEventElapsedTime(&ms, before, c->ev_class[i]) != hipSuccess) return DCP_EFAIL;
@@ -3939,19 +3941,19 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_
     out->waves_per_pair = kClasses[k].W;
     out->nprofiles = (unsigned)np;
     out->cells = out->algorithmic_bytes = 0;
-    if (c->last_kernel == 2 || c->launched_redo[i]) return DCP_OK; // a redo launch: its pairs are counted in the launch before it
-    if (c->last_pair_scan) // dcp_gpu_scan_pairs: the class's listed pairs
+    if (c->last.kernel == 2 || c->last.launched_redo[i]) return DCP_OK; // a redo launch: its pairs are counted in the launch before it
+    if (c->last.pair_scan) // dcp_gpu_scan_pairs: the class's listed pairs
     {
-        out->cells = c->pair_class_cells[k];
-        out->algorithmic_bytes = c->pair_class_bytes[k];
+        out->cells = c->last.pair_class_cells[k];
+        out->algorithmic_bytes = c->last.pair_class_bytes[k];
         return DCP_OK;
     }
     uint64_t sumM = 0, len = 0;
     for (unsigned j = c->class_first[k]; j < c->class_first[k + 1]; ++j)
         sumM += c->metas[j].core_size;
-    for (unsigned q = c->last_q0; q < c->last_q1; ++q)
+    for (unsigned q = c->last.q0; q < c->last.q1; ++q)
         len += c->seq_len[q];
-    uint64_t const nq = c->last_q1 - c->last_q0;
+    uint64_t const nq = c->last.q1 - c->last.q0;
     out->cells = sumM * len;
     out->algorithmic_bytes = 20ull * sumM * len + 32ull * (sumM + np) * nq + len * np + 8ull * np * nq;
     return DCP_OK;
@@ -3960,7 +3962,7 @@ int dcp_gpu_last_scan_launch_info(dcp_gpu_ctx *c, unsigned i, struct dcp_launch_
 int dcp_gpu_fetch_scores(dcp_gpu_ctx *c, float *null_out, float *alt_out)
 {
     if (!c) return DCP_EINVAL;
-    if (c->scanned && c->last_f64)
+    if (c->last.scanned && c->last.f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its scores with dcp_gpu_fetch_scores64");
     return fetch_scores(c, c->res, null_out, alt_out);
 }
@@ -3968,8 +3970,8 @@ int dcp_gpu_fetch_scores(dcp_gpu_ctx *c, float *null_out, float *alt_out)
 int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsigned *nhits)
 {
     if (!c || !nhits) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
-    if (c->last_f64)
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
+    if (c->last.f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a double DB: fetch its hits with dcp_gpu_fetch_hits64");
     return fetch_hits(c, c->res, hits, cap, nhits);
 }
@@ -3977,7 +3979,7 @@ int dcp_gpu_fetch_hits(dcp_gpu_ctx *c, struct dcp_hit *hits, unsigned cap, unsig
 int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
 {
     if (!c) return DCP_EINVAL;
-    if (c->scanned && !c->last_f64)
+    if (c->last.scanned && !c->last.f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its scores with dcp_gpu_fetch_scores");
     return fetch_scores(c, c->f64.res, null_out, alt_out);
 }
@@ -3985,13 +3987,13 @@ int dcp_gpu_fetch_scores64(dcp_gpu_ctx *c, double *null_out, double *alt_out)
 // What either fit needs: a scan of the whole batch that kept its dense scores, completed.
 static int fit_ready(dcp_gpu_ctx *c)
 {
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan yet: the fit is over the last scan's dense scores");
-    bool const have = c->last_f64 ? c->f64.res.have_scores : c->res.have_scores;
-    if (c->last_pair_scan || !have)
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan yet: the fit is over the last scan's dense scores");
+    bool const have = c->last.f64 ? c->f64.res.have_scores : c->res.have_scores;
+    if (c->last.pair_scan || !have)
         return c->fail(DCP_EINVAL, "no dense scores kept by the last scan (keep_scores = 0, or a scan of a pair list)");
-    if (c->last_q0 != 0 || c->last_q1 != c->nseqs)
-        return c->fail(DCP_EINVAL, "the last scan covered sequences [%u, %u) of %u: the fit is over the whole batch", c->last_q0,
-                       c->last_q1, c->nseqs);
+    if (c->last.q0 != 0 || c->last.q1 != c->nseqs)
+        return c->fail(DCP_EINVAL, "the last scan covered sequences [%u, %u) of %u: the fit is over the whole batch", c->last.q0,
+                       c->last.q1, c->nseqs);
     if (c->nseqs < 2u) return c->fail(DCP_EINVAL, "a fit needs at least 2 sequences: %u resident", c->nseqs);
     HIP_TRY(c, hipSetDevice(c->device));
     return finish_scan(c); // a query-lane scan completes its redo pairs there
@@ -4004,14 +4006,14 @@ int dcp_gpu_fit_gumbel(dcp_gpu_ctx *c, double *mu_out, double *lambda_out, uint8
     if (!mu_out || !lambda_out || !status_out) return c->fail(DCP_EINVAL, "dcp_gpu_fit_gumbel: a null output");
     if (int rc = fit_ready(c)) return rc;
     unsigned const np = c->nprof;
-    if (c->d_fit.n < 2u * (size_t)np) HIP_TRY(c, c->d_fit.alloc(2u * (size_t)np));
-    if (c->d_fit_status.n < np) HIP_TRY(c, c->d_fit_status.alloc(np));
+    HIP_TRY(c, c->d_fit.reserve(2u * (size_t)np));
+    HIP_TRY(c, c->d_fit_status.reserve(np));
     for (hipEvent_t &e : c->ev_calib)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
-    void const *nl = c->last_f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
-    void const *al = c->last_f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
+    void const *nl = c->last.f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
+    void const *al = c->last.f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
     HIP_TRY(c, hipEventRecord(c->ev_calib[2], c->stream));
-    HIP_TRY(c, (hipError_t)dcp_launch_gumbel_fit(nl, al, c->nseqs, np, c->last_f64 ? 8 : 4, c->d_fit.p, c->d_fit.p + np,
+    HIP_TRY(c, (hipError_t)dcp_launch_gumbel_fit(nl, al, c->nseqs, np, c->last.f64 ? 8 : 4, c->d_fit.p, c->d_fit.p + np,
                                                   c->d_fit_status.p, c->stream));
     HIP_TRY(c, hipEventRecord(c->ev_calib[3], c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -4065,15 +4067,15 @@ int dcp_gpu_fit_gumbel_tail(dcp_gpu_ctx *c, unsigned k, double *mu_out, double *
     if (k < 2u || k > c->nseqs)
         return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the resident sequences", k, c->nseqs);
     unsigned const np = c->nprof;
-    if (c->d_fit.n < 2u * (size_t)np) HIP_TRY(c, c->d_fit.alloc(2u * (size_t)np));
-    if (c->d_fit_status.n < np) HIP_TRY(c, c->d_fit_status.alloc(np));
-    if (c->d_tail_tau.n < np) HIP_TRY(c, c->d_tail_tau.alloc(np));
-    if (c->d_tail_keff.n < np) HIP_TRY(c, c->d_tail_keff.alloc(np));
+    HIP_TRY(c, c->d_fit.reserve(2u * (size_t)np));
+    HIP_TRY(c, c->d_fit_status.reserve(np));
+    HIP_TRY(c, c->d_tail_tau.reserve(np));
+    HIP_TRY(c, c->d_tail_keff.reserve(np));
     for (hipEvent_t &e : c->ev_tail)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
-    void const *nl = c->last_f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
-    void const *al = c->last_f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
-    int const real_bytes = c->last_f64 ? 8 : 4;
+    void const *nl = c->last.f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
+    void const *al = c->last.f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
+    int const real_bytes = c->last.f64 ? 8 : 4;
     HIP_TRY(c, hipEventRecord(c->ev_tail[0], c->stream));
     HIP_TRY(c, (hipError_t)dcp_launch_tail_select(nl, al, c->nseqs, np, real_bytes, k, c->d_tail_tau.p, c->d_tail_keff.p,
                                                    c->stream));
@@ -4132,8 +4134,8 @@ float dcp_gpu_calib_kernel_ms(dcp_gpu_ctx *c, int which)
 int dcp_gpu_fetch_hits64(dcp_gpu_ctx *c, struct dcp_hit64 *hits, unsigned cap, unsigned *nhits)
 {
     if (!c || !nhits) return DCP_EINVAL;
-    if (!c->scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
-    if (!c->last_f64)
+    if (!c->last.scanned) return c->fail(DCP_EINVAL, "no scan to fetch hits from");
+    if (!c->last.f64)
         return c->fail(DCP_EINVAL, "the last scan ran on a float DB: fetch its hits with dcp_gpu_fetch_hits");
     return fetch_hits(c, c->f64.res, hits, cap, nhits);
 }
@@ -4153,11 +4155,8 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
     step_off[0] = step_off[nhits] = 0;
     HIP_TRY(c, hipSetDevice(c->device));
     if (nhits == 0) return DCP_OK;
-    for (unsigned h = 0; h < nhits; ++h)
-        if (hits[h].seq_idx >= c->nseqs || hits[h].profile_idx >= c->nprof)
-            return c->fail(DCP_EINVAL, "hit %u is outside the resident batch / DB", h);
-    if (!c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
+    if (int rc = check_pairs(c, &hits->seq_idx, &hits->profile_idx, sizeof *hits / sizeof(uint32_t), nhits, true)) return rc;
+    if (int rc = check_xtrans_precision(c)) return rc;
     if (int rc = ensure_xtrans(c, multi_hits, hmmer3_compat)) return rc;
     if (int rc = ensure_rowsweep_layout(c)) return rc;
 
@@ -4212,21 +4211,8 @@ int dcp_gpu_trace_paths(dcp_gpu_ctx *c, struct dcp_hit const *hits, unsigned nhi
             HIP_TRY(c, d_counts.alloc(kNumClasses));
             HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_pair), hipMemcpyHostToDevice));
             HIP_TRY(c, hipMemcpy(d_counts.p, counts, sizeof counts, hipMemcpyHostToDevice));
-            dcp_scan_args fa{};
-            fa.profs = c->d_metas.p;
-            fa.emis_match = c->d_emis_match.p;
-            fa.emis_insert = c->d_emis_insert.p;
-            fa.emis_null = c->d_emis_null.p;
-            fa.trans8 = c->d_trans8.p;
-            fa.seq_words = c->d_seq_words.p;
-            fa.seq_woff = c->d_seq_woff.p;
-            fa.seq_len = c->d_seq_len.p;
-            fa.xtrans = c->d_xtrans.p;
-            fa.nprof_total = c->nprof;
+            dcp_scan_args fa = scan_inputs(c, 0, c->nseqs);
             fa.nprof = c->nprof;
-            fa.nseqs = c->nseqs;
-            fa.qchunk = 1u;
-            fa.nchunks = c->nseqs;
             fa.trace_work = r.work;
             // the classes' launches side by side on their own streams, largest profiles first: a class's launch lasts as
             // long as its longest hit and seldom fills the chip (one after the other they took 0.31 of a job's 0.40 s of
@@ -4300,14 +4286,9 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
     step_off[0] = step_off[nhits] = 0;
     HIP_TRY(c, hipSetDevice(c->device));
     if (nhits == 0) return DCP_OK;
-    for (unsigned h = 0; h < nhits; ++h)
-        if (hits[h].seq_idx >= c->nseqs || hits[h].profile_idx >= c->nprof)
-            return c->fail(DCP_EINVAL, "hit %u is outside the resident batch / DB", h);
+    if (int rc = check_pairs(c, &hits->seq_idx, &hits->profile_idx, sizeof *hits / sizeof(uint32_t), nhits, true)) return rc;
     auto &F = c->f64;
-    // entry of F.profs (group-sorted) of each caller's profile index
-    std::vector<uint32_t> slot(c->nprof);
-    for (unsigned i = 0; i < (unsigned)F.profs.size(); ++i)
-        slot[F.profs[i].pidx] = i;
+    std::vector<uint32_t> const &slot = F.slot_of_pidx;
     // per-hit work area (doubles) and step capacity: 2L + 2M + 16 is an estimate, not a bound
     std::vector<uint64_t> need(nhits);
     std::vector<uint32_t> cap(nhits);
@@ -4344,8 +4325,8 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
         HIP_TRY(c, hipMemcpy(d_pairs.p, pairs.data(), n * sizeof(dcp_f64_pair), hipMemcpyHostToDevice));
         if (!null_model)
         {
-            uint64_t col_stride = 0, seg_waves = 0;
-            if (int e = f64_seg_columns(c, seg_lmax, gfirst[4] - gfirst[3], &col_stride, &seg_waves)) return e;
+            F64Seg seg;
+            if (int e = f64_seg_columns(c, seg_lmax, gfirst[4] - gfirst[3], &seg)) return e;
             dcp_f64_trace_args fa{};
             fa.profs = F.d_profs.p;
             fa.nprof_total = c->nprof;
@@ -4367,10 +4348,7 @@ int dcp_gpu_trace_paths64(dcp_gpu_ctx *c, struct dcp_hit64 const *hits, unsigned
                 fa.xtrans = d_xt.p + (size_t)gfirst[g] * DCP_F64_XSTRIDE;
                 fa.trace_woff = r.woff.p + gfirst[g];
                 fa.trace_alt = r.alt.p + gfirst[g];
-                fa.col = g == 3 ? F.d_col.p : nullptr;
-                fa.col_stride = g == 3 ? col_stride : 0;
-                uint64_t const waves = g == 3 ? seg_waves : std::min<uint64_t>(cnt, 1ull << 24);
-                if (dcp_f64_launch_trace_forward(kF64R[g], &fa, (unsigned)waves, c->stream))
+                if (dcp_f64_launch_trace_forward(kF64R[g], &fa, f64_group_geometry(c, g, cnt, seg, fa), c->stream))
                     return c->fail(DCP_EFAIL, "no f64 traceback kernel for %d nodes per lane", kF64R[g]);
             }
             HIP_TRY(c, hipGetLastError());
@@ -4430,10 +4408,7 @@ int path_domains(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profil
                                        : "dcp_gpu_path_domains works on a float DB: the resident DB is double (dcp_gpu_path_domains64)");
     if (npaths == 0) return DCP_OK;
     if (!seq_idx || !profile_idx || !step_off || !dom_off) return c->fail(DCP_EINVAL, "null index array");
-    if (!f64 && !c->xt64.empty())
-        return c->fail(DCP_EINVAL, "the explicit special transitions are double: a float DB takes them from dcp_gpu_seqs_set_xtrans");
-    if (f64 && c->xt_explicit)
-        return c->fail(DCP_EINVAL, "the explicit special transitions are float: a double DB takes them from dcp_gpu_seqs_set_xtrans64");
+    if (int rc = check_xtrans_precision(c)) return rc;
     // everything integers decide is checked before anything is launched or written
     uint64_t nemit = 0;
     if (int rc = check_path_steps(c, seq_idx, profile_idx, npaths, steps, step_off, true, &nemit)) return rc;
@@ -4490,11 +4465,8 @@ int path_domains(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profil
     {
         std::vector<uint32_t> seqs(seq_idx, seq_idx + npaths);
         if (int rc = fill_xtrans(c, seqs, multi_hits, hmmer3_compat, DCP_F64_XSTRIDE, xt)) return rc;
-        std::vector<uint32_t> slot(c->nprof);
-        for (unsigned i = 0; i < (unsigned)c->f64.profs.size(); ++i)
-            slot[c->f64.profs[i].pidx] = i;
         for (unsigned h = 0; h < npaths; ++h)
-            recs[h] = dcp_dom_path{seq_idx[h], slot[profile_idx[h]], step_off[h] - first, doff[h]};
+            recs[h] = dcp_dom_path{seq_idx[h], c->f64.slot_of_pidx[profile_idx[h]], step_off[h] - first, doff[h]};
     }
     else
     {
@@ -4507,11 +4479,11 @@ int path_domains(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profil
 
     // sums: [ndom] core, [ndom] null, [npaths] total, then the error word, in 8-byte units
     size_t const nsums = 2u * (size_t)ndom + npaths + 1u;
-    if (c->d_dom_steps.n < total) HIP_TRY(c, c->d_dom_steps.alloc(total));
-    if (c->d_dom_paths.n < recs.size()) HIP_TRY(c, c->d_dom_paths.alloc(recs.size()));
-    if (c->d_dom_sums.n < nsums) HIP_TRY(c, c->d_dom_sums.alloc(nsums));
-    if (ndom && c->d_dom_recs.n < 12u * (size_t)ndom) HIP_TRY(c, c->d_dom_recs.alloc(12u * (size_t)ndom));
-    if (f64 && c->d_dom_xt.n < xt.size()) HIP_TRY(c, c->d_dom_xt.alloc(xt.size()));
+    HIP_TRY(c, c->d_dom_steps.reserve(total));
+    HIP_TRY(c, c->d_dom_paths.reserve(recs.size()));
+    HIP_TRY(c, c->d_dom_sums.reserve(nsums));
+    HIP_TRY(c, c->d_dom_recs.reserve(12u * (size_t)ndom));
+    HIP_TRY(c, c->d_dom_xt.reserve(xt.size())); // a float DB: none
     for (hipEvent_t &e : c->ev_dom)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
     unsigned long long const none = ~0ull;
@@ -4624,7 +4596,7 @@ static void last_range(dcp_gpu_ctx const *c, uint64_t *sumM, uint64_t *len, uint
     *sumM = *len = 0;
     for (unsigned m : c->core_sizes)
         *sumM += m;
-    unsigned q0 = c->scanned ? c->last_q0 : 0, q1 = c->scanned ? c->last_q1 : c->nseqs;
+    unsigned q0 = c->last.scanned ? c->last.q0 : 0, q1 = c->last.scanned ? c->last.q1 : c->nseqs;
     for (unsigned q = q0; q < q1; ++q)
         *len += c->seq_len[q];
     *nq = q1 - q0;
@@ -4633,7 +4605,7 @@ static void last_range(dcp_gpu_ctx const *c, uint64_t *sumM, uint64_t *len, uint
 uint64_t dcp_gpu_scan_cells(dcp_gpu_ctx const *c)
 {
     if (!c) return 0;
-    if (c->scanned && c->last_pair_scan) return c->pair_cells; // dcp_gpu_scan_pairs: the listed pairs
+    if (c->last.scanned && c->last.pair_scan) return c->last.pair_cells; // dcp_gpu_scan_pairs: the listed pairs
     uint64_t sumM, len, nq;
     last_range(c, &sumM, &len, &nq);
     return sumM * len;
@@ -4643,7 +4615,7 @@ uint64_t dcp_gpu_scan_algorithmic_bytes(dcp_gpu_ctx const *c)
 {
     // per pair 20*M*L + 32*(M+1) + L + 8
     if (!c) return 0;
-    if (c->scanned && c->last_pair_scan) return c->pair_bytes;
+    if (c->last.scanned && c->last.pair_scan) return c->last.pair_bytes;
     uint64_t sumM, len, Q, P = c->core_sizes.size();
     last_range(c, &sumM, &len, &Q);
     return 20ull * sumM * len + 32ull * (sumM + P) * Q + len * P + 8ull * P * Q;

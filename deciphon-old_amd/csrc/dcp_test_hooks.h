@@ -7,7 +7,8 @@
 
 #include "dcp_host.h"
 
-#ifdef DCP_TEST_HOOKS
+// The words of the records below.  Defined in both builds: the shipped library's launch loops name them in calls of
+// note_pair_launch / note_rowsweep_plan (dcp_gpu.hip), which are empty there.
 // how launch_rowsweep_scan ran a size class
 #define DCP_RS_PATH_NONE 0u      // no profile of the class is resident
 #define DCP_RS_PATH_PLAIN 1u     // the grid-mode one-profile kernel rowsweep_variant chose (viterbi_rowsweep_kernel)
@@ -20,6 +21,7 @@
 #define DCP_PL_SEG_REDO 3u   // the segmented sweep's seg_redo list (launch_segsweep_class)
 #define DCP_PL_WORDS 7u
 
+#ifdef DCP_TEST_HOOKS
 extern "C" {
 // What the last scan did, if it was a float row-sweep scan (else DCP_EINVAL); waits for it.  *nwords receives
 // 2 + DCP_RS_PLAN_WORDS x classes, out -- if cap holds them, else DCP_ENOMEM -- the words

@@ -7,7 +7,8 @@ list of {query, profile}.  The drivers (dcp_gpu.hip) size its launches:
           tpb = dcp_rowsweep_tasks_per_block(W) = 4 for W == 1, else 1; launch_segsweep_class (W > 1): min(n, 8 x CUs)
           rounded up the same way
   double  scan_pairs64: min(n, 2^24) wavefronts, the segmented group (more than 256 nodes) seg_waves = min(n, 2^27 /
-          (5 (lmax + 1))) (f64_seg_columns); kernel 4's redo launches: min(seg_waves | 4096, capacity, 4096)
+          (5 (lmax + 1))) (f64_seg_columns); kernel 4's redo launches: min(seg_waves | 4096, capacity, 4096) -- both
+          from f64_group_geometry, the latter with its cap of 4 096
 
 so a block (wavefront) takes a second task only from T + 1 listed pairs on, T = tpb x 8 x CUs (float), seg_waves or
 4 096 (double).  Restated here as functions of the CU count, W and lmax, with the list builder of the GPU cases and

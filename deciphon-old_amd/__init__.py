@@ -100,6 +100,8 @@ ABI_SYMBOLS = [
     "dcp_forward_tables", "dcp_gpu_forward_pairs", "dcp_gpu_forward_kernel_ms",
     # Backward sweep and posterior decoding of a pair list, the host twin, envelopes from the core row
     "dcp_posterior_tables", "dcp_posterior_envelopes", "dcp_gpu_posterior_pairs", "dcp_gpu_posterior_kernel_ms",
+    # the posterior-decoded alignment of a pair list: a max-plus sweep over word posteriors, and its host twins
+    "dcp_mea_tables", "dcp_mea_path_gain", "dcp_gpu_mea_pairs", "dcp_gpu_mea_kernel_ms",
 ]
 
 
@@ -298,6 +300,10 @@ def _load(path=None, hooks=False):
         "dcp_posterior_envelopes": (I, [P, U, C.c_double, U, P, P, U, C.POINTER(U)]),
         "dcp_gpu_posterior_pairs": (I, [P, I, I, P, P, U, P, P, P, P, C.c_uint64, P, P]),
         "dcp_gpu_posterior_kernel_ms": (F, [P]),
+        "dcp_mea_tables": (I, [U, U, P, P, P, P, P, P, U, P, U, C.POINTER(U), P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "dcp_mea_path_gain": (I, [U, U, P, P, P, P, P, P, U, P, U, C.POINTER(C.c_double), P]),
+        "dcp_gpu_mea_pairs": (I, [P, I, I, P, P, U, P, U, P, P, P, P]),
+        "dcp_gpu_mea_kernel_ms": (F, [P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -311,6 +317,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_set_forward_waves"] = (I, [P, U])
         sig["dcp_gpu_test_set_posterior_budget"] = (I, [P, C.c_ulonglong])
+        sig["dcp_gpu_test_set_mea_budget"] = (I, [P, C.c_ulonglong])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -684,6 +691,55 @@ def posterior_tables(t8, em, ei, en, xt, seq):
     return begin, end, core, fwd.value, bwd.value
 
 
+def _mea_tables_args(t8, em, ei, en, xt, seq):
+    t8, em, ei, en, xt = _f64(t8), _f64(em), _f64(ei), _f64(en), _f64(xt)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if t8.ndim != 2 or em.ndim != 2 or t8.shape != (8, em.shape[1]) or em.shape[0] != NCODES or \
+            ei.shape != (NCODES,) or en.shape != (NCODES,) or xt.shape != (NXTRANS,) or seq.ndim != 1:
+        raise DcpError(RC_EINVAL, "tables of shapes [8, ldk], [1364, ldk], [1364], [1364], [13]")
+    return t8, em, ei, en, xt, seq
+
+
+def mea_tables(t8, em, ei, en, xt, seq):
+    """(steps, post, gain, alt_fwd) of one sequence against one profile on the host (dcp_mea_tables): the
+    posterior-decoded path -- the S .. T path over finite transitions and emissions that emits len(seq) bases and has
+    the largest sum of seqlen x word posterior over its emitting steps -- as a STEP_DTYPE array in trace_paths' format,
+    the word posterior of every step (-1 for a step that emits nothing), that sum, and the Forward alt score.  No path
+    at all (alt_fwd = -inf): zero steps and gain -inf.  The tables are forward_tables' ones."""
+    t8, em, ei, en, xt, seq = _mea_tables_args(t8, em, ei, en, xt, seq)
+    n, gain, fwd = C.c_uint(0), C.c_double(0.0), C.c_double(0.0)
+    cap = 2 * len(seq) + 2 * em.shape[1] + 16
+    for _ in range(2):  # a longer path is walked once more at its exact count
+        steps, post = np.zeros(max(cap, 1), STEP_DTYPE), np.zeros(max(cap, 1), np.float64)
+        rc = lib.dcp_mea_tables(em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data,
+                                xt.ctypes.data, seq.ctypes.data, len(seq), steps.ctypes.data, cap, C.byref(n),
+                                post.ctypes.data, C.byref(gain), C.byref(fwd))
+        if rc != RC_ENOMEM or n.value <= cap:
+            break
+        cap = n.value
+    if rc:
+        raise DcpError(rc, "dcp_mea_tables")
+    return steps[:n.value].copy(), post[:n.value].copy(), gain.value, fwd.value
+
+
+def mea_path_gain(t8, em, ei, en, xt, seq, steps):
+    """(gain, post) of a given alt path of one sequence against one profile on the host (dcp_mea_path_gain): the sum
+    of seqlen x word posterior over its emitting steps under mea_tables' own sweeps, and every step's word posterior
+    (-1 for a step that emits nothing).  DcpError(EINVAL): the path is not S .. T, uses an edge that is not in the
+    graph or a transition or emission that is -inf, names a node outside 1 .. M, or does not emit len(seq) bases."""
+    t8, em, ei, en, xt, seq = _mea_tables_args(t8, em, ei, en, xt, seq)
+    st = np.ascontiguousarray(steps, STEP_DTYPE)
+    if st.ndim != 1:
+        raise DcpError(RC_EINVAL, "one array of steps")
+    gain, post = C.c_double(0.0), np.zeros(max(len(st), 1), np.float64)
+    rc = lib.dcp_mea_path_gain(em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data,
+                               xt.ctypes.data, seq.ctypes.data, len(seq), st.ctypes.data if len(st) else None, len(st),
+                               C.byref(gain), post.ctypes.data)
+    if rc:
+        raise DcpError(rc, "dcp_mea_path_gain")
+    return gain.value, post[:len(st)]
+
+
 def posterior_envelopes(core, threshold=0.5, min_len=1):
     """[(begin, end), ..]: the maximal runs of bases whose core posterior is at least `threshold` and that are at least
     min_len bases long, as half-open base intervals in order (dcp_posterior_envelopes).  core is a row of
@@ -989,6 +1045,7 @@ class Scanner:
         if not self._c:
             raise DcpError(RC_EFAIL, f"no HIP device {device}: this engine has no CPU fallback")
         self._profiles = None
+        self._seq_lens = np.zeros(0, np.int64)  # of the resident batch
 
     def close(self):
         c, self._c = getattr(self, "_c", None), None
@@ -1341,6 +1398,49 @@ class Scanner:
         """TEST-ONLY (test-hooks build): the device memory the following posterior_pairs calls give their row records
         (0: the default, 1 GiB)."""
         self._check(self._lib.dcp_gpu_test_set_posterior_budget(self._c, int(nbytes)))
+
+    def mea_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
+        """(paths, posts, gain, alt_fwd) of the pairs (resident sequence seq_idx[i], resident profile profile_idx[i])
+        on a float or a double DB (dcp_gpu_mea_pairs): the posterior-decoded path of every pair -- a list of
+        STEP_DTYPE arrays that decode_paths and path_domains take as they are -- the word posterior of every step
+        (-1 for a step that emits nothing), the path's gain (the sum of seqlen x posterior) and the Forward alt score
+        (forward_pairs' bits).  A pair with no path at all has zero steps and gain -inf.  Returns synchronised; the
+        last scan's results stay what they were."""
+        sq = np.ascontiguousarray(seq_idx, np.uint32)
+        pr = np.ascontiguousarray(profile_idx, np.uint32)
+        if sq.ndim != 1 or sq.shape != pr.shape:
+            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        n = len(sq)
+        # the driver's own first estimate, L + M + 16 steps a pair; the call names the true count if that is short.  An
+        # index out of range, a missing DB or batch are the call's to refuse, with its message
+        lens = self._seq_lens
+        sizes = np.array([p.core_size for p in self._profiles or []], np.int64)
+        ok = (sq < len(lens)) & (pr < len(sizes))
+        cap = int(np.sum(lens[sq[ok]] + sizes[pr[ok]] + 16))
+        off = np.zeros(n + 1, np.uint32)
+        gain, fwd = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        for _ in range(2):
+            steps, post = np.zeros(max(cap, 1), STEP_DTYPE), np.zeros(max(cap, 1), np.float64)
+            rc = self._lib.dcp_gpu_mea_pairs(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data, pr.ctypes.data, n,
+                                             steps.ctypes.data, cap, off.ctypes.data, post.ctypes.data, gain.ctypes.data,
+                                             fwd.ctypes.data)
+            if rc != RC_ENOMEM or int(off[n]) <= cap:
+                break
+            cap = int(off[n])
+        self._check(rc)
+        paths = [steps[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+        posts = [post[int(off[i]):int(off[i + 1])].copy() for i in range(n)]
+        return paths, posts, gain, fwd
+
+    @property
+    def mea_kernel_ms(self):
+        """Milliseconds of the last mea_pairs call's kernel launches, by HIP events; negative before any."""
+        return self._lib.dcp_gpu_mea_kernel_ms(self._c)
+
+    def test_set_mea_budget(self, nbytes):
+        """TEST-ONLY (test-hooks build): the device memory the following mea_pairs calls give their matrices and
+        choices (0: the default, 8 GiB)."""
+        self._check(self._lib.dcp_gpu_test_set_mea_budget(self._c, int(nbytes)))
 
     def set_hit_buffer(self, hits_dev_ptr, cap, nhits_dev_ptr):
         """Route hit records into caller-owned device memory (e.g. a torch tensor for RCCL)."""

@@ -122,6 +122,12 @@ struct dcp_fwd_args
     double *rows;
     uint64_t const *row_off; // [the caller's list + 1]
     uint64_t row_base;       // row_off of the round's first pair
+    // the matrix-storing variants of the two sweeps only (dcp_mea.h): pair `pos` has rows j = 0 .. L of core_size
+    // doubles each from mat0 / mat1 + (cell_off[pos] - cell_base) on -- P and Q of the Forward sweep, bM and bI of the
+    // Backward sweep
+    double *mat0, *mat1;
+    uint64_t const *cell_off; // [the caller's list + 1]
+    uint64_t cell_base;       // cell_off of the round's first pair
 };
 
 #ifdef __cplusplus

@@ -13,6 +13,8 @@
 // Both take a compile-time flag ROWS: the same sweep that also stores, per row j = 0 .. L, the five values the posterior
 // rows are built from -- PN(j), PJ(j), PC(j), B(j), E(j), dcp_posterior.h -- from lane 0 (dcp_gpu_posterior_pairs' first
 // half).  ROWS = false is dcp_gpu_forward_pairs' kernel, with the registers it had before the flag.
+// And a flag MAT, with ROWS: every lane also stores P_k(j) and Q_k(j) of its own columns, rows j = 0 .. L, the matrices
+// the posterior-decoded alignment reads (dcp_mea.h, dcp_gpu_mea_pairs' first sweep).
 //
 // Real is the tables' scalar (a float DB's values are promoted to double, which is exact); the arithmetic is double.
 // The recursion is the Viterbi one of dcp_f64.hip with every max replaced by lse (dcp_forward.h), every candidate
@@ -30,6 +32,7 @@
 // padding columns carry -inf and stay -inf, whatever the DB's own padding is (a float DB's small profiles share rows).
 #include "dcp_forward.h"
 #include "dcp_host.h"
+#include "dcp_mea.h"
 #include "dcp_posterior.h"
 
 #include <hip/hip_runtime.h>
@@ -61,9 +64,28 @@ template <int PH> __device__ __forceinline__ void store_record(double const (&PX
     if (lane == 0u) rec[0] = pn, rec[1] = pj, rec[2] = pc, rec[3] = B, rec[4] = E;
 }
 
-template <class Real, int R, int PH, bool ROWS>
+// MAT: row j of the pair's P and Q matrices, the lane's own columns below core_size
+struct Mats
+{
+    double *p, *q;
+};
+__device__ __forceinline__ Mats mats_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
+{
+    uint64_t const at = a.cell_off[pp.pos] - a.cell_base;
+    return Mats{a.mat0 + at, a.mat1 + at};
+}
+template <int R>
+__device__ __forceinline__ void store_cells(Mats const &mt, double const (&p)[R], double const (&q)[R], unsigned j, unsigned k0, unsigned M)
+{
+    uint64_t const at = (uint64_t)j * M;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (k0 + r < M) mt.p[at + k0 + r] = p[r], mt.q[at + k0 + r] = q[r];
+}
+
+template <class Real, int R, int PH, bool ROWS, bool MAT>
 __device__ __forceinline__ void forward_row(State<R> &s, Trans<R> const &t, XF const &x, Tabs<Real> const &g, unsigned j,
-                                            unsigned lane, double *rec)
+                                            unsigned lane, double *rec, Mats const &mt)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH}; // slot of row j - l
     unsigned const i = j - 1u;
@@ -117,9 +139,10 @@ __device__ __forceinline__ void forward_row(State<R> &s, Trans<R> const &t, XF c
     s.PX[PH] = dcp_lse2(E + x.xa, X + x.xb);
     s.E = E, s.Cc = Cc, s.Rr = Rr;
     if constexpr (ROWS) store_record<PH>(s.PX, B, E, rec + (uint64_t)DCP_POST_REC * j, lane);
+    if constexpr (MAT) store_cells<R>(mt, s.P[PH], s.Q[PH], j, k0, g.M);
 }
 
-template <class Real, int R, bool ROWS> __global__ __launch_bounds__(256) void forward_kernel(dcp_fwd_args a)
+template <class Real, int R, bool ROWS, bool MAT> __global__ __launch_bounds__(256) void forward_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -170,9 +193,15 @@ template <class Real, int R, bool ROWS> __global__ __launch_bounds__(256) void f
             rec = a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
             store_record<0>(s.PX, B0, ninf(), rec, lane); // row 0: PN = SN, B = SB, no J, C, E yet
         }
+        Mats mt{nullptr, nullptr};
+        if constexpr (MAT)
+        {
+            mt = mats_of(a, pp);
+            store_cells<R>(mt, s.P[0], s.Q[0], 0u, k0, g.M);
+        }
         unsigned j = 1u;
 #define DCP_FWD_ROW(PH)                                                                                                \
-    forward_row<Real, R, PH, ROWS>(s, t, x, g, j, lane, rec);                                                          \
+    forward_row<Real, R, PH, ROWS, MAT>(s, t, x, g, j, lane, rec, mt);                                                 \
     if (j == L) break;                                                                                                 \
     ++j;
         for (;;)
@@ -212,9 +241,9 @@ struct WideArea // rows of ldk doubles: P and Q slots, then the row's M, I, D
     __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
 };
 
-template <class Real, int PH, bool ROWS>
+template <class Real, int PH, bool ROWS, bool MAT>
 __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs<Real> const &g, WideArea const &wa, unsigned j,
-                                                 unsigned lane, double *rec)
+                                                 unsigned lane, double *rec, Mats const &mt)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
     unsigned const i = j - 1u;
@@ -296,6 +325,8 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
             p[r] = dcp_lse4(B + load_col(g.trans + DCP_T_ENTRY * g.ld, k, g.M), pm[r] + load_col(g.trans + DCP_T_MM * g.ld, k, g.M),
                             pi[r] + load_col(g.trans + DCP_T_IM * g.ld, k, g.M), pd[r] + load_col(g.trans + DCP_T_DM * g.ld, k, g.M));
             q[r] = dcp_lse2(m[r] + load_col(g.trans + DCP_T_MI * g.ld, k, g.M), ins[r] + load_col(g.trans + DCP_T_II * g.ld, k, g.M));
+            if constexpr (MAT)
+                if (k < g.M) mt.p[(uint64_t)j * g.M + k] = p[r], mt.q[(uint64_t)j * g.M + k] = q[r];
         }
         bm = readlane(m[WR - 1], 63), bi = readlane(ins[WR - 1], 63), bd = readlane(d[WR - 1], 63);
     }
@@ -304,7 +335,7 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
     if constexpr (ROWS) store_record<PH>(s.PX, B, E, rec + (uint64_t)DCP_POST_REC * j, lane);
 }
 
-template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_wide_kernel(dcp_fwd_args a)
+template <class Real, bool ROWS, bool MAT> __global__ __launch_bounds__(256) void forward_wide_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -322,6 +353,8 @@ template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_
         wa.nchunks = (pr.core_size + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
         wa.ldk = (uint64_t)wa.nchunks * DCP_FWD_CHUNK; // <= work_stride / DCP_FWD_WORK_ROWS: the host sized it by the widest
         wa.base = a.work + gw * a.work_stride;
+        Mats mt{nullptr, nullptr};
+        if constexpr (MAT) mt = mats_of(a, pp);
         // row 0, anew for every pair (the pair before may have been of another width): the rings' own columns
         double const B0 = 0.0 + xt[DCP_X_SB];
         for (unsigned ch = 0; ch < wa.nchunks; ++ch)
@@ -332,6 +365,8 @@ template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_
             {
                 wa.P(0)[k0 + r] = B0 + load_col(g.trans + DCP_T_ENTRY * g.ld, k0 + r, g.M);
                 wa.Q(0)[k0 + r] = ninf();
+                if constexpr (MAT)
+                    if (k0 + r < g.M) mt.p[k0 + r] = wa.P(0)[k0 + r], mt.q[k0 + r] = ninf();
 #pragma unroll
                 for (int h = 1; h < 5; ++h)
                     wa.P(h)[k0 + r] = wa.Q(h)[k0 + r] = ninf();
@@ -352,7 +387,7 @@ template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_
         }
         unsigned j = 1u;
 #define DCP_FWD_ROW(PH)                                                                                                \
-    forward_wide_row<Real, PH, ROWS>(s, x, g, wa, j, lane, rec);                                                       \
+    forward_wide_row<Real, PH, ROWS, MAT>(s, x, g, wa, j, lane, rec, mt);                                              \
     if (j == L) break;                                                                                                 \
     ++j;
         for (;;)
@@ -372,15 +407,15 @@ template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_
     }
 }
 
-template <class Real, bool ROWS> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
+template <class Real, bool ROWS, bool MAT = false> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
     {
-    case 0: hipLaunchKernelGGL((forward_wide_kernel<Real, ROWS>), grid, block, 0, st, a); return 0;
-    case 1: hipLaunchKernelGGL((forward_kernel<Real, 1, ROWS>), grid, block, 0, st, a); return 0;
-    case 2: hipLaunchKernelGGL((forward_kernel<Real, 2, ROWS>), grid, block, 0, st, a); return 0;
-    case 4: hipLaunchKernelGGL((forward_kernel<Real, 4, ROWS>), grid, block, 0, st, a); return 0;
+    case 0: hipLaunchKernelGGL((forward_wide_kernel<Real, ROWS, MAT>), grid, block, 0, st, a); return 0;
+    case 1: hipLaunchKernelGGL((forward_kernel<Real, 1, ROWS, MAT>), grid, block, 0, st, a); return 0;
+    case 2: hipLaunchKernelGGL((forward_kernel<Real, 2, ROWS, MAT>), grid, block, 0, st, a); return 0;
+    case 4: hipLaunchKernelGGL((forward_kernel<Real, 4, ROWS, MAT>), grid, block, 0, st, a); return 0;
     default: return 1;
     }
 }
@@ -405,5 +440,17 @@ extern "C" int dcp_forward_rows_launch(int precision, int R, struct dcp_fwd_args
     hipStream_t const st = (hipStream_t)stream;
     if (precision == 32) return launch<float, true>(R, *a, st);
     if (precision == 64) return launch<double, true>(R, *a, st);
+    return 1;
+}
+
+// the same again, P and Q of every row stored as well (a->mat0, a->mat1, a->cell_off, a->cell_base): dcp_gpu_mea_pairs'
+// first sweep
+extern "C" int dcp_forward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+{
+    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off || !a->mat0 || !a->mat1 || !a->cell_off) return 1;
+    if (R == 0 && !a->work) return 1;
+    hipStream_t const st = (hipStream_t)stream;
+    if (precision == 32) return launch<float, true, true>(R, *a, st);
+    if (precision == 64) return launch<double, true, true>(R, *a, st);
     return 1;
 }

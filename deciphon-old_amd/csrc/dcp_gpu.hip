@@ -12,6 +12,7 @@
 #include "dcp_domains.h"
 #include "dcp_calib.h"
 #include "dcp_forward.h"
+#include "dcp_mea.h"
 #include "dcp_posterior.h"
 #include "dcp_test_hooks.h"
 
@@ -436,6 +437,24 @@ struct dcp_gpu_ctx
         uint64_t budget = 0;
         float ms = -1.0f;
     } post;
+    // The posterior-decoded alignment of a pair list (dcp_gpu_mea_pairs, dcp_mea.hip): the call's own buffers, kept
+    // between calls and grown when a call needs more -- the list's row and cell offsets, the special transitions, the
+    // scores (null, alt by Forward, alt by Backward, gain), a round's bucketed and listed pairs, its two sweeps' row records
+    // and matrices (P, Q, bM, bI), its cell and row choices, S's choices, its steps and their posteriors with where each
+    // pair's go, how many fit and how many there are, and the max-plus sweep's work areas.  The profiles, the two sweeps'
+    // work areas and the wavefront cap are fwd's.  budget: the hooks build's bound on a round's matrices, choices and
+    // records (0: 8 GiB).  ms: the last call's kernel time, summed over its rounds.
+    struct MeaState
+    {
+        DevBuf<uint64_t> d_off, d_step_idx;
+        DevBuf<dcp_fwd_pair> d_pairs;
+        DevBuf<double> d_xt, d_score, d_rec, d_mat, d_work, d_post;
+        DevBuf<uint16_t> d_cell;
+        DevBuf<uint32_t> d_rowc, d_start, d_steps;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint64_t budget = 0;
+        float ms = -1.0f;
+    } mea;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -775,6 +794,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     for (hipEvent_t e : c->fwd.ev)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->post.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->mea.ev)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -3695,6 +3716,216 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
 
 float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->post.ms : -1.0f; }
 
+// ---- The posterior-decoded alignment of a pair list (dcp_mea.hip) ---------------------------------------------------
+// The list runs in rounds of consecutive pairs whose matrices (P, Q, bM, bI: 32 bytes a cell), cell choices (2 bytes a
+// cell), row records (80 bytes a row) and row choices (8 bytes a row) fit the budget (a single pair that exceeds it gets
+// a round of its own).  A round: the matrix-storing Forward launches by class, the Backward launches by class, the
+// max-plus sweep and the walk over the round's pairs in list order; a pair whose path is longer than the first estimate
+// (L + M + 16 steps) makes the round's walk run once more at the exact counts; the round's steps copied out; then the next.
+static constexpr uint64_t kMeaCellBytes = 4u * sizeof(double) + sizeof(uint16_t);
+static constexpr uint64_t kMeaRowBytes = 2u * DCP_POST_REC * sizeof(double) + DCP_MEA_ROWC * sizeof(uint32_t);
+
+int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx, uint32_t const *profile_idx,
+                      unsigned npairs, struct dcp_step *steps_out, unsigned cap_steps, uint32_t *step_off, double *post_out,
+                      double *gain_out, double *alt_fwd_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, gain_out && alt_fwd_out)) return rc;
+    if (!step_off) return c->fail(DCP_EINVAL, "a pair list without its step offsets");
+    if (npairs && cap_steps && !steps_out) return c->fail(DCP_EINVAL, "a pair list without its step array");
+    if (npairs == 0)
+    {
+        step_off[0] = 0u;
+        return DCP_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->mea;
+    bool const f64 = c->precision == 64;
+    if (!f64)
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+    if (int rc = forward_profiles(c)) return rc;
+    std::vector<double> xt;
+    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
+
+    // rows and cells of the list, one array: [npairs + 1] row offsets, then [npairs + 1] cell offsets
+    size_t const no = (size_t)npairs + 1u;
+    std::vector<uint64_t> off(2u * no, 0u);
+    uint64_t *const roff = off.data(), *const coff = off.data() + no;
+    for (unsigned i = 0; i < npairs; ++i)
+    {
+        uint64_t const rows = (uint64_t)c->seq_len[seq_idx[i]] + 1u;
+        roff[i + 1u] = roff[i] + rows;
+        coff[i + 1u] = coff[i] + rows * c->core_sizes[profile_idx[i]];
+    }
+    uint64_t const budget = W.budget ? W.budget : (uint64_t)8u << 30;
+    auto const bytes_of = [&](unsigned i0, unsigned i1) {
+        return (coff[i1] - coff[i0]) * kMeaCellBytes + (roff[i1] - roff[i0]) * kMeaRowBytes;
+    };
+    auto const round_end = [&](unsigned i0) {
+        unsigned i1 = i0 + 1u;
+        while (i1 < npairs && bytes_of(i0, i1 + 1u) <= budget)
+            ++i1;
+        return i1;
+    };
+    HIP_TRY(c, W.d_off.reserve(off.size()));
+    HIP_TRY(c, W.d_xt.reserve(xt.size()));
+    HIP_TRY(c, W.d_score.reserve(4u * (size_t)npairs));
+    for (hipEvent_t &e : W.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipMemcpyAsync(W.d_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+
+    dcp_fwd_args a = forward_args(c, W.d_xt.p);
+    a.row_off = W.d_off.p, a.cell_off = W.d_off.p + no;
+    double *const d_null = W.d_score.p, *const d_fwd = d_null + npairs, *const d_bwd = d_fwd + npairs, *const d_gain = d_bwd + npairs;
+    dcp_mea_args ma{};
+    ma.profs = a.profs, ma.tab = a.tab, ma.trans = a.trans, ma.ei = a.ei, ma.en = a.en;
+    ma.seq_words = a.seq_words, ma.seq_woff = a.seq_woff, ma.seq_len = a.seq_len, ma.xtrans = a.xtrans;
+    ma.alt_fwd = d_fwd, ma.gain = d_gain;
+
+    // the call's own copy of every pair's steps, in list order: the caller's arrays stay untouched until all is known
+    std::vector<uint32_t> steps, round_steps;
+    std::vector<double> post, round_post;
+    std::vector<uint64_t> count((size_t)npairs, 0u), idx;
+    std::vector<dcp_fwd_pair> list;
+    float ms_total = 0.0f;
+    for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
+    {
+        i1 = round_end(i0);
+        unsigned const n = i1 - i0;
+        uint64_t const nrows = roff[i1] - roff[i0], ncells = coff[i1] - coff[i0];
+        ForwardBuckets b;
+        forward_bucket(c, seq_idx + i0, profile_idx + i0, n, i0, b);
+        list.resize(n);
+        unsigned chunks = 0; // of the round's widest profile
+        idx.assign(3u * (size_t)n, 0u); // where a pair's steps go, how many fit, how many there are
+        uint64_t nsteps_cap = 0;
+        for (unsigned i = 0; i < n; ++i)
+        {
+            list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
+            unsigned const M = c->core_sizes[profile_idx[i0 + i]];
+            chunks = std::max(chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
+            idx[i] = nsteps_cap, idx[n + i] = (uint64_t)c->seq_len[seq_idx[i0 + i]] + M + 16u;
+            nsteps_cap += idx[n + i];
+        }
+        uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
+        unsigned mea_waves = (unsigned)std::min<uint64_t>(n, 4ull * c->num_cus); // one wavefront per SIMD
+        if (c->fwd.waves_cap) mea_waves = std::min(mea_waves, c->fwd.waves_cap);
+        uint64_t const mea_stride = (uint64_t)DCP_MEA_WORK_ROWS * chunks * DCP_FWD_CHUNK;
+        HIP_TRY(c, c->fwd.d_work.reserve(work_stride * b.waves[3]));
+        HIP_TRY(c, W.d_work.reserve(mea_stride * mea_waves));
+        HIP_TRY(c, W.d_pairs.reserve(2u * (size_t)n));
+        HIP_TRY(c, W.d_rec.reserve(2u * DCP_POST_REC * nrows));
+        HIP_TRY(c, W.d_mat.reserve(4u * ncells));
+        HIP_TRY(c, W.d_cell.reserve(ncells));
+        HIP_TRY(c, W.d_rowc.reserve(DCP_MEA_ROWC * nrows));
+        HIP_TRY(c, W.d_start.reserve(n));
+        HIP_TRY(c, W.d_step_idx.reserve(idx.size()));
+        HIP_TRY(c, W.d_steps.reserve(nsteps_cap));
+        HIP_TRY(c, W.d_post.reserve(nsteps_cap));
+        dcp_fwd_pair *const d_bucketed = W.d_pairs.p, *const d_list = W.d_pairs.p + n;
+        HIP_TRY(c, hipMemcpyAsync(d_bucketed, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(W.d_step_idx.p, idx.data(), idx.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below
+
+        a.work = c->fwd.d_work.p, a.work_stride = work_stride;
+        a.row_base = roff[i0], a.cell_base = coff[i0];
+        a.out_null = d_null;
+        HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+        for (int sweep = 0; sweep < 2; ++sweep)
+        {
+            a.rows = W.d_rec.p + (sweep ? (size_t)DCP_POST_REC * nrows : 0u);
+            a.mat0 = W.d_mat.p + (sweep ? 2u * ncells : 0u), a.mat1 = a.mat0 + ncells;
+            a.out_alt = sweep ? d_bwd : d_fwd;
+            for (int k = 0; k < 4; ++k)
+            {
+                if (b.count[k] == 0) continue;
+                a.pairs = d_bucketed + b.first[k];
+                a.npairs = b.count[k];
+                a.nwaves = b.waves[k];
+                if ((sweep ? dcp_backward_mat_launch : dcp_forward_mat_launch)(c->precision, kFwdR[k], &a, c->stream))
+                    return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
+                HIP_TRY(c, hipGetLastError());
+            }
+        }
+        ma.list = d_list, ma.nlist = n, ma.nwaves = mea_waves;
+        ma.row_off = W.d_off.p + i0, ma.cell_off = W.d_off.p + no + i0;
+        ma.P = W.d_mat.p, ma.Q = ma.P + ncells, ma.bM = ma.Q + ncells, ma.bI = ma.bM + ncells;
+        ma.rows_f = W.d_rec.p, ma.rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
+        ma.cell = W.d_cell.p, ma.rowc = W.d_rowc.p, ma.start = W.d_start.p;
+        ma.work = W.d_work.p, ma.work_stride = mea_stride;
+        if (dcp_mea_sweep_launch(c->precision, &ma, c->stream)) return c->fail(DCP_EFAIL, "no max-plus sweep kernel");
+        HIP_TRY(c, hipGetLastError());
+        for (int walk = 0; walk < 2; ++walk)
+        {
+            ma.steps = W.d_steps.p, ma.post = W.d_post.p;
+            ma.step_at = W.d_step_idx.p, ma.step_cap = W.d_step_idx.p + n, ma.nsteps = W.d_step_idx.p + 2u * (size_t)n;
+            if (dcp_mea_walk_launch(c->precision, &ma, c->stream)) return c->fail(DCP_EFAIL, "no walk kernel");
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+            HIP_TRY(c, hipMemcpyAsync(idx.data() + 2u * (size_t)n, ma.nsteps, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            float ms = 0.0f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+            ms_total += ms;
+            bool fits = true;
+            for (unsigned i = 0; i < n; ++i)
+                fits = fits && idx[2u * (size_t)n + i] <= idx[n + i];
+            if (fits) break;
+            if (walk) return c->fail(DCP_EFAIL, "a path grew between two walks of the same choices");
+            // once more at the exact counts
+            nsteps_cap = 0;
+            for (unsigned i = 0; i < n; ++i)
+            {
+                idx[i] = nsteps_cap, idx[n + i] = idx[2u * (size_t)n + i];
+                nsteps_cap += idx[n + i];
+            }
+            HIP_TRY(c, W.d_steps.reserve(nsteps_cap));
+            HIP_TRY(c, W.d_post.reserve(nsteps_cap));
+            HIP_TRY(c, hipMemcpyAsync(W.d_step_idx.p, idx.data(), 2u * (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+        }
+        round_steps.resize(nsteps_cap), round_post.resize(nsteps_cap);
+        HIP_TRY(c, hipMemcpyAsync(round_steps.data(), W.d_steps.p, nsteps_cap * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(round_post.data(), W.d_post.p, nsteps_cap * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        for (unsigned i = 0; i < n; ++i)
+        {
+            uint64_t const ns = idx[2u * (size_t)n + i];
+            count[i0 + i] = ns;
+            steps.insert(steps.end(), round_steps.begin() + idx[i], round_steps.begin() + idx[i] + ns);
+            post.insert(post.end(), round_post.begin() + idx[i], round_post.begin() + idx[i] + ns);
+        }
+    }
+    std::vector<double> score(3u * (size_t)npairs); // alt by Forward, alt by Backward, gain
+    HIP_TRY(c, hipMemcpy(score.data(), d_fwd, score.size() * sizeof(double), hipMemcpyDeviceToHost));
+    double const *const gain = score.data() + 2u * (size_t)npairs;
+    uint64_t total = 0;
+    for (unsigned i = 0; i < npairs; ++i)
+    {
+        if (count[i] == 0u && gain[i] != -std::numeric_limits<double>::infinity())
+            return c->fail(DCP_EFAIL, "pair %u has a gain and no path", i);
+        total += count[i];
+    }
+    if (total > 0xffffffffull) return c->fail(DCP_EFAIL, "the list's paths hold %llu steps, more than 32 bits count", (unsigned long long)total);
+    W.ms = ms_total;
+    step_off[0] = 0u;
+    for (unsigned i = 0; i < npairs; ++i)
+        step_off[i + 1u] = step_off[i] + (uint32_t)count[i];
+    if (total > cap_steps)
+        return c->fail(DCP_ENOMEM, "the list's paths hold %llu steps, the arrays hold %u", (unsigned long long)total, cap_steps);
+    static_assert(sizeof(dcp_step) == sizeof(uint32_t), "a step is one word: state_id | seqlen << 16");
+    if (total) std::memcpy(steps_out, steps.data(), (size_t)total * sizeof(uint32_t));
+    if (total && post_out) std::memcpy(post_out, post.data(), (size_t)total * sizeof(double));
+    std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
+    std::memcpy(gain_out, gain, (size_t)npairs * sizeof(double));
+    return DCP_OK;
+}
+
+float dcp_gpu_mea_kernel_ms(dcp_gpu_ctx *c) { return c ? c->mea.ms : -1.0f; }
+
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
 static int rerun_with_rowsweep(dcp_gpu_ctx *c)
 {
@@ -3827,6 +4058,13 @@ int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *c, unsigned long long bytes)
 {
     if (!c) return DCP_EINVAL;
     c->post.budget = bytes;
+    return DCP_OK;
+}
+
+int dcp_gpu_test_set_mea_budget(dcp_gpu_ctx *c, unsigned long long bytes)
+{
+    if (!c) return DCP_EINVAL;
+    c->mea.budget = bytes;
     return DCP_OK;
 }
 

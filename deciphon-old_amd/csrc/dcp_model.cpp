@@ -1850,9 +1850,10 @@ int dcp_hits_evalues64(struct dcp_hit64 const *hits, unsigned n, double const *m
 
 // The sweep itself, arguments checked.  rec, if given, receives per row j = 0 .. L the five values a word starting
 // after row j, or a domain beginning or ending there, leaves from: PN(j), PJ(j), PC(j), B(j), E(j) (dcp_posterior.h).
+// Pm and Qm, if given, receive P_k(j) and Q_k(j), rows j = 0 .. L of M (dcp_mea.h).
 static int forward_sweep(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
                          double const *emis_null, double const *xtrans, unsigned char const *seq, unsigned L, double *rec,
-                         double *null_out, double *alt_out)
+                         double *null_out, double *alt_out, double *Pm = nullptr, double *Qm = nullptr)
 {
     double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
                  *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
@@ -1877,6 +1878,9 @@ static int forward_sweep(unsigned M, unsigned ldk, double const *trans8, double 
     PN[0] = 0.0 + x[DCP_X_SN];
     PR[0] = 0.0;
     if (rec) rec[0] = PN[0], rec[1] = ninf, rec[2] = ninf, rec[3] = B0, rec[4] = ninf;
+    if (Pm)
+        for (unsigned k = 0; k < M; ++k)
+            Pm[k] = P[k], Qm[k] = Q[k];
 
     static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
     double E = ninf, Cc = ninf, Rr = ninf;
@@ -1934,6 +1938,9 @@ static int forward_sweep(unsigned M, unsigned ldk, double const *trans8, double 
             pm[k] = k ? dcp_lse4(B + ENT[k], Mr[k - 1] + MM[k], Ir[k - 1] + IM[k], Dr[k - 1] + DM[k]) : B + ENT[0];
             qi[k] = dcp_lse2(Mr[k] + MI[k], Ir[k] + II[k]);
         }
+        if (Pm)
+            for (unsigned k = 0; k < M; ++k)
+                Pm[(size_t)j * M + k] = pm[k], Qm[(size_t)j * M + k] = qi[k];
         PN[r] = N + x[DCP_X_NN];
         PJ[r] = dcp_lse2(E + x[DCP_X_EJ], J + x[DCP_X_JJ]);
         PC[r] = dcp_lse2(E + x[DCP_X_EC], Cc + x[DCP_X_CC]);
@@ -1966,36 +1973,19 @@ extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8
 // dcp_posterior.h's; sequential in k, every lse in the order written, bB and E summed in k order from the maximum.  It
 // holds the full matrices of bM and bI: it is no hot path.  No device.
 // ---------------------------------------------------------------------------
-extern "C" int dcp_posterior_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
-                                    double const *emis_insert, double const *emis_null, double const xtrans[13],
-                                    unsigned char const *seq, unsigned L, double *begin_out, double *end_out,
-                                    double *core_out, double *alt_fwd_out, double *alt_bwd_out)
+// The Backward sweep itself, arguments checked: br the row records, bM and bI the full matrices, rows 0 .. L + 5 of M
+// (rows past L are -inf already), row3 three rows of M for bP, bQ, bD.  Returns bPN(0).
+static double backward_sweep(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+                             double const *emis_null, double const *xtrans, unsigned char const *seq, unsigned L, double *br,
+                             double *bM, double *bI, double *row3)
 {
-    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
-    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq) return DCP_EINVAL;
-    if (!begin_out || !end_out || !core_out || !alt_fwd_out || !alt_bwd_out) return DCP_EINVAL;
-    for (unsigned i = 0; i < L; ++i)
-        if (seq[i] > 3) return DCP_EINVAL;
     double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
                  *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
                  *MD = trans8 + (size_t)DCP_T_MD * ldk, *DD = trans8 + (size_t)DCP_T_DD * ldk,
                  *MI = trans8 + (size_t)DCP_T_MI * ldk, *II = trans8 + (size_t)DCP_T_II * ldk;
     double const *x = xtrans;
     double const ninf = dcp_fwd_ninf();
-    size_t const rows = (size_t)L + 6u; // rows L + 1 .. L + 5 stay -inf: words that would end past L
-    size_t const nrec = 2u * (size_t)DCP_POST_REC * rows, nmat = 2u * rows * M, nrow = 3u * (size_t)M;
-    double *const mem = (double *)std::malloc(sizeof(double) * (nrec + nmat + nrow));
-    if (!mem) return DCP_ENOMEM;
-    double *const fr = mem, *const br = fr + DCP_POST_REC * rows, *const bM = mem + nrec, *const bI = bM + rows * M,
-                 *const bP = mem + nrec + nmat, *const bQ = bP + M, *const bD = bQ + M;
-    for (size_t i = 0; i < nrec + nmat; ++i)
-        mem[i] = ninf;
-    double null_fwd, alt_fwd;
-    if (int rc = forward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, fr, &null_fwd, &alt_fwd))
-    {
-        std::free(mem);
-        return rc;
-    }
+    double *const bP = row3, *const bQ = bP + M, *const bD = bQ + M;
     static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
     double bPN0 = ninf;
     for (unsigned j = L;; --j)
@@ -2058,6 +2048,36 @@ extern "C" int dcp_posterior_tables(unsigned M, unsigned ldk, double const *tran
             break;
         }
     }
+    return bPN0;
+}
+
+extern "C" int dcp_posterior_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                    double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                    unsigned char const *seq, unsigned L, double *begin_out, double *end_out,
+                                    double *core_out, double *alt_fwd_out, double *alt_bwd_out)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq) return DCP_EINVAL;
+    if (!begin_out || !end_out || !core_out || !alt_fwd_out || !alt_bwd_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    double const *x = xtrans;
+    double const ninf = dcp_fwd_ninf();
+    size_t const rows = (size_t)L + 6u; // rows L + 1 .. L + 5 stay -inf: words that would end past L
+    size_t const nrec = 2u * (size_t)DCP_POST_REC * rows, nmat = 2u * rows * M, nrow = 3u * (size_t)M;
+    double *const mem = (double *)std::malloc(sizeof(double) * (nrec + nmat + nrow));
+    if (!mem) return DCP_ENOMEM;
+    double *const fr = mem, *const br = fr + DCP_POST_REC * rows, *const bM = mem + nrec, *const bI = bM + rows * M,
+                 *const bP = mem + nrec + nmat;
+    for (size_t i = 0; i < nrec + nmat; ++i)
+        mem[i] = ninf;
+    double null_fwd, alt_fwd;
+    if (int rc = forward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, fr, &null_fwd, &alt_fwd))
+    {
+        std::free(mem);
+        return rc;
+    }
+    double const bPN0 = backward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, br, bM, bI, bP);
     double const alt_bwd = dcp_lse2(x[DCP_X_SB] + br[3], x[DCP_X_SN] + bPN0);
     for (unsigned j = 0; j <= L; ++j)
     {
@@ -2101,5 +2121,270 @@ extern "C" int dcp_posterior_envelopes(double const *core, unsigned L, double th
         i = e;
     }
     *n_out = n;
+    return DCP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The posterior-decoded alignment on the host: the twin of dcp_mea.hip and the tests' yardstick.  The rule, the choice
+// codes and the walk are dcp_mea.h's; the two sweeps are the ones above, with their full matrices.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_mea.h"
+
+namespace
+{
+
+struct MeaSeq
+{
+    unsigned char const *s;
+    unsigned operator()(unsigned i) const { return s[i]; }
+};
+
+// the two sweeps' matrices of one pair, and the max-plus sweep's choices over them
+struct MeaHost
+{
+    void *mem = nullptr;
+    double *fr, *br, *bM, *bI, *P, *Q; // records and bM, bI: rows 0 .. L + 5; P, Q: rows 0 .. L
+    double *gM, *gI, *gX;              // suffix gains: rows 0 .. L + 5 of M, M and 3
+    uint16_t *cell;
+    uint32_t *rowc;
+    double alt, gain;
+    unsigned start;
+    ~MeaHost() { std::free(mem); }
+};
+
+int mea_sweeps(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+               double const *emis_null, double const *xtrans, unsigned char const *seq, unsigned L, MeaHost &h)
+{
+    double const ninf = dcp_fwd_ninf();
+    size_t const rows = (size_t)L + 6u, cells = ((size_t)L + 1u) * M;
+    size_t const nrec = 2u * (size_t)DCP_POST_REC * rows, nmat = 4u * rows * M + 3u * rows, npq = 2u * cells, nrow = 3u * (size_t)M;
+    size_t const ndbl = nrec + nmat + npq + nrow;
+    h.mem = std::malloc(sizeof(double) * ndbl + sizeof(uint32_t) * DCP_MEA_ROWC * rows + sizeof(uint16_t) * cells);
+    if (!h.mem) return DCP_ENOMEM;
+    double *const d = (double *)h.mem;
+    h.fr = d, h.br = h.fr + DCP_POST_REC * rows;
+    h.bM = d + nrec, h.bI = h.bM + rows * M, h.gM = h.bI + rows * M, h.gI = h.gM + rows * M, h.gX = h.gI + rows * M;
+    h.P = d + nrec + nmat, h.Q = h.P + cells;
+    double *const row3 = h.Q + cells;
+    h.rowc = (uint32_t *)(d + ndbl);
+    h.cell = (uint16_t *)(h.rowc + DCP_MEA_ROWC * rows);
+    for (size_t i = 0; i < nrec + nmat; ++i)
+        d[i] = ninf;
+    double null_fwd;
+    if (int rc = forward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, h.fr, &null_fwd, &h.alt, h.P, h.Q))
+        return rc;
+    backward_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, h.br, h.bM, h.bI, row3);
+
+    double const *ENT = trans8 + (size_t)DCP_T_ENTRY * ldk, *MM = trans8 + (size_t)DCP_T_MM * ldk,
+                 *IM = trans8 + (size_t)DCP_T_IM * ldk, *DM = trans8 + (size_t)DCP_T_DM * ldk,
+                 *MD = trans8 + (size_t)DCP_T_MD * ldk, *DD = trans8 + (size_t)DCP_T_DD * ldk,
+                 *MI = trans8 + (size_t)DCP_T_MI * ldk, *II = trans8 + (size_t)DCP_T_II * ldk;
+    double const *x = xtrans;
+    double const a = h.alt;
+    double *const gP = row3, *const gQ = gP + M, *const gD = gQ + M;
+    MeaSeq const sq{seq};
+    double gPN0 = ninf;
+    for (unsigned j = L;; --j)
+    {
+        bool const last = j == L;
+        unsigned code[5] = {0, 0, 0, 0, 0};
+        unsigned const nl = L - j < 5u ? L - j : 5u; // words that end at or before L
+        for (unsigned l = 1; l <= nl; ++l)
+            code[l - 1] = dcp_mea_code(sq, j, l);
+        dcp_mea_best px[3];
+        for (unsigned X = 0; X < 3u; ++X)
+        {
+            px[X] = dcp_mea_none();
+            for (unsigned l = 1; l <= nl; ++l)
+                dcp_mea_take(px[X], dcp_mea_word(h.fr[(size_t)DCP_POST_REC * j + X], emis_null[code[l - 1]],
+                                                 h.br[(size_t)DCP_POST_REC * (j + l) + X], a, l, h.gX[3u * (size_t)(j + l) + X]), l);
+        }
+        dcp_mea_best bb = dcp_mea_none();
+        uint16_t *const cj = h.cell + (size_t)j * M;
+        for (unsigned k = 0; k < M; ++k)
+        {
+            dcp_mea_best p = dcp_mea_none(), q = dcp_mea_none();
+            for (unsigned l = 1; l <= nl; ++l)
+            {
+                size_t const to = (size_t)(j + l) * M + k;
+                dcp_mea_take(p, dcp_mea_word(h.P[(size_t)j * M + k], emis_match[(size_t)code[l - 1] * ldk + k], h.bM[to], a, l, h.gM[to]), l);
+                dcp_mea_take(q, dcp_mea_word(h.Q[(size_t)j * M + k], emis_insert[code[l - 1]], h.bI[to], a, l, h.gI[to]), l);
+            }
+            gP[k] = p.g, gQ[k] = q.g;
+            cj[k] = (uint16_t)((p.c << DCP_MEA_SH_P) | (q.c << DCP_MEA_SH_Q));
+            dcp_mea_take(bb, dcp_mea_link(ENT[k], p.g), k + 1u);
+        }
+        dcp_mea_best const c = dcp_mea_c(last, x[DCP_X_CT], x[DCP_X_CC], px[2].g);
+        dcp_mea_best const jj = dcp_mea_nj(x[DCP_X_JB], x[DCP_X_JJ], bb.g, px[1].g);
+        dcp_mea_best const n = dcp_mea_nj(x[DCP_X_NB], x[DCP_X_NN], bb.g, px[0].g);
+        dcp_mea_best const e = dcp_mea_e(last, x[DCP_X_ET], x[DCP_X_EB], x[DCP_X_EJ], x[DCP_X_EC], bb.g, px[1].g, px[2].g);
+        double *const gx = h.gX + 3u * (size_t)j;
+        gx[0] = n.g, gx[1] = jj.g, gx[2] = c.g;
+        h.rowc[(size_t)DCP_MEA_ROWC * j] = (px[0].c << DCP_MEA_SH_PN) | (px[1].c << DCP_MEA_SH_PJ) | (px[2].c << DCP_MEA_SH_PC) |
+                                           (n.c << DCP_MEA_SH_N) | (jj.c << DCP_MEA_SH_J) | (c.c << DCP_MEA_SH_C) | (e.c << DCP_MEA_SH_E);
+        h.rowc[(size_t)DCP_MEA_ROWC * j + 1u] = bb.c;
+        double *const gm = h.gM + (size_t)j * M, *const gi = h.gI + (size_t)j * M;
+        for (unsigned k = M; k-- > 0;)
+        {
+            bool const nx = k + 1u < M; // node k + 1 exists
+            double const dn = nx ? gD[k + 1] : ninf, pn = nx ? gP[k + 1] : ninf;
+            dcp_mea_best const dd = dcp_mea_d(e.g, nx ? DD[k + 1] : ninf, nx ? DM[k + 1] : ninf, dn, pn);
+            dcp_mea_best const mm = dcp_mea_m(e.g, nx ? MD[k + 1] : ninf, nx ? MM[k + 1] : ninf, MI[k], dn, pn, gQ[k]);
+            dcp_mea_best const ii = dcp_mea_i(nx ? IM[k + 1] : ninf, II[k], pn, gQ[k]);
+            gD[k] = dd.g, gm[k] = mm.g, gi[k] = ii.g;
+            cj[k] = (uint16_t)(cj[k] | (mm.c << DCP_MEA_SH_M) | (ii.c << DCP_MEA_SH_I) | (dd.c << DCP_MEA_SH_D));
+        }
+        if (j == 0)
+        {
+            gPN0 = px[0].g;
+            dcp_mea_best const s = dcp_mea_nj(x[DCP_X_SB], x[DCP_X_SN], bb.g, gPN0);
+            h.gain = s.g, h.start = s.c;
+            break;
+        }
+    }
+    return DCP_OK;
+}
+
+dcp_mea_view<double> mea_view(MeaHost const &h, unsigned M, unsigned ldk, unsigned L, double const *emis_match,
+                              double const *emis_insert, double const *emis_null)
+{
+    dcp_mea_view<double> v;
+    v.M = M, v.L = L, v.ldm = M;
+    v.P = h.P, v.Q = h.Q, v.bM = h.bM, v.bI = h.bI;
+    v.cell = h.cell, v.rowc = h.rowc, v.fr = h.fr, v.br = h.br;
+    v.em = emis_match, v.ei = emis_insert, v.en = emis_null, v.ld = ldk;
+    return v;
+}
+
+bool mea_inputs_ok(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+                   double const *emis_null, double const *xtrans, unsigned char const *seq, unsigned L)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0) return false;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq) return false;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return false;
+    return true;
+}
+
+} // namespace
+
+extern "C" int dcp_mea_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                              double const *emis_insert, double const *emis_null, double const xtrans[13],
+                              unsigned char const *seq, unsigned L, struct dcp_step *steps_out, unsigned cap_steps,
+                              unsigned *nsteps_out, double *post_out, double *gain_out, double *alt_fwd_out)
+{
+    static_assert(sizeof(dcp_step) == sizeof(uint32_t), "a step is one word: state_id | seqlen << 16");
+    if (!mea_inputs_ok(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L)) return DCP_EINVAL;
+    if (!nsteps_out || !gain_out || !alt_fwd_out || (cap_steps && (!steps_out || !post_out))) return DCP_EINVAL;
+    MeaHost h;
+    if (int rc = mea_sweeps(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, h)) return rc;
+    dcp_mea_view<double> const v = mea_view(h, M, ldk, L, emis_match, emis_insert, emis_null);
+    MeaSeq const sq{seq};
+    uint64_t const n = dcp_mea_walk(v, sq, h.alt, h.start, (uint32_t *)nullptr, (double *)nullptr, 0u);
+    if (n > 0xffffffffull) return DCP_EFAIL;
+    *nsteps_out = (unsigned)n;
+    if (n > cap_steps) return DCP_ENOMEM;
+    dcp_mea_walk(v, sq, h.alt, h.start, (uint32_t *)steps_out, post_out, n);
+    *gain_out = n ? h.gain : dcp_fwd_ninf();
+    *alt_fwd_out = h.alt;
+    return DCP_OK;
+}
+
+extern "C" int dcp_mea_path_gain(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                 double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                 unsigned char const *seq, unsigned L, struct dcp_step const *steps, unsigned nsteps,
+                                 double *gain_out, double *post_out)
+{
+    if (!mea_inputs_ok(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L)) return DCP_EINVAL;
+    if (!steps || nsteps < 2u || !gain_out) return DCP_EINVAL;
+    double const ninf = dcp_fwd_ninf();
+    unsigned const EXT = 3u << 14;
+    if (steps[0].state_id != (EXT | 1u) || steps[nsteps - 1u].state_id != (EXT | 7u)) return DCP_EINVAL;
+    // first the integers and the edges: the graph of dcp_domains.hip's edge(), every transition and emission finite
+    MeaSeq const sq{seq};
+    uint64_t pos = 0;
+    for (unsigned i = 0; i < nsteps; ++i)
+    {
+        unsigned const id = steps[i].state_id, kind = id >> 14, xx = id & 0x3fffu, len = steps[i].seqlen;
+        bool const emits = kind < 2u || (kind == 3u && (xx == 2u || xx == 5u || xx == 6u));
+        if (kind < 3u && (xx < 1u || xx > M)) return DCP_EINVAL;
+        if (kind == 3u && (xx == 0u || xx > 7u)) return DCP_EINVAL;
+        if (emits ? (len < 1u || len > 5u) : len != 0u) return DCP_EINVAL;
+        if (pos + len > L) return DCP_EINVAL;
+        if (i > 0u)
+        {
+            unsigned const pid = steps[i - 1u].state_id, pkind = pid >> 14, pk = pid & 0x3fffu, k = xx - 1u;
+            unsigned const from = pkind == 3u ? pk : 100u;
+            double t = ninf;
+            if (kind == 0u)
+            {
+                if (from == 3u) t = trans8[(size_t)DCP_T_ENTRY * ldk + k];
+                else if (k > 0u && pk == k && pkind < 3u) t = trans8[(size_t)(DCP_T_MM + pkind) * ldk + k];
+            }
+            else if (kind == 1u)
+            {
+                if (pk == k + 1u && pkind < 2u) t = trans8[(size_t)(DCP_T_MI + pkind) * ldk + k];
+            }
+            else if (kind == 2u)
+            {
+                if (k > 0u && pk == k && (pkind == 0u || pkind == 2u)) t = trans8[(size_t)(pkind == 0u ? DCP_T_MD : DCP_T_DD) * ldk + k];
+            }
+            else
+            {
+                int r = -1;
+                switch (xx)
+                {
+                case 2: r = from == 1u ? DCP_X_SN : from == 2u ? DCP_X_NN : -1; break;
+                case 3: r = from == 1u ? DCP_X_SB : from == 2u ? DCP_X_NB : from == 4u ? DCP_X_EB : from == 5u ? DCP_X_JB : -1; break;
+                case 4: t = pkind == 0u || (pkind == 2u && pk >= 2u) ? 0.0 : ninf; break;
+                case 5: r = from == 4u ? DCP_X_EJ : from == 5u ? DCP_X_JJ : -1; break;
+                case 6: r = from == 4u ? DCP_X_EC : from == 6u ? DCP_X_CC : -1; break;
+                case 7: r = from == 4u ? DCP_X_ET : from == 6u ? DCP_X_CT : -1; break;
+                default: break;
+                }
+                if (r >= 0) t = xtrans[r];
+            }
+            if (t == ninf) return DCP_EINVAL;
+        }
+        if (emits)
+        {
+            unsigned const code = dcp_mea_code(sq, (unsigned)pos, len);
+            double const e = kind == 0u ? emis_match[(size_t)code * ldk + (xx - 1u)] : kind == 1u ? emis_insert[code] : emis_null[code];
+            if (e == ninf) return DCP_EINVAL;
+        }
+        pos += len;
+    }
+    if (pos != L) return DCP_EINVAL;
+    MeaHost h;
+    if (int rc = mea_sweeps(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, h)) return rc;
+    // the gain from the path's end, as the sweep forms it: suffix + l w
+    double g = 0.0;
+    unsigned j = L;
+    for (unsigned i = nsteps; i-- > 0u;)
+    {
+        unsigned const id = steps[i].state_id, kind = id >> 14, xx = id & 0x3fffu, l = steps[i].seqlen;
+        double w = -1.0;
+        if (l)
+        {
+            unsigned const s = j - l, code = dcp_mea_code(sq, s, l);
+            if (kind == 3u)
+            {
+                unsigned const X = xx == 2u ? 0u : xx == 5u ? 1u : 2u;
+                w = dcp_post_prob(h.fr[(size_t)DCP_POST_REC * s + X] + emis_null[code], h.br[(size_t)DCP_POST_REC * j + X], h.alt);
+            }
+            else
+            {
+                unsigned const k = xx - 1u;
+                size_t const from = (size_t)s * M + k, to = (size_t)j * M + k;
+                w = kind == 0u ? dcp_post_prob(h.P[from] + emis_match[(size_t)code * ldk + k], h.bM[to], h.alt)
+                               : dcp_post_prob(h.Q[from] + emis_insert[code], h.bI[to], h.alt);
+            }
+            double const lw = (double)l * w;
+            g = g + lw;
+            j = s;
+        }
+        if (post_out) post_out[i] = w;
+    }
+    *gain_out = g;
     return DCP_OK;
 }

@@ -20,9 +20,14 @@
 // lanes' order reversed: (s, c) pairs, six __shfl_down steps, and the lane's chain run again from its true input.
 // Device and host twin differ in exp and log and in the association of the delete chain and of bB(j).
 //
+// Both sweeps take a compile-time flag MAT: every lane also stores bM_k(j) and bI_k(j) of its own columns, rows
+// j = 0 .. L, the matrices the posterior-decoded alignment reads (dcp_mea.h, dcp_gpu_mea_pairs' second sweep).
+// MAT = false is dcp_gpu_posterior_pairs' kernel, with the registers it had before the flag.
+//
 // A column at or past core_size is never loaded: its entry, emissions and transitions are -inf here, so it adds nothing
 // to bB, and the transitions into it (DD, DM, MD, MM, IM of node k + 1 >= core_size) are -inf, so what it holds -- bE at
 // most -- reaches no real column.
+#include "dcp_mea.h"
 #include "dcp_posterior.h"
 
 #include "dcp_forward_dev.h"
@@ -142,6 +147,17 @@ __device__ __forceinline__ double *record_of(dcp_fwd_args const &a, dcp_fwd_pair
     return a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
 }
 
+// MAT: the pair's bM and bI matrices, the lane's own columns below core_size
+struct Mats
+{
+    double *m, *i;
+};
+__device__ __forceinline__ Mats mats_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
+{
+    uint64_t const at = a.cell_off[pp.pos] - a.cell_base;
+    return Mats{a.mat0 + at, a.mat1 + at};
+}
+
 // ---- profiles of at most 64 R nodes: everything in registers -------------------------------------------------------
 template <int R> struct BTrans // n..: the transitions into node k + 1
 {
@@ -157,9 +173,9 @@ template <int R> struct BState
     unsigned w;
 };
 
-template <class Real, int R, int PH>
+template <class Real, int R, int PH, bool MAT>
 __device__ __forceinline__ void backward_row(BState<R> &s, BTrans<R> const &t, XB const &x, Tabs<Real> const &g, unsigned j,
-                                             unsigned L, unsigned lane, double *rec)
+                                             unsigned L, unsigned lane, double *rec, Mats const &mt)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH}; // slot of row j + l
     unsigned code[5];
@@ -206,12 +222,14 @@ __device__ __forceinline__ void backward_row(BState<R> &s, BTrans<R> const &t, X
     {
         s.bM[PH][r] = dcp_lse4(sp.bE, t.nmd[r] + dn[r], t.nmm[r] + bPn[r], t.mi[r] + bQ[r]);
         s.bI[PH][r] = dcp_lse2(t.nim[r] + bPn[r], t.ii[r] + bQ[r]);
+        if constexpr (MAT)
+            if (k0 + r < g.M) mt.m[(uint64_t)j * g.M + k0 + r] = s.bM[PH][r], mt.i[(uint64_t)j * g.M + k0 + r] = s.bI[PH][r];
     }
     s.bX[PH] = sp.own;
     s.bB = bB, s.bPN = readlane(bX, 0);
 }
 
-template <class Real, int R> __global__ __launch_bounds__(256) void backward_kernel(dcp_fwd_args a)
+template <class Real, int R, bool MAT> __global__ __launch_bounds__(256) void backward_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -252,9 +270,11 @@ template <class Real, int R> __global__ __launch_bounds__(256) void backward_ker
         s.bB = s.bPN = ninf();
         s.w = 0u;
         double *const rec = record_of(a, pp);
+        Mats mt{nullptr, nullptr};
+        if constexpr (MAT) mt = mats_of(a, pp);
         unsigned j = L;
 #define DCP_BWD_ROW(PH)                                                                                                \
-    backward_row<Real, R, PH>(s, t, x, g, j, L, lane, rec);                                                            \
+    backward_row<Real, R, PH, MAT>(s, t, x, g, j, L, lane, rec, mt);                                                   \
     if (j == 0u) break;                                                                                                \
     --j;
         for (;;)
@@ -290,9 +310,9 @@ struct BWideArea // rows of ldk doubles: bM and bI slots, then the row's bP, bQ
     __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
 };
 
-template <class Real, int PH>
+template <class Real, int PH, bool MAT>
 __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Tabs<Real> const &g, BWideArea const &wa, unsigned j,
-                                                  unsigned L, unsigned lane, double *rec)
+                                                  unsigned L, unsigned lane, double *rec, Mats const &mt)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
     unsigned code[5];
@@ -368,6 +388,8 @@ __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Ta
             m[r] = dcp_lse4(sp.bE, load_col(g.trans + DCP_T_MD * g.ld, k + 1u, g.M) + dn[r],
                             load_col(g.trans + DCP_T_MM * g.ld, k + 1u, g.M) + bPn[r], load_col(g.trans + DCP_T_MI * g.ld, k, g.M) + bQ[r]);
             i[r] = dcp_lse2(load_col(g.trans + DCP_T_IM * g.ld, k + 1u, g.M) + bPn[r], load_col(g.trans + DCP_T_II * g.ld, k, g.M) + bQ[r]);
+            if constexpr (MAT)
+                if (k < g.M) mt.m[(uint64_t)j * g.M + k] = m[r], mt.i[(uint64_t)j * g.M + k] = i[r];
         }
         carry_p = readlane(bP[0], 0), carry_d = readlane(d[0], 0);
     }
@@ -375,7 +397,7 @@ __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Ta
     s.bB = bB, s.bPN = readlane(bX, 0);
 }
 
-template <class Real> __global__ __launch_bounds__(256) void backward_wide_kernel(dcp_fwd_args a)
+template <class Real, bool MAT> __global__ __launch_bounds__(256) void backward_wide_kernel(dcp_fwd_args a)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -411,9 +433,11 @@ template <class Real> __global__ __launch_bounds__(256) void backward_wide_kerne
         s.bB = s.bPN = ninf();
         s.w = 0u;
         double *const rec = record_of(a, pp);
+        Mats mt{nullptr, nullptr};
+        if constexpr (MAT) mt = mats_of(a, pp);
         unsigned j = L;
 #define DCP_BWD_ROW(PH)                                                                                                \
-    backward_wide_row<Real, PH>(s, x, g, wa, j, L, lane, rec);                                                         \
+    backward_wide_row<Real, PH, MAT>(s, x, g, wa, j, L, lane, rec, mt);                                                \
     if (j == 0u) break;                                                                                                \
     --j;
         for (;;)
@@ -460,15 +484,15 @@ template <class Real> __global__ __launch_bounds__(256) void posterior_combine_k
                             a.begin + t, a.end + t, a.core + t);
 }
 
-template <class Real> int launch_backward(int R, dcp_fwd_args const &a, hipStream_t st)
+template <class Real, bool MAT = false> int launch_backward(int R, dcp_fwd_args const &a, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
     {
-    case 0: hipLaunchKernelGGL((backward_wide_kernel<Real>), grid, block, 0, st, a); return 0;
-    case 1: hipLaunchKernelGGL((backward_kernel<Real, 1>), grid, block, 0, st, a); return 0;
-    case 2: hipLaunchKernelGGL((backward_kernel<Real, 2>), grid, block, 0, st, a); return 0;
-    case 4: hipLaunchKernelGGL((backward_kernel<Real, 4>), grid, block, 0, st, a); return 0;
+    case 0: hipLaunchKernelGGL((backward_wide_kernel<Real, MAT>), grid, block, 0, st, a); return 0;
+    case 1: hipLaunchKernelGGL((backward_kernel<Real, 1, MAT>), grid, block, 0, st, a); return 0;
+    case 2: hipLaunchKernelGGL((backward_kernel<Real, 2, MAT>), grid, block, 0, st, a); return 0;
+    case 4: hipLaunchKernelGGL((backward_kernel<Real, 4, MAT>), grid, block, 0, st, a); return 0;
     default: return 1;
     }
 }
@@ -482,6 +506,18 @@ extern "C" int dcp_backward_launch(int precision, int R, struct dcp_fwd_args con
     hipStream_t const st = (hipStream_t)stream;
     if (precision == 32) return launch_backward<float>(R, *a, st);
     if (precision == 64) return launch_backward<double>(R, *a, st);
+    return 1;
+}
+
+// the same sweeps, bM and bI of every row stored as well (a->mat0, a->mat1, a->cell_off, a->cell_base):
+// dcp_gpu_mea_pairs' second sweep
+extern "C" int dcp_backward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+{
+    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off || !a->mat0 || !a->mat1 || !a->cell_off) return 1;
+    if (R == 0 && !a->work) return 1;
+    hipStream_t const st = (hipStream_t)stream;
+    if (precision == 32) return launch_backward<float, true>(R, *a, st);
+    if (precision == 64) return launch_backward<double, true>(R, *a, st);
     return 1;
 }
 

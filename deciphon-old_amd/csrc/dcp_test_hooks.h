@@ -47,6 +47,10 @@ int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *, unsigned nwaves);
 // Bound, in bytes, on the device memory of the row records of each of the following dcp_gpu_posterior_pairs calls: a
 // small one makes the list run in several rounds; 0 restores the default (1 GiB).  Results must not change with it.
 int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *, unsigned long long bytes);
+// The same for dcp_gpu_mea_pairs: the bound on the device memory of a round's matrices, choices and row records; 0
+// restores the default (8 GiB).  Results must not change with it.  (Its launches take dcp_gpu_test_set_forward_waves'
+// cap too.)
+int dcp_gpu_test_set_mea_budget(dcp_gpu_ctx *, unsigned long long bytes);
 }
 #endif
 

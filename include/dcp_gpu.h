@@ -983,6 +983,59 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, ui
 float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *);
 
 /* ------------------------------------------------------------------------ */
+/* Posterior-decoded (maximum expected accuracy) alignment for a list of pairs */
+/* ------------------------------------------------------------------------ */
+/* Every path above is a Viterbi path.  The posterior-decoded path is chosen by what all paths say about each step: with
+ * the word posterior w of an emitting step (state, s, l) -- exp(Forward value the word leaves from + its emission +
+ * Backward value where it arrives - a), a the Forward alt score; csrc/dcp_mea.h has the rule -- the gain of a path is the
+ * sum of l w over its emitting steps, the expected number of bases the true path emits with the same word of the same
+ * state, 0 <= gain <= L.  The decoded path is an S .. T path of the alt model graph, over finite transitions and
+ * emissions only (its dcp_gpu_path_domains total is finite), that emits exactly L bases and has the largest gain: the
+ * scan's recursion with every transition replaced by 0 or -inf, every emission by l w or -inf, every combiner by max,
+ * ties to the first candidate in dcp_mea.h's order.  Steps are those dcp_gpu_trace_paths writes for an alt path (S, N
+ * words, B, core steps, E, J / C words, T): dcp_gpu_decode_paths and dcp_gpu_path_domains take them as they are.  It is
+ * optimal for the gain, not for likelihood: its total is at most the Viterbi score.  When a is -inf there is no such
+ * path: zero steps, gain -inf, no error.
+ *
+ * The host twins take dcp_forward_tables' tables and refuse as dcp_posterior_tables does, nothing written; they hold
+ * full matrices of both sweeps: the tests' yardstick, no hot path.  No device.
+ * dcp_mea_tables: the decoded path into steps_out [cap_steps], post_out[i] the word posterior of step i (-1.0 for a step
+ * that emits nothing), its gain and a (dcp_forward_tables' bits).  *nsteps_out is the true count; if it exceeds
+ * cap_steps the call returns DCP_ENOMEM and writes nothing else.  steps_out and post_out may be NULL with cap_steps 0. */
+int dcp_mea_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+                   double const *emis_null, double const xtrans[13], unsigned char const *seq, unsigned L,
+                   struct dcp_step *steps_out, unsigned cap_steps, unsigned *nsteps_out, double *post_out,
+                   double *gain_out, double *alt_fwd_out);
+/* The gain and the per-step word posteriors (post_out [nsteps], may be NULL) of any given alt path under the same
+ * sweeps: how good a Viterbi path, or a device path, is by this measure.  Of dcp_mea_tables' own path it returns the
+ * reported gain and posteriors bit for bit.  DCP_EINVAL, nothing written: the path is not S .. T, uses an edge that is
+ * not in the graph or a transition or emission that is -inf, does not emit exactly L bases, names a node outside
+ * 1 .. M, or is NULL. */
+int dcp_mea_path_gain(unsigned M, unsigned ldk, double const *trans8, double const *emis_match, double const *emis_insert,
+                      double const *emis_null, double const xtrans[13], unsigned char const *seq, unsigned L,
+                      struct dcp_step const *steps, unsigned nsteps, double *gain_out, double *post_out);
+/* The decoded paths of the npairs pairs (resident sequence seq_idx[i], resident profile profile_idx[i]), in list order:
+ * pair i's steps are [step_off[i], step_off[i + 1]) of steps_out / post_out [cap_steps] (post_out may be NULL);
+ * step_off [npairs + 1] is written by the call; gain_out / alt_fwd_out [npairs] (alt_fwd: dcp_gpu_forward_pairs' bits).
+ * Device work (csrc/dcp_mea.hip): the Forward and Backward kernels in a variant that also stores their core-state
+ * matrices (P, Q, bM, bI: 32 bytes a cell of L + 1 rows by M nodes), a max-plus sweep over the word posteriors formed
+ * from them, one wavefront per pair, which parks 13 bits of choices a cell (2 bytes) and 8 bytes a row, and a walk, one
+ * thread per pair.  Matrices, choices and row records live in device memory of the call's own, bounded by a budget
+ * (8 GiB): a longer list runs in rounds of consecutive pairs, a single pair that exceeds it in a round of its own.
+ * Device and host twin differ in exp and log and in the association of the two sweeps' sums, so among candidates whose
+ * gains are equal within that error they may choose differently: the device's path has, on the host's numbers, the
+ * host's optimum within the error of the two gains.  Checks, messages, special transitions, batches, precisions, stream
+ * and what is left untouched: all as dcp_gpu_forward_pairs.  DCP_ENOMEM if the paths hold more than cap_steps steps:
+ * step_off is written in full (step_off[npairs] is the need) and every other output stays untouched.  A pair listed
+ * twice is decoded twice; npairs == 0 is DCP_OK. */
+int dcp_gpu_mea_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                      uint32_t const *profile_idx, unsigned npairs, struct dcp_step *steps_out, unsigned cap_steps,
+                      uint32_t *step_off, double *post_out, double *gain_out, double *alt_fwd_out);
+/* Milliseconds, by HIP events, summed over the rounds' kernel launches of the context's last dcp_gpu_mea_pairs that
+ * ran all its rounds -- one that then returned DCP_ENOMEM for its cap_steps included; negative before. */
+float dcp_gpu_mea_kernel_ms(dcp_gpu_ctx *);
+
+/* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum

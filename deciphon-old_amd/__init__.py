@@ -1035,6 +1035,15 @@ def device_count():
     return lib.dcp_gpu_device_count()
 
 
+def _pair_list(seq_idx, profile_idx):
+    """A pair list's two index arrays as contiguous uint32, one profile index per sequence index."""
+    sq = np.ascontiguousarray(seq_idx, np.uint32)
+    pr = np.ascontiguousarray(profile_idx, np.uint32)
+    if sq.ndim != 1 or sq.shape != pr.shape:
+        raise DcpError(RC_EINVAL, "one profile index per sequence index")
+    return sq, pr
+
+
 class Scanner:
     """One device context = one reference "partition" (thread_run's unit, scan.c:239-249):
     holds a profile shard resident in HBM and scans sequence batches against it."""
@@ -1333,10 +1342,7 @@ class Scanner:
         kernels over the list (dcp_gpu_scan_pairs), on a float or a double DB: hits() then holds the listed pairs that
         pass the LRT filter, with the bits of a KERNEL_ROWSWEEP scan; lrt_threshold=-inf reports every pair whose scores
         are finite.  A pair listed twice is reported twice.  No dense scores are kept: scores() fails afterwards."""
-        sq = np.ascontiguousarray(seq_idx, np.uint32)
-        pr = np.ascontiguousarray(profile_idx, np.uint32)
-        if sq.ndim != 1 or sq.shape != pr.shape:
-            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        sq, pr = _pair_list(seq_idx, profile_idx)
         prm = ScanParams(int(multi_hits), int(hmmer3_compat), float(lrt_threshold), 0, KERNEL_AUTO)
         self._check(self._lib.dcp_gpu_set_lrt_threshold64(self._c, float(lrt_threshold)))
         self._check(self._lib.dcp_gpu_scan_pairs(self._c, C.byref(prm), sq.ctypes.data, pr.ctypes.data, len(sq)))
@@ -1348,10 +1354,7 @@ class Scanner:
         resident profile profile_idx[i]) on a float or a double DB (dcp_gpu_forward_pairs): the log of the summed
         weight of all paths, where a scan's score is the weight of the best one.  Returns synchronised; the last scan's
         results stay what they were.  A pair listed twice is scored twice."""
-        sq = np.ascontiguousarray(seq_idx, np.uint32)
-        pr = np.ascontiguousarray(profile_idx, np.uint32)
-        if sq.ndim != 1 or sq.shape != pr.shape:
-            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        sq, pr = _pair_list(seq_idx, profile_idx)
         null, alt = np.zeros(len(sq), np.float64), np.zeros(len(sq), np.float64)
         self._check(self._lib.dcp_gpu_forward_pairs(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data,
                                                     pr.ctypes.data, len(sq), null.ctypes.data, alt.ctypes.data))
@@ -1373,10 +1376,7 @@ class Scanner:
         domain begins at row j, that one ends there, and that base j - 1 is emitted by a core state -- and the alt score
         by the Forward sweep (forward_pairs' bits) and by the Backward sweep.  Returns synchronised; the last scan's
         results stay what they were."""
-        sq = np.ascontiguousarray(seq_idx, np.uint32)
-        pr = np.ascontiguousarray(profile_idx, np.uint32)
-        if sq.ndim != 1 or sq.shape != pr.shape:
-            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        sq, pr = _pair_list(seq_idx, profile_idx)
         lens = getattr(self, "_seq_lens", np.zeros(0, np.int64))
         ok = sq < len(lens)  # an index out of range is the call's to refuse, with its message
         cap = int(np.sum(lens[sq[ok]] + 1)) if len(sq) else 0
@@ -1406,10 +1406,7 @@ class Scanner:
         (-1 for a step that emits nothing), the path's gain (the sum of seqlen x posterior) and the Forward alt score
         (forward_pairs' bits).  A pair with no path at all has zero steps and gain -inf.  Returns synchronised; the
         last scan's results stay what they were."""
-        sq = np.ascontiguousarray(seq_idx, np.uint32)
-        pr = np.ascontiguousarray(profile_idx, np.uint32)
-        if sq.ndim != 1 or sq.shape != pr.shape:
-            raise DcpError(RC_EINVAL, "one profile index per sequence index")
+        sq, pr = _pair_list(seq_idx, profile_idx)
         n = len(sq)
         # the driver's own first estimate, L + M + 16 steps a pair; the call names the true count if that is short.  An
         # index out of range, a missing DB or batch are the call's to refuse, with its message

@@ -130,12 +130,35 @@ struct dcp_fwd_args
     uint64_t cell_base;       // cell_off of the round's first pair
 };
 
+// What a sweep leaves beside its scores: nothing (dcp_gpu_forward_pairs), every row's record (dcp_gpu_posterior_pairs),
+// or the records and the two matrices of every row (dcp_gpu_mea_pairs).
+enum
+{
+    DCP_FWD_STORE_NONE = 0,
+    DCP_FWD_STORE_ROWS = 1, // rows, row_off, row_base
+    DCP_FWD_STORE_MATS = 2  // and mat0, mat1, cell_off, cell_base
+};
+
+// What a launch refuses: no work, a wide sweep without its work area, or a pointer missing that `store` writes through.
+static inline int dcp_fwd_args_refused(struct dcp_fwd_args const *a, int R, int store)
+{
+    if (store < DCP_FWD_STORE_NONE || store > DCP_FWD_STORE_MATS) return 1;
+    if (!a || a->nwaves == 0 || a->npairs == 0) return 1;
+    if (R == 0 && !a->work) return 1;
+    if (store >= DCP_FWD_STORE_ROWS && (!a->rows || !a->row_off)) return 1;
+    if (store >= DCP_FWD_STORE_MATS && (!a->mat0 || !a->mat1 || !a->cell_off)) return 1;
+    return 0;
+}
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// The Forward sweep (dcp_forward.hip) and the Backward sweep (dcp_posterior.hip; there is none that stores nothing).
 // precision 32 / 64: the tables' scalar.  R = 1, 2 or 4 nodes per lane with the profile in registers (core sizes up to
-// 64 R), or R = 0: the wide sweep in chunks of DCP_FWD_CHUNK columns through the work area.  != 0: no such kernel.
-int dcp_forward_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream);
+// 64 R), or R = 0: the wide sweep in chunks of DCP_FWD_CHUNK columns through the work area.  store: DCP_FWD_STORE_*.
+// != 0: no such kernel, or dcp_fwd_args_refused.
+int dcp_forward_launch(int precision, int R, int store, struct dcp_fwd_args const *a, void *stream);
+int dcp_backward_launch(int precision, int R, int store, struct dcp_fwd_args const *a, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -64,23 +64,14 @@ template <int PH> __device__ __forceinline__ void store_record(double const (&PX
     if (lane == 0u) rec[0] = pn, rec[1] = pj, rec[2] = pc, rec[3] = B, rec[4] = E;
 }
 
-// MAT: row j of the pair's P and Q matrices, the lane's own columns below core_size
-struct Mats
-{
-    double *p, *q;
-};
-__device__ __forceinline__ Mats mats_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
-{
-    uint64_t const at = a.cell_off[pp.pos] - a.cell_base;
-    return Mats{a.mat0 + at, a.mat1 + at};
-}
+// MAT: row j of the pair's P (m0) and Q (m1) matrices, the lane's own columns below core_size
 template <int R>
 __device__ __forceinline__ void store_cells(Mats const &mt, double const (&p)[R], double const (&q)[R], unsigned j, unsigned k0, unsigned M)
 {
     uint64_t const at = (uint64_t)j * M;
 #pragma unroll
     for (int r = 0; r < R; ++r)
-        if (k0 + r < M) mt.p[at + k0 + r] = p[r], mt.q[at + k0 + r] = q[r];
+        if (k0 + r < M) mt.m0[at + k0 + r] = p[r], mt.m1[at + k0 + r] = q[r];
 }
 
 template <class Real, int R, int PH, bool ROWS, bool MAT>
@@ -150,10 +141,7 @@ template <class Real, int R, bool ROWS, bool MAT> __global__ __launch_bounds__(2
     if (gw >= nw) return; // the grid's last block may hold wavefronts past nwaves
     for (uint64_t pair = gw; pair < a.npairs; pair += nw)
     {
-        dcp_fwd_pair const pp = a.pairs[pair];
-        dcp_fwd_prof const pr = a.profs[pp.prof];
-        unsigned const L = a.seq_len[pp.q];
-        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        auto const [pp, pr, L, xt] = pair_head(a, pair);
         XF const x = special_transitions(xt, lane);
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
         unsigned const k0 = lane * R;
@@ -190,7 +178,7 @@ template <class Real, int R, bool ROWS, bool MAT> __global__ __launch_bounds__(2
         double *rec = nullptr;
         if constexpr (ROWS)
         {
-            rec = a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
+            rec = record_of(a, pp);
             store_record<0>(s.PX, B0, ninf(), rec, lane); // row 0: PN = SN, B = SB, no J, C, E yet
         }
         Mats mt{nullptr, nullptr};
@@ -222,23 +210,12 @@ template <class Real, int R, bool ROWS, bool MAT> __global__ __launch_bounds__(2
 }
 
 // ---- wider profiles: row-major over chunks of 256 columns, the rings in the wavefront's work area ------------------
-constexpr int WR = 4; // nodes per lane of a chunk
-
+// (WideArea: ring0 holds the slots of P, ring1 those of Q; rows 0 .. 2 the row's M, I, D)
 struct WideState
 {
     double PX[5];
     double E, Cc, Rr;
     unsigned w;
-};
-
-struct WideArea // rows of ldk doubles: P and Q slots, then the row's M, I, D
-{
-    double *base;
-    uint64_t ldk;
-    unsigned nchunks;
-    __device__ __forceinline__ double *P(int slot) const { return base + (uint64_t)slot * ldk; }
-    __device__ __forceinline__ double *Q(int slot) const { return base + (uint64_t)(5 + slot) * ldk; }
-    __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
 };
 
 template <class Real, int PH, bool ROWS, bool MAT>
@@ -270,7 +247,7 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
         for (int l = 0; l < 5; ++l)
         {
             Real const *em = g.tab + (uint64_t)code[l] * g.ld;
-            double const *p = wa.P(sl[l]) + k0, *q = wa.Q(sl[l]) + k0;
+            double const *p = wa.ring0(sl[l]) + k0, *q = wa.ring1(sl[l]) + k0;
 #pragma unroll
             for (int r = 0; r < WR; ++r)
             {
@@ -317,7 +294,7 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
 #pragma unroll
         for (int r = 1; r < WR; ++r)
             pm[r] = m[r - 1], pi[r] = ins[r - 1], pd[r] = d[r - 1];
-        double *const p = wa.P(PH) + k0, *const q = wa.Q(PH) + k0;
+        double *const p = wa.ring0(PH) + k0, *const q = wa.ring1(PH) + k0;
 #pragma unroll
         for (int r = 0; r < WR; ++r)
         {
@@ -326,7 +303,7 @@ __device__ __forceinline__ void forward_wide_row(WideState &s, XF const &x, Tabs
                             pi[r] + load_col(g.trans + DCP_T_IM * g.ld, k, g.M), pd[r] + load_col(g.trans + DCP_T_DM * g.ld, k, g.M));
             q[r] = dcp_lse2(m[r] + load_col(g.trans + DCP_T_MI * g.ld, k, g.M), ins[r] + load_col(g.trans + DCP_T_II * g.ld, k, g.M));
             if constexpr (MAT)
-                if (k < g.M) mt.p[(uint64_t)j * g.M + k] = p[r], mt.q[(uint64_t)j * g.M + k] = q[r];
+                if (k < g.M) mt.m0[(uint64_t)j * g.M + k] = p[r], mt.m1[(uint64_t)j * g.M + k] = q[r];
         }
         bm = readlane(m[WR - 1], 63), bi = readlane(ins[WR - 1], 63), bd = readlane(d[WR - 1], 63);
     }
@@ -343,16 +320,10 @@ template <class Real, bool ROWS, bool MAT> __global__ __launch_bounds__(256) voi
     if (gw >= nw) return; // wavefronts past nwaves have no work area
     for (uint64_t pair = gw; pair < a.npairs; pair += nw)
     {
-        dcp_fwd_pair const pp = a.pairs[pair];
-        dcp_fwd_prof const pr = a.profs[pp.prof];
-        unsigned const L = a.seq_len[pp.q];
-        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        auto const [pp, pr, L, xt] = pair_head(a, pair);
         XF const x = special_transitions(xt, lane);
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
-        WideArea wa;
-        wa.nchunks = (pr.core_size + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
-        wa.ldk = (uint64_t)wa.nchunks * DCP_FWD_CHUNK; // <= work_stride / DCP_FWD_WORK_ROWS: the host sized it by the widest
-        wa.base = a.work + gw * a.work_stride;
+        WideArea const wa = wide_area(a.work, a.work_stride, gw, pr.core_size);
         Mats mt{nullptr, nullptr};
         if constexpr (MAT) mt = mats_of(a, pp);
         // row 0, anew for every pair (the pair before may have been of another width): the rings' own columns
@@ -363,13 +334,13 @@ template <class Real, bool ROWS, bool MAT> __global__ __launch_bounds__(256) voi
 #pragma unroll
             for (int r = 0; r < WR; ++r)
             {
-                wa.P(0)[k0 + r] = B0 + load_col(g.trans + DCP_T_ENTRY * g.ld, k0 + r, g.M);
-                wa.Q(0)[k0 + r] = ninf();
+                wa.ring0(0)[k0 + r] = B0 + load_col(g.trans + DCP_T_ENTRY * g.ld, k0 + r, g.M);
+                wa.ring1(0)[k0 + r] = ninf();
                 if constexpr (MAT)
-                    if (k0 + r < g.M) mt.p[k0 + r] = wa.P(0)[k0 + r], mt.q[k0 + r] = ninf();
+                    if (k0 + r < g.M) mt.m0[k0 + r] = wa.ring0(0)[k0 + r], mt.m1[k0 + r] = ninf();
 #pragma unroll
                 for (int h = 1; h < 5; ++h)
-                    wa.P(h)[k0 + r] = wa.Q(h)[k0 + r] = ninf();
+                    wa.ring0(h)[k0 + r] = wa.ring1(h)[k0 + r] = ninf();
             }
         }
         WideState s;
@@ -382,7 +353,7 @@ template <class Real, bool ROWS, bool MAT> __global__ __launch_bounds__(256) voi
         double *rec = nullptr;
         if constexpr (ROWS)
         {
-            rec = a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
+            rec = record_of(a, pp);
             store_record<0>(s.PX, B0, ninf(), rec, lane);
         }
         unsigned j = 1u;
@@ -407,7 +378,7 @@ template <class Real, bool ROWS, bool MAT> __global__ __launch_bounds__(256) voi
     }
 }
 
-template <class Real, bool ROWS, bool MAT = false> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
+template <class Real, bool ROWS, bool MAT> int launch(int R, dcp_fwd_args const &a, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
@@ -420,37 +391,21 @@ template <class Real, bool ROWS, bool MAT = false> int launch(int R, dcp_fwd_arg
     }
 }
 
+// (float first, then double, of each variant in turn: the order in which the unit's kernels are emitted)
+template <bool ROWS, bool MAT> int launch(int precision, int R, dcp_fwd_args const &a, hipStream_t st)
+{
+    if (precision == 32) return launch<float, ROWS, MAT>(R, a, st);
+    if (precision == 64) return launch<double, ROWS, MAT>(R, a, st);
+    return 1;
+}
+
 } // namespace
 
-extern "C" int dcp_forward_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+extern "C" int dcp_forward_launch(int precision, int R, int store, struct dcp_fwd_args const *a, void *stream)
 {
-    if (!a || a->nwaves == 0 || a->npairs == 0) return 1;
-    if (R == 0 && !a->work) return 1;
+    if (dcp_fwd_args_refused(a, R, store)) return 1;
     hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch<float, false>(R, *a, st);
-    if (precision == 64) return launch<double, false>(R, *a, st);
-    return 1;
-}
-
-// the same sweeps, every row's record stored as well (a->rows, a->row_off, a->row_base): dcp_gpu_posterior_pairs' first half
-extern "C" int dcp_forward_rows_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
-{
-    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off) return 1;
-    if (R == 0 && !a->work) return 1;
-    hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch<float, true>(R, *a, st);
-    if (precision == 64) return launch<double, true>(R, *a, st);
-    return 1;
-}
-
-// the same again, P and Q of every row stored as well (a->mat0, a->mat1, a->cell_off, a->cell_base): dcp_gpu_mea_pairs'
-// first sweep
-extern "C" int dcp_forward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
-{
-    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off || !a->mat0 || !a->mat1 || !a->cell_off) return 1;
-    if (R == 0 && !a->work) return 1;
-    hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch<float, true, true>(R, *a, st);
-    if (precision == 64) return launch<double, true, true>(R, *a, st);
-    return 1;
+    if (store == DCP_FWD_STORE_NONE) return launch<false, false>(precision, R, *a, st);
+    if (store == DCP_FWD_STORE_ROWS) return launch<true, false>(precision, R, *a, st);
+    return launch<true, true>(precision, R, *a, st);
 }

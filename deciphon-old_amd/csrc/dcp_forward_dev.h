@@ -1,11 +1,14 @@
-// dcp_forward_dev.h -- device helpers the Forward kernels (dcp_forward.hip) and the Backward kernels
-// (dcp_posterior.hip) share: lane moves of doubles, the wave-wide maximum and sum, the tables of a pair, the word codes,
-// the Forward delete chain and E(j), the special states' per-lane layout.  Local to each unit.
+// dcp_forward_dev.h -- device helpers the Forward kernels (dcp_forward.hip), the Backward kernels (dcp_posterior.hip) and
+// the max-plus sweep (dcp_mea.hip) share: lane moves of doubles, the wave-wide maximum and sum, the head of the loop
+// over a launch's pairs (the pair, its profile, length, special transitions and tables), where a pair's row records and
+// matrices lie, the wide sweeps' work area, the word codes, the Forward delete chain and E(j), the special states'
+// per-lane layout.  Local to each unit.
 #ifndef DCP_FORWARD_DEV_H
 #define DCP_FORWARD_DEV_H
 
 #include "dcp_forward.h"
 #include "dcp_host.h"
+#include "dcp_posterior.h"
 
 #include <hip/hip_runtime.h>
 
@@ -22,6 +25,12 @@ __device__ __forceinline__ double shr1(double v, double first) // value of lane 
     int const lo = __builtin_amdgcn_update_dpp((int)(unsigned)fb, (int)(unsigned)vb, 0x138 /*wave_shr:1*/, 0xf, 0xf, false);
     int const hi = __builtin_amdgcn_update_dpp((int)(unsigned)(fb >> 32), (int)(unsigned)(vb >> 32), 0x138, 0xf, 0xf, false);
     return __builtin_bit_cast(double, ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ double shl1(double v, double last, unsigned lane) // value of lane + 1; lane 63 receives `last`
+{
+    double const n = __shfl_down(v, 1, 64);
+    return lane == 63u ? last : n;
 }
 
 __device__ __forceinline__ double readlane(double v, int lane)
@@ -151,6 +160,62 @@ template <class Real> __device__ __forceinline__ Tabs<Real> tables_of(dcp_fwd_ar
     g.M = pr.core_size;
     g.words = a.seq_words + a.seq_woff[q];
     return g;
+}
+
+// the head of the loop over a launch's pairs.  (The pair's tables, tables_of, follow the sweep's own special transitions
+// at each use: formed in here, their loads move ahead of those and the kernels' schedules change.)
+struct PairHead
+{
+    dcp_fwd_pair pp;
+    dcp_fwd_prof pr;
+    unsigned L;
+    double const *xt; // the sequence's special transitions
+};
+__device__ __forceinline__ PairHead pair_head(dcp_fwd_args const &a, uint64_t pair)
+{
+    dcp_fwd_pair const pp = a.pairs[pair];
+    dcp_fwd_prof const pr = a.profs[pp.prof];
+    return PairHead{pp, pr, a.seq_len[pp.q], a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE};
+}
+
+// the pair's row records (dcp_posterior.h), row 0 first
+__device__ __forceinline__ double *record_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
+{
+    return a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
+}
+
+// the pair's two matrices (dcp_mea.h), rows j = 0 .. L of core_size columns: a lane stores its own columns below core_size
+struct Mats
+{
+    double *m0, *m1;
+};
+__device__ __forceinline__ Mats mats_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
+{
+    uint64_t const at = a.cell_off[pp.pos] - a.cell_base;
+    return Mats{a.mat0 + at, a.mat1 + at};
+}
+
+// ---- the wide sweeps: chunks of DCP_FWD_CHUNK columns through the wavefront's work area ------------------------------
+constexpr int WR = 4; // nodes per lane of a chunk
+
+// wavefront gw's work area for a profile of M nodes: rows of ldk doubles, two rings of five slots, then the row's own
+// values.  ldk x the sweep's rows <= work_stride: the host sized the stride by the widest listed profile.
+struct WideArea
+{
+    double *base;
+    uint64_t ldk;
+    unsigned nchunks;
+    __device__ __forceinline__ double *ring0(unsigned slot) const { return base + (uint64_t)slot * ldk; }
+    __device__ __forceinline__ double *ring1(unsigned slot) const { return base + (uint64_t)(5u + slot) * ldk; }
+    __device__ __forceinline__ double *row(unsigned which) const { return base + (uint64_t)(10u + which) * ldk; }
+};
+__device__ __forceinline__ WideArea wide_area(double *work, uint64_t work_stride, uint64_t gw, unsigned M)
+{
+    WideArea wa;
+    wa.nchunks = (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
+    wa.ldk = (uint64_t)wa.nchunks * DCP_FWD_CHUNK;
+    wa.base = work + gw * work_stride;
+    return wa;
 }
 
 } // namespace

@@ -403,58 +403,43 @@ struct dcp_gpu_ctx
     DevBuf<uint32_t> d_tail_keff;
     hipEvent_t ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
     bool tail_timed = false;
-    // Forward scores of a pair list (dcp_gpu_forward_pairs, dcp_forward.hip): the resident DB's profiles as that kernel
-    // addresses them, by caller index (built on first use, void with the DB), and the call's own buffers -- the bucketed
-    // list, the special transitions, the two score arrays, the wide sweep's work areas -- kept between calls and grown
-    // when a call needs more; nothing of a scan's is written.  ev_fwd: around the launches of the last call that
-    // launched any.  waves_cap: the hooks build's cap on a launch's wavefronts (0: none).
-    struct ForwardState
+    // The pair-list sweeps (dcp_gpu_forward_pairs, dcp_gpu_posterior_pairs, dcp_gpu_mea_pairs; dcp_forward.hip,
+    // dcp_posterior.hip, dcp_mea.hip).  The three calls are synchronous and share one workspace, kept between calls and
+    // grown when a call needs more; nothing of a scan's is written, and a call reads nothing an earlier call left but
+    // the profile table:
+    //  d_profs   the resident DB's profiles as the kernels address them, by caller index (built on first use, void
+    //            with the DB)
+    //  d_xt      the call's special transitions (xt: on the host, until the call's first synchronise)
+    //  d_pairs   a round's pairs bucketed by class, then the same in list order
+    //  d_off     the list's row offsets, then (mea) its cell offsets
+    //  d_score   [the list] null, alt by Forward, alt by Backward, gain: as far as the call goes
+    //  d_rec     a round's row records of the two sweeps;  d_work: the wide sweeps' work areas
+    //  d_rows    posterior's three output rows of a round
+    //  mea's own: a round's matrices (P, Q, bM, bI), cell and row choices, S's choices, where each pair's steps go, how
+    //            many fit and how many there are, the steps and their posteriors, the max-plus sweep's work areas
+    // ev: around the launches of the round in flight.  waves_cap, post_budget, mea_budget: the hooks build's cap on a
+    // launch's wavefronts (0: none) and bounds on a round's bytes (0: 1 GiB of row records; 8 GiB of matrices, choices and
+    // records).  fwd_ms, post_ms, mea_ms: the kernel time of the last call of each kind, summed over its rounds.
+    struct PairSweeps
     {
         bool profs_ready = false;
         DevBuf<dcp_fwd_prof> d_profs;
         DevBuf<dcp_fwd_pair> d_pairs;
-        DevBuf<double> d_xt, d_out, d_work;
+        DevBuf<uint64_t> d_off, d_step_idx;
+        DevBuf<double> d_xt, d_score, d_rec, d_work, d_rows, d_mat, d_mea_work, d_post;
+        std::vector<double> xt;
+        DevBuf<uint16_t> d_cell;
+        DevBuf<uint32_t> d_rowc, d_start, d_steps;
         hipEvent_t ev[2] = {nullptr, nullptr};
-        bool timed = false;
         unsigned waves_cap = 0;
+        uint64_t post_budget = 0, mea_budget = 0;
+        float fwd_ms = -1.0f, post_ms = -1.0f, mea_ms = -1.0f;
         void release() // a new DB
         {
             profs_ready = false;
             d_profs.release();
         }
-    } fwd;
-    // Backward sweep and posterior rows of a pair list (dcp_gpu_posterior_pairs, dcp_posterior.hip): the call's own
-    // buffers, kept between calls and grown when a call needs more -- the list's row offsets, the special transitions,
-    // the scores (null, alt by Forward, alt by Backward), a round's bucketed and listed pairs, its two sweeps' row records
-    // and its three output rows.  The profiles, the wide sweep's work areas and the wavefront cap are fwd's.  budget: the
-    // hooks build's bound on the row records' bytes (0: 1 GiB).  ms: the last call's kernel time, summed over its rounds.
-    struct PosteriorState
-    {
-        DevBuf<uint64_t> d_row_off;
-        DevBuf<dcp_fwd_pair> d_pairs;
-        DevBuf<double> d_xt, d_score, d_rec, d_rows;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        uint64_t budget = 0;
-        float ms = -1.0f;
-    } post;
-    // The posterior-decoded alignment of a pair list (dcp_gpu_mea_pairs, dcp_mea.hip): the call's own buffers, kept
-    // between calls and grown when a call needs more -- the list's row and cell offsets, the special transitions, the
-    // scores (null, alt by Forward, alt by Backward, gain), a round's bucketed and listed pairs, its two sweeps' row records
-    // and matrices (P, Q, bM, bI), its cell and row choices, S's choices, its steps and their posteriors with where each
-    // pair's go, how many fit and how many there are, and the max-plus sweep's work areas.  The profiles, the two sweeps'
-    // work areas and the wavefront cap are fwd's.  budget: the hooks build's bound on a round's matrices, choices and
-    // records (0: 8 GiB).  ms: the last call's kernel time, summed over its rounds.
-    struct MeaState
-    {
-        DevBuf<uint64_t> d_off, d_step_idx;
-        DevBuf<dcp_fwd_pair> d_pairs;
-        DevBuf<double> d_xt, d_score, d_rec, d_mat, d_work, d_post;
-        DevBuf<uint16_t> d_cell;
-        DevBuf<uint32_t> d_rowc, d_start, d_steps;
-        hipEvent_t ev[2] = {nullptr, nullptr};
-        uint64_t budget = 0;
-        float ms = -1.0f;
-    } mea;
+    } sweeps;
 
     int fail(int rc, char const *fmt, ...)
     {
@@ -509,6 +494,16 @@ template <class ClassOf> std::vector<unsigned> sort_into_classes(unsigned n, int
     for (unsigned i = 0; i < n; ++i)
         order[at[class_of(i)]++] = i;
     return order;
+}
+
+// A list that runs in rounds of consecutive pairs: the end of the round that begins at pair i0, the furthest i1 with
+// bytes_of(i0, i1) within the budget.  A single pair that exceeds it gets a round of its own.
+template <class BytesOf> unsigned round_end(unsigned i0, unsigned npairs, uint64_t budget, BytesOf bytes_of)
+{
+    unsigned i1 = i0 + 1u;
+    while (i1 < npairs && bytes_of(i0, i1 + 1u) <= budget)
+        ++i1;
+    return i1;
 }
 
 template <class Real> int fetch_table_rows(dcp_gpu_ctx *c, Real const *src, unsigned ldk, unsigned core_size, Real *out)
@@ -791,11 +786,7 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_tail)
         if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->fwd.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->post.ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->mea.ev)
+    for (hipEvent_t e : c->sweeps.ev)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -910,7 +901,7 @@ int dcp_gpu_db_upload(dcp_gpu_ctx *c, dcp_profile *const *profiles,
     HIP_TRY(c, hipSetDevice(c->device));
     void_last_scan(c);
     c->dec.release();
-    c->fwd.release();
+    c->sweeps.release();
     if (c->precision == 64) // one resident DB per context: the double one goes
     {
         c->f64.release();
@@ -1438,7 +1429,7 @@ int dcp_gpu_db_upload64(dcp_gpu_ctx *c, dcp_profile *const *profiles, unsigned n
     // one resident DB per context: whatever was there goes, also if this upload fails half way
     void_last_scan(c);
     c->dec.release();
-    c->fwd.release();
+    c->sweeps.release();
     c->precision = 0;
     c->nprof = 0;
     c->f64.release();
@@ -3402,17 +3393,18 @@ int dcp_gpu_scan_pairs(dcp_gpu_ctx *c, struct dcp_scan_params const *prm, uint32
     return DCP_OK;
 }
 
-// ---- Forward scores of a pair list (dcp_forward.hip) ---------------------------------------------------------------
-// The kernel's classes: nodes per lane with the whole profile in registers (core sizes up to 64 R), or 0: the wide
+// ---- The pair-list sweeps: what the three calls share (dcp_forward.hip, dcp_posterior.hip) ---------------------------
+// The kernels' classes: nodes per lane with the whole profile in registers (core sizes up to 64 R), or 0: the wide
 // sweep through a work area per wavefront.
 static constexpr int kFwdR[4] = {1, 2, 4, 0};
 static int fwd_class(unsigned M) { return M <= 64u ? 0 : M <= 128u ? 1 : M <= (unsigned)DCP_FWD_CHUNK ? 2 : 3; }
+static unsigned chunks_of(unsigned M) { return (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK; }
 
 // The resident DB's profiles as the Forward kernel addresses them, by caller index: base, row stride and core size.  A
 // float DB's small profiles share their rows (dcp_mp_group): a member's meta is already a column view of them.
 static int forward_profiles(dcp_gpu_ctx *c)
 {
-    auto &W = c->fwd;
+    auto &W = c->sweeps;
     if (W.profs_ready) return DCP_OK;
     std::vector<dcp_fwd_prof> profs(c->nprof);
     if (c->precision == 64)
@@ -3428,7 +3420,7 @@ static int forward_profiles(dcp_gpu_ctx *c)
     return DCP_OK;
 }
 
-// What dcp_gpu_forward_pairs and dcp_gpu_posterior_pairs refuse alike, on the host, before anything runs.
+// What the three pair-list calls refuse alike, on the host, before anything runs.
 static int forward_check_list(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npairs, bool outputs)
 {
     if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
@@ -3472,7 +3464,7 @@ static int forward_special_transitions(dcp_gpu_ctx *c, int multi_hits, int hmmer
 static dcp_fwd_args forward_args(dcp_gpu_ctx const *c, double const *xt)
 {
     dcp_fwd_args a{};
-    a.profs = c->fwd.d_profs.p;
+    a.profs = c->sweeps.d_profs.p;
     if (c->precision == 64) a.tab = c->f64.d_tab.p, a.trans = c->f64.d_trans.p, a.ei = a.en = c->f64.d_xe.p;
     else a.tab = c->d_emis_match.p, a.trans = c->d_trans8.p, a.ei = c->d_emis_insert.p, a.en = c->d_emis_null.p;
     a.seq_words = c->d_seq_words.p, a.seq_woff = c->d_seq_woff.p, a.seq_len = c->d_seq_len.p;
@@ -3480,49 +3472,133 @@ static dcp_fwd_args forward_args(dcp_gpu_ctx const *c, double const *xt)
     return a;
 }
 
+// Everything between a call's refusals and its first launch: the DB's layout and profile table, the special transitions
+// and the list's offsets (none: Forward) uploaded anew, room for nscores scores a pair, the events.  a: forward_args,
+// with work, row_off and out_null in place.  Returns synchronised if there are offsets, which are the caller's to drop;
+// Forward's transitions go up under the synchronise of its one round's lists (if upload_round fails before that, the
+// copy from W.xt is still queued: the vector is the workspace's and stays).
+static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *profile_idx, unsigned npairs,
+                        unsigned nscores, std::vector<uint64_t> const &off, dcp_fwd_args *a)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->sweeps;
+    if (c->precision != 64)
+        if (int rc = ensure_rowsweep_layout(c)) return rc;
+    if (int rc = forward_profiles(c)) return rc;
+    std::vector<double> &xt = W.xt;
+    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
+    // The wide sweep's work areas, by far the largest of the buffers, come first, as much as any round of this list
+    // can ask for (forward_bucket: a round's widest profile and its wavefronts are at most the list's).  Reserved
+    // behind the small buffers on a context's first call, a float DB's Forward sweeps measured 1 % slower.
+    unsigned wide = 0, wide_chunks = 0;
+    for (unsigned i = 0; i < npairs; ++i)
+    {
+        unsigned const M = c->core_sizes[profile_idx[i]];
+        if (fwd_class(M) == 3) ++wide, wide_chunks = std::max(wide_chunks, chunks_of(M));
+    }
+    uint64_t wide_waves = std::min<uint64_t>(wide, 4ull * c->num_cus);
+    if (W.waves_cap) wide_waves = std::min<uint64_t>(wide_waves, W.waves_cap);
+    HIP_TRY(c, W.d_work.reserve((uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK * wide_waves));
+    HIP_TRY(c, W.d_off.reserve(off.size()));
+    HIP_TRY(c, W.d_xt.reserve(xt.size()));
+    HIP_TRY(c, W.d_score.reserve((size_t)nscores * npairs));
+    for (hipEvent_t &e : W.ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    if (!off.empty())
+    {
+        HIP_TRY(c, hipMemcpyAsync(W.d_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream)); // (and whatever was outstanding is done)
+    }
+    *a = forward_args(c, W.d_xt.p);
+    a->work = W.d_work.p;
+    if (!off.empty()) a->row_off = W.d_off.p;
+    a->out_null = W.d_score.p;
+    return DCP_OK;
+}
+
 // The list by class, each class in list order, the dearest pairs of a class first; a pair remembers its position pos0 + i
-// in the caller's list.  waves: the wavefronts of each class's launch.
+// in the caller's list.  waves: the wavefronts of each class's launch.  list: the same pairs in list order, for the
+// kernels that follow the sweeps (upload_round fills it where there are any).
 struct ForwardBuckets
 {
     unsigned first[5] = {0, 0, 0, 0, 0}, count[4] = {0, 0, 0, 0}, waves[4] = {0, 0, 0, 0};
     unsigned wide_chunks = 0;
-    std::vector<dcp_fwd_pair> pairs;
+    std::vector<dcp_fwd_pair> pairs, list;
 };
 
 static void forward_bucket(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned npairs, unsigned pos0,
                            ForwardBuckets &b)
 {
-    unsigned(&first)[5] = b.first, (&count)[4] = b.count, (&waves)[4] = b.waves;
-    unsigned &wide_chunks = b.wide_chunks;
-    std::vector<dcp_fwd_pair> &pairs = b.pairs;
     std::vector<unsigned> const order =
-        sort_into_classes(npairs, 4, first, [&](unsigned i) { return fwd_class(c->core_sizes[profile_idx[i]]); });
-    pairs.resize(npairs);
+        sort_into_classes(npairs, 4, b.first, [&](unsigned i) { return fwd_class(c->core_sizes[profile_idx[i]]); });
+    b.pairs.resize(npairs);
+    for (int k = 0; k < 4; ++k)
+        b.count[k] = b.first[k + 1] - b.first[k];
+    for (unsigned j = 0; j < npairs; ++j)
     {
-        for (int k = 0; k < 4; ++k)
-            count[k] = first[k + 1] - first[k];
-        for (unsigned j = 0; j < npairs; ++j)
-        {
-            unsigned const i = order[j], M = c->core_sizes[profile_idx[i]];
-            pairs[j] = dcp_fwd_pair{seq_idx[i], profile_idx[i], pos0 + i};
-            if (j >= first[3]) wide_chunks = std::max(wide_chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
-        }
-        // a pair costs its rows times its chunks: the dearest first, so that the wavefronts striding over a class's
-        // list end together (pairs of one cost keep their list order)
-        auto const cost = [&](dcp_fwd_pair const &p) {
-            return (uint64_t)c->seq_len[p.q] * ((c->core_sizes[p.prof] + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
-        };
-        for (int k = 0; k < 4; ++k)
-            std::stable_sort(pairs.begin() + first[k], pairs.begin() + first[k + 1],
-                             [&](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return cost(x) > cost(y); });
+        unsigned const i = order[j];
+        b.pairs[j] = dcp_fwd_pair{seq_idx[i], profile_idx[i], pos0 + i};
+        if (j >= b.first[3]) b.wide_chunks = std::max(b.wide_chunks, chunks_of(c->core_sizes[profile_idx[i]]));
     }
+    // a pair costs its rows times its chunks: the dearest first, so that the wavefronts striding over a class's
+    // list end together (pairs of one cost keep their list order)
+    auto const cost = [&](dcp_fwd_pair const &p) { return (uint64_t)c->seq_len[p.q] * chunks_of(c->core_sizes[p.prof]); };
+    for (int k = 0; k < 4; ++k)
+        std::stable_sort(b.pairs.begin() + b.first[k], b.pairs.begin() + b.first[k + 1],
+                         [&](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return cost(x) > cost(y); });
     // wavefronts per launch: a grid's worth (the register-resident classes hold one or two wavefronts per SIMD and
     // leave some waiting, the wide sweep one), striding over the class's list
     for (int k = 0; k < 4; ++k)
     {
-        waves[k] = (unsigned)std::min<uint64_t>(count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
-        if (c->fwd.waves_cap) waves[k] = std::min(waves[k], c->fwd.waves_cap);
+        b.waves[k] = (unsigned)std::min<uint64_t>(b.count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
+        if (c->sweeps.waves_cap) b.waves[k] = std::min(b.waves[k], c->sweeps.waves_cap);
     }
+}
+
+// Pairs [i0, i0 + n) of the list as a round: bucketed by class at d_pairs and, if listed, in list order behind that, and
+// the stride of the wide sweep's work areas for them (a.work_stride).  The copies are queued from b: the caller
+// synchronises, with whatever it queues of its own, before b leaves scope.
+static int upload_round(dcp_gpu_ctx *c, uint32_t const *seq_idx, uint32_t const *profile_idx, unsigned i0, unsigned n,
+                        bool listed, ForwardBuckets &b, dcp_fwd_args &a)
+{
+    auto &W = c->sweeps;
+    forward_bucket(c, seq_idx + i0, profile_idx + i0, n, i0, b);
+    b.list.resize(listed ? n : 0u);
+    for (unsigned i = 0; i < b.list.size(); ++i)
+        b.list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
+    a.work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
+    HIP_TRY(c, W.d_pairs.reserve((size_t)n + b.list.size()));
+    HIP_TRY(c, hipMemcpyAsync(W.d_pairs.p, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+    if (listed)
+        HIP_TRY(c, hipMemcpyAsync(W.d_pairs.p + n, b.list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+    return DCP_OK;
+}
+
+// The round's sweeps over its classes: Forward (alt into the list's second score array), then, of two, Backward (into
+// the third).  store: what a sweep leaves beside the scores (dcp_forward.h) -- sweep s's records at d_rec + s x nrows
+// records, its two matrices at d_mat + 2 s x ncells.
+static int run_sweeps(dcp_gpu_ctx *c, dcp_fwd_args &a, ForwardBuckets const &b, int nsweeps, int store, unsigned npairs,
+                      uint64_t nrows, uint64_t ncells)
+{
+    auto &W = c->sweeps;
+    for (int sweep = 0; sweep < nsweeps; ++sweep)
+    {
+        if (store >= DCP_FWD_STORE_ROWS) a.rows = W.d_rec.p + (sweep ? (size_t)DCP_POST_REC * nrows : 0u);
+        if (store >= DCP_FWD_STORE_MATS) a.mat0 = W.d_mat.p + (sweep ? 2u * ncells : 0u), a.mat1 = a.mat0 + ncells;
+        a.out_alt = a.out_null + (size_t)(1 + sweep) * npairs;
+        for (int k = 0; k < 4; ++k)
+        {
+            if (b.count[k] == 0) continue;
+            a.pairs = W.d_pairs.p + b.first[k];
+            a.npairs = b.count[k];
+            a.nwaves = b.waves[k];
+            if ((sweep ? dcp_backward_launch : dcp_forward_launch)(c->precision, kFwdR[k], store, &a, c->stream))
+                return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    return DCP_OK;
 }
 
 int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
@@ -3531,62 +3607,28 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
     if (!c) return DCP_EINVAL;
     if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, null_out && alt_out)) return rc;
     if (npairs == 0) return DCP_OK;
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto &W = c->fwd;
-    bool const f64 = c->precision == 64;
-    if (!f64)
-        if (int rc = ensure_rowsweep_layout(c)) return rc;
-    if (int rc = forward_profiles(c)) return rc;
-    std::vector<double> xt;
-    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
+    auto &W = c->sweeps;
+    dcp_fwd_args a{};
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 2u, {}, &a)) return rc;
     ForwardBuckets b;
-    forward_bucket(c, seq_idx, profile_idx, npairs, 0u, b);
-    unsigned const(&first)[5] = b.first, (&count)[4] = b.count, (&waves)[4] = b.waves;
-    unsigned const wide_chunks = b.wide_chunks;
-    std::vector<dcp_fwd_pair> const &pairs = b.pairs;
-    uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK;
-    HIP_TRY(c, W.d_work.reserve(work_stride * waves[3]));
-    HIP_TRY(c, W.d_pairs.reserve(npairs));
-    HIP_TRY(c, W.d_xt.reserve(xt.size()));
-    HIP_TRY(c, W.d_out.reserve(2u * (size_t)npairs));
-    for (hipEvent_t &e : W.ev)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipMemcpyAsync(W.d_pairs.p, pairs.data(), (size_t)npairs * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below (and whatever was outstanding is done)
-
-    dcp_fwd_args a = forward_args(c, W.d_xt.p);
-    a.work = W.d_work.p, a.work_stride = work_stride;
-    a.out_null = W.d_out.p, a.out_alt = W.d_out.p + npairs;
+    if (int rc = upload_round(c, seq_idx, profile_idx, 0u, npairs, false, b, a)) return rc;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the transitions and the list are up (and whatever was outstanding is done)
     HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
-    for (int k = 0; k < 4; ++k)
-    {
-        if (count[k] == 0) continue;
-        a.pairs = W.d_pairs.p + first[k];
-        a.npairs = count[k];
-        a.nwaves = waves[k];
-        if (dcp_forward_launch(c->precision, kFwdR[k], &a, c->stream))
-            return c->fail(DCP_EFAIL, "no Forward kernel for %d nodes per lane", kFwdR[k]);
-        HIP_TRY(c, hipGetLastError());
-    }
+    if (int rc = run_sweeps(c, a, b, 1, DCP_FWD_STORE_NONE, npairs, 0u, 0u)) return rc;
     HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
     // into a buffer of the call's own first: the caller's arrays stay untouched if the copy fails
     std::vector<double> out(2u * (size_t)npairs);
-    HIP_TRY(c, hipMemcpyAsync(out.data(), W.d_out.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out.data(), W.d_score.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    W.timed = true;
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    W.fwd_ms = ms;
     std::memcpy(null_out, out.data(), (size_t)npairs * sizeof(double));
     std::memcpy(alt_out, out.data() + npairs, (size_t)npairs * sizeof(double));
     return DCP_OK;
 }
 
-float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c)
-{
-    float ms = -1.0f;
-    if (!c || !c->fwd.timed) return -1.0f;
-    if (hipEventElapsedTime(&ms, c->fwd.ev[0], c->fwd.ev[1]) != hipSuccess) return -1.0f;
-    return ms;
-}
+float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.fwd_ms : -1.0f; }
 
 // ---- Backward sweep and posterior rows of a pair list (dcp_posterior.hip) -------------------------------------------
 // The list runs in rounds of consecutive pairs whose row records -- 2 x DCP_POST_REC doubles a row -- fit the budget (a
@@ -3611,83 +3653,41 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
         row_off[0] = 0u;
         return DCP_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto &W = c->post;
-    bool const f64 = c->precision == 64;
-    if (!f64)
-        if (int rc = ensure_rowsweep_layout(c)) return rc;
-    if (int rc = forward_profiles(c)) return rc;
-    std::vector<double> xt;
-    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
-
-    uint64_t const budget = W.budget ? W.budget : (uint64_t)1u << 30;
-    uint64_t const rows_cap = std::max<uint64_t>(1u, budget / (2u * DCP_POST_REC * sizeof(double)));
-    uint64_t round_rows = 0; // the largest round's
+    auto &W = c->sweeps;
+    dcp_fwd_args a{};
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 3u, off, &a)) return rc;
+    // a round's row records fit the budget; room for the largest round's before the first one runs
+    uint64_t const budget = W.post_budget ? W.post_budget : (uint64_t)1u << 30;
+    auto const bytes_of = [&](unsigned i0, unsigned i1) { return (off[i1] - off[i0]) * (2u * DCP_POST_REC * sizeof(double)); };
+    uint64_t round_rows = 0;
     for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
     {
-        for (i1 = i0 + 1u; i1 < npairs && off[i1 + 1u] - off[i0] <= rows_cap; ++i1) {}
+        i1 = round_end(i0, npairs, budget, bytes_of);
         round_rows = std::max(round_rows, off[i1] - off[i0]);
     }
-    HIP_TRY(c, W.d_row_off.reserve(off.size()));
-    HIP_TRY(c, W.d_xt.reserve(xt.size()));
-    HIP_TRY(c, W.d_score.reserve(3u * (size_t)npairs));
     HIP_TRY(c, W.d_rec.reserve(2u * DCP_POST_REC * round_rows));
     HIP_TRY(c, W.d_rows.reserve(3u * round_rows));
-    for (hipEvent_t &e : W.ev)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipMemcpyAsync(W.d_row_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
 
-    dcp_fwd_args a = forward_args(c, W.d_xt.p);
-    a.row_off = W.d_row_off.p;
-    double *const d_null = W.d_score.p, *const d_fwd = d_null + npairs, *const d_bwd = d_fwd + npairs;
+    double *const d_fwd = W.d_score.p + npairs;
     dcp_post_args pa{};
     pa.profs = a.profs, pa.en = a.en;
     pa.seq_words = a.seq_words, pa.seq_woff = a.seq_woff, pa.seq_len = a.seq_len;
     pa.alt_fwd = d_fwd;
 
     std::vector<double> rows;
-    std::vector<dcp_fwd_pair> list;
     float ms_total = 0.0f;
     for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
     {
-        for (i1 = i0 + 1u; i1 < npairs && off[i1 + 1u] - off[i0] <= rows_cap; ++i1) {}
+        i1 = round_end(i0, npairs, budget, bytes_of);
         unsigned const n = i1 - i0;
         uint64_t const nrows = off[i1] - off[i0];
         ForwardBuckets b;
-        forward_bucket(c, seq_idx + i0, profile_idx + i0, n, i0, b);
-        list.resize(n);
-        for (unsigned i = 0; i < n; ++i)
-            list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
-        uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
-        HIP_TRY(c, c->fwd.d_work.reserve(work_stride * b.waves[3]));
-        HIP_TRY(c, W.d_pairs.reserve(2u * (size_t)n));
-        dcp_fwd_pair *const d_bucketed = W.d_pairs.p, *const d_list = W.d_pairs.p + n;
-        HIP_TRY(c, hipMemcpyAsync(d_bucketed, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below
-
-        a.work = c->fwd.d_work.p, a.work_stride = work_stride;
+        if (int rc = upload_round(c, seq_idx, profile_idx, i0, n, true, b, a)) return rc;
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         a.row_base = off[i0];
-        a.out_null = d_null;
         HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
-        for (int sweep = 0; sweep < 2; ++sweep)
-        {
-            a.rows = W.d_rec.p + (sweep ? (size_t)DCP_POST_REC * nrows : 0u);
-            a.out_alt = sweep ? d_bwd : d_fwd;
-            for (int k = 0; k < 4; ++k)
-            {
-                if (b.count[k] == 0) continue;
-                a.pairs = d_bucketed + b.first[k];
-                a.npairs = b.count[k];
-                a.nwaves = b.waves[k];
-                if ((sweep ? dcp_backward_launch : dcp_forward_rows_launch)(c->precision, kFwdR[k], &a, c->stream))
-                    return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
-                HIP_TRY(c, hipGetLastError());
-            }
-        }
-        pa.list = d_list, pa.nlist = n, pa.row_off = W.d_row_off.p + i0;
+        if (int rc = run_sweeps(c, a, b, 2, DCP_FWD_STORE_ROWS, npairs, nrows, 0u)) return rc;
+        pa.list = W.d_pairs.p + n, pa.nlist = n, pa.row_off = W.d_off.p + i0;
         pa.rows_f = W.d_rec.p, pa.rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
         pa.begin = W.d_rows.p, pa.end = pa.begin + nrows, pa.core = pa.end + nrows;
         if (dcp_posterior_combine_launch(c->precision, &pa, nrows, c->stream))
@@ -3710,11 +3710,11 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
     std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
     std::memcpy(alt_bwd_out, score.data() + npairs, (size_t)npairs * sizeof(double));
     std::memcpy(row_off, off.data(), off.size() * sizeof(uint64_t));
-    W.ms = ms_total;
+    W.post_ms = ms_total;
     return DCP_OK;
 }
 
-float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->post.ms : -1.0f; }
+float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.post_ms : -1.0f; }
 
 // ---- The posterior-decoded alignment of a pair list (dcp_mea.hip) ---------------------------------------------------
 // The list runs in rounds of consecutive pairs whose matrices (P, Q, bM, bI: 32 bytes a cell), cell choices (2 bytes a
@@ -3738,15 +3738,6 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
         step_off[0] = 0u;
         return DCP_OK;
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    auto &W = c->mea;
-    bool const f64 = c->precision == 64;
-    if (!f64)
-        if (int rc = ensure_rowsweep_layout(c)) return rc;
-    if (int rc = forward_profiles(c)) return rc;
-    std::vector<double> xt;
-    if (int rc = forward_special_transitions(c, multi_hits, hmmer3_compat, xt)) return rc;
-
     // rows and cells of the list, one array: [npairs + 1] row offsets, then [npairs + 1] cell offsets
     size_t const no = (size_t)npairs + 1u;
     std::vector<uint64_t> off(2u * no, 0u);
@@ -3757,28 +3748,15 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
         roff[i + 1u] = roff[i] + rows;
         coff[i + 1u] = coff[i] + rows * c->core_sizes[profile_idx[i]];
     }
-    uint64_t const budget = W.budget ? W.budget : (uint64_t)8u << 30;
+    auto &W = c->sweeps;
+    dcp_fwd_args a{};
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 4u, off, &a)) return rc;
+    a.cell_off = W.d_off.p + no;
+    uint64_t const budget = W.mea_budget ? W.mea_budget : (uint64_t)8u << 30;
     auto const bytes_of = [&](unsigned i0, unsigned i1) {
         return (coff[i1] - coff[i0]) * kMeaCellBytes + (roff[i1] - roff[i0]) * kMeaRowBytes;
     };
-    auto const round_end = [&](unsigned i0) {
-        unsigned i1 = i0 + 1u;
-        while (i1 < npairs && bytes_of(i0, i1 + 1u) <= budget)
-            ++i1;
-        return i1;
-    };
-    HIP_TRY(c, W.d_off.reserve(off.size()));
-    HIP_TRY(c, W.d_xt.reserve(xt.size()));
-    HIP_TRY(c, W.d_score.reserve(4u * (size_t)npairs));
-    for (hipEvent_t &e : W.ev)
-        if (!e) HIP_TRY(c, hipEventCreate(&e));
-    HIP_TRY(c, hipMemcpyAsync(W.d_off.p, off.data(), off.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-
-    dcp_fwd_args a = forward_args(c, W.d_xt.p);
-    a.row_off = W.d_off.p, a.cell_off = W.d_off.p + no;
-    double *const d_null = W.d_score.p, *const d_fwd = d_null + npairs, *const d_bwd = d_fwd + npairs, *const d_gain = d_bwd + npairs;
+    double *const d_fwd = W.d_score.p + npairs, *const d_gain = d_fwd + 2u * (size_t)npairs;
     dcp_mea_args ma{};
     ma.profs = a.profs, ma.tab = a.tab, ma.trans = a.trans, ma.ei = a.ei, ma.en = a.en;
     ma.seq_words = a.seq_words, ma.seq_woff = a.seq_woff, ma.seq_len = a.seq_len, ma.xtrans = a.xtrans;
@@ -3788,34 +3766,26 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
     std::vector<uint32_t> steps, round_steps;
     std::vector<double> post, round_post;
     std::vector<uint64_t> count((size_t)npairs, 0u), idx;
-    std::vector<dcp_fwd_pair> list;
     float ms_total = 0.0f;
     for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
     {
-        i1 = round_end(i0);
+        i1 = round_end(i0, npairs, budget, bytes_of);
         unsigned const n = i1 - i0;
         uint64_t const nrows = roff[i1] - roff[i0], ncells = coff[i1] - coff[i0];
-        ForwardBuckets b;
-        forward_bucket(c, seq_idx + i0, profile_idx + i0, n, i0, b);
-        list.resize(n);
         unsigned chunks = 0; // of the round's widest profile
         idx.assign(3u * (size_t)n, 0u); // where a pair's steps go, how many fit, how many there are
         uint64_t nsteps_cap = 0;
         for (unsigned i = 0; i < n; ++i)
         {
-            list[i] = dcp_fwd_pair{seq_idx[i0 + i], profile_idx[i0 + i], i0 + i};
             unsigned const M = c->core_sizes[profile_idx[i0 + i]];
-            chunks = std::max(chunks, (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK);
+            chunks = std::max(chunks, chunks_of(M));
             idx[i] = nsteps_cap, idx[n + i] = (uint64_t)c->seq_len[seq_idx[i0 + i]] + M + 16u;
             nsteps_cap += idx[n + i];
         }
-        uint64_t const work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK;
         unsigned mea_waves = (unsigned)std::min<uint64_t>(n, 4ull * c->num_cus); // one wavefront per SIMD
-        if (c->fwd.waves_cap) mea_waves = std::min(mea_waves, c->fwd.waves_cap);
+        if (W.waves_cap) mea_waves = std::min(mea_waves, W.waves_cap);
         uint64_t const mea_stride = (uint64_t)DCP_MEA_WORK_ROWS * chunks * DCP_FWD_CHUNK;
-        HIP_TRY(c, c->fwd.d_work.reserve(work_stride * b.waves[3]));
-        HIP_TRY(c, W.d_work.reserve(mea_stride * mea_waves));
-        HIP_TRY(c, W.d_pairs.reserve(2u * (size_t)n));
+        HIP_TRY(c, W.d_mea_work.reserve(mea_stride * mea_waves));
         HIP_TRY(c, W.d_rec.reserve(2u * DCP_POST_REC * nrows));
         HIP_TRY(c, W.d_mat.reserve(4u * ncells));
         HIP_TRY(c, W.d_cell.reserve(ncells));
@@ -3824,38 +3794,19 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
         HIP_TRY(c, W.d_step_idx.reserve(idx.size()));
         HIP_TRY(c, W.d_steps.reserve(nsteps_cap));
         HIP_TRY(c, W.d_post.reserve(nsteps_cap));
-        dcp_fwd_pair *const d_bucketed = W.d_pairs.p, *const d_list = W.d_pairs.p + n;
-        HIP_TRY(c, hipMemcpyAsync(d_bucketed, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_list, list.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+        ForwardBuckets b;
+        if (int rc = upload_round(c, seq_idx, profile_idx, i0, n, true, b, a)) return rc;
         HIP_TRY(c, hipMemcpyAsync(W.d_step_idx.p, idx.data(), idx.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream)); // the lists may leave scope on any error below
-
-        a.work = c->fwd.d_work.p, a.work_stride = work_stride;
         a.row_base = roff[i0], a.cell_base = coff[i0];
-        a.out_null = d_null;
         HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
-        for (int sweep = 0; sweep < 2; ++sweep)
-        {
-            a.rows = W.d_rec.p + (sweep ? (size_t)DCP_POST_REC * nrows : 0u);
-            a.mat0 = W.d_mat.p + (sweep ? 2u * ncells : 0u), a.mat1 = a.mat0 + ncells;
-            a.out_alt = sweep ? d_bwd : d_fwd;
-            for (int k = 0; k < 4; ++k)
-            {
-                if (b.count[k] == 0) continue;
-                a.pairs = d_bucketed + b.first[k];
-                a.npairs = b.count[k];
-                a.nwaves = b.waves[k];
-                if ((sweep ? dcp_backward_mat_launch : dcp_forward_mat_launch)(c->precision, kFwdR[k], &a, c->stream))
-                    return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
-                HIP_TRY(c, hipGetLastError());
-            }
-        }
-        ma.list = d_list, ma.nlist = n, ma.nwaves = mea_waves;
+        if (int rc = run_sweeps(c, a, b, 2, DCP_FWD_STORE_MATS, npairs, nrows, ncells)) return rc;
+        ma.list = W.d_pairs.p + n, ma.nlist = n, ma.nwaves = mea_waves;
         ma.row_off = W.d_off.p + i0, ma.cell_off = W.d_off.p + no + i0;
         ma.P = W.d_mat.p, ma.Q = ma.P + ncells, ma.bM = ma.Q + ncells, ma.bI = ma.bM + ncells;
         ma.rows_f = W.d_rec.p, ma.rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
         ma.cell = W.d_cell.p, ma.rowc = W.d_rowc.p, ma.start = W.d_start.p;
-        ma.work = W.d_work.p, ma.work_stride = mea_stride;
+        ma.work = W.d_mea_work.p, ma.work_stride = mea_stride;
         if (dcp_mea_sweep_launch(c->precision, &ma, c->stream)) return c->fail(DCP_EFAIL, "no max-plus sweep kernel");
         HIP_TRY(c, hipGetLastError());
         for (int walk = 0; walk < 2; ++walk)
@@ -3910,7 +3861,7 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
         total += count[i];
     }
     if (total > 0xffffffffull) return c->fail(DCP_EFAIL, "the list's paths hold %llu steps, more than 32 bits count", (unsigned long long)total);
-    W.ms = ms_total;
+    W.mea_ms = ms_total; // the call ran all its rounds, whatever cap_steps makes of it
     step_off[0] = 0u;
     for (unsigned i = 0; i < npairs; ++i)
         step_off[i + 1u] = step_off[i] + (uint32_t)count[i];
@@ -3924,7 +3875,7 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
     return DCP_OK;
 }
 
-float dcp_gpu_mea_kernel_ms(dcp_gpu_ctx *c) { return c ? c->mea.ms : -1.0f; }
+float dcp_gpu_mea_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.mea_ms : -1.0f; }
 
 // A redo list was full and lost pairs: the scan is repeated with the row-sweep kernel, which needs no list.
 static int rerun_with_rowsweep(dcp_gpu_ctx *c)
@@ -4057,21 +4008,21 @@ int dcp_gpu_test_set_trace_mode(dcp_gpu_ctx *c, int own_forward, unsigned long l
 int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *c, unsigned long long bytes)
 {
     if (!c) return DCP_EINVAL;
-    c->post.budget = bytes;
+    c->sweeps.post_budget = bytes;
     return DCP_OK;
 }
 
 int dcp_gpu_test_set_mea_budget(dcp_gpu_ctx *c, unsigned long long bytes)
 {
     if (!c) return DCP_EINVAL;
-    c->mea.budget = bytes;
+    c->sweeps.mea_budget = bytes;
     return DCP_OK;
 }
 
 int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *c, unsigned nwaves)
 {
     if (!c) return DCP_EINVAL;
-    c->fwd.waves_cap = nwaves;
+    c->sweeps.waves_cap = nwaves;
     return DCP_OK;
 }
 

@@ -281,9 +281,8 @@ struct dcp_mea_args
 #ifdef __cplusplus
 extern "C" {
 #endif
-// precision 32 / 64 and R as dcp_forward_launch.  != 0: no such kernel.
-int dcp_forward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream);
-int dcp_backward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream);
+// (the two sweeps: dcp_forward_launch and dcp_backward_launch with DCP_FWD_STORE_MATS, dcp_forward.h)
+// precision 32 / 64 as there.  != 0: no such kernel.
 int dcp_mea_sweep_launch(int precision, struct dcp_mea_args const *a, void *stream);
 int dcp_mea_walk_launch(int precision, struct dcp_mea_args const *a, void *stream);
 #ifdef __cplusplus

@@ -30,29 +30,13 @@
 namespace
 {
 
-constexpr int WR = 4; // nodes per lane of a chunk
-
-__device__ __forceinline__ double shl1(double v, double last, unsigned lane) // value of lane + 1; lane 63 receives `last`
-{
-    double const n = __shfl_down(v, 1, 64);
-    return lane == 63u ? last : n;
-}
-
 struct DevSeq // base i of a resident sequence: 2 bits each, 16 a word
 {
     uint32_t const *w;
     __device__ __forceinline__ unsigned operator()(unsigned i) const { return (w[i >> 4] >> ((i & 15u) * 2u)) & 3u; }
 };
 
-struct Area // rows of ldk doubles: gM and gI slots, then the row's gP, gQ
-{
-    double *base;
-    uint64_t ldk;
-    __device__ __forceinline__ double *M(unsigned slot) const { return base + (uint64_t)slot * ldk; }
-    __device__ __forceinline__ double *I(unsigned slot) const { return base + (uint64_t)(5u + slot) * ldk; }
-    __device__ __forceinline__ double *row(unsigned which) const { return base + (uint64_t)(10u + which) * ldk; }
-};
-
+// (WideArea: ring0 holds the slots of gM, ring1 those of gI; rows 0, 1 the row's gP, gQ)
 // gD of the lane's WR nodes, downwards: h[r] the node's own part, s[r] = 0 or -inf the link DD_{k+1}, carry = gD of the
 // node after lane 63's last.  dn[r] receives gD_{k+1}.
 __device__ __forceinline__ void chain_down(double const (&h)[WR], double const (&s)[WR], double carry, double (&dn)[WR], unsigned lane)
@@ -115,10 +99,8 @@ template <class Real> __global__ __launch_bounds__(256) void mea_sweep_kernel(dc
         uint16_t *const cell = a.cell + cell0;
         uint32_t *const rowc = a.rowc + row0 * DCP_MEA_ROWC;
         double const alt = a.alt_fwd[pp.pos];
-        unsigned const nchunks = (M + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
-        Area wa;
-        wa.ldk = (uint64_t)nchunks * DCP_FWD_CHUNK; // <= work_stride / DCP_MEA_WORK_ROWS: the host sized it by the widest
-        wa.base = a.work + gw * a.work_stride;
+        WideArea const wa = wide_area(a.work, a.work_stride, gw, M);
+        unsigned const nchunks = wa.nchunks;
         // rows L + 1 .. L + 5, anew for every pair: the rings' own columns
         for (unsigned ch = 0; ch < nchunks; ++ch)
         {
@@ -127,7 +109,7 @@ template <class Real> __global__ __launch_bounds__(256) void mea_sweep_kernel(dc
             for (int r = 0; r < WR; ++r)
 #pragma unroll
                 for (unsigned h = 0; h < 5u; ++h)
-                    wa.M(h)[k0 + r] = wa.I(h)[k0 + r] = ninf();
+                    wa.ring0(h)[k0 + r] = wa.ring1(h)[k0 + r] = ninf();
         }
         unsigned const X = (lane & 3u) < 2u ? (lane & 3u) : 2u; // the lane's own one of N, J, C
         double gx[5]; // its suffix gains at rows j + 1 .. j + 5
@@ -179,8 +161,8 @@ template <class Real> __global__ __launch_bounds__(256) void mea_sweep_kernel(dc
                             {
                                 uint64_t const to = (uint64_t)(j + l) * M + k;
                                 unsigned const slot = (j + l) % 5u;
-                                dcp_mea_take(p, dcp_mea_word(fp, (double)tab[(uint64_t)code[l - 1u] * ld + k], bM[to], alt, l, wa.M(slot)[k]), l);
-                                dcp_mea_take(q, dcp_mea_word(fq, eI[l - 1u], bI[to], alt, l, wa.I(slot)[k]), l);
+                                dcp_mea_take(p, dcp_mea_word(fp, (double)tab[(uint64_t)code[l - 1u] * ld + k], bM[to], alt, l, wa.ring0(slot)[k]), l);
+                                dcp_mea_take(q, dcp_mea_word(fq, eI[l - 1u], bI[to], alt, l, wa.ring1(slot)[k]), l);
                             }
                         cell[(uint64_t)j * M + k] = (uint16_t)((p.c << DCP_MEA_SH_P) | (q.c << DCP_MEA_SH_Q));
                         dcp_mea_take(bb, dcp_mea_link((double)trans[(uint64_t)DCP_T_ENTRY * ld + k], p.g), k + 1u);
@@ -235,7 +217,7 @@ template <class Real> __global__ __launch_bounds__(256) void mea_sweep_kernel(dc
                     s[r] = dcp_mea_link(DDn[r], 0.0);
                 }
                 chain_down(h, s, carry_d, dn, lane);
-                double *const gm = wa.M(slot) + k0, *const gi = wa.I(slot) + k0;
+                double *const gm = wa.ring0(slot) + k0, *const gi = wa.ring1(slot) + k0;
                 double d0 = ninf();
 #pragma unroll
                 for (int r = 0; r < WR; ++r)

@@ -94,10 +94,8 @@ struct dcp_post_args
 #ifdef __cplusplus
 extern "C" {
 #endif
-// precision 32 / 64 and R as dcp_forward_launch.  != 0: no such kernel.
-int dcp_forward_rows_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream);
-int dcp_backward_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream);
-// total_rows: the round's rows, row_off[nlist] - row_off[0]
+// (the two sweeps: dcp_forward_launch and dcp_backward_launch with DCP_FWD_STORE_ROWS, dcp_forward.h)
+// precision 32 / 64 as there; total_rows: the round's rows, row_off[nlist] - row_off[0].  != 0: no such kernel.
 int dcp_posterior_combine_launch(int precision, struct dcp_post_args const *a, uint64_t total_rows, void *stream);
 #ifdef __cplusplus
 }

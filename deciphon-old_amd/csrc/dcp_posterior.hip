@@ -35,12 +35,6 @@
 namespace
 {
 
-__device__ __forceinline__ double shl1(double v, double last, unsigned lane) // value of lane + 1; lane 63 receives `last`
-{
-    double const n = __shfl_down(v, 1, 64);
-    return lane == 63u ? last : n;
-}
-
 struct XB // the pair's special transitions as the Backward rows use them
 {
     double EB, EJ, EC, ET, CT;
@@ -142,22 +136,6 @@ __device__ __forceinline__ Specials backward_specials(XB const &x, double bB, do
     return s;
 }
 
-__device__ __forceinline__ double *record_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
-{
-    return a.rows + (a.row_off[pp.pos] - a.row_base) * DCP_POST_REC;
-}
-
-// MAT: the pair's bM and bI matrices, the lane's own columns below core_size
-struct Mats
-{
-    double *m, *i;
-};
-__device__ __forceinline__ Mats mats_of(dcp_fwd_args const &a, dcp_fwd_pair const &pp)
-{
-    uint64_t const at = a.cell_off[pp.pos] - a.cell_base;
-    return Mats{a.mat0 + at, a.mat1 + at};
-}
-
 // ---- profiles of at most 64 R nodes: everything in registers -------------------------------------------------------
 template <int R> struct BTrans // n..: the transitions into node k + 1
 {
@@ -173,6 +151,7 @@ template <int R> struct BState
     unsigned w;
 };
 
+// MAT: bM goes to the pair's first matrix (Mats::m0), bI to its second
 template <class Real, int R, int PH, bool MAT>
 __device__ __forceinline__ void backward_row(BState<R> &s, BTrans<R> const &t, XB const &x, Tabs<Real> const &g, unsigned j,
                                              unsigned L, unsigned lane, double *rec, Mats const &mt)
@@ -223,7 +202,7 @@ __device__ __forceinline__ void backward_row(BState<R> &s, BTrans<R> const &t, X
         s.bM[PH][r] = dcp_lse4(sp.bE, t.nmd[r] + dn[r], t.nmm[r] + bPn[r], t.mi[r] + bQ[r]);
         s.bI[PH][r] = dcp_lse2(t.nim[r] + bPn[r], t.ii[r] + bQ[r]);
         if constexpr (MAT)
-            if (k0 + r < g.M) mt.m[(uint64_t)j * g.M + k0 + r] = s.bM[PH][r], mt.i[(uint64_t)j * g.M + k0 + r] = s.bI[PH][r];
+            if (k0 + r < g.M) mt.m0[(uint64_t)j * g.M + k0 + r] = s.bM[PH][r], mt.m1[(uint64_t)j * g.M + k0 + r] = s.bI[PH][r];
     }
     s.bX[PH] = sp.own;
     s.bB = bB, s.bPN = readlane(bX, 0);
@@ -237,10 +216,7 @@ template <class Real, int R, bool MAT> __global__ __launch_bounds__(256) void ba
     if (gw >= nw) return; // the grid's last block may hold wavefronts past nwaves
     for (uint64_t pair = gw; pair < a.npairs; pair += nw)
     {
-        dcp_fwd_pair const pp = a.pairs[pair];
-        dcp_fwd_prof const pr = a.profs[pp.prof];
-        unsigned const L = a.seq_len[pp.q];
-        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        auto const [pp, pr, L, xt] = pair_head(a, pair);
         XB const x = backward_transitions(xt, lane);
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
         unsigned const k0 = lane * R;
@@ -291,8 +267,7 @@ template <class Real, int R, bool MAT> __global__ __launch_bounds__(256) void ba
 }
 
 // ---- wider profiles: chunks of 256 columns, the rings in the wavefront's work area ---------------------------------
-constexpr int WR = 4; // nodes per lane of a chunk
-
+// (WideArea: ring0 holds the slots of bM, ring1 those of bI; rows 0, 1 the row's bP, bQ)
 struct BWideState
 {
     double bX[5];
@@ -300,18 +275,8 @@ struct BWideState
     unsigned w;
 };
 
-struct BWideArea // rows of ldk doubles: bM and bI slots, then the row's bP, bQ
-{
-    double *base;
-    uint64_t ldk;
-    unsigned nchunks;
-    __device__ __forceinline__ double *M(int slot) const { return base + (uint64_t)slot * ldk; }
-    __device__ __forceinline__ double *I(int slot) const { return base + (uint64_t)(5 + slot) * ldk; }
-    __device__ __forceinline__ double *row(int which) const { return base + (uint64_t)(10 + which) * ldk; }
-};
-
 template <class Real, int PH, bool MAT>
-__device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Tabs<Real> const &g, BWideArea const &wa, unsigned j,
+__device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Tabs<Real> const &g, WideArea const &wa, unsigned j,
                                                   unsigned L, unsigned lane, double *rec, Mats const &mt)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
@@ -336,7 +301,7 @@ __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Ta
         for (int l = 0; l < 5; ++l)
         {
             Real const *em = g.tab + (uint64_t)code[l] * g.ld;
-            double const *m = wa.M(sl[l]) + k0, *i = wa.I(sl[l]) + k0;
+            double const *m = wa.ring0(sl[l]) + k0, *i = wa.ring1(sl[l]) + k0;
 #pragma unroll
             for (int r = 0; r < WR; ++r)
             {
@@ -380,7 +345,7 @@ __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Ta
             dd[r] = load_col(g.trans + DCP_T_DD * g.ld, k0 + r + 1u, g.M);
         }
         delete_chain_down<WR>(sp.bE, c, dd, carry_d, d, dn, lane);
-        double *const m = wa.M(PH) + k0, *const i = wa.I(PH) + k0;
+        double *const m = wa.ring0(PH) + k0, *const i = wa.ring1(PH) + k0;
 #pragma unroll
         for (int r = 0; r < WR; ++r)
         {
@@ -389,7 +354,7 @@ __device__ __forceinline__ void backward_wide_row(BWideState &s, XB const &x, Ta
                             load_col(g.trans + DCP_T_MM * g.ld, k + 1u, g.M) + bPn[r], load_col(g.trans + DCP_T_MI * g.ld, k, g.M) + bQ[r]);
             i[r] = dcp_lse2(load_col(g.trans + DCP_T_IM * g.ld, k + 1u, g.M) + bPn[r], load_col(g.trans + DCP_T_II * g.ld, k, g.M) + bQ[r]);
             if constexpr (MAT)
-                if (k < g.M) mt.m[(uint64_t)j * g.M + k] = m[r], mt.i[(uint64_t)j * g.M + k] = i[r];
+                if (k < g.M) mt.m0[(uint64_t)j * g.M + k] = m[r], mt.m1[(uint64_t)j * g.M + k] = i[r];
         }
         carry_p = readlane(bP[0], 0), carry_d = readlane(d[0], 0);
     }
@@ -405,16 +370,10 @@ template <class Real, bool MAT> __global__ __launch_bounds__(256) void backward_
     if (gw >= nw) return; // wavefronts past nwaves have no work area
     for (uint64_t pair = gw; pair < a.npairs; pair += nw)
     {
-        dcp_fwd_pair const pp = a.pairs[pair];
-        dcp_fwd_prof const pr = a.profs[pp.prof];
-        unsigned const L = a.seq_len[pp.q];
-        double const *xt = a.xtrans + (size_t)pp.q * DCP_FWD_XSTRIDE;
+        auto const [pp, pr, L, xt] = pair_head(a, pair);
         XB const x = backward_transitions(xt, lane);
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
-        BWideArea wa;
-        wa.nchunks = (pr.core_size + (unsigned)DCP_FWD_CHUNK - 1u) / (unsigned)DCP_FWD_CHUNK;
-        wa.ldk = (uint64_t)wa.nchunks * DCP_FWD_CHUNK; // <= work_stride / DCP_FWD_WORK_ROWS: the host sized it by the widest
-        wa.base = a.work + gw * a.work_stride;
+        WideArea const wa = wide_area(a.work, a.work_stride, gw, pr.core_size);
         static_assert((int)DCP_POST_WORK_ROWS <= (int)DCP_FWD_WORK_ROWS, "the Forward sweep's work area serves");
         // rows L + 1 .. L + 5, anew for every pair: the rings' own columns
         for (unsigned ch = 0; ch < wa.nchunks; ++ch)
@@ -424,7 +383,7 @@ template <class Real, bool MAT> __global__ __launch_bounds__(256) void backward_
             for (int r = 0; r < WR; ++r)
 #pragma unroll
                 for (int h = 0; h < 5; ++h)
-                    wa.M(h)[k0 + r] = wa.I(h)[k0 + r] = ninf();
+                    wa.ring0(h)[k0 + r] = wa.ring1(h)[k0 + r] = ninf();
         }
         BWideState s;
 #pragma unroll
@@ -484,7 +443,7 @@ template <class Real> __global__ __launch_bounds__(256) void posterior_combine_k
                             a.begin + t, a.end + t, a.core + t);
 }
 
-template <class Real, bool MAT = false> int launch_backward(int R, dcp_fwd_args const &a, hipStream_t st)
+template <class Real, bool MAT> int launch_backward(int R, dcp_fwd_args const &a, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
@@ -497,28 +456,22 @@ template <class Real, bool MAT = false> int launch_backward(int R, dcp_fwd_args 
     }
 }
 
-} // namespace
-
-extern "C" int dcp_backward_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+// (float first, then double, of each variant in turn: the order in which the unit's kernels are emitted)
+template <bool MAT> int launch_backward(int precision, int R, dcp_fwd_args const &a, hipStream_t st)
 {
-    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off) return 1;
-    if (R == 0 && !a->work) return 1;
-    hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch_backward<float>(R, *a, st);
-    if (precision == 64) return launch_backward<double>(R, *a, st);
+    if (precision == 32) return launch_backward<float, MAT>(R, a, st);
+    if (precision == 64) return launch_backward<double, MAT>(R, a, st);
     return 1;
 }
 
-// the same sweeps, bM and bI of every row stored as well (a->mat0, a->mat1, a->cell_off, a->cell_base):
-// dcp_gpu_mea_pairs' second sweep
-extern "C" int dcp_backward_mat_launch(int precision, int R, struct dcp_fwd_args const *a, void *stream)
+} // namespace
+
+extern "C" int dcp_backward_launch(int precision, int R, int store, struct dcp_fwd_args const *a, void *stream)
 {
-    if (!a || a->nwaves == 0 || a->npairs == 0 || !a->rows || !a->row_off || !a->mat0 || !a->mat1 || !a->cell_off) return 1;
-    if (R == 0 && !a->work) return 1;
+    if (store == DCP_FWD_STORE_NONE || dcp_fwd_args_refused(a, R, store)) return 1; // Backward always writes its records
     hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch_backward<float, true>(R, *a, st);
-    if (precision == 64) return launch_backward<double, true>(R, *a, st);
-    return 1;
+    if (store == DCP_FWD_STORE_ROWS) return launch_backward<false>(precision, R, *a, st);
+    return launch_backward<true>(precision, R, *a, st);
 }
 
 extern "C" int dcp_posterior_combine_launch(int precision, struct dcp_post_args const *a, uint64_t total_rows, void *stream)

@@ -102,6 +102,10 @@ ABI_SYMBOLS = [
     "dcp_posterior_tables", "dcp_posterior_envelopes", "dcp_gpu_posterior_pairs", "dcp_gpu_posterior_kernel_ms",
     # the posterior-decoded alignment of a pair list: a max-plus sweep over word posteriors, and its host twins
     "dcp_mea_tables", "dcp_mea_path_gain", "dcp_gpu_mea_pairs", "dcp_gpu_mea_kernel_ms",
+    # Forward E-values: the dense Forward scan, the exponential tail fit per profile, E-values of score arrays
+    "dcp_gpu_forward_dense", "dcp_gpu_fetch_forward_scores", "dcp_gpu_forward_dense_kernel_ms", "dcp_exp_tail_fit",
+    "dcp_gpu_fit_exp_tail", "dcp_gpu_exp_tail_kernel_ms", "dcp_gpu_db_calibrate_forward", "dcp_exp_sf",
+    "dcp_scores_evalues",
 ]
 
 
@@ -304,6 +308,16 @@ def _load(path=None, hooks=False):
         "dcp_mea_path_gain": (I, [U, U, P, P, P, P, P, P, U, P, U, C.POINTER(C.c_double), P]),
         "dcp_gpu_mea_pairs": (I, [P, I, I, P, P, U, P, U, P, P, P, P]),
         "dcp_gpu_mea_kernel_ms": (F, [P]),
+        "dcp_gpu_forward_dense": (I, [P, I, I]),
+        "dcp_gpu_fetch_forward_scores": (I, [P, P, P]),
+        "dcp_gpu_forward_dense_kernel_ms": (F, [P]),
+        "dcp_exp_tail_fit": (I, [P, U, C.c_size_t, U, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_double), C.POINTER(C.c_uint)]),
+        "dcp_gpu_fit_exp_tail": (I, [P, I, U, P, P, P, P, P]),
+        "dcp_gpu_exp_tail_kernel_ms": (F, [P, I]),
+        "dcp_gpu_db_calibrate_forward": (I, [P, U, U, C.c_uint64, P, I, I, U, P, P, P, P, P]),
+        "dcp_exp_sf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+        "dcp_scores_evalues": (I, [P, P, P, U, P, P, P, U, C.c_double, I, P]),
     }
     if hooks:
         sig["dcp_gpu_test_set_redo_cap"] = (I, [P, U])
@@ -316,6 +330,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_last_rowsweep_plan"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_set_forward_waves"] = (I, [P, U])
+        sig["dcp_gpu_test_set_dense_round"] = (I, [P, U])
         sig["dcp_gpu_test_set_posterior_budget"] = (I, [P, C.c_ulonglong])
         sig["dcp_gpu_test_set_mea_budget"] = (I, [P, C.c_ulonglong])
     for name, (res, args) in sig.items():
@@ -1031,6 +1046,59 @@ def hit_evalues(hits, mu, lam, status, nsearched):
     return out
 
 
+# which law an E-value is taken under (score_evalues), and which dense matrices a device fit reads (Scanner.fit_exp_tail)
+LAW_GUMBEL, LAW_EXP = 0, 1
+SCORES_SCAN, SCORES_FORWARD = 0, 1
+
+
+def exp_tail_fit(x, k):
+    """(mu, lambda, status, tau, k_eff) of the exponential tail fit of a 1-d sample (dcp_exp_tail_fit; a strided view is
+    fitted in place): tau is the k-th largest value, lambda = k_eff / sum(x - tau over the k_eff values >= tau) and mu =
+    tau + log(k_eff / n) / lambda, so that P(X >= s) = exp(-lambda (s - mu)) is k_eff / n at tau.  Closed-form: status is
+    FIT_OK, FIT_FLAT (every value >= tau equals tau) or FIT_NONFINITE (tau NaN, k_eff 0); mu and lambda are NaN unless
+    FIT_OK.  Fewer than 2 values, k < 2 or k > len(x): DcpError(RC_EINVAL).  The law holds for scores >= tau only."""
+    x = np.asarray(x, np.float64)
+    if x.ndim != 1 or (len(x) > 1 and (x.strides[0] <= 0 or x.strides[0] % 8)):
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+    stride = x.strides[0] // 8 if len(x) > 1 else 1
+    if not 0 <= k < 2 ** 32:
+        raise DcpError(RC_EINVAL, "the tail count: 2 .. len(x)")
+    mu, lam, tau, k_eff = C.c_double(0), C.c_double(0), C.c_double(0), C.c_uint(0)
+    rc = lib.dcp_exp_tail_fit(x.ctypes.data, len(x), stride, int(k), C.byref(mu), C.byref(lam), C.byref(tau), C.byref(k_eff))
+    if rc == RC_EINVAL:
+        raise DcpError(rc, "a tail fit needs at least 2 values and a tail count in 2 .. len(x)")
+    return mu.value, lam.value, rc, tau.value, k_eff.value
+
+
+def exp_sf(mu, lam, s):
+    """P(X >= s) under an exponential tail fit: 1 for s <= mu, else exp(-lam (s - mu)) (dcp_exp_sf)."""
+    return lib.dcp_exp_sf(float(mu), float(lam), float(s))
+
+
+def score_evalues(profile_idx, null, alt, mu, lam, status, nsearched, law):
+    """E-values of scores that are not hit records -- the arrays forward_pairs and scan_pairs return -- under a
+    calibration (mu, lam, status) of the resident DB: nsearched * P(score >= alt - null) per entry under LAW_GUMBEL
+    (gumbel_sf: hit_evalues' numbers) or LAW_EXP (exp_sf: a calibrate_forward calibration); NaN where the profile's fit
+    is not FIT_OK (dcp_scores_evalues)."""
+    profile_idx = np.ascontiguousarray(profile_idx)
+    if profile_idx.ndim != 1 or profile_idx.dtype.kind not in "iu" or (len(profile_idx) and
+                                                                        (profile_idx.min() < 0 or profile_idx.max() >= 2 ** 32)):
+        raise DcpError(RC_EINVAL, "profile indices: a 1-d array of integers in 32 bits")
+    profile_idx = np.ascontiguousarray(profile_idx, np.uint32)
+    null, alt, mu, lam = _f64(null), _f64(alt), _f64(mu), _f64(lam)
+    status = np.ascontiguousarray(status, np.uint8)
+    if not (null.shape == alt.shape == profile_idx.shape):
+        raise DcpError(RC_EINVAL, "profile_idx, null and alt: one entry per score")
+    if not (mu.ndim == 1 and mu.shape == lam.shape == status.shape):
+        raise DcpError(RC_EINVAL, "mu, lam and status: one entry per profile")
+    out = np.zeros(len(profile_idx), np.float64)
+    rc = lib.dcp_scores_evalues(profile_idx.ctypes.data, null.ctypes.data, alt.ctypes.data, len(profile_idx), mu.ctypes.data,
+                                lam.ctypes.data, status.ctypes.data, len(mu), float(nsearched), int(law), out.ctypes.data)
+    if rc:
+        raise DcpError(rc, "a profile index outside the calibration, nsearched not finite or negative, or an unknown law")
+    return out
+
+
 def device_count():
     return lib.dcp_gpu_device_count()
 
@@ -1368,6 +1436,69 @@ class Scanner:
     def test_set_forward_waves(self, nwaves):
         """TEST-ONLY (test-hooks build): cap the wavefronts of the following forward_pairs launches (0: default)."""
         self._check(self._lib.dcp_gpu_test_set_forward_waves(self._c, int(nwaves)))
+
+    def forward_dense(self, multi_hits=True, hmmer3_compat=False):
+        """The dense Forward scan (dcp_gpu_forward_dense): every resident sequence against every resident profile with
+        forward_pairs' kernels and bits, the pair lists written on the device.  The two [n, P] matrices stay on the
+        device (forward_scores, fit_exp_tail) until the DB, the batch or the explicit transitions change; scans and
+        pair-list calls leave them alone, and this call leaves the last scan's results alone.  Returns synchronised."""
+        self._check(self._lib.dcp_gpu_forward_dense(self._c, int(multi_hits), int(hmmer3_compat)))
+
+    def forward_scores(self):
+        """(null, alt), two [n, P] float64 arrays: the matrices of the last forward_dense
+        (dcp_gpu_fetch_forward_scores).  DcpError(RC_EINVAL) while there are none, or they are void."""
+        null = np.zeros((self.nseqs, self.nprofiles), np.float64)
+        alt = np.zeros_like(null)
+        self._check(self._lib.dcp_gpu_fetch_forward_scores(self._c, null.ctypes.data, alt.ctypes.data))
+        return null, alt
+
+    def forward_dense_kernel_ms(self):
+        """Milliseconds of the last forward_dense call's launches, by HIP events; negative before any."""
+        return self._lib.dcp_gpu_forward_dense_kernel_ms(self._c)
+
+    def fit_exp_tail(self, k, source="forward"):
+        """(mu, lam, status, tau, k_eff), one entry per resident profile: the exponential tail fit of alt - null
+        (dcp_gpu_fit_exp_tail; two launches: fit_gumbel_tail's selection of the k-th largest score tau, then the
+        closed-form fit over the k_eff scores >= tau) over the matrices of the last forward_dense (source "forward") or
+        the dense scores of the last scan (source "scan", fit_gumbel_tail's preconditions).  k in 2 .. nseqs.  tau,
+        k_eff, status and lam are exp_tail_fit's bits on the same scores.  The law -- exp_sf, score_evalues(LAW_EXP) --
+        holds for scores >= tau[p]: below it the survival is at least k_eff / nseqs, and not calibrated."""
+        if source not in ("forward", "scan"):
+            raise DcpError(RC_EINVAL, 'source: "forward" or "scan"')
+        if not 0 <= k < 2 ** 32:
+            raise DcpError(RC_EINVAL, "the tail count: 2 .. nseqs")
+        mu, lam, status = self._fit_outputs()
+        tau, k_eff = np.zeros(len(mu), np.float64), np.zeros(len(mu), np.uint32)
+        self._check(self._lib.dcp_gpu_fit_exp_tail(self._c, SCORES_FORWARD if source == "forward" else SCORES_SCAN, int(k),
+                                                   mu.ctypes.data, lam.ctypes.data, status.ctypes.data, tau.ctypes.data,
+                                                   k_eff.ctypes.data))
+        return mu, lam, status, tau, k_eff
+
+    def exp_tail_kernel_ms(self, which):
+        """Milliseconds of the last fit_exp_tail's selection kernel (which = 0) or fit kernel (1) alone, by HIP events;
+        negative if none has run."""
+        return self._lib.dcp_gpu_exp_tail_kernel_ms(self._c, which)
+
+    def calibrate_forward(self, n, length, seed, k, probs=None, multi_hits=True, hmmer3_compat=False):
+        """random_seqs(n, length, seed, probs), forward_dense(multi_hits, hmmer3_compat), fit_exp_tail(k): (mu, lam,
+        status, tau, k_eff) for score_evalues(..., LAW_EXP) (dcp_gpu_db_calibrate_forward).  A k outside 2 .. n is refused
+        before the batch is replaced.  The random batch and the matrices STAY resident: upload the real batch
+        afterwards.  The fit holds for this length, these flags and this base composition."""
+        if not (0 <= n < 2 ** 32 and 0 <= length < 2 ** 32 and 0 <= seed < 2 ** 64 and 0 <= k < 2 ** 32):
+            raise DcpError(RC_EINVAL, "n, length and k in 32 bits, seed in 64")
+        probs = _probs(probs)
+        mu, lam, status = self._fit_outputs()
+        tau, k_eff = np.zeros(len(mu), np.float64), np.zeros(len(mu), np.uint32)
+        self._check(self._lib.dcp_gpu_db_calibrate_forward(self._c, n, length, seed, None if probs is None else probs.ctypes.data,
+                                                           int(multi_hits), int(hmmer3_compat), int(k), mu.ctypes.data,
+                                                           lam.ctypes.data, status.ctypes.data, tau.ctypes.data,
+                                                           k_eff.ctypes.data))
+        self._seq_lens = np.full(n, length, np.int64)
+        return mu, lam, status, tau, k_eff
+
+    def test_set_dense_round(self, npairs):
+        """TEST-ONLY (test-hooks build): bound the pairs of a round of the following forward_dense calls (0: default)."""
+        self._check(self._lib.dcp_gpu_test_set_dense_round(self._c, int(npairs)))
 
     def posterior_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
         """(row_off, begin, end, core, alt_fwd, alt_bwd) of the pairs (resident sequence seq_idx[i], resident profile

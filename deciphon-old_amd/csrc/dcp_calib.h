@@ -253,6 +253,34 @@ DCP_HD inline int dcp_gumbel_fit_tail_rule(X const &x, unsigned n, double tau, u
     return DCP_FITR_OK;
 }
 
+// ---- the exponential tail fit ------------------------------------------------------------------------------------------
+// The upper tail of Forward scores: P(X >= s) = exp(-lambda (s - mu)) for s >= mu, fitted to the scores
+// >= tau by censored maximum likelihood, which is closed-form.  Given tau and k_eff = #{x >= tau} of
+// dcp_tail_select_rule: two passes.  Pass 1: non-finite -> NONFINITE.  Pass 2: so = sum_obs (x - tau), the observed set
+// {x >= tau} in index order, every term >= 0; so == 0 -> FLAT (the whole observed set sits at tau).  lambda = k_eff / so
+// and mu = tau + log(k_eff / n) / lambda, so that P(X >= tau) = k_eff / n: the fitted law is (k_eff / n) exp(-lambda
+// (s - tau)).  No Newton step, no exp: comparisons, one ordered sum and one division give lambda, equal in bits wherever
+// it runs; only mu passes through the side's own log.  With k_eff = n the log is of 1: mu = tau, the minimum.  Any
+// status but OK gives NaN in both outputs.
+template <class X>
+DCP_HD inline int dcp_exp_tail_fit_rule(X const &x, unsigned n, double tau, unsigned k_eff, double *mu, double *lambda)
+{
+    *mu = *lambda = dcp_fit_nan();
+    bool bad = false;
+    dcp_fit_pass(x, n, [&](double v) { bad |= !dcp_fit_finite(v); });
+    if (bad) return DCP_FITR_NONFINITE;
+    double so = 0.0;
+    dcp_fit_pass(x, n, [&](double v) {
+        if (v >= tau) so += v - tau;
+    });
+    if (so == 0.0) return DCP_FITR_FLAT;
+    double const ke = (double)k_eff;
+    double const lam = ke / so;
+    *lambda = lam;
+    *mu = tau + log(ke / (double)n) / lam;
+    return DCP_FITR_OK;
+}
+
 // ---- the launches (dcp_calib.hip) -----------------------------------------------------------------------------------
 extern "C" {
 // A batch of nseqs sequences of len bases in the resident layout (dcp_seqs.hip: len / 16 + 3 words each, every bit
@@ -271,6 +299,10 @@ int dcp_launch_tail_select(void const *null_scores, void const *alt_scores, unsi
 int dcp_launch_gumbel_fit_tail(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof,
                                int real_bytes, double const *tau, uint32_t const *k_eff, double *mu, double *lambda,
                                uint8_t *status, void *stream);
+// The exponential tail fit behind the same selection: one launch on `stream`, the same arrays.
+int dcp_launch_exp_tail_fit(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof, int real_bytes,
+                            double const *tau, uint32_t const *k_eff, double *mu, double *lambda, uint8_t *status,
+                            void *stream);
 }
 
 #endif

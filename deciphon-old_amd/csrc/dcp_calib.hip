@@ -18,6 +18,9 @@
 // The selection finds each lane's k-th largest score by descending the 64 bits of an order-preserving key, one counting
 // pass over the rows per bit: comparisons only, so tau and k_eff are the host's bits; no LDS, no atomics, nothing
 // crosses lanes.  The fit is the 16 passes of the censored rule over the rows with x >= tau, a lane's own tau.
+//
+// exp_tail_fit_kernel<Real> (dcp_gpu_fit_exp_tail): the same lane and row layout behind the same selection; the two
+// passes of dcp_exp_tail_fit_rule, no exp in them.
 #include "dcp_calib.h"
 
 #include <hip/hip_runtime.h>
@@ -115,6 +118,27 @@ __global__ __launch_bounds__(kFitBlock) void gumbel_fit_tail_kernel(Real const *
     status[p] = (uint8_t)st;
 }
 
+template <class Real>
+__global__ __launch_bounds__(kFitBlock) void exp_tail_fit_kernel(Real const *__restrict__ null_scores,
+                                                                 Real const *__restrict__ alt_scores, unsigned nseqs,
+                                                                 unsigned nprof, double const *__restrict__ tau,
+                                                                 uint32_t const *__restrict__ k_eff, double *__restrict__ mu,
+                                                                 double *__restrict__ lambda, uint8_t *__restrict__ status)
+{
+    unsigned const p = blockIdx.x * kFitBlock + threadIdx.x;
+    if (p >= nprof) return;
+    Real const *nl = null_scores + p, *al = alt_scores + p;
+    auto x = [=](unsigned q) {
+        size_t const at = (size_t)q * nprof;
+        return (double)al[at] - (double)nl[at];
+    };
+    double m = 0.0, l = 0.0;
+    int const st = dcp_exp_tail_fit_rule(x, nseqs, tau[p], k_eff[p], &m, &l);
+    mu[p] = m;
+    lambda[p] = l;
+    status[p] = (uint8_t)st;
+}
+
 } // namespace
 
 extern "C" int dcp_launch_random(uint32_t *words, uint32_t *woff, uint32_t *len_out, unsigned nseqs, uint32_t len,
@@ -175,6 +199,24 @@ extern "C" int dcp_launch_gumbel_fit_tail(void const *null_scores, void const *a
     else if (real_bytes == 8)
         gumbel_fit_tail_kernel<double><<<blocks, kFitBlock, 0, s>>>((double const *)null_scores, (double const *)alt_scores,
                                                                     nseqs, nprof, tau, k_eff, mu, lambda, status);
+    else return (int)hipErrorInvalidValue;
+    return (int)hipGetLastError();
+}
+
+extern "C" int dcp_launch_exp_tail_fit(void const *null_scores, void const *alt_scores, unsigned nseqs, unsigned nprof,
+                                       int real_bytes, double const *tau, uint32_t const *k_eff, double *mu, double *lambda,
+                                       uint8_t *status, void *stream)
+{
+    if (!null_scores || !alt_scores || !tau || !k_eff || !mu || !lambda || !status || nseqs < 2u || nprof == 0)
+        return (int)hipErrorInvalidValue;
+    unsigned const blocks = (nprof + kFitBlock - 1u) / kFitBlock;
+    hipStream_t const s = (hipStream_t)stream;
+    if (real_bytes == 4)
+        exp_tail_fit_kernel<float><<<blocks, kFitBlock, 0, s>>>((float const *)null_scores, (float const *)alt_scores, nseqs,
+                                                                nprof, tau, k_eff, mu, lambda, status);
+    else if (real_bytes == 8)
+        exp_tail_fit_kernel<double><<<blocks, kFitBlock, 0, s>>>((double const *)null_scores, (double const *)alt_scores,
+                                                                 nseqs, nprof, tau, k_eff, mu, lambda, status);
     else return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }

@@ -150,9 +150,29 @@ static inline int dcp_fwd_args_refused(struct dcp_fwd_args const *a, int R, int 
     return 0;
 }
 
+// The dense Forward scan's lists (dcp_gpu_forward_dense): every resident sequence against every resident profile, the
+// records written on the device.  The outer product in one line: the profiles' classes one after the other (class k
+// holds the profiles prof_order[class_first[k] .. class_first[k + 1]) and the line's positions [nseqs class_first[k],
+// nseqs class_first[k + 1])), within a class sequence-major -- position nseqs class_first[k] + s np + i, np the class's
+// profiles, is (seq_order[s], prof_order[class_first[k] + i]).  A round is positions [t0, t0 + n) of the line: its
+// records go to pairs[0 .. n), so a round's classes lie back to back as the sweeps' launches take them.  pos = q nprof +
+// prof, the dense layout; nseqs nprof fits 32 bits (the caller checks), so every index here does.
+struct dcp_fwd_dense_args
+{
+    uint32_t const *seq_order;  // [nseqs]
+    uint32_t const *prof_order; // [nprof]
+    uint32_t class_first[5];
+    uint32_t nseqs, nprof;
+    uint32_t t0, n;
+    dcp_fwd_pair *pairs; // [n]
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// The records of one round of the dense scan, one thread per record: one launch on `stream`.  != 0: nothing to write, a
+// null pointer, or a round that reaches past the line's end.
+int dcp_forward_dense_pairs_launch(struct dcp_fwd_dense_args const *a, void *stream);
 // The Forward sweep (dcp_forward.hip) and the Backward sweep (dcp_posterior.hip; there is none that stores nothing).
 // precision 32 / 64: the tables' scalar.  R = 1, 2 or 4 nodes per lane with the profile in registers (core sizes up to
 // 64 R), or R = 0: the wide sweep in chunks of DCP_FWD_CHUNK columns through the work area.  store: DCP_FWD_STORE_*.

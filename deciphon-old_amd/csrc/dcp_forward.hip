@@ -16,6 +16,10 @@
 // And a flag MAT, with ROWS: every lane also stores P_k(j) and Q_k(j) of its own columns, rows j = 0 .. L, the matrices
 // the posterior-decoded alignment reads (dcp_mea.h, dcp_gpu_mea_pairs' first sweep).
 //
+//  dense_pairs_kernel        the pair records of one round of the dense scan (dcp_gpu_forward_dense): every resident
+//                            sequence against every resident profile, one thread per record, so that no list of
+//                            pairs is built on the host or copied up (dcp_forward.h: dcp_fwd_dense_args has the order).
+//
 // Real is the tables' scalar (a float DB's values are promoted to double, which is exact); the arithmetic is double.
 // The recursion is the Viterbi one of dcp_f64.hip with every max replaced by lse (dcp_forward.h), every candidate
 // (predecessor + transition) or (predecessor + emission) formed once.  Two things max allowed there do not carry over:
@@ -399,7 +403,34 @@ template <bool ROWS, bool MAT> int launch(int precision, int R, dcp_fwd_args con
     return 1;
 }
 
+// ---- the dense scan's lists: one thread per record of a round (dcp_fwd_dense_args has the order) --------------------
+__global__ __launch_bounds__(256) void dense_pairs_kernel(dcp_fwd_dense_args a)
+{
+    uint32_t const i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= a.n) return;
+    uint32_t const t = a.t0 + i;
+    int k = 0;
+    while (k < 3 && t >= a.nseqs * a.class_first[k + 1])
+        ++k;
+    uint32_t const local = t - a.nseqs * a.class_first[k], np = a.class_first[k + 1] - a.class_first[k];
+    uint32_t const s = local / np;
+    uint32_t const q = a.seq_order[s], prof = a.prof_order[a.class_first[k] + (local - s * np)];
+    a.pairs[i] = dcp_fwd_pair{q, prof, q * a.nprof + prof};
+}
+
 } // namespace
+
+extern "C" int dcp_forward_dense_pairs_launch(struct dcp_fwd_dense_args const *a, void *stream)
+{
+    if (!a || !a->seq_order || !a->prof_order || !a->pairs || a->n == 0 || a->nseqs == 0 || a->nprof == 0) return 1;
+    if (a->class_first[0] != 0 || a->class_first[4] != a->nprof) return 1;
+    for (int k = 0; k < 4; ++k)
+        if (a->class_first[k] > a->class_first[k + 1]) return 1;
+    uint64_t const total = (uint64_t)a->nseqs * a->nprof;
+    if (total > 0xffffffffull || a->n > (1u << 30) || (uint64_t)a->t0 + a->n > total) return 1;
+    hipLaunchKernelGGL(dense_pairs_kernel, dim3((a->n + 255u) / 256u), dim3(256), 0, (hipStream_t)stream, *a);
+    return 0;
+}
 
 extern "C" int dcp_forward_launch(int precision, int R, int store, struct dcp_fwd_args const *a, void *stream)
 {

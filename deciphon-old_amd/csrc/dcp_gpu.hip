@@ -403,6 +403,10 @@ struct dcp_gpu_ctx
     DevBuf<uint32_t> d_tail_keff;
     hipEvent_t ev_tail[4] = {nullptr, nullptr, nullptr, nullptr};
     bool tail_timed = false;
+    // the exponential tail fit (dcp_gpu_fit_exp_tail) goes through the same four buffers; its own events around its
+    // tail_select_kernel ([0], [1]) and its exp_tail_fit_kernel ([2], [3])
+    hipEvent_t ev_exp[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool exp_timed = false;
     // The pair-list sweeps (dcp_gpu_forward_pairs, dcp_gpu_posterior_pairs, dcp_gpu_mea_pairs; dcp_forward.hip,
     // dcp_posterior.hip, dcp_mea.hip).  The three calls are synchronous and share one workspace, kept between calls and
     // grown when a call needs more; nothing of a scan's is written, and a call reads nothing an earlier call left but
@@ -420,8 +424,19 @@ struct dcp_gpu_ctx
     // ev: around the launches of the round in flight.  waves_cap, post_budget, mea_budget: the hooks build's cap on a
     // launch's wavefronts (0: none) and bounds on a round's bytes (0: 1 GiB of row records; 8 GiB of matrices, choices and
     // records).  fwd_ms, post_ms, mea_ms: the kernel time of the last call of each kind, summed over its rounds.
+    // The dense Forward scan (dcp_gpu_forward_dense) runs the same sweeps over every sequence x every profile, its lists
+    // written on the device into d_pairs, and keeps what no pair-list call touches:
+    //  d_dense   [2][nseqs x nprof] null, alt in the scan's dense layout, valid (dense_valid) until the DB, the batch or
+    //            the explicit transitions change (void_forward_dense)
+    //  d_order   the sequences by falling length, then the profiles by class
+    // dense_round: the hooks build's bound on a round's pairs (0: kDenseRound); dense_ms: the last call's launches.
     struct PairSweeps
     {
+        DevBuf<double> d_dense;
+        DevBuf<uint32_t> d_order;
+        bool dense_valid = false;
+        unsigned dense_round = 0;
+        float dense_ms = -1.0f;
         bool profs_ready = false;
         DevBuf<dcp_fwd_prof> d_profs;
         DevBuf<dcp_fwd_pair> d_pairs;
@@ -463,8 +478,16 @@ struct dcp_gpu_ctx
                                "%s: %s", #call, hipGetErrorString(e_));        \
     } while (0)
 
-// A new DB or a new batch: the last scan is void, and so is whatever of it has not been looked at yet.
-static void void_last_scan(dcp_gpu_ctx *c) { c->last = LastScan{}; }
+// The dense Forward matrices are void: whatever they were computed from has changed (the buffer stays for the next call).
+static void void_forward_dense(dcp_gpu_ctx *c) { c->sweeps.dense_valid = false; }
+
+// A new DB or a new batch: the last scan is void, and so is whatever of it has not been looked at yet; and so are the
+// dense Forward matrices.
+static void void_last_scan(dcp_gpu_ctx *c)
+{
+    c->last = LastScan{};
+    void_forward_dense(c);
+}
 
 // What the float and the double path share (templates: outside the extern "C" block)
 extern "C" { static int finish_scan(dcp_gpu_ctx *c); } // defined behind dcp_gpu_scan_range
@@ -785,6 +808,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     for (hipEvent_t e : c->ev_calib)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->ev_tail)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->ev_exp)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sweeps.ev)
         if (e) (void)hipEventDestroy(e);
@@ -2212,6 +2237,7 @@ int dcp_gpu_seqs_set_xtrans(dcp_gpu_ctx *c, float const *xt, unsigned nseqs)
     c->xt_explicit = true;
     c->xt64.clear(); // one explicit set holds: the last one given
     c->xt_multi = c->xt_h3 = -1;
+    void_forward_dense(c);
     return DCP_OK;
 }
 
@@ -2224,6 +2250,7 @@ int dcp_gpu_seqs_set_xtrans64(dcp_gpu_ctx *c, double const *xt, unsigned nseqs)
     c->xt64.assign(xt, xt + (size_t)nseqs * DCP_NXTRANS);
     c->xt_explicit = false; // one explicit set holds: the last one given
     c->xt_multi = c->xt_h3 = -1;
+    void_forward_dense(c);
     return DCP_OK;
 }
 
@@ -3473,12 +3500,31 @@ static dcp_fwd_args forward_args(dcp_gpu_ctx const *c, double const *xt)
 }
 
 // Everything between a call's refusals and its first launch: the DB's layout and profile table, the special transitions
-// and the list's offsets (none: Forward) uploaded anew, room for nscores scores a pair, the events.  a: forward_args,
+// and the list's offsets (none: Forward) uploaded anew, room for nscores scores in d_score, the events.  a: forward_args,
 // with work, row_off and out_null in place.  Returns synchronised if there are offsets, which are the caller's to drop;
 // Forward's transitions go up under the synchronise of its one round's lists (if upload_round fails before that, the
 // copy from W.xt is still queued: the vector is the workspace's and stays).
-static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *profile_idx, unsigned npairs,
-                        unsigned nscores, std::vector<uint64_t> const &off, dcp_fwd_args *a)
+// wide: the wide class's pairs and the widest profile's chunks -- of a list (wide_of_list), or of the dense scan's outer
+// product.
+struct WidePairs
+{
+    uint64_t pairs = 0;
+    unsigned chunks = 0;
+};
+
+static WidePairs wide_of_list(dcp_gpu_ctx const *c, uint32_t const *profile_idx, unsigned npairs)
+{
+    WidePairs w;
+    for (unsigned i = 0; i < npairs; ++i)
+    {
+        unsigned const M = c->core_sizes[profile_idx[i]];
+        if (fwd_class(M) == 3) ++w.pairs, w.chunks = std::max(w.chunks, chunks_of(M));
+    }
+    return w;
+}
+
+static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, WidePairs wide, size_t nscores,
+                        std::vector<uint64_t> const &off, dcp_fwd_args *a)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     auto &W = c->sweeps;
@@ -3490,18 +3536,12 @@ static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint3
     // The wide sweep's work areas, by far the largest of the buffers, come first, as much as any round of this list
     // can ask for (forward_bucket: a round's widest profile and its wavefronts are at most the list's).  Reserved
     // behind the small buffers on a context's first call, a float DB's Forward sweeps measured 1 % slower.
-    unsigned wide = 0, wide_chunks = 0;
-    for (unsigned i = 0; i < npairs; ++i)
-    {
-        unsigned const M = c->core_sizes[profile_idx[i]];
-        if (fwd_class(M) == 3) ++wide, wide_chunks = std::max(wide_chunks, chunks_of(M));
-    }
-    uint64_t wide_waves = std::min<uint64_t>(wide, 4ull * c->num_cus);
+    uint64_t wide_waves = std::min<uint64_t>(wide.pairs, 4ull * c->num_cus);
     if (W.waves_cap) wide_waves = std::min<uint64_t>(wide_waves, W.waves_cap);
-    HIP_TRY(c, W.d_work.reserve((uint64_t)DCP_FWD_WORK_ROWS * wide_chunks * DCP_FWD_CHUNK * wide_waves));
+    HIP_TRY(c, W.d_work.reserve((uint64_t)DCP_FWD_WORK_ROWS * wide.chunks * DCP_FWD_CHUNK * wide_waves));
     HIP_TRY(c, W.d_off.reserve(off.size()));
     HIP_TRY(c, W.d_xt.reserve(xt.size()));
-    HIP_TRY(c, W.d_score.reserve((size_t)nscores * npairs));
+    HIP_TRY(c, W.d_score.reserve(nscores));
     for (hipEvent_t &e : W.ev)
         if (!e) HIP_TRY(c, hipEventCreate(&e));
     HIP_TRY(c, hipMemcpyAsync(W.d_xt.p, xt.data(), xt.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -3609,7 +3649,7 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
     if (npairs == 0) return DCP_OK;
     auto &W = c->sweeps;
     dcp_fwd_args a{};
-    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 2u, {}, &a)) return rc;
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)2u * npairs, {}, &a)) return rc;
     ForwardBuckets b;
     if (int rc = upload_round(c, seq_idx, profile_idx, 0u, npairs, false, b, a)) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the transitions and the list are up (and whatever was outstanding is done)
@@ -3629,6 +3669,107 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
 }
 
 float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.fwd_ms : -1.0f; }
+
+// ---- The dense Forward scan: every resident sequence x every resident profile --------------------------
+// The host orders the profiles (by class, the wide ones by falling chunk count) and the sequences (by falling length),
+// nothing per pair: the outer product is a line of positions (dcp_fwd_dense_args), a round is at most kDenseRound
+// consecutive positions of it, its records written by dense_pairs_kernel into d_pairs, where the classes of a round lie
+// back to back for run_sweeps.  Everything is queued on the stream without a wait between rounds: the list kernel of
+// round r + 1 runs behind the sweeps of round r that read d_pairs.
+static constexpr unsigned kDenseRound = 1u << 22; // pairs: 48 MiB of records
+
+int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
+{
+    if (!c) return DCP_EINVAL;
+    if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
+    if (c->nseqs == 0) return c->fail(DCP_EINVAL, "no sequences resident");
+    if (int rc = check_xtrans_precision(c)) return rc;
+    uint64_t const total64 = (uint64_t)c->nseqs * c->nprof;
+    if (total64 > 0xffffffffull)
+        return c->fail(DCP_EINVAL, "%u sequences x %u profiles exceed the 2^32 - 1 pairs of one dense Forward scan", c->nseqs, c->nprof);
+    unsigned const total = (unsigned)total64, nseqs = c->nseqs, nprof = c->nprof;
+    auto &W = c->sweeps;
+    W.dense_valid = false; // the buffer is about to be written
+
+    // the two orders: [nseqs] sequences by falling length, [nprof] profiles by class, the wide ones by falling chunk count
+    // (equals keep the caller's order)
+    ForwardBuckets b;
+    std::vector<uint32_t> order(nseqs);
+    std::iota(order.begin(), order.end(), 0u);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return c->seq_len[x] > c->seq_len[y]; });
+    unsigned cfirst[5];
+    std::vector<unsigned> porder = sort_into_classes(nprof, 4, cfirst, [&](unsigned i) { return fwd_class(c->core_sizes[i]); });
+    std::stable_sort(porder.begin() + cfirst[3], porder.end(),
+                     [&](unsigned x, unsigned y) { return chunks_of(c->core_sizes[x]) > chunks_of(c->core_sizes[y]); });
+    order.insert(order.end(), porder.begin(), porder.end());
+    WidePairs wide;
+    if (cfirst[4] > cfirst[3]) wide.pairs = (uint64_t)nseqs * (cfirst[4] - cfirst[3]), wide.chunks = chunks_of(c->core_sizes[porder[cfirst[3]]]);
+
+    dcp_fwd_args a{};
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide, 0u, {}, &a)) return rc;
+    HIP_TRY(c, W.d_dense.reserve(2u * (size_t)total));
+    HIP_TRY(c, W.d_order.reserve(order.size()));
+    unsigned const round = std::min(W.dense_round ? W.dense_round : kDenseRound, kDenseRound);
+    HIP_TRY(c, W.d_pairs.reserve(std::min(round, total)));
+    HIP_TRY(c, hipMemcpyAsync(W.d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the transitions and the orders are up (and whatever was outstanding is done)
+    a.out_null = W.d_dense.p;
+    a.work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide.chunks * DCP_FWD_CHUNK;
+    dcp_fwd_dense_args d{};
+    d.seq_order = W.d_order.p, d.prof_order = W.d_order.p + nseqs;
+    std::copy(cfirst, cfirst + 5, d.class_first);
+    d.nseqs = nseqs, d.nprof = nprof;
+    d.pairs = W.d_pairs.p;
+    HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+    for (uint64_t t0 = 0; t0 < total; t0 += round)
+    {
+        uint64_t const t1 = std::min<uint64_t>(t0 + round, total);
+        d.t0 = (uint32_t)t0, d.n = (uint32_t)(t1 - t0);
+        if (dcp_forward_dense_pairs_launch(&d, c->stream)) return c->fail(DCP_EFAIL, "the dense scan's list kernel refused its round");
+        HIP_TRY(c, hipGetLastError());
+        // the part of each class in [t0, t1): the classes follow each other on the line, so in d_pairs too
+        for (int k = 0; k < 4; ++k)
+        {
+            uint64_t const lo = std::max<uint64_t>(t0, (uint64_t)nseqs * cfirst[k]), hi = std::min<uint64_t>(t1, (uint64_t)nseqs * cfirst[k + 1]);
+            b.count[k] = hi > lo ? (unsigned)(hi - lo) : 0u;
+            b.first[k + 1] = b.first[k] + b.count[k];
+            b.waves[k] = (unsigned)std::min<uint64_t>(b.count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
+            if (W.waves_cap) b.waves[k] = std::min(b.waves[k], W.waves_cap);
+        }
+        if (int rc = run_sweeps(c, a, b, 1, DCP_FWD_STORE_NONE, total, 0u, 0u)) return rc;
+    }
+    HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    W.dense_ms = ms;
+    W.dense_valid = true;
+    return DCP_OK;
+}
+
+static int forward_dense_ready(dcp_gpu_ctx *c)
+{
+    if (c->sweeps.dense_valid) return DCP_OK;
+    return c->fail(DCP_EINVAL, "no dense Forward scores: none computed by dcp_gpu_forward_dense since the DB, the batch or the "
+                               "explicit transitions last changed");
+}
+
+int dcp_gpu_fetch_forward_scores(dcp_gpu_ctx *c, double *null_out, double *alt_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!null_out || !alt_out) return c->fail(DCP_EINVAL, "dcp_gpu_fetch_forward_scores: a null output");
+    if (int rc = forward_dense_ready(c)) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    size_t const total = (size_t)c->nseqs * c->nprof;
+    // into a buffer of the call's own first: the caller's arrays stay untouched if the copy fails
+    std::vector<double> out(2u * total);
+    HIP_TRY(c, hipMemcpy(out.data(), c->sweeps.d_dense.p, out.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(null_out, out.data(), total * sizeof(double));
+    std::memcpy(alt_out, out.data() + total, total * sizeof(double));
+    return DCP_OK;
+}
+
+float dcp_gpu_forward_dense_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.dense_ms : -1.0f; }
 
 // ---- Backward sweep and posterior rows of a pair list (dcp_posterior.hip) -------------------------------------------
 // The list runs in rounds of consecutive pairs whose row records -- 2 x DCP_POST_REC doubles a row -- fit the budget (a
@@ -3655,7 +3796,7 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
     }
     auto &W = c->sweeps;
     dcp_fwd_args a{};
-    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 3u, off, &a)) return rc;
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)3u * npairs, off, &a)) return rc;
     // a round's row records fit the budget; room for the largest round's before the first one runs
     uint64_t const budget = W.post_budget ? W.post_budget : (uint64_t)1u << 30;
     auto const bytes_of = [&](unsigned i0, unsigned i1) { return (off[i1] - off[i0]) * (2u * DCP_POST_REC * sizeof(double)); };
@@ -3750,7 +3891,7 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_
     }
     auto &W = c->sweeps;
     dcp_fwd_args a{};
-    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, profile_idx, npairs, 4u, off, &a)) return rc;
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)4u * npairs, off, &a)) return rc;
     a.cell_off = W.d_off.p + no;
     uint64_t const budget = W.mea_budget ? W.mea_budget : (uint64_t)8u << 30;
     auto const bytes_of = [&](unsigned i0, unsigned i1) {
@@ -4023,6 +4164,13 @@ int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *c, unsigned nwaves)
 {
     if (!c) return DCP_EINVAL;
     c->sweeps.waves_cap = nwaves;
+    return DCP_OK;
+}
+
+int dcp_gpu_test_set_dense_round(dcp_gpu_ctx *c, unsigned npairs)
+{
+    if (!c) return DCP_EINVAL;
+    c->sweeps.dense_round = npairs;
     return DCP_OK;
 }
 
@@ -4302,6 +4450,88 @@ int dcp_gpu_db_calibrate_tail(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint
         return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the sequences asked for", k, nseqs);
     if (int rc = calibration_scan(c, nseqs, len, seed, probs, multi_hits, hmmer3_compat, kernel)) return rc;
     return dcp_gpu_fit_gumbel_tail(c, k, mu_out, lambda_out, status_out, tau_out, k_eff_out);
+}
+
+// The exponential tail fit: the same selection, then the closed-form fit (dcp_calib.hip), over the last scan's dense
+// matrices or the last dense Forward ones.
+int dcp_gpu_fit_exp_tail(dcp_gpu_ctx *c, int source, unsigned k, double *mu_out, double *lambda_out, uint8_t *status_out,
+                         double *tau_out, uint32_t *k_eff_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out || !tau_out || !k_eff_out)
+        return c->fail(DCP_EINVAL, "dcp_gpu_fit_exp_tail: a null output");
+    void const *nl = nullptr, *al = nullptr;
+    int real_bytes = 8;
+    if (source == DCP_SCORES_SCAN)
+    {
+        if (int rc = fit_ready(c)) return rc;
+        nl = c->last.f64 ? (void const *)c->f64.res.d_null.p : (void const *)c->res.d_null.p;
+        al = c->last.f64 ? (void const *)c->f64.res.d_alt.p : (void const *)c->res.d_alt.p;
+        real_bytes = c->last.f64 ? 8 : 4;
+    }
+    else if (source == DCP_SCORES_FORWARD)
+    {
+        if (int rc = forward_dense_ready(c)) return rc;
+        if (c->nseqs < 2u) return c->fail(DCP_EINVAL, "a fit needs at least 2 sequences: %u resident", c->nseqs);
+        HIP_TRY(c, hipSetDevice(c->device));
+        nl = c->sweeps.d_dense.p, al = c->sweeps.d_dense.p + (size_t)c->nseqs * c->nprof;
+    }
+    else return c->fail(DCP_EINVAL, "dcp_gpu_fit_exp_tail: source %d is neither DCP_SCORES_SCAN nor DCP_SCORES_FORWARD", source);
+    if (k < 2u || k > c->nseqs)
+        return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the resident sequences", k, c->nseqs);
+    unsigned const np = c->nprof;
+    HIP_TRY(c, c->d_fit.reserve(2u * (size_t)np));
+    HIP_TRY(c, c->d_fit_status.reserve(np));
+    HIP_TRY(c, c->d_tail_tau.reserve(np));
+    HIP_TRY(c, c->d_tail_keff.reserve(np));
+    for (hipEvent_t &e : c->ev_exp)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    HIP_TRY(c, hipEventRecord(c->ev_exp[0], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_tail_select(nl, al, c->nseqs, np, real_bytes, k, c->d_tail_tau.p, c->d_tail_keff.p,
+                                                   c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_exp[1], c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_exp[2], c->stream));
+    HIP_TRY(c, (hipError_t)dcp_launch_exp_tail_fit(nl, al, c->nseqs, np, real_bytes, c->d_tail_tau.p, c->d_tail_keff.p,
+                                                    c->d_fit.p, c->d_fit.p + np, c->d_fit_status.p, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_exp[3], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->exp_timed = true;
+    // into buffers of the call's own first: the caller's arrays stay untouched if a copy fails
+    std::vector<double> fit(3u * (size_t)np);
+    std::vector<uint32_t> ke(np);
+    std::vector<uint8_t> st(np);
+    HIP_TRY(c, hipMemcpy(fit.data(), c->d_fit.p, 2u * (size_t)np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(fit.data() + 2u * (size_t)np, c->d_tail_tau.p, np * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ke.data(), c->d_tail_keff.p, np * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(st.data(), c->d_fit_status.p, np, hipMemcpyDeviceToHost));
+    std::memcpy(mu_out, fit.data(), np * sizeof(double));
+    std::memcpy(lambda_out, fit.data() + np, np * sizeof(double));
+    std::memcpy(tau_out, fit.data() + 2u * (size_t)np, np * sizeof(double));
+    std::memcpy(k_eff_out, ke.data(), np * sizeof(uint32_t));
+    std::memcpy(status_out, st.data(), np);
+    return DCP_OK;
+}
+
+int dcp_gpu_db_calibrate_forward(dcp_gpu_ctx *c, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4],
+                                 int multi_hits, int hmmer3_compat, unsigned k, double *mu_out, double *lambda_out,
+                                 uint8_t *status_out, double *tau_out, uint32_t *k_eff_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (!mu_out || !lambda_out || !status_out || !tau_out || !k_eff_out)
+        return c->fail(DCP_EINVAL, "dcp_gpu_db_calibrate_forward: a null output");
+    if (nseqs != 0 && (k < 2u || k > nseqs)) // before the batch is replaced (nseqs == 0 is the generator's refusal)
+        return c->fail(DCP_EINVAL, "the tail count k = %u is outside 2 .. %u, the sequences asked for", k, nseqs);
+    if (int rc = dcp_gpu_seqs_random(c, nseqs, len, seed, probs)) return rc;
+    if (int rc = dcp_gpu_forward_dense(c, multi_hits, hmmer3_compat)) return rc;
+    return dcp_gpu_fit_exp_tail(c, DCP_SCORES_FORWARD, k, mu_out, lambda_out, status_out, tau_out, k_eff_out);
+}
+
+float dcp_gpu_exp_tail_kernel_ms(dcp_gpu_ctx *c, int which)
+{
+    float ms = -1.0f;
+    if (!c || which < 0 || which > 1 || !c->exp_timed) return -1.0f;
+    if (hipEventElapsedTime(&ms, c->ev_exp[2 * which], c->ev_exp[2 * which + 1]) != hipSuccess) return -1.0f;
+    return ms;
 }
 
 float dcp_gpu_calib_tail_kernel_ms(dcp_gpu_ctx *c, int which)

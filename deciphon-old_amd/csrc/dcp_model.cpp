@@ -1800,6 +1800,38 @@ int dcp_gumbel_fit_tail(double const *x, unsigned n, size_t stride, unsigned k, 
 
 double dcp_gumbel_sf(double mu, double lambda, double s) { return -std::expm1(-std::exp(-lambda * (s - mu))); }
 
+int dcp_exp_tail_fit(double const *x, unsigned n, size_t stride, unsigned k, double *mu, double *lambda, double *tau,
+                     unsigned *k_eff)
+{
+    if (!x || !mu || !lambda || !tau || !k_eff || n < 2u || stride == 0 || k < 2u || k > n) return DCP_EINVAL;
+    auto const at = [=](unsigned i) { return x[(size_t)i * stride]; };
+    *mu = *lambda = dcp_fit_nan();
+    if (int st = dcp_tail_select_rule(at, n, k, tau, k_eff)) return st;
+    return dcp_exp_tail_fit_rule(at, n, *tau, *k_eff, mu, lambda);
+}
+
+double dcp_exp_sf(double mu, double lambda, double s) { return s <= mu ? 1.0 : std::exp(-lambda * (s - mu)); }
+
+int dcp_scores_evalues(uint32_t const *profile_idx, double const *null, double const *alt, unsigned n, double const *mu,
+                       double const *lambda, uint8_t const *status, unsigned nprofiles, double nsearched, int law,
+                       double *evalue_out)
+{
+    if (!std::isfinite(nsearched) || nsearched < 0.0) return DCP_EINVAL;
+    if (law != DCP_LAW_GUMBEL && law != DCP_LAW_EXP) return DCP_EINVAL;
+    if (n == 0) return DCP_OK;
+    if (!profile_idx || !null || !alt || !mu || !lambda || !status || !evalue_out) return DCP_EINVAL;
+    for (unsigned i = 0; i < n; ++i) // everything is checked before anything is written
+        if (profile_idx[i] >= nprofiles) return DCP_EINVAL;
+    for (unsigned i = 0; i < n; ++i)
+    {
+        uint32_t const p = profile_idx[i];
+        double const s = alt[i] - null[i];
+        double const sf = law == DCP_LAW_EXP ? dcp_exp_sf(mu[p], lambda[p], s) : dcp_gumbel_sf(mu[p], lambda[p], s);
+        evalue_out[i] = status[p] == DCP_FIT_OK ? nsearched * sf : dcp_fit_nan();
+    }
+    return DCP_OK;
+}
+
 } // extern "C"
 
 namespace

@@ -43,7 +43,12 @@ int dcp_gpu_test_last_pair_launches(dcp_gpu_ctx *, unsigned *out, unsigned cap, 
 // pairs per wavefront, of whatever widths follow each other in the class's list); 0 restores the default.  Results
 // must not change with it.
 // (dcp_gpu_posterior_pairs' launches take the same cap.)
+// (dcp_gpu_forward_dense's launches take it as well.)
 int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *, unsigned nwaves);
+// Bound, in pairs, on a round of each of the following dcp_gpu_forward_dense calls: a small one makes the outer product
+// run in several rounds, whose boundaries fall inside classes and between them; 0, or more than the default, restores
+// the default (2^22 pairs).  Results must not change with it.
+int dcp_gpu_test_set_dense_round(dcp_gpu_ctx *, unsigned npairs);
 // Bound, in bytes, on the device memory of the row records of each of the following dcp_gpu_posterior_pairs calls: a
 // small one makes the list run in several rounds; 0 restores the default (1 GiB).  Results must not change with it.
 int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *, unsigned long long bytes);

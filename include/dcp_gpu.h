@@ -941,6 +941,73 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint
 float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *);
 
 /* ------------------------------------------------------------------------ */
+/* Forward E-values: the dense Forward scan and the exponential tail fit */
+/* ------------------------------------------------------------------------ */
+/* Every resident sequence against every resident profile with the Forward kernels: two nseqs x nprofiles double
+ * matrices, null and alt, left on the device in the scan's dense layout, entry [q * nprofiles + p].  Every entry has the
+ * bits dcp_gpu_forward_pairs returns for that pair with the same flags, whatever batch is resident and whichever
+ * transitions hold.  No list of pairs exists on the host: it orders the profiles (by the kernels' classes, the wide ones by
+ * falling width) and the sequences (by falling length), and a small kernel writes each round's pair records -- at most
+ * 2^22 of them -- on the device; the order is a matter of speed alone.  nseqs x nprofiles above 2^32 - 1 is DCP_EINVAL.
+ * The buffer is the call's own: a later scan or pair-list call (Forward, posterior, decoded alignment) leaves it as it
+ * is, and this call leaves the last scan's hits, dense scores, hit buffer and accounting what they were.  The matrices
+ * are void from the moment the DB or the batch is replaced (an upload, dcp_gpu_seqs_random, ..._add_revcomp,
+ * ..._cut_windows, ..._cut_regions) or explicit transitions are set; a call that fails leaves them void as well.  The
+ * call runs on the context's stream behind whatever is outstanding and returns synchronised.  DCP_EINVAL with a
+ * message: no DB or no batch resident, explicit transitions of the other precision. */
+int dcp_gpu_forward_dense(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat);
+/* The two matrices: null_out / alt_out [nseqs * nprofiles] doubles.  DCP_EINVAL with a message, outputs untouched: a
+ * null pointer, or matrices that are void or were never computed. */
+int dcp_gpu_fetch_forward_scores(dcp_gpu_ctx *, double *null_out, double *alt_out);
+/* Milliseconds, by HIP events around all launches (every round's list kernel and sweeps) of the context's last
+ * dcp_gpu_forward_dense that ran to its end; negative before. */
+float dcp_gpu_forward_dense_kernel_ms(dcp_gpu_ctx *);
+
+/* The upper tail of Forward scores is taken as exponential: P(X >= s) = exp(-lambda (s - mu)) for s >= mu.  The censored
+ * maximum-likelihood fit is closed-form.  tau, the k-th largest by value, and k_eff = #{x >= tau} are dcp_gumbel_fit_tail's
+ * (the same selection).  Pass 1 over all n: a non-finite x is DCP_FIT_NONFINITE.  Pass 2: so = sum (x - tau) over the
+ * x >= tau in index order; so == 0 -- the whole observed set sits at tau -- is DCP_FIT_FLAT.  lambda = k_eff / so, and
+ * mu = tau + log(k_eff / n) / lambda, so that the law is (k_eff / n) exp(-lambda (s - tau)): the observed fraction at tau.
+ * With k = n, mu = tau = the minimum.  There is no iteration and no DCP_FIT_DIVERGED.  tau and k_eff are written with every
+ * status but DCP_FIT_NONFINITE, which writes NaN and 0; mu and lambda are NaN with every status but DCP_FIT_OK.
+ * DCP_EINVAL, nothing written: n < 2, stride == 0, k < 2, k > n, a null pointer.  No device.
+ *
+ * The law holds from tau[p] up only: a score below tau[p] has a survival of at least k_eff / n under it and is not
+ * calibrated (below mu the survival is 1). */
+int dcp_exp_tail_fit(double const *x, unsigned n, size_t stride, unsigned k, double *mu, double *lambda, double *tau,
+                     unsigned *k_eff);
+/* Which dense matrices a device fit reads: the last scan's (float or double, dcp_gpu_fit_gumbel_tail's preconditions and
+ * messages) or the last dcp_gpu_forward_dense's (doubles; DCP_EINVAL with a message while they are void, or with fewer
+ * than 2 sequences resident). */
+enum { DCP_SCORES_SCAN = 0, DCP_SCORES_FORWARD = 1 };
+/* The same fit, one lane per resident profile, of x_q = alt[q][p] - null[q][p]: two launches (csrc/dcp_calib.hip: the
+ * selection of dcp_gpu_fit_gumbel_tail, then exp_tail_fit_kernel).  Given the same scores, tau, k_eff, status and lambda
+ * are the host twin's bits -- comparisons, ordered sums, one division; mu differs by the side's log.  Outputs as
+ * dcp_gpu_fit_gumbel_tail's, untouched on every error; k < 2 or k > the resident sequences and an unknown source are
+ * DCP_EINVAL with a message.  Returns synchronised. */
+int dcp_gpu_fit_exp_tail(dcp_gpu_ctx *, int source, unsigned k, double *mu_out, double *lambda_out, uint8_t *status_out,
+                         double *tau_out, uint32_t *k_eff_out);
+/* Milliseconds, by HIP events around the kernel alone, of the last dcp_gpu_fit_exp_tail's tail_select_kernel (which = 0)
+ * or exp_tail_fit_kernel (1); negative if none has run.  (dcp_gpu_calib_tail_kernel_ms does not see these launches.) */
+float dcp_gpu_exp_tail_kernel_ms(dcp_gpu_ctx *, int which);
+/* Exactly three steps: dcp_gpu_seqs_random(nseqs, len, seed, probs), dcp_gpu_forward_dense(multi_hits, hmmer3_compat),
+ * dcp_gpu_fit_exp_tail(DCP_SCORES_FORWARD, k); the first failing step's code.  A null output, or k < 2 or k > nseqs, is
+ * refused before the batch is replaced.  The random batch and the matrices stay resident. */
+int dcp_gpu_db_calibrate_forward(dcp_gpu_ctx *, unsigned nseqs, unsigned len, uint64_t seed, double const probs[4],
+                                 int multi_hits, int hmmer3_compat, unsigned k, double *mu_out, double *lambda_out,
+                                 uint8_t *status_out, double *tau_out, uint32_t *k_eff_out);
+/* P(X >= s) under the exponential law: 1 for s <= mu, else exp(-lambda (s - mu)). */
+double dcp_exp_sf(double mu, double lambda, double s);
+/* dcp_hits_evalues for scores that are not hit records -- the arrays dcp_gpu_forward_pairs and dcp_gpu_scan_pairs
+ * return: evalue_out[i] = nsearched * sf(mu[p], lambda[p], alt[i] - null[i]), p = profile_idx[i], sf = dcp_gumbel_sf
+ * (DCP_LAW_GUMBEL) or dcp_exp_sf (DCP_LAW_EXP).  NaN where status[p] != DCP_FIT_OK.  DCP_EINVAL, nothing written: a
+ * profile_idx >= nprofiles, a null pointer with n > 0, nsearched not finite or negative, an unknown law. */
+enum { DCP_LAW_GUMBEL = 0, DCP_LAW_EXP = 1 };
+int dcp_scores_evalues(uint32_t const *profile_idx, double const *null, double const *alt, unsigned n, double const *mu,
+                       double const *lambda, uint8_t const *status, unsigned nprofiles, double nsearched, int law,
+                       double *evalue_out);
+
+/* ------------------------------------------------------------------------ */
 /* Backward sweep and posterior decoding for a list of pairs                   */
 /* ------------------------------------------------------------------------ */
 /* With the Backward value of a state at row j -- the log of the summed weight of all path suffixes from it to the end

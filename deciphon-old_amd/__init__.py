@@ -106,6 +106,10 @@ ABI_SYMBOLS = [
     "dcp_gpu_forward_dense", "dcp_gpu_fetch_forward_scores", "dcp_gpu_forward_dense_kernel_ms", "dcp_exp_tail_fit",
     "dcp_gpu_fit_exp_tail", "dcp_gpu_exp_tail_kernel_ms", "dcp_gpu_db_calibrate_forward", "dcp_exp_sf",
     "dcp_scores_evalues",
+    # the scaled probability-space Forward sweep: pair lists and the dense scan, the host twin, the float factor rule
+    "dcp_fwd_factor_f32", "dcp_forward_scaled_tables", "dcp_forward_scaled_tables_band", "dcp_gpu_forward_pairs_scaled",
+    "dcp_gpu_forward_scaled_redo_pairs", "dcp_gpu_forward_scaled_kernel_ms", "dcp_gpu_forward_dense_scaled",
+    "dcp_gpu_forward_dense_is_scaled",
 ]
 
 
@@ -309,6 +313,16 @@ def _load(path=None, hooks=False):
         "dcp_gpu_mea_pairs": (I, [P, I, I, P, P, U, P, U, P, P, P, P]),
         "dcp_gpu_mea_kernel_ms": (F, [P]),
         "dcp_gpu_forward_dense": (I, [P, I, I]),
+        "dcp_fwd_factor_f32": (C.c_double, [C.c_float]),
+        "dcp_forward_scaled_tables": (I, [U, U, P, P, P, P, P, P, U, I, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                          C.POINTER(I)]),
+        "dcp_forward_scaled_tables_band": (I, [U, U, P, P, P, P, P, P, U, I, I, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                               C.POINTER(I)]),
+        "dcp_gpu_forward_pairs_scaled": (I, [P, I, I, P, P, U, P, P]),
+        "dcp_gpu_forward_scaled_redo_pairs": (U, [P]),
+        "dcp_gpu_forward_scaled_kernel_ms": (F, [P]),
+        "dcp_gpu_forward_dense_scaled": (I, [P, I, I]),
+        "dcp_gpu_forward_dense_is_scaled": (I, [P]),
         "dcp_gpu_fetch_forward_scores": (I, [P, P, P]),
         "dcp_gpu_forward_dense_kernel_ms": (F, [P]),
         "dcp_exp_tail_fit": (I, [P, U, C.c_size_t, U, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -331,6 +345,7 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_last_pair_launches"] = (I, [P, P, U, C.POINTER(U)])
         sig["dcp_gpu_test_set_forward_waves"] = (I, [P, U])
         sig["dcp_gpu_test_set_dense_round"] = (I, [P, U])
+        sig["dcp_gpu_test_set_forward_scale_band"] = (I, [P, U])
         sig["dcp_gpu_test_set_posterior_budget"] = (I, [P, C.c_ulonglong])
         sig["dcp_gpu_test_set_mea_budget"] = (I, [P, C.c_ulonglong])
     for name, (res, args) in sig.items():
@@ -684,6 +699,34 @@ def forward_tables(t8, em, ei, en, xt, seq):
     if rc:
         raise DcpError(rc, "dcp_forward_tables")
     return null.value, alt.value
+
+
+def fwd_factor_f32(t):
+    """exp(t) of the float32 t as the scaled Forward sweeps form it on a float DB (dcp_fwd_factor_f32): float
+    arithmetic alone, the same bits on host and device.  0 below -708 and for -inf, +inf above 708."""
+    return lib.dcp_fwd_factor_f32(float(np.float32(t)))
+
+
+def forward_scaled_tables(t8, em, ei, en, xt, seq, float_factors=False, band=None):
+    """(null, alt, out_of_range) of one sequence against one profile by the scaled probability-space Forward on the
+    host (dcp_forward_scaled_tables): forward_tables' arguments; float_factors applies the float DB's factor rule to
+    float32(t) of every table value, else exp(t) in double.  out_of_range: a value left the double range and the two
+    scores are None.  band (tests): the rescaling rule's band in bits, which the scores do not depend on."""
+    t8, em, ei, en, xt = _f64(t8), _f64(em), _f64(ei), _f64(en), _f64(xt)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if t8.ndim != 2 or em.ndim != 2 or t8.shape != (8, em.shape[1]) or em.shape[0] != NCODES or \
+            ei.shape != (NCODES,) or en.shape != (NCODES,) or xt.shape != (NXTRANS,) or seq.ndim != 1:
+        raise DcpError(RC_EINVAL, "tables of shapes [8, ldk], [1364, ldk], [1364], [1364], [13]")
+    null, alt, oor = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    args = (em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data, xt.ctypes.data,
+            seq.ctypes.data, len(seq), int(bool(float_factors)))
+    outs = (C.byref(null), C.byref(alt), C.byref(oor))
+    rc = lib.dcp_forward_scaled_tables(*args, *outs) if band is None else lib.dcp_forward_scaled_tables_band(*args, int(band), *outs)
+    if rc:
+        raise DcpError(rc, "dcp_forward_scaled_tables")
+    if oor.value:
+        return None, None, True
+    return null.value, alt.value, False
 
 
 def posterior_tables(t8, em, ei, en, xt, seq):
@@ -1432,6 +1475,41 @@ class Scanner:
     def forward_kernel_ms(self):
         """Milliseconds of the last forward_pairs call's kernel launches, by HIP events; negative before any."""
         return self._lib.dcp_gpu_forward_kernel_ms(self._c)
+
+    def forward_pairs_scaled(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
+        """forward_pairs by the scaled probability-space sweep (dcp_gpu_forward_pairs_scaled): no log and one exp per
+        table value in the loop.  The same lists, batches and refusals; scores within 2^-32 (|x| + 1) of forward_pairs'
+        on a double DB and within DESIGN 24's looser allowance on a float DB.  Pairs whose values leave the double range
+        are rerun by forward_pairs' kernels in the same call (last_forward_scaled_redo_pairs) and have its bits."""
+        sq, pr = _pair_list(seq_idx, profile_idx)
+        null, alt = np.zeros(len(sq), np.float64), np.zeros(len(sq), np.float64)
+        self._check(self._lib.dcp_gpu_forward_pairs_scaled(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data,
+                                                           pr.ctypes.data, len(sq), null.ctypes.data, alt.ctypes.data))
+        return null, alt
+
+    @property
+    def last_forward_scaled_redo_pairs(self):
+        """How many pairs the last forward_pairs_scaled or forward_dense_scaled reran in log space."""
+        return self._lib.dcp_gpu_forward_scaled_redo_pairs(self._c)
+
+    @property
+    def forward_scaled_kernel_ms(self):
+        """Milliseconds of the last forward_pairs_scaled call's launches, the rerun's included; negative before any."""
+        return self._lib.dcp_gpu_forward_scaled_kernel_ms(self._c)
+
+    def forward_dense_scaled(self, multi_hits=True, hmmer3_compat=False):
+        """forward_dense by the scaled sweep (dcp_gpu_forward_dense_scaled): forward_pairs_scaled's bits in the same
+        matrices, for forward_scores and fit_exp_tail unchanged."""
+        self._check(self._lib.dcp_gpu_forward_dense_scaled(self._c, int(multi_hits), int(hmmer3_compat)))
+
+    @property
+    def forward_dense_is_scaled(self):
+        """Whether the dense Forward matrices were filled by forward_dense_scaled."""
+        return bool(self._lib.dcp_gpu_forward_dense_is_scaled(self._c))
+
+    def test_set_forward_scale_band(self, bits):
+        """TEST-ONLY (test-hooks build): the band of the scaled sweeps' rescaling rule in bits (0: the default, 64)."""
+        self._check(self._lib.dcp_gpu_test_set_forward_scale_band(self._c, int(bits)))
 
     def test_set_forward_waves(self, nwaves):
         """TEST-ONLY (test-hooks build): cap the wavefronts of the following forward_pairs launches (0: default)."""

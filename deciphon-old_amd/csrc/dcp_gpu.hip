@@ -12,6 +12,7 @@
 #include "dcp_domains.h"
 #include "dcp_calib.h"
 #include "dcp_forward.h"
+#include "dcp_forward_scaled.h"
 #include "dcp_mea.h"
 #include "dcp_posterior.h"
 #include "dcp_test_hooks.h"
@@ -430,8 +431,19 @@ struct dcp_gpu_ctx
     //            the explicit transitions change (void_forward_dense)
     //  d_order   the sequences by falling length, then the profiles by class
     // dense_round: the hooks build's bound on a round's pairs (0: kDenseRound); dense_ms: the last call's launches.
+    // The scaled sweeps (dcp_gpu_forward_pairs_scaled, dcp_gpu_forward_dense_scaled; dcp_forward_scaled.hip) add:
+    //  d_redo    the pairs a round's scaled launches could not sweep, appended on the device;  d_nredo: how many
+    //  d_redo_pairs  the same bucketed by class for the log-space kernels
+    // band: the hooks build's band of the rescaling rule (0: DCP_FWS_BAND); scaled_ms, scaled_redo: the last scaled
+    // pair-list call's launches, the last scaled call's rerun pairs; dense_scaled: which sweep filled d_dense.
     struct PairSweeps
     {
+        DevBuf<dcp_fwd_pair> d_redo, d_redo_pairs;
+        DevBuf<uint32_t> d_nredo;
+        int band = 0;
+        float scaled_ms = -1.0f;
+        unsigned scaled_redo = 0;
+        bool dense_scaled = false;
         DevBuf<double> d_dense;
         DevBuf<uint32_t> d_order;
         bool dense_valid = false;
@@ -3524,7 +3536,7 @@ static WidePairs wide_of_list(dcp_gpu_ctx const *c, uint32_t const *profile_idx,
 }
 
 static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, WidePairs wide, size_t nscores,
-                        std::vector<uint64_t> const &off, dcp_fwd_args *a)
+                        std::vector<uint64_t> const &off, dcp_fwd_args *a, unsigned work_rows = DCP_FWD_WORK_ROWS)
 {
     HIP_TRY(c, hipSetDevice(c->device));
     auto &W = c->sweeps;
@@ -3538,7 +3550,7 @@ static int sweeps_setup(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, WideP
     // behind the small buffers on a context's first call, a float DB's Forward sweeps measured 1 % slower.
     uint64_t wide_waves = std::min<uint64_t>(wide.pairs, 4ull * c->num_cus);
     if (W.waves_cap) wide_waves = std::min<uint64_t>(wide_waves, W.waves_cap);
-    HIP_TRY(c, W.d_work.reserve((uint64_t)DCP_FWD_WORK_ROWS * wide.chunks * DCP_FWD_CHUNK * wide_waves));
+    HIP_TRY(c, W.d_work.reserve((uint64_t)work_rows * wide.chunks * DCP_FWD_CHUNK * wide_waves));
     HIP_TRY(c, W.d_off.reserve(off.size()));
     HIP_TRY(c, W.d_xt.reserve(xt.size()));
     HIP_TRY(c, W.d_score.reserve(nscores));
@@ -3670,6 +3682,110 @@ int dcp_gpu_forward_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uin
 
 float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.fwd_ms : -1.0f; }
 
+// ---- The scaled probability-space sweeps (dcp_forward_scaled.hip) ----------------------------------------
+// A round's scaled launches over its classes, the pairs at d_pairs as run_sweeps takes them; alt goes `stride` scores
+// behind null.  The round's redo list starts empty and has room for every pair of the round.
+static int run_scaled_sweeps(dcp_gpu_ctx *c, dcp_fwd_args &a, ForwardBuckets const &b, size_t stride)
+{
+    auto &W = c->sweeps;
+    unsigned const n = b.first[4];
+    HIP_TRY(c, W.d_redo.reserve(n));
+    HIP_TRY(c, W.d_nredo.reserve(1u));
+    HIP_TRY(c, hipMemsetAsync(W.d_nredo.p, 0, sizeof(uint32_t), c->stream));
+    a.out_alt = a.out_null + stride;
+    for (int k = 0; k < 4; ++k)
+    {
+        if (b.count[k] == 0) continue;
+        a.pairs = W.d_pairs.p + b.first[k];
+        a.npairs = b.count[k];
+        a.nwaves = b.waves[k];
+        if (dcp_forward_scaled_launch(c->precision, kFwdR[k], &a, W.d_redo.p, W.d_nredo.p, n, W.band ? W.band : (int)DCP_FWS_BAND,
+                                      c->stream))
+            return c->fail(DCP_EFAIL, "no scaled Forward kernel for %d nodes per lane", kFwdR[k]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    return DCP_OK;
+}
+
+// The redo list of the round just launched: waits for the round, and reruns the pairs on it -- those whose values left
+// the double range -- by the log-space kernels into the same score arrays.  cap: the round's pairs.  The launches are
+// queued; *redone grows by their pairs.
+static int rerun_scaled_redo(dcp_gpu_ctx *c, dcp_fwd_args &a, unsigned cap, size_t stride, unsigned *redone)
+{
+    auto &W = c->sweeps;
+    uint32_t n = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n, W.d_nredo.p, sizeof n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (n == 0) return DCP_OK;
+    if (n > cap) return c->fail(DCP_EFAIL, "the scaled sweeps' redo list holds %u pairs of a round of %u", n, cap);
+    std::vector<dcp_fwd_pair> rec(n);
+    HIP_TRY(c, hipMemcpy(rec.data(), W.d_redo.p, (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyDeviceToHost));
+    // (the device appended them in whatever order the wavefronts ended: by position, so that a call repeats itself)
+    std::sort(rec.begin(), rec.end(), [](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return x.pos < y.pos; });
+    std::vector<uint32_t> sq(n), pr(n);
+    for (uint32_t i = 0; i < n; ++i)
+        sq[i] = rec[i].q, pr[i] = rec[i].prof;
+    ForwardBuckets b;
+    forward_bucket(c, sq.data(), pr.data(), n, 0u, b);
+    for (dcp_fwd_pair &p : b.pairs)
+        p.pos = rec[p.pos].pos;
+    HIP_TRY(c, W.d_redo_pairs.reserve(n));
+    HIP_TRY(c, hipMemcpyAsync(W.d_redo_pairs.p, b.pairs.data(), (size_t)n * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+    uint64_t const stride_was = a.work_stride;
+    a.work_stride = (uint64_t)DCP_FWD_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK; // at most the round's: its pairs are of the round
+    a.out_alt = a.out_null + stride;
+    for (int k = 0; k < 4; ++k)
+    {
+        if (b.count[k] == 0) continue;
+        a.pairs = W.d_redo_pairs.p + b.first[k];
+        a.npairs = b.count[k];
+        a.nwaves = b.waves[k];
+        if (dcp_forward_launch(c->precision, kFwdR[k], DCP_FWD_STORE_NONE, &a, c->stream))
+            return c->fail(DCP_EFAIL, "no Forward kernel for %d nodes per lane", kFwdR[k]);
+        HIP_TRY(c, hipGetLastError());
+    }
+    a.work_stride = stride_was;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // b's records are up
+    *redone += n;
+    return DCP_OK;
+}
+
+int dcp_gpu_forward_pairs_scaled(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                                 uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out)
+{
+    if (!c) return DCP_EINVAL;
+    if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, null_out && alt_out)) return rc;
+    if (npairs == 0) return DCP_OK;
+    auto &W = c->sweeps;
+    dcp_fwd_args a{};
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)2u * npairs, {}, &a,
+                              DCP_FWS_WORK_ROWS))
+        return rc;
+    ForwardBuckets b;
+    if (int rc = upload_round(c, seq_idx, profile_idx, 0u, npairs, false, b, a)) return rc;
+    a.work_stride = (uint64_t)DCP_FWS_WORK_ROWS * b.wide_chunks * DCP_FWD_CHUNK; // the scaled wide sweep's rows
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // the transitions and the list are up (and whatever was outstanding is done)
+    HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+    if (int rc = run_scaled_sweeps(c, a, b, npairs)) return rc;
+    unsigned redone = 0;
+    if (int rc = rerun_scaled_redo(c, a, npairs, npairs, &redone)) return rc;
+    HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+    // into a buffer of the call's own first: the caller's arrays stay untouched if the copy fails
+    std::vector<double> out(2u * (size_t)npairs);
+    HIP_TRY(c, hipMemcpyAsync(out.data(), W.d_score.p, out.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+    W.scaled_ms = ms;
+    W.scaled_redo = redone;
+    std::memcpy(null_out, out.data(), (size_t)npairs * sizeof(double));
+    std::memcpy(alt_out, out.data() + npairs, (size_t)npairs * sizeof(double));
+    return DCP_OK;
+}
+
+unsigned dcp_gpu_forward_scaled_redo_pairs(dcp_gpu_ctx *c) { return c ? c->sweeps.scaled_redo : 0u; }
+float dcp_gpu_forward_scaled_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.scaled_ms : -1.0f; }
+
 // ---- The dense Forward scan: every resident sequence x every resident profile --------------------------
 // The host orders the profiles (by class, the wide ones by falling chunk count) and the sequences (by falling length),
 // nothing per pair: the outer product is a line of positions (dcp_fwd_dense_args), a round is at most kDenseRound
@@ -3678,7 +3794,7 @@ float dcp_gpu_forward_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.fwd_ms : 
 // round r + 1 runs behind the sweeps of round r that read d_pairs.
 static constexpr unsigned kDenseRound = 1u << 22; // pairs: 48 MiB of records
 
-int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
+static int forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, bool scaled)
 {
     if (!c) return DCP_EINVAL;
     if (c->nprof == 0) return c->fail(DCP_EINVAL, "no profile DB resident");
@@ -3706,7 +3822,8 @@ int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
     if (cfirst[4] > cfirst[3]) wide.pairs = (uint64_t)nseqs * (cfirst[4] - cfirst[3]), wide.chunks = chunks_of(c->core_sizes[porder[cfirst[3]]]);
 
     dcp_fwd_args a{};
-    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide, 0u, {}, &a)) return rc;
+    unsigned const work_rows = scaled ? (unsigned)DCP_FWS_WORK_ROWS : (unsigned)DCP_FWD_WORK_ROWS;
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide, 0u, {}, &a, work_rows)) return rc;
     HIP_TRY(c, W.d_dense.reserve(2u * (size_t)total));
     HIP_TRY(c, W.d_order.reserve(order.size()));
     unsigned const round = std::min(W.dense_round ? W.dense_round : kDenseRound, kDenseRound);
@@ -3714,13 +3831,14 @@ int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
     HIP_TRY(c, hipMemcpyAsync(W.d_order.p, order.data(), order.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream)); // the transitions and the orders are up (and whatever was outstanding is done)
     a.out_null = W.d_dense.p;
-    a.work_stride = (uint64_t)DCP_FWD_WORK_ROWS * wide.chunks * DCP_FWD_CHUNK;
+    a.work_stride = (uint64_t)work_rows * wide.chunks * DCP_FWD_CHUNK;
     dcp_fwd_dense_args d{};
     d.seq_order = W.d_order.p, d.prof_order = W.d_order.p + nseqs;
     std::copy(cfirst, cfirst + 5, d.class_first);
     d.nseqs = nseqs, d.nprof = nprof;
     d.pairs = W.d_pairs.p;
     HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
+    unsigned redone = 0;
     for (uint64_t t0 = 0; t0 < total; t0 += round)
     {
         uint64_t const t1 = std::min<uint64_t>(t0 + round, total);
@@ -3736,7 +3854,14 @@ int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
             b.waves[k] = (unsigned)std::min<uint64_t>(b.count[k], (uint64_t)(k == 3 ? 4u : 12u) * c->num_cus);
             if (W.waves_cap) b.waves[k] = std::min(b.waves[k], W.waves_cap);
         }
-        if (int rc = run_sweeps(c, a, b, 1, DCP_FWD_STORE_NONE, total, 0u, 0u)) return rc;
+        if (!scaled)
+        {
+            if (int rc = run_sweeps(c, a, b, 1, DCP_FWD_STORE_NONE, total, 0u, 0u)) return rc;
+            continue;
+        }
+        // the scaled sweeps, and the round's redo list before the next round's records overwrite d_pairs' order
+        if (int rc = run_scaled_sweeps(c, a, b, total)) return rc;
+        if (int rc = rerun_scaled_redo(c, a, d.n, total, &redone)) return rc;
     }
     HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -3744,8 +3869,14 @@ int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat)
     HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
     W.dense_ms = ms;
     W.dense_valid = true;
+    W.dense_scaled = scaled;
+    if (scaled) W.scaled_redo = redone;
     return DCP_OK;
 }
+
+int dcp_gpu_forward_dense(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat) { return forward_dense(c, multi_hits, hmmer3_compat, false); }
+int dcp_gpu_forward_dense_scaled(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat) { return forward_dense(c, multi_hits, hmmer3_compat, true); }
+int dcp_gpu_forward_dense_is_scaled(dcp_gpu_ctx *c) { return c && c->sweeps.dense_valid && c->sweeps.dense_scaled ? 1 : 0; }
 
 static int forward_dense_ready(dcp_gpu_ctx *c)
 {
@@ -4164,6 +4295,13 @@ int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *c, unsigned nwaves)
 {
     if (!c) return DCP_EINVAL;
     c->sweeps.waves_cap = nwaves;
+    return DCP_OK;
+}
+
+int dcp_gpu_test_set_forward_scale_band(dcp_gpu_ctx *c, unsigned bits)
+{
+    if (!c || bits > 500u) return DCP_EINVAL;
+    c->sweeps.band = (int)bits;
     return DCP_OK;
 }
 

@@ -2001,6 +2001,173 @@ extern "C" int dcp_forward_tables(unsigned M, unsigned ldk, double const *trans8
 }
 
 // ---------------------------------------------------------------------------
+// The scaled probability-space Forward on the host: the twin of dcp_forward_scaled.hip.  forward_sweep's recursion by
+// dcp_forward_scaled.h's rule, sequential in k, every sum in index order.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_forward_scaled.h"
+
+extern "C" double dcp_fwd_factor_f32(float t) { return dcp_fws_factor_f32(t); }
+
+namespace
+{
+struct ScaledFactor
+{
+    bool f32;
+    double operator()(double t) const { return f32 ? dcp_fws_factor((float)t) : dcp_fws_factor(t); }
+};
+} // namespace
+
+extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                              double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                              unsigned char const *seq, unsigned L, int float_factors, int band,
+                                              double *null_out, double *alt_out, int *out_of_range)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0 || band < 1 || band > 500) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq || !null_out || !alt_out || !out_of_range)
+        return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    ScaledFactor const f{float_factors != 0};
+    // the transitions' factors once ([8][M]), the rings of P and Q, the row's M, I, D
+    double *const rows = (double *)std::malloc(sizeof(double) * (DCP_FWD_WORK_ROWS + 8) * (size_t)M);
+    if (!rows) return DCP_ENOMEM;
+    double *const P = rows, *const Q = rows + 5 * (size_t)M, *const Mr = rows + 10 * (size_t)M, *const Ir = Mr + M,
+                 *const Dr = Ir + M, *const T = Dr + M;
+    for (int t = 0; t < 8; ++t)
+        for (unsigned k = 0; k < M; ++k)
+            T[(size_t)t * M + k] = f(trans8[(size_t)t * ldk + k]);
+    double const *ENT = T + (size_t)DCP_T_ENTRY * M, *MM = T + (size_t)DCP_T_MM * M, *IM = T + (size_t)DCP_T_IM * M,
+                 *DM = T + (size_t)DCP_T_DM * M, *MD = T + (size_t)DCP_T_MD * M, *DD = T + (size_t)DCP_T_DD * M,
+                 *MI = T + (size_t)DCP_T_MI * M, *II = T + (size_t)DCP_T_II * M;
+    double x[13];
+    for (int i = 0; i < 13; ++i)
+        x[i] = f(xtrans[i]);
+    double PN[5], PJ[5], PC[5], PR[5];
+    for (size_t i = 0; i < 10 * (size_t)M; ++i)
+        rows[i] = 0.0;
+    for (int h = 0; h < 5; ++h)
+        PN[h] = PJ[h] = PC[h] = PR[h] = 0.0;
+    // row 0: S = 1, B = SB; N = SN; R starts at 1
+    for (unsigned k = 0; k < M; ++k)
+        P[k] = x[DCP_X_SB] * ENT[k];
+    PN[0] = x[DCP_X_SN];
+    PR[0] = 1.0;
+    int s = 0, sR = 0;
+    bool bad = false;
+    for (unsigned k = 0; k < M; ++k)
+        bad |= !dcp_fws_finite(P[k]);
+    bad |= !dcp_fws_finite(PN[0]);
+
+    static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
+    double E = 0.0, Cc = 0.0, Rr = 0.0;
+    unsigned w = 0;
+    for (unsigned j = 1; j <= L && !bad; ++j)
+    {
+        w = ((w << 2) | seq[j - 1]) & 1023u;
+        unsigned code[5], slot[5];
+        double fN[5], fI[5];
+        for (unsigned l = 1; l <= 5u; ++l)
+        {
+            code[l - 1] = code_off[l - 1] + (w & ((1u << (2 * l)) - 1u));
+            slot[l - 1] = (j + 5u - l) % 5u;
+            fN[l - 1] = f(emis_null[code[l - 1]]);
+            fI[l - 1] = f(emis_insert[code[l - 1]]);
+        }
+        double N = 0.0, J = 0.0;
+        Cc = 0.0, Rr = 0.0;
+        for (int l = 0; l < 5; ++l)
+        {
+            N = dcp_fws_fma(PN[slot[l]], fN[l], N), J = dcp_fws_fma(PJ[slot[l]], fN[l], J);
+            Cc = dcp_fws_fma(PC[slot[l]], fN[l], Cc), Rr = dcp_fws_fma(PR[slot[l]], fN[l], Rr);
+        }
+        for (unsigned k = 0; k < M; ++k)
+        {
+            double m = 0.0, ins = 0.0;
+            for (int l = 0; l < 5; ++l)
+            {
+                m = dcp_fws_fma(P[(size_t)slot[l] * M + k], f(emis_match[(size_t)code[l] * ldk + k]), m);
+                ins = dcp_fws_fma(Q[(size_t)slot[l] * M + k], fI[l], ins);
+            }
+            Mr[k] = m, Ir[k] = ins;
+        }
+        Dr[0] = 0.0;
+        for (unsigned k = 1; k < M; ++k)
+            Dr[k] = dcp_fws_fma(DD[k], Dr[k - 1], Mr[k - 1] * MD[k]);
+        E = 0.0; // M_0, M_1, D_1, M_2, D_2, .. in this order
+        for (unsigned k = 0; k < M; ++k)
+        {
+            E += Mr[k];
+            if (k) E += Dr[k];
+        }
+        double B = N * x[DCP_X_NB];
+        B = dcp_fws_fma(E, x[DCP_X_EB], B);
+        B = dcp_fws_fma(J, x[DCP_X_JB], B);
+        unsigned const r = j % 5u;
+        double *const pm = P + (size_t)r * M, *const qi = Q + (size_t)r * M;
+        for (unsigned k = 0; k < M; ++k)
+        {
+            double p = B * ENT[k];
+            if (k)
+            {
+                p = dcp_fws_fma(Mr[k - 1], MM[k], p);
+                p = dcp_fws_fma(Ir[k - 1], IM[k], p);
+                p = dcp_fws_fma(Dr[k - 1], DM[k], p);
+            }
+            pm[k] = p;
+            qi[k] = dcp_fws_fma(Ir[k], II[k], Mr[k] * MI[k]);
+            bad |= !dcp_fws_finite(p) || !dcp_fws_finite(qi[k]);
+        }
+        PN[r] = N * x[DCP_X_NN];
+        PJ[r] = dcp_fws_fma(J, x[DCP_X_JJ], E * x[DCP_X_EJ]);
+        PC[r] = dcp_fws_fma(Cc, x[DCP_X_CC], E * x[DCP_X_EC]);
+        PR[r] = Rr * x[DCP_X_RR];
+        bad |= !dcp_fws_finite(E) || !dcp_fws_finite(B) || !dcp_fws_finite(PN[r]) || !dcp_fws_finite(PJ[r]) ||
+               !dcp_fws_finite(PC[r]) || !dcp_fws_finite(PR[r]);
+        if (bad) break;
+        double const ref = dcp_fwd_max(dcp_fwd_max(dcp_fwd_max(PN[r], PJ[r]), dcp_fwd_max(PC[r], E)), B);
+        if (int const k = dcp_fws_rescale_by(ref, band))
+        {
+            double const c = dcp_fws_pow2(-k);
+            for (size_t i = 0; i < 10 * (size_t)M; ++i)
+                rows[i] *= c;
+            for (int h = 0; h < 5; ++h)
+                PN[h] *= c, PJ[h] *= c, PC[h] *= c;
+            E *= c, Cc *= c;
+            s += k;
+        }
+        if (int const k = dcp_fws_rescale_by(PR[r], band))
+        {
+            double const c = dcp_fws_pow2(-k);
+            for (int h = 0; h < 5; ++h)
+                PR[h] *= c;
+            Rr *= c;
+            sR += k;
+        }
+    }
+    double alt = 0.0;
+    if (!bad)
+    {
+        alt = dcp_fws_fma(Cc, x[DCP_X_CT], E * x[DCP_X_ET]);
+        bad = !dcp_fws_finite(alt);
+    }
+    std::free(rows);
+    *out_of_range = bad ? 1 : 0;
+    if (bad) return DCP_OK; // the scores stay unwritten: the values left the double range
+    *null_out = dcp_fws_score(Rr, sR);
+    *alt_out = dcp_fws_score(alt, s);
+    return DCP_OK;
+}
+
+extern "C" int dcp_forward_scaled_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                         double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                         unsigned char const *seq, unsigned L, int float_factors, double *null_out,
+                                         double *alt_out, int *out_of_range)
+{
+    return dcp_forward_scaled_tables_band(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, float_factors,
+                                          DCP_FWS_BAND, null_out, alt_out, out_of_range);
+}
+
+// ---------------------------------------------------------------------------
 // Backward and the posterior rows on the host: the twin of dcp_posterior.hip and the tests' yardstick.  The rule is
 // dcp_posterior.h's; sequential in k, every lse in the order written, bB and E summed in k order from the maximum.  It
 // holds the full matrices of bM and bI: it is no hot path.  No device.

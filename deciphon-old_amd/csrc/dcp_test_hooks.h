@@ -49,6 +49,11 @@ int dcp_gpu_test_set_forward_waves(dcp_gpu_ctx *, unsigned nwaves);
 // run in several rounds, whose boundaries fall inside classes and between them; 0, or more than the default, restores
 // the default (2^22 pairs).  Results must not change with it.
 int dcp_gpu_test_set_dense_round(dcp_gpu_ctx *, unsigned npairs);
+// The band of the scaled Forward sweeps' rescaling rule (dcp_forward_scaled.h), in bits, for the following
+// dcp_gpu_forward_pairs_scaled and dcp_gpu_forward_dense_scaled calls: a small one rescales every few rows; 0 restores
+// the default (64).  Results must not change with it.  (The scaled launches take dcp_gpu_test_set_forward_waves' cap and
+// dcp_gpu_test_set_dense_round's bound too.)
+int dcp_gpu_test_set_forward_scale_band(dcp_gpu_ctx *, unsigned bits);
 // Bound, in bytes, on the device memory of the row records of each of the following dcp_gpu_posterior_pairs calls: a
 // small one makes the list run in several rounds; 0 restores the default (1 GiB).  Results must not change with it.
 int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *, unsigned long long bytes);

@@ -963,6 +963,51 @@ int dcp_gpu_fetch_forward_scores(dcp_gpu_ctx *, double *null_out, double *alt_ou
  * dcp_gpu_forward_dense that ran to its end; negative before. */
 float dcp_gpu_forward_dense_kernel_ms(dcp_gpu_ctx *);
 
+/* ------------------------------------------------------------------------ */
+/* The scaled probability-space Forward sweep */
+/* ------------------------------------------------------------------------ */
+/* The Forward recursion with every value held as a probability beside a power-of-two exponent (csrc/
+ * dcp_forward_scaled.h): a table value t enters as a factor -- exp(t) in double on a double DB, the float rule
+ * dcp_fwd_factor_f32 on a float DB -- every lse becomes a chain of fused multiply-adds, and a score is formed once, at
+ * the end.  The scores agree with dcp_forward_tables' to 2^-32 (|x| + 1) with double factors and to n(L, M) delta with
+ * float factors (looser than the log-space sweep's).
+ *
+ * The float rule: exp of a float in -708 .. 708 as a double, by float arithmetic alone (host and device: the same
+ * bits); 0 below -708 and for -inf, +inf above 708. */
+double dcp_fwd_factor_f32(float t);
+/* The host twin.  Arguments and refusals are dcp_forward_tables'; float_factors != 0 applies the float rule to
+ * (float)t of every table value, 0 takes exp(t) in double.  *out_of_range = 1, and no score written: a value left the
+ * double range (a delete chain that multiplies up, which dcp_forward_tables handles); else 0 and both scores.  A null
+ * out_of_range is DCP_EINVAL too.  No device. */
+int dcp_forward_scaled_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                              double const *emis_insert, double const *emis_null, double const xtrans[13],
+                              unsigned char const *seq, unsigned L, int float_factors, double *null_out, double *alt_out,
+                              int *out_of_range);
+/* The same with the band of the rescaling rule given (1 .. 500; dcp_forward_scaled_tables: 64): the scores do not
+ * depend on it. */
+int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                   double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                   unsigned char const *seq, unsigned L, int float_factors, int band, double *null_out,
+                                   double *alt_out, int *out_of_range);
+/* dcp_gpu_forward_pairs by the scaled sweep (csrc/dcp_forward_scaled.hip): the same lists, batches, transitions,
+ * refusals and messages; it returns synchronised and leaves a scan's results, and the dense Forward matrices, what they
+ * were.  Pairs whose values leave the double range are collected on the device and rerun by dcp_gpu_forward_pairs'
+ * kernels in the same call: those come back with dcp_gpu_forward_pairs' bits, and every returned score is valid. */
+int dcp_gpu_forward_pairs_scaled(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                                 uint32_t const *profile_idx, unsigned npairs, double *null_out, double *alt_out);
+/* How many pairs the context's last scaled call (pair list or dense) reran in log space. */
+unsigned dcp_gpu_forward_scaled_redo_pairs(dcp_gpu_ctx *);
+/* Milliseconds, by HIP events around all launches (the rerun's included) of the context's last
+ * dcp_gpu_forward_pairs_scaled that launched any; negative before. */
+float dcp_gpu_forward_scaled_kernel_ms(dcp_gpu_ctx *);
+/* dcp_gpu_forward_dense by the scaled sweep: the same list kernel, rounds, buffer and dense layout, the same lifetime
+ * and voiding rules; dcp_gpu_fetch_forward_scores and dcp_gpu_fit_exp_tail(DCP_SCORES_FORWARD, ..) work on its result
+ * unchanged, and dcp_gpu_forward_dense_kernel_ms covers it.  Every entry has dcp_gpu_forward_pairs_scaled's bits. */
+int dcp_gpu_forward_dense_scaled(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat);
+/* 1 if the dense Forward matrices were filled by dcp_gpu_forward_dense_scaled, 0 if by dcp_gpu_forward_dense (or by
+ * neither yet). */
+int dcp_gpu_forward_dense_is_scaled(dcp_gpu_ctx *);
+
 /* The upper tail of Forward scores is taken as exponential: P(X >= s) = exp(-lambda (s - mu)) for s >= mu.  The censored
  * maximum-likelihood fit is closed-form.  tau, the k-th largest by value, and k_eff = #{x >= tau} are dcp_gumbel_fit_tail's
  * (the same selection).  Pass 1 over all n: a non-finite x is DCP_FIT_NONFINITE.  Pass 2: so = sum (x - tau) over the

@@ -10,7 +10,11 @@
 //   * all history rows of P, Q, PN, PJ, PC of a pair share one exponent; the null state R has one of its own.  After a
 //     row, ref = max(PN, PJ, PC, E, B) of that row; if ref != 0 lies outside [2^-band, 2^band], every ring value (and
 //     the carried E and C) is multiplied by the power of two that brings ref into [1, 2) -- exact -- and the exponent
-//     follows.  R's ring does the same on PR;
+//     follows.  R's ring does the same on PR.  Row 0 is a row: its ref is max(PN, B) = max(SN, SB), and the rule applies
+//     before P(0) = B ENT is formed, so that special transitions near e^-708 do not leave rows 0 and 1 in the subnormals;
+//   * at the finish the last row's E and C are multiplied by the power of two that brings the larger of them into
+//     [1, 2) (dcp_fws_rescale_by with band 0), then alt = fma(C, ct, E et): with et, ct near e^-708 the sum stays normal
+//     and does not depend on where the band left E;
 //   * a score is formed once, at the end: u 2^s = m 2^e with m in [0.5, 1), score = log(m) + e ln 2; 0 gives -inf.
 //
 // Factors.  A double DB: f(t) = exp(t) in double, each side its own exp.  A float DB: dcp_fws_factor_f32 below (exported as dcp_fwd_factor_f32), the

@@ -105,7 +105,9 @@ __device__ __forceinline__ void delete_chain_scaled(double const (&a)[R], double
     }
     // lanes 0 .. l - 1 composed, applied to the carry: lane 0 receives (1, 0), the identity
     double const cb = shr1(c, 0.0), sb = shr1(s, 1.0);
-    double const d_in = dcp_fws_fma(carry, sb, cb);
+    // (a chain that carries no mass has D = 0 by the rule, whatever its dd: the product sb may have left the range,
+    // and 0 x inf is no value of the rule)
+    double const d_in = carry != 0.0 ? dcp_fws_fma(carry, sb, cb) : cb;
     d[0] = dcp_fws_fma(dd[0], d_in, a[0]);
 #pragma unroll
     for (int r = 1; r < R; ++r)
@@ -142,13 +144,31 @@ __device__ __forceinline__ void rescale_specials(Specials &s, int kA, int kR, un
     s.sA += kA, s.sR += kR;
 }
 
+// Row 0 under the rescaling rule, before its P is formed: ref = max(PN, B) = max(SN, SB).  Returns B for row 0's P.
+__device__ __forceinline__ double rescale_row0(double B0, Specials &s, int band, unsigned lane)
+{
+    double const sn = readlane(s.PX[0], 0);
+    if (!dcp_fws_finite(sn) || !dcp_fws_finite(B0)) return B0; // row 1 ends the pair
+    int const k = dcp_fws_rescale_by(dcp_fwd_max(sn, B0), band);
+    if (k == 0) return B0;
+    double const c = dcp_fws_pow2(-k);
+    if ((lane & 3u) != 3u) s.PX[0] *= c;
+    s.sA = k;
+    return B0 * c;
+}
+
 __device__ __forceinline__ void finish_pair(dcp_fwd_args const &a, Redo const &rd, dcp_fwd_pair const &pp, Specials const &s,
                                             XS const &x, bool bad, unsigned lane)
 {
     double alt = 0.0;
+    int sA = s.sA;
     if (!bad)
     {
-        alt = dcp_fws_fma(s.Cc, x.CT, s.E * x.ET);
+        // the last row's E and C with the larger of them in [1, 2): the product with ET, CT near e^-708 stays normal
+        int const k = dcp_fws_rescale_by(dcp_fwd_max(s.E, s.Cc), 0);
+        double const c = dcp_fws_pow2(-k);
+        alt = dcp_fws_fma(s.Cc * c, x.CT, (s.E * c) * x.ET);
+        sA += k;
         bad = !dcp_fws_finite(alt);
     }
     if (lane == 0u)
@@ -159,7 +179,7 @@ __device__ __forceinline__ void finish_pair(dcp_fwd_args const &a, Redo const &r
             if (at < rd.cap) rd.list[at] = pp;
         }
         a.out_null[pp.pos] = bad ? ninf() : dcp_fws_score(s.Rr, s.sR);
-        a.out_alt[pp.pos] = bad ? ninf() : dcp_fws_score(alt, s.sA);
+        a.out_alt[pp.pos] = bad ? ninf() : dcp_fws_score(alt, sA);
     }
 }
 
@@ -271,6 +291,16 @@ template <class Real, int R> __global__ __launch_bounds__(256) void forward_scal
         XS const x = special_factors<Real>(xt, lane);
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
         unsigned const k0 = lane * R;
+        // row 0 of the special states and its rescaling, anew for every pair: S = 1, B = SB
+        Specials s;
+#pragma unroll
+        for (int h = 1; h < 5; ++h)
+            s.PX[h] = 0.0;
+        s.PX[0] = special_row0_fac<Real>(xt, lane);
+        s.E = s.Cc = s.Rr = 0.0;
+        s.sA = s.sR = 0;
+        s.w = 0u;
+        double const B0 = rescale_row0(fac_of<Real>(xt[DCP_X_SB]), s, rd.band, lane);
         Trans<R> t;
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -284,25 +314,16 @@ template <class Real, int R> __global__ __launch_bounds__(256) void forward_scal
             t.mi[r] = load_fac(g.trans + DCP_T_MI * g.ld, k0 + r, g.M);
             t.ii[r] = load_fac(g.trans + DCP_T_II * g.ld, k0 + r, g.M);
         }
-        // row 0, anew for every pair: S = 1, B = SB; the rings are 0 but for row 0's slot
+        // row 0 of the rings: 0 but for row 0's slot
         Rings<R> g5;
-        Specials s;
 #pragma unroll
         for (int h = 0; h < 5; ++h)
-        {
 #pragma unroll
             for (int r = 0; r < R; ++r)
                 g5.P[h][r] = g5.Q[h][r] = 0.0;
-            s.PX[h] = 0.0;
-        }
-        double const B0 = fac_of<Real>(xt[DCP_X_SB]);
 #pragma unroll
         for (int r = 0; r < R; ++r)
             g5.P[0][r] = B0 * t.ent[r];
-        s.PX[0] = special_row0_fac<Real>(xt, lane);
-        s.E = s.Cc = s.Rr = 0.0;
-        s.sA = s.sR = 0;
-        s.w = 0u;
         bool bad = false;
         unsigned j = 1u;
 #define DCP_FWS_ROW(PH)                                                                                                \
@@ -465,7 +486,15 @@ template <class Real> __global__ __launch_bounds__(256) void forward_scaled_wide
         Tabs<Real> const g = tables_of<Real>(a, pr, pp.q);
         WideArea const wa = wide_area(a.work, a.work_stride, gw, pr.core_size);
         // row 0, anew for every pair (the pair before may have been of another width): the rings' own columns
-        double const B0 = fac_of<Real>(xt[DCP_X_SB]);
+        Specials s;
+#pragma unroll
+        for (int h = 0; h < 5; ++h)
+            s.PX[h] = 0.0;
+        s.PX[0] = special_row0_fac<Real>(xt, lane);
+        s.E = s.Cc = s.Rr = 0.0;
+        s.sA = s.sR = 0;
+        s.w = 0u;
+        double const B0 = rescale_row0(fac_of<Real>(xt[DCP_X_SB]), s, rd.band, lane);
         for (unsigned ch = 0; ch < wa.nchunks; ++ch)
         {
             unsigned const k0 = ch * (unsigned)DCP_FWD_CHUNK + lane * WR;
@@ -482,14 +511,6 @@ template <class Real> __global__ __launch_bounds__(256) void forward_scaled_wide
                     wa.ring0(h)[k0 + r] = wa.ring1(h)[k0 + r] = 0.0;
             }
         }
-        Specials s;
-#pragma unroll
-        for (int h = 0; h < 5; ++h)
-            s.PX[h] = 0.0;
-        s.PX[0] = special_row0_fac<Real>(xt, lane);
-        s.E = s.Cc = s.Rr = 0.0;
-        s.sA = s.sR = 0;
-        s.w = 0u;
         bool bad = false;
         unsigned j = 1u;
 #define DCP_FWS_ROW(PH)                                                                                                \

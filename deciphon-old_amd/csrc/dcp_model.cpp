@@ -2047,12 +2047,20 @@ extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double c
         rows[i] = 0.0;
     for (int h = 0; h < 5; ++h)
         PN[h] = PJ[h] = PC[h] = PR[h] = 0.0;
-    // row 0: S = 1, B = SB; N = SN; R starts at 1
-    for (unsigned k = 0; k < M; ++k)
-        P[k] = x[DCP_X_SB] * ENT[k];
-    PN[0] = x[DCP_X_SN];
-    PR[0] = 1.0;
+    // row 0: S = 1, B = SB; N = SN; R starts at 1.  The row's ref is max(PN, B), and the rule applies before P is formed
     int s = 0, sR = 0;
+    double B0 = x[DCP_X_SB];
+    PN[0] = x[DCP_X_SN];
+    if (dcp_fws_finite(B0) && dcp_fws_finite(PN[0]))
+        if (int const k = dcp_fws_rescale_by(dcp_fwd_max(PN[0], B0), band))
+        {
+            double const c = dcp_fws_pow2(-k);
+            B0 *= c, PN[0] *= c;
+            s = k;
+        }
+    for (unsigned k = 0; k < M; ++k)
+        P[k] = B0 * ENT[k];
+    PR[0] = 1.0;
     bool bad = false;
     for (unsigned k = 0; k < M; ++k)
         bad |= !dcp_fws_finite(P[k]);
@@ -2147,7 +2155,11 @@ extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double c
     double alt = 0.0;
     if (!bad)
     {
-        alt = dcp_fws_fma(Cc, x[DCP_X_CT], E * x[DCP_X_ET]);
+        // the last row's E and C with the larger of them in [1, 2): the product with ET, CT near e^-708 stays normal
+        int const k = dcp_fws_rescale_by(dcp_fwd_max(E, Cc), 0);
+        double const c = dcp_fws_pow2(-k);
+        alt = dcp_fws_fma(Cc * c, x[DCP_X_CT], (E * c) * x[DCP_X_ET]);
+        s += k;
         bad = !dcp_fws_finite(alt);
     }
     std::free(rows);

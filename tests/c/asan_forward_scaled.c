@@ -1,6 +1,7 @@
 /* dcp_forward_scaled_tables and dcp_fwd_factor_f32, the host side of the scaled probability-space Forward sweep, as a
  * program of its own for ASan + UBSan (tests/test_forward_scaled.py builds it with csrc/dcp_model.cpp alone: no device
- * code).  Tables are allocated at their exact sizes, so a read one column or one code too far is a finding. */
+ * code).  Tables are allocated at their exact sizes, so a read one column or one code too far is a finding.  Special
+ * transitions at both ends of the range: the exits of row 1, of the finish and of R alone, and rows 0 and 1 near e^-708. */
 #include "dcp_gpu.h"
 
 #include <math.h>
@@ -135,6 +136,48 @@ int main(void)
         CHECK(dcp_forward_tables(M, M, t.t8, t.em, t.ei, t.en, xt, seq, 6, &nul, &alt) == DCP_OK);
         CHECK(isfinite(nul) && isfinite(alt));
         drop(&t);
+    }
+    /* special transitions at the ends of the range (xtrans order: RR, SB, SN, NN, NB, ET, EC, CC, CT, EB, EJ, JJ, JB): an exit
+     * in row 1, one at the finish, rows 0 and 1 near the bottom of the range, and R alone on the one-node profile.  A flagged
+     * pair writes nothing, at either band and by either factor rule */
+    {
+        enum { X_RR = 0, X_SB = 1, X_SN = 2, X_NB = 4, X_ET = 5, X_CT = 8 };
+        static struct
+        {
+            unsigned M, L;
+            int which[2];
+            double value;
+            int oor;
+        } const cases[] = {{5, 12, {X_NB, X_NB}, 710.0, 1}, {67, 7, {X_ET, X_CT}, 710.0, 1}, {5, 12, {X_SB, X_SN}, -705.0, 0}, {1, 3, {X_RR, X_RR}, 710.0, 1}};
+        for (unsigned s = 0; s < sizeof cases / sizeof cases[0]; ++s)
+        {
+            unsigned const M = cases[s].M, L = cases[s].L;
+            struct tables t = make(M, M);
+            unsigned char seq[12];
+            for (unsigned i = 0; i < L; ++i)
+                seq[i] = (unsigned char)((unsigned)(-draw() * 1000.0) & 3u);
+            double xt[DCP_NXTRANS], ref_nul = 0, ref_alt = 0;
+            CHECK(dcp_xtrans64(L, 1, 0, xt) == DCP_OK);
+            xt[cases[s].which[0]] = xt[cases[s].which[1]] = cases[s].value;
+            CHECK(dcp_forward_tables(M, M, t.t8, t.em, t.ei, t.en, xt, seq, L, &ref_nul, &ref_alt) == DCP_OK);
+            CHECK(isfinite(ref_nul) && isfinite(ref_alt));
+            for (int f32 = 0; f32 < 2; ++f32)
+                for (int band = 4; band <= 64; band += 60)
+                {
+                    double nul = 1.5, alt = 2.5;
+                    int oor = 7;
+                    CHECK(dcp_forward_scaled_tables_band(M, M, t.t8, t.em, t.ei, t.en, xt, seq, L, f32, band, &nul, &alt, &oor) == DCP_OK);
+                    CHECK(oor == cases[s].oor);
+                    if (oor)
+                    {
+                        CHECK(nul == 1.5 && alt == 2.5);
+                        continue;
+                    }
+                    double const tol = f32 ? 1e-7 * ((double)L * (M + 2) + 2) : 2.4e-10 * (fabs(ref_alt) + 1.0);
+                    CHECK(fabs(nul - ref_nul) <= tol && fabs(alt - ref_alt) <= tol);
+                }
+            drop(&t);
+        }
     }
     puts("asan_forward_scaled ok");
     return 0;

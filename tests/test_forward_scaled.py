@@ -159,9 +159,23 @@ _LIBM.fma.restype, _LIBM.fma.argtypes = C.c_double, [C.c_double] * 3
 fma = _LIBM.fma
 
 
-def restate_scaled(t8, em, ei, en, xt, seq, band):
-    """dcp_forward_scaled.h's rule with double factors, in Python: (null, alt)"""
-    f = lambda t: math.exp(t) if t != NEG_INF else 0.0  # noqa: E731
+def exp_or_inf(t):
+    """exp in double as the C library rounds it: 0 for -inf, +inf past the range (math.exp raises there)"""
+    try:
+        return math.exp(t) if t != NEG_INF else 0.0
+    except OverflowError:
+        return math.inf
+
+
+def restate_scaled(t8, em, ei, en, xt, seq, band, where=False):
+    """dcp_forward_scaled.h's rule with double factors, in Python: (null, alt, s, sR).
+
+    where: also where the rule ends the pair, by the twin's checks in the twin's order -- row 0's P and PN; per row P,
+    Q, E, B, PN, PJ, PC, PR; then alt.  Returns (null, alt, s, sR, exit, names): exit is None for a pair that stays in
+    range, ("row", j) for a non-finite value in row j, ("finish",) for a non-finite alt, the scores are None with an
+    exit, s and sR are the exponents reached by then, and names are the row's non-finite values in the order checked."""
+    f = exp_or_inf
+    fin = math.isfinite
     T = [[f(float(v)) for v in row] for row in np.asarray(t8, np.float64)]
     ENT, MM, IM, DM, MD, DD, MI, II = T
     RR, SB, SN, NN, NB, ET, EC, CC, CT, EB, EJ, JJ, JB = (f(float(v)) for v in xt)
@@ -169,16 +183,23 @@ def restate_scaled(t8, em, ei, en, xt, seq, band):
     M, L = len(ENT), len(seq)
     P, Q = [[0.0] * M for _ in range(5)], [[0.0] * M for _ in range(5)]
     PN, PJ, PC, PR = [0.0] * 5, [0.0] * 5, [0.0] * 5, [0.0] * 5
-    P[0] = [SB * e for e in ENT]
-    PN[0], PR[0] = SN, 1.0
     s = sR = 0
     w, E, Cc, Rr = 0, 0.0, 0.0, 0.0
 
-    def step_of(ref):
+    def step_of(ref, band=band):
         if ref == 0.0:
             return 0
         k = max((struct.unpack("<Q", struct.pack("<d", ref))[0] >> 52) & 0x7FF, 1) - 1023
         return 0 if -band <= k < band else min(k, 1022)
+
+    B0, PN[0], PR[0] = SB, SN, 1.0
+    if fin(B0) and fin(PN[0]):  # row 0 is a row: ref = max(PN, B), before P is formed
+        s = step_of(max(PN[0], B0))
+        B0, PN[0] = B0 * 2.0 ** -s, PN[0] * 2.0 ** -s
+    P[0] = [B0 * e for e in ENT]
+    names = (["P"] if not all(fin(v) for v in P[0]) else []) + (["PN"] if not fin(PN[0]) else [])
+    if where and names:
+        return None, None, s, sR, ("row", 0), names
 
     for j in range(1, L + 1):
         w = ((w << 2) | int(seq[j - 1])) & 1023
@@ -210,6 +231,12 @@ def restate_scaled(t8, em, ei, en, xt, seq, band):
                 p = fma(Dr[k - 1], DM[k], fma(Ir[k - 1], IM[k], fma(Mr[k - 1], MM[k], p)))
             P[r][k], Q[r][k] = p, fma(Ir[k], II[k], Mr[k] * MI[k])
         PN[r], PJ[r], PC[r], PR[r] = N * NN, fma(J, JJ, E * EJ), fma(Cc, CC, E * EC), Rr * RR
+        if where:
+            checked = (("P", P[r]), ("Q", Q[r]), ("E", [E]), ("B", [B]), ("PN", [PN[r]]), ("PJ", [PJ[r]]), ("PC", [PC[r]]),
+                       ("PR", [PR[r]]))
+            names = [name for name, vals in checked if not all(fin(v) for v in vals)]
+            if names:
+                return None, None, s, sR, ("row", j), names
         k = step_of(max(PN[r], PJ[r], PC[r], E, B))
         if k:
             c = 2.0 ** -k
@@ -226,7 +253,13 @@ def restate_scaled(t8, em, ei, en, xt, seq, band):
         m, e = math.frexp(u)
         return math.log(m) + float(e + s) * 0.693147180559945309417232121458
 
-    return score(Rr, sR), score(fma(Cc, CT, E * ET), s), s, sR
+    k = step_of(max(E, Cc), 0) if fin(E) and fin(Cc) else 0  # the finish: the larger of E and C into [1, 2), whatever the band
+    alt = fma(Cc * 2.0 ** -k, CT, (E * 2.0 ** -k) * ET)  # (s, as returned, is the rows' exponent: where the band left it)
+    if not where:
+        return score(Rr, sR), score(alt, s + k), s, sR
+    if not fin(alt):
+        return None, None, s, sR, ("finish",), ["alt"]
+    return score(Rr, sR), score(alt, s + k), s, sR, None, []
 
 
 @pytest.mark.parametrize("M", [2, 40])

@@ -110,6 +110,9 @@ ABI_SYMBOLS = [
     "dcp_fwd_factor_f32", "dcp_forward_scaled_tables", "dcp_forward_scaled_tables_band", "dcp_gpu_forward_pairs_scaled",
     "dcp_gpu_forward_scaled_redo_pairs", "dcp_gpu_forward_scaled_kernel_ms", "dcp_gpu_forward_dense_scaled",
     "dcp_gpu_forward_dense_is_scaled",
+    # the scaled Backward sweep and posterior rows of a pair list, and the host twin
+    "dcp_posterior_scaled_tables", "dcp_posterior_scaled_tables_band", "dcp_gpu_posterior_pairs_scaled",
+    "dcp_gpu_posterior_scaled_redo_pairs", "dcp_gpu_posterior_scaled_kernel_ms",
 ]
 
 
@@ -323,6 +326,13 @@ def _load(path=None, hooks=False):
         "dcp_gpu_forward_scaled_kernel_ms": (F, [P]),
         "dcp_gpu_forward_dense_scaled": (I, [P, I, I]),
         "dcp_gpu_forward_dense_is_scaled": (I, [P]),
+        "dcp_posterior_scaled_tables": (I, [U, U, P, P, P, P, P, P, U, I, P, P, P, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int)]),
+        "dcp_posterior_scaled_tables_band": (I, [U, U, P, P, P, P, P, P, U, I, I, P, P, P, C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+        "dcp_gpu_posterior_pairs_scaled": (I, [P, I, I, P, P, U, P, P, P, P, C.c_uint64, P, P]),
+        "dcp_gpu_posterior_scaled_redo_pairs": (U, [P]),
+        "dcp_gpu_posterior_scaled_kernel_ms": (F, [P]),
         "dcp_gpu_fetch_forward_scores": (I, [P, P, P]),
         "dcp_gpu_forward_dense_kernel_ms": (F, [P]),
         "dcp_exp_tail_fit": (I, [P, U, C.c_size_t, U, C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -747,6 +757,31 @@ def posterior_tables(t8, em, ei, en, xt, seq):
     if rc:
         raise DcpError(rc, "dcp_posterior_tables")
     return begin, end, core, fwd.value, bwd.value
+
+
+def posterior_scaled_tables(t8, em, ei, en, xt, seq, float_factors=False, band=None):
+    """(begin, end, core, alt_fwd, alt_bwd, out_of_range) of one sequence against one profile by the scaled
+    probability-space sweeps on the host (dcp_posterior_scaled_tables): posterior_tables' arguments and rows;
+    float_factors as forward_scaled_tables.  out_of_range: a value left the double range, or a row's records may have
+    lost a term that matters to underflow, and the five results are None.  band (tests): the rescaling rule's band in
+    bits, which the results of a pair in range do not depend on."""
+    t8, em, ei, en, xt = _f64(t8), _f64(em), _f64(ei), _f64(en), _f64(xt)
+    seq = np.ascontiguousarray(seq, np.uint8)
+    if t8.ndim != 2 or em.ndim != 2 or t8.shape != (8, em.shape[1]) or em.shape[0] != NCODES or \
+            ei.shape != (NCODES,) or en.shape != (NCODES,) or xt.shape != (NXTRANS,) or seq.ndim != 1:
+        raise DcpError(RC_EINVAL, "tables of shapes [8, ldk], [1364, ldk], [1364], [1364], [13]")
+    begin, end, core = (np.zeros(len(seq) + 1, np.float64) for _ in range(3))
+    fwd, bwd, oor = C.c_double(0.0), C.c_double(0.0), C.c_int(0)
+    args = (em.shape[1], em.shape[1], t8.ctypes.data, em.ctypes.data, ei.ctypes.data, en.ctypes.data, xt.ctypes.data,
+            seq.ctypes.data, len(seq), int(bool(float_factors)))
+    outs = (begin.ctypes.data, end.ctypes.data, core.ctypes.data, C.byref(fwd), C.byref(bwd), C.byref(oor))
+    rc = lib.dcp_posterior_scaled_tables(*args, *outs) if band is None else \
+        lib.dcp_posterior_scaled_tables_band(*args, int(band), *outs)
+    if rc:
+        raise DcpError(rc, "dcp_posterior_scaled_tables")
+    if oor.value:
+        return None, None, None, None, None, True
+    return begin, end, core, fwd.value, bwd.value, False
 
 
 def _mea_tables_args(t8, em, ei, en, xt, seq):
@@ -1597,6 +1632,34 @@ class Scanner:
                                                       end.ctypes.data, core.ctypes.data, cap, fwd.ctypes.data,
                                                       bwd.ctypes.data))
         return row_off, begin, end, core, fwd, bwd
+
+    def posterior_pairs_scaled(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
+        """posterior_pairs by the scaled probability-space sweeps (dcp_gpu_posterior_pairs_scaled): the same six
+        results, no log-space cell, five logs per row.  Pairs that leave the double range, or whose records may have
+        lost a term that matters to underflow, are rerun by posterior_pairs' kernels in the same call
+        (last_posterior_scaled_redo_pairs) and have its bits."""
+        sq, pr = _pair_list(seq_idx, profile_idx)
+        lens = getattr(self, "_seq_lens", np.zeros(0, np.int64))
+        ok = sq < len(lens)  # an index out of range is the call's to refuse, with its message
+        cap = int(np.sum(lens[sq[ok]] + 1)) if len(sq) else 0
+        row_off = np.zeros(len(sq) + 1, np.uint64)
+        begin, end, core = (np.zeros(cap, np.float64) for _ in range(3))
+        fwd, bwd = np.zeros(len(sq), np.float64), np.zeros(len(sq), np.float64)
+        self._check(self._lib.dcp_gpu_posterior_pairs_scaled(self._c, int(multi_hits), int(hmmer3_compat), sq.ctypes.data,
+                                                             pr.ctypes.data, len(sq), row_off.ctypes.data,
+                                                             begin.ctypes.data, end.ctypes.data, core.ctypes.data, cap,
+                                                             fwd.ctypes.data, bwd.ctypes.data))
+        return row_off, begin, end, core, fwd, bwd
+
+    @property
+    def last_posterior_scaled_redo_pairs(self):
+        """How many pairs the last posterior_pairs_scaled reran in log space."""
+        return self._lib.dcp_gpu_posterior_scaled_redo_pairs(self._c)
+
+    @property
+    def posterior_scaled_kernel_ms(self):
+        """Milliseconds of the last posterior_pairs_scaled call's launches, the reruns included; negative before any."""
+        return self._lib.dcp_gpu_posterior_scaled_kernel_ms(self._c)
 
     @property
     def posterior_kernel_ms(self):

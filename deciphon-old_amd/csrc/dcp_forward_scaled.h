@@ -107,13 +107,13 @@ DCP_FWD_HD inline double dcp_fws_score(double u, int s)
 extern "C" {
 #endif
 // The scaled Forward sweep (dcp_forward_scaled.hip): dcp_forward_launch's classes (R = 1, 2, 4, or 0: the wide sweep),
-// scores only.  A pair whose values left the double range is appended to redo[atomicAdd(nredo, 1)] (while that is below
+// scores only (store = DCP_FWD_STORE_NONE) or with every row's record as logs (DCP_FWD_STORE_ROWS).  A pair whose values left the double range is appended to redo[atomicAdd(nredo, 1)] (while that is below
 // redo_cap: give the launches that share a counter room for all their pairs) and its scores are -inf and mean nothing:
 // the caller reruns it by dcp_forward_launch.  band: DCP_FWS_BAND, or the hooks build's.  != 0: no such kernel, no redo
 // list, a band outside 1 .. 500, a wide sweep whose work_stride is no multiple of DCP_FWS_WORK_ROWS, or
 // dcp_fwd_args_refused.
-int dcp_forward_scaled_launch(int precision, int R, struct dcp_fwd_args const *a, struct dcp_fwd_pair *redo, uint32_t *nredo,
-                              uint32_t redo_cap, int band, void *stream);
+int dcp_forward_scaled_launch(int precision, int R, int store, struct dcp_fwd_args const *a, struct dcp_fwd_pair *redo,
+                              uint32_t *nredo, uint32_t redo_cap, int band, void *stream);
 #ifdef __cplusplus
 }
 #endif

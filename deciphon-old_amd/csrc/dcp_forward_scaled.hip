@@ -17,6 +17,11 @@
 // launch's redo list, which the driver hands to the log-space kernels.
 //
 // A column at or past core_size is never loaded: its factors are 0, so the padding columns carry 0 and stay 0.
+//
+// Both sweeps take a compile-time flag ROWS: lanes 0 .. 4 also store the row's record for the posteriors (PN, PJ, PC,
+// B, E) as five logs under the exponent in force, what dcp_gpu_posterior_pairs_scaled's Backward sweep and the combining
+// kernel read (dcp_backward_scaled.h).  ROWS = false is the scores-only kernel, with the registers it had
+// before the flag.
 #include "dcp_forward_scaled.h"
 #include "dcp_host.h"
 
@@ -183,6 +188,15 @@ __device__ __forceinline__ void finish_pair(dcp_fwd_args const &a, Redo const &r
     }
 }
 
+// ROWS: the row's record for the posteriors (dcp_posterior.h) -- PN(j), PJ(j), PC(j), B(j), E(j) -- as logs under the
+// exponent in force, one per lane: lanes 0 .. 2 hold their own state's value in px, lane 3 takes B, lane 4 E
+__device__ __forceinline__ void store_record(double px, double B, double E, int sA, double *rec, unsigned lane)
+{
+    double const v = lane < 3u ? px : lane == 3u ? B : E;
+    double const lg = dcp_fws_score(v, sA);
+    if (lane < 5u) rec[lane] = lg;
+}
+
 // ---- profiles of at most 64 R nodes: everything in registers -------------------------------------------------------
 template <int R> struct Trans
 {
@@ -195,9 +209,9 @@ template <int R> struct Rings
 };
 
 // one row; returns true if a value left the double range (wave-uniform)
-template <class Real, int R, int PH>
+template <class Real, int R, int PH, bool ROWS>
 __device__ __forceinline__ bool scaled_row(Rings<R> &g5, Specials &s, Trans<R> const &t, XS const &x, Tabs<Real> const &g,
-                                           unsigned j, unsigned lane, int band)
+                                           unsigned j, unsigned lane, int band, double *rec)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH}; // slot of row j - l
     unsigned const i = j - 1u;
@@ -260,6 +274,7 @@ __device__ __forceinline__ bool scaled_row(Rings<R> &g5, Specials &s, Trans<R> c
     s.E = E, s.Cc = Cc, s.Rr = Rr;
     fin = fin && dcp_fws_finite(px) && dcp_fws_finite(E) && dcp_fws_finite(B);
     if (__any(!fin)) return true;
+    if constexpr (ROWS) store_record(px, B, E, s.sA, rec + (uint64_t)DCP_POST_REC * j, lane);
 
     int kA, kR;
     rescale_steps(px, E, B, band, kA, kR);
@@ -279,7 +294,7 @@ __device__ __forceinline__ bool scaled_row(Rings<R> &g5, Specials &s, Trans<R> c
     return false;
 }
 
-template <class Real, int R> __global__ __launch_bounds__(256) void forward_scaled_kernel(dcp_fwd_args a, Redo rd)
+template <class Real, int R, bool ROWS> __global__ __launch_bounds__(256) void forward_scaled_kernel(dcp_fwd_args a, Redo rd)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -324,10 +339,16 @@ template <class Real, int R> __global__ __launch_bounds__(256) void forward_scal
 #pragma unroll
         for (int r = 0; r < R; ++r)
             g5.P[0][r] = B0 * t.ent[r];
+        double *rec = nullptr;
+        if constexpr (ROWS)
+        {
+            rec = record_of(a, pp);
+            store_record(s.PX[0], B0, 0.0, s.sA, rec, lane); // row 0: PN = SN, B = SB, no J, C, E yet
+        }
         bool bad = false;
         unsigned j = 1u;
 #define DCP_FWS_ROW(PH)                                                                                                \
-    bad = scaled_row<Real, R, PH>(g5, s, t, x, g, j, lane, rd.band);                                                   \
+    bad = scaled_row<Real, R, PH, ROWS>(g5, s, t, x, g, j, lane, rd.band, rec);                                        \
     if (bad || j == L) break;                                                                                          \
     ++j;
         for (;;)
@@ -352,9 +373,9 @@ __device__ __forceinline__ double *trans_fac(WideArea const &wa, int which)
     return wa.base + (uint64_t)(DCP_FWD_WORK_ROWS + which) * wa.ldk;
 }
 
-template <class Real, int PH>
+template <class Real, int PH, bool ROWS>
 __device__ __forceinline__ bool scaled_wide_row(Specials &s, XS const &x, Tabs<Real> const &g, WideArea const &wa, unsigned j,
-                                                unsigned lane, int band)
+                                                unsigned lane, int band, double *rec)
 {
     constexpr int sl[5] = {(PH + 4) % 5, (PH + 3) % 5, (PH + 2) % 5, (PH + 1) % 5, PH};
     unsigned const i = j - 1u;
@@ -449,6 +470,7 @@ __device__ __forceinline__ bool scaled_wide_row(Specials &s, XS const &x, Tabs<R
     s.E = E, s.Cc = Cc, s.Rr = Rr;
     fin = fin && dcp_fws_finite(px) && dcp_fws_finite(E) && dcp_fws_finite(B);
     if (__any(!fin)) return true;
+    if constexpr (ROWS) store_record(px, B, E, s.sA, rec + (uint64_t)DCP_POST_REC * j, lane);
 
     int kA, kR;
     rescale_steps(px, E, B, band, kA, kR);
@@ -473,7 +495,7 @@ __device__ __forceinline__ bool scaled_wide_row(Specials &s, XS const &x, Tabs<R
     return false;
 }
 
-template <class Real> __global__ __launch_bounds__(256) void forward_scaled_wide_kernel(dcp_fwd_args a, Redo rd)
+template <class Real, bool ROWS> __global__ __launch_bounds__(256) void forward_scaled_wide_kernel(dcp_fwd_args a, Redo rd)
 {
     unsigned const lane = threadIdx.x & 63u;
     uint64_t const gw = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
@@ -511,10 +533,16 @@ template <class Real> __global__ __launch_bounds__(256) void forward_scaled_wide
                     wa.ring0(h)[k0 + r] = wa.ring1(h)[k0 + r] = 0.0;
             }
         }
+        double *rec = nullptr;
+        if constexpr (ROWS)
+        {
+            rec = record_of(a, pp);
+            store_record(s.PX[0], B0, 0.0, s.sA, rec, lane);
+        }
         bool bad = false;
         unsigned j = 1u;
 #define DCP_FWS_ROW(PH)                                                                                                \
-    bad = scaled_wide_row<Real, PH>(s, x, g, wa, j, lane, rd.band);                                                    \
+    bad = scaled_wide_row<Real, PH, ROWS>(s, x, g, wa, j, lane, rd.band, rec);                                         \
     if (bad || j == L) break;                                                                                          \
     ++j;
         for (;;)
@@ -530,30 +558,36 @@ template <class Real> __global__ __launch_bounds__(256) void forward_scaled_wide
     }
 }
 
-template <class Real> int launch(int R, dcp_fwd_args const &a, Redo const &rd, hipStream_t st)
+template <class Real, bool ROWS> int launch(int R, dcp_fwd_args const &a, Redo const &rd, hipStream_t st)
 {
     dim3 const grid((a.nwaves + 3u) / 4u), block(256);
     switch (R)
     {
-    case 0: hipLaunchKernelGGL((forward_scaled_wide_kernel<Real>), grid, block, 0, st, a, rd); return 0;
-    case 1: hipLaunchKernelGGL((forward_scaled_kernel<Real, 1>), grid, block, 0, st, a, rd); return 0;
-    case 2: hipLaunchKernelGGL((forward_scaled_kernel<Real, 2>), grid, block, 0, st, a, rd); return 0;
-    case 4: hipLaunchKernelGGL((forward_scaled_kernel<Real, 4>), grid, block, 0, st, a, rd); return 0;
+    case 0: hipLaunchKernelGGL((forward_scaled_wide_kernel<Real, ROWS>), grid, block, 0, st, a, rd); return 0;
+    case 1: hipLaunchKernelGGL((forward_scaled_kernel<Real, 1, ROWS>), grid, block, 0, st, a, rd); return 0;
+    case 2: hipLaunchKernelGGL((forward_scaled_kernel<Real, 2, ROWS>), grid, block, 0, st, a, rd); return 0;
+    case 4: hipLaunchKernelGGL((forward_scaled_kernel<Real, 4, ROWS>), grid, block, 0, st, a, rd); return 0;
     default: return 1;
     }
 }
 
+template <bool ROWS> int launch(int precision, int R, dcp_fwd_args const &a, Redo const &rd, hipStream_t st)
+{
+    if (precision == 32) return launch<float, ROWS>(R, a, rd, st);
+    if (precision == 64) return launch<double, ROWS>(R, a, rd, st);
+    return 1;
+}
+
 } // namespace
 
-extern "C" int dcp_forward_scaled_launch(int precision, int R, struct dcp_fwd_args const *a, struct dcp_fwd_pair *redo,
+extern "C" int dcp_forward_scaled_launch(int precision, int R, int store, struct dcp_fwd_args const *a, struct dcp_fwd_pair *redo,
                                          uint32_t *nredo, uint32_t redo_cap, int band, void *stream)
 {
-    if (dcp_fwd_args_refused(a, R, DCP_FWD_STORE_NONE)) return 1;
+    if (store > DCP_FWD_STORE_ROWS || dcp_fwd_args_refused(a, R, store)) return 1; // there is no matrix-storing variant
     if (R == 0 && a->work_stride % DCP_FWS_WORK_ROWS) return 1; // a work area sized for the log-space sweep
     if (!redo || !nredo || redo_cap == 0 || band < 1 || band > 500) return 1;
     Redo const rd{redo, nredo, redo_cap, band};
     hipStream_t const st = (hipStream_t)stream;
-    if (precision == 32) return launch<float>(R, *a, rd, st);
-    if (precision == 64) return launch<double>(R, *a, rd, st);
-    return 1;
+    if (store == DCP_FWD_STORE_ROWS) return launch<true>(precision, R, *a, rd, st);
+    return launch<false>(precision, R, *a, rd, st);
 }

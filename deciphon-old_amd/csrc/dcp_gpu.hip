@@ -13,6 +13,7 @@
 #include "dcp_calib.h"
 #include "dcp_forward.h"
 #include "dcp_forward_scaled.h"
+#include "dcp_backward_scaled.h"
 #include "dcp_mea.h"
 #include "dcp_posterior.h"
 #include "dcp_test_hooks.h"
@@ -436,6 +437,7 @@ struct dcp_gpu_ctx
     //  d_redo_pairs  the same bucketed by class for the log-space kernels
     // band: the hooks build's band of the rescaling rule (0: DCP_FWS_BAND); scaled_ms, scaled_redo: the last scaled
     // pair-list call's launches, the last scaled call's rerun pairs; dense_scaled: which sweep filled d_dense.
+    // post_scaled_ms, post_scaled_redo: the same of the last dcp_gpu_posterior_pairs_scaled, summed over its rounds.
     struct PairSweeps
     {
         DevBuf<dcp_fwd_pair> d_redo, d_redo_pairs;
@@ -443,6 +445,8 @@ struct dcp_gpu_ctx
         int band = 0;
         float scaled_ms = -1.0f;
         unsigned scaled_redo = 0;
+        float post_scaled_ms = -1.0f;
+        unsigned post_scaled_redo = 0;
         bool dense_scaled = false;
         DevBuf<double> d_dense;
         DevBuf<uint32_t> d_order;
@@ -3699,7 +3703,7 @@ static int run_scaled_sweeps(dcp_gpu_ctx *c, dcp_fwd_args &a, ForwardBuckets con
         a.pairs = W.d_pairs.p + b.first[k];
         a.npairs = b.count[k];
         a.nwaves = b.waves[k];
-        if (dcp_forward_scaled_launch(c->precision, kFwdR[k], &a, W.d_redo.p, W.d_nredo.p, n, W.band ? W.band : (int)DCP_FWS_BAND,
+        if (dcp_forward_scaled_launch(c->precision, kFwdR[k], DCP_FWD_STORE_NONE, &a, W.d_redo.p, W.d_nredo.p, n, W.band ? W.band : (int)DCP_FWS_BAND,
                                       c->stream))
             return c->fail(DCP_EFAIL, "no scaled Forward kernel for %d nodes per lane", kFwdR[k]);
         HIP_TRY(c, hipGetLastError());
@@ -3906,9 +3910,88 @@ float dcp_gpu_forward_dense_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.den
 // The list runs in rounds of consecutive pairs whose row records -- 2 x DCP_POST_REC doubles a row -- fit the budget (a
 // single pair that exceeds it gets a round of its own).  A round: the row-storing Forward launches by class, the
 // Backward launches by class, the combining kernel, the round's rows copied out; then the next.
-int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
-                            uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
-                            double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
+//
+// The scaled call differs in the sweeps alone: the row-storing scaled Forward and the scaled Backward by class,
+// then one wait for the round's redo list -- the pairs either sweep could not return -- which the log-space sweeps rerun
+// into the same record and score slots before the combining kernel runs.
+static int run_scaled_posterior_sweeps(dcp_gpu_ctx *c, dcp_fwd_args &a, ForwardBuckets const &b, unsigned npairs, uint64_t nrows,
+                                       unsigned *redone)
+{
+    auto &W = c->sweeps;
+    unsigned const n = b.first[4], cap = 2u * n; // both sweeps may flag the same pair
+    int const band = W.band ? W.band : (int)DCP_FWS_BAND;
+    double *const rows_f = W.d_rec.p, *const rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
+    double *const alt_fwd = a.out_null + npairs, *const alt_bwd = a.out_null + 2u * (size_t)npairs;
+    uint64_t const chunk_cols = (uint64_t)b.wide_chunks * DCP_FWD_CHUNK, stride_was = a.work_stride;
+    HIP_TRY(c, W.d_redo.reserve(cap));
+    HIP_TRY(c, W.d_nredo.reserve(1u));
+    HIP_TRY(c, hipMemsetAsync(W.d_nredo.p, 0, sizeof(uint32_t), c->stream));
+    for (int sweep = 0; sweep < 2; ++sweep)
+    {
+        a.rows = sweep ? rows_b : rows_f;
+        a.out_alt = sweep ? alt_bwd : alt_fwd;
+        a.work_stride = (uint64_t)(sweep ? DCP_BWS_WORK_ROWS : DCP_FWS_WORK_ROWS) * chunk_cols;
+        for (int k = 0; k < 4; ++k)
+        {
+            if (b.count[k] == 0) continue;
+            a.pairs = W.d_pairs.p + b.first[k];
+            a.npairs = b.count[k];
+            a.nwaves = b.waves[k];
+            int const rc = sweep ? dcp_backward_scaled_launch(c->precision, kFwdR[k], &a, rows_f, alt_fwd, W.d_redo.p, W.d_nredo.p, cap,
+                                                              band, c->stream)
+                                 : dcp_forward_scaled_launch(c->precision, kFwdR[k], DCP_FWD_STORE_ROWS, &a, W.d_redo.p, W.d_nredo.p,
+                                                             cap, band, c->stream);
+            if (rc) return c->fail(DCP_EFAIL, "no scaled %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    a.work_stride = stride_was;
+    // the round's redo list: sorted by position and without the pairs both sweeps flagged, so that a call repeats itself
+    uint32_t nr = 0;
+    HIP_TRY(c, hipMemcpyAsync(&nr, W.d_nredo.p, sizeof nr, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (nr == 0) return DCP_OK;
+    if (nr > cap) return c->fail(DCP_EFAIL, "the scaled sweeps' redo list holds %u pairs of a round of %u", nr, n);
+    std::vector<dcp_fwd_pair> rec(nr);
+    HIP_TRY(c, hipMemcpy(rec.data(), W.d_redo.p, (size_t)nr * sizeof(dcp_fwd_pair), hipMemcpyDeviceToHost));
+    std::sort(rec.begin(), rec.end(), [](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return x.pos < y.pos; });
+    rec.erase(std::unique(rec.begin(), rec.end(), [](dcp_fwd_pair const &x, dcp_fwd_pair const &y) { return x.pos == y.pos; }), rec.end());
+    nr = (uint32_t)rec.size();
+    std::vector<uint32_t> sq(nr), pr(nr);
+    for (uint32_t i = 0; i < nr; ++i)
+        sq[i] = rec[i].q, pr[i] = rec[i].prof;
+    ForwardBuckets rb;
+    forward_bucket(c, sq.data(), pr.data(), nr, 0u, rb);
+    for (dcp_fwd_pair &p : rb.pairs)
+        p.pos = rec[p.pos].pos;
+    HIP_TRY(c, W.d_redo_pairs.reserve(nr));
+    HIP_TRY(c, hipMemcpyAsync(W.d_redo_pairs.p, rb.pairs.data(), (size_t)nr * sizeof(dcp_fwd_pair), hipMemcpyHostToDevice, c->stream));
+    // both sweeps in log space, so that the two records agree: dcp_gpu_posterior_pairs' launches over the redo list
+    a.work_stride = (uint64_t)DCP_FWD_WORK_ROWS * rb.wide_chunks * DCP_FWD_CHUNK; // at most the round's: its pairs are of the round
+    for (int sweep = 0; sweep < 2; ++sweep)
+    {
+        a.rows = sweep ? rows_b : rows_f;
+        a.out_alt = sweep ? alt_bwd : alt_fwd;
+        for (int k = 0; k < 4; ++k)
+        {
+            if (rb.count[k] == 0) continue;
+            a.pairs = W.d_redo_pairs.p + rb.first[k];
+            a.npairs = rb.count[k];
+            a.nwaves = rb.waves[k];
+            if ((sweep ? dcp_backward_launch : dcp_forward_launch)(c->precision, kFwdR[k], DCP_FWD_STORE_ROWS, &a, c->stream))
+                return c->fail(DCP_EFAIL, "no %s kernel for %d nodes per lane", sweep ? "Backward" : "Forward", kFwdR[k]);
+            HIP_TRY(c, hipGetLastError());
+        }
+    }
+    a.work_stride = stride_was;
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // rb's records are up
+    *redone += nr;
+    return DCP_OK;
+}
+
+static int posterior_pairs(dcp_gpu_ctx *c, bool scaled, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                           uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                           double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
 {
     if (!c) return DCP_EINVAL;
     if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, alt_fwd_out && alt_bwd_out)) return rc;
@@ -3927,7 +4010,9 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
     }
     auto &W = c->sweeps;
     dcp_fwd_args a{};
-    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)3u * npairs, off, &a)) return rc;
+    if (int rc = sweeps_setup(c, multi_hits, hmmer3_compat, wide_of_list(c, profile_idx, npairs), (size_t)3u * npairs, off, &a,
+                              scaled ? (unsigned)DCP_FWS_WORK_ROWS : (unsigned)DCP_FWD_WORK_ROWS)) // (the widest of a round's sweeps)
+        return rc;
     // a round's row records fit the budget; room for the largest round's before the first one runs
     uint64_t const budget = W.post_budget ? W.post_budget : (uint64_t)1u << 30;
     auto const bytes_of = [&](unsigned i0, unsigned i1) { return (off[i1] - off[i0]) * (2u * DCP_POST_REC * sizeof(double)); };
@@ -3948,6 +4033,7 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
 
     std::vector<double> rows;
     float ms_total = 0.0f;
+    unsigned redone = 0;
     for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
     {
         i1 = round_end(i0, npairs, budget, bytes_of);
@@ -3958,7 +4044,9 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         a.row_base = off[i0];
         HIP_TRY(c, hipEventRecord(W.ev[0], c->stream));
-        if (int rc = run_sweeps(c, a, b, 2, DCP_FWD_STORE_ROWS, npairs, nrows, 0u)) return rc;
+        if (int rc = scaled ? run_scaled_posterior_sweeps(c, a, b, npairs, nrows, &redone)
+                            : run_sweeps(c, a, b, 2, DCP_FWD_STORE_ROWS, npairs, nrows, 0u))
+            return rc;
         pa.list = W.d_pairs.p + n, pa.nlist = n, pa.row_off = W.d_off.p + i0;
         pa.rows_f = W.d_rec.p, pa.rows_b = W.d_rec.p + (size_t)DCP_POST_REC * nrows;
         pa.begin = W.d_rows.p, pa.end = pa.begin + nrows, pa.core = pa.end + nrows;
@@ -3982,11 +4070,30 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
     std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
     std::memcpy(alt_bwd_out, score.data() + npairs, (size_t)npairs * sizeof(double));
     std::memcpy(row_off, off.data(), off.size() * sizeof(uint64_t));
-    W.post_ms = ms_total;
+    if (scaled) W.post_scaled_ms = ms_total, W.post_scaled_redo = redone;
+    else W.post_ms = ms_total;
     return DCP_OK;
 }
 
+int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                            uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                            double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
+{
+    return posterior_pairs(c, false, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, row_off, begin_out, end_out, core_out,
+                           cap_rows, alt_fwd_out, alt_bwd_out);
+}
+
+int dcp_gpu_posterior_pairs_scaled(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                                   uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                                   double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
+{
+    return posterior_pairs(c, true, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, row_off, begin_out, end_out, core_out,
+                           cap_rows, alt_fwd_out, alt_bwd_out);
+}
+
 float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.post_ms : -1.0f; }
+unsigned dcp_gpu_posterior_scaled_redo_pairs(dcp_gpu_ctx *c) { return c ? c->sweeps.post_scaled_redo : 0u; }
+float dcp_gpu_posterior_scaled_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.post_scaled_ms : -1.0f; }
 
 // ---- The posterior-decoded alignment of a pair list (dcp_mea.hip) ---------------------------------------------------
 // The list runs in rounds of consecutive pairs whose matrices (P, Q, bM, bI: 32 bytes a cell), cell choices (2 bytes a

@@ -2017,10 +2017,12 @@ struct ScaledFactor
 };
 } // namespace
 
-extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
-                                              double const *emis_insert, double const *emis_null, double const xtrans[13],
-                                              unsigned char const *seq, unsigned L, int float_factors, int band,
-                                              double *null_out, double *alt_out, int *out_of_range)
+// The sweep itself.  rec, if given, receives the row records PN(j), PJ(j), PC(j), B(j), E(j) as logs under the exponent
+// in force (dcp_backward_scaled.h), rows 0 .. L of an unflagged pair (a flagged one: the rows before its last).
+static int forward_scaled_sweep(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                unsigned char const *seq, unsigned L, int float_factors, int band, double *null_out,
+                                double *alt_out, int *out_of_range, double *rec)
 {
     if (M == 0 || M > 4096u || ldk < M || L == 0 || band < 1 || band > 500) return DCP_EINVAL;
     if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq || !null_out || !alt_out || !out_of_range)
@@ -2065,6 +2067,11 @@ extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double c
     for (unsigned k = 0; k < M; ++k)
         bad |= !dcp_fws_finite(P[k]);
     bad |= !dcp_fws_finite(PN[0]);
+    if (rec && !bad)
+    {
+        double const ninf = dcp_fwd_ninf();
+        rec[0] = dcp_fws_score(PN[0], s), rec[1] = ninf, rec[2] = ninf, rec[3] = dcp_fws_score(B0, s), rec[4] = ninf;
+    }
 
     static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
     double E = 0.0, Cc = 0.0, Rr = 0.0;
@@ -2132,6 +2139,12 @@ extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double c
         bad |= !dcp_fws_finite(E) || !dcp_fws_finite(B) || !dcp_fws_finite(PN[r]) || !dcp_fws_finite(PJ[r]) ||
                !dcp_fws_finite(PC[r]) || !dcp_fws_finite(PR[r]);
         if (bad) break;
+        if (rec)
+        {
+            double *const o = rec + (size_t)DCP_POST_REC * j;
+            o[0] = dcp_fws_score(PN[r], s), o[1] = dcp_fws_score(PJ[r], s), o[2] = dcp_fws_score(PC[r], s);
+            o[3] = dcp_fws_score(B, s), o[4] = dcp_fws_score(E, s);
+        }
         double const ref = dcp_fwd_max(dcp_fwd_max(dcp_fwd_max(PN[r], PJ[r]), dcp_fwd_max(PC[r], E)), B);
         if (int const k = dcp_fws_rescale_by(ref, band))
         {
@@ -2168,6 +2181,15 @@ extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double c
     *null_out = dcp_fws_score(Rr, sR);
     *alt_out = dcp_fws_score(alt, s);
     return DCP_OK;
+}
+
+extern "C" int dcp_forward_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                              double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                              unsigned char const *seq, unsigned L, int float_factors, int band,
+                                              double *null_out, double *alt_out, int *out_of_range)
+{
+    return forward_scaled_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, float_factors, band,
+                                null_out, alt_out, out_of_range, nullptr);
 }
 
 extern "C" int dcp_forward_scaled_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
@@ -2304,6 +2326,194 @@ extern "C" int dcp_posterior_tables(unsigned M, unsigned ldk, double const *tran
     *alt_bwd_out = alt_bwd;
     std::free(mem);
     return DCP_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The scaled Backward and the posterior rows on the host: the twin of dcp_backward_scaled.hip.  backward_sweep's
+// recursion by dcp_backward_scaled.h's rule, sequential in k, every sum in index order; the rings of bM and bI are five
+// rows each, as on the device.  The Forward half is forward_scaled_sweep with its records.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_backward_scaled.h"
+
+extern "C" int dcp_posterior_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                                double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                                unsigned char const *seq, unsigned L, int float_factors, int band,
+                                                double *begin_out, double *end_out, double *core_out, double *alt_fwd_out,
+                                                double *alt_bwd_out, int *out_of_range)
+{
+    if (M == 0 || M > 4096u || ldk < M || L == 0 || band < 1 || band > 500) return DCP_EINVAL;
+    if (!trans8 || !emis_match || !emis_insert || !emis_null || !xtrans || !seq) return DCP_EINVAL;
+    if (!begin_out || !end_out || !core_out || !alt_fwd_out || !alt_bwd_out || !out_of_range) return DCP_EINVAL;
+    for (unsigned i = 0; i < L; ++i)
+        if (seq[i] > 3) return DCP_EINVAL;
+    ScaledFactor const f{float_factors != 0};
+    size_t const rows = (size_t)L + 1u;
+    // the two sweeps' records, the transitions' factors ([8][M]), the rings of bM and bI, the row's bP, bQ, bD
+    size_t const nrec = 2u * (size_t)DCP_POST_REC * rows, nwork = (size_t)(8 + 10 + 3) * M;
+    double *const mem = (double *)std::malloc(sizeof(double) * (nrec + nwork));
+    if (!mem) return DCP_ENOMEM;
+    double *const fr = mem, *const br = fr + DCP_POST_REC * rows, *const T = mem + nrec, *const bM = T + 8 * (size_t)M,
+                 *const bI = bM + 5 * (size_t)M, *const bP = bI + 5 * (size_t)M, *const bQ = bP + M, *const bD = bQ + M;
+    for (size_t i = 0; i < nrec; ++i)
+        mem[i] = dcp_fwd_ninf();
+    double null_fwd = 0.0, alt_fwd = 0.0;
+    int oor = 0;
+    if (int rc = forward_scaled_sweep(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, float_factors, band,
+                                      &null_fwd, &alt_fwd, &oor, fr))
+    {
+        std::free(mem);
+        return rc;
+    }
+    if (oor)
+    {
+        std::free(mem);
+        *out_of_range = 1;
+        return DCP_OK;
+    }
+    for (int t = 0; t < 8; ++t)
+        for (unsigned k = 0; k < M; ++k)
+            T[(size_t)t * M + k] = f(trans8[(size_t)t * ldk + k]);
+    double const *ENT = T + (size_t)DCP_T_ENTRY * M, *MM = T + (size_t)DCP_T_MM * M, *IM = T + (size_t)DCP_T_IM * M,
+                 *DM = T + (size_t)DCP_T_DM * M, *MD = T + (size_t)DCP_T_MD * M, *DD = T + (size_t)DCP_T_DD * M,
+                 *MI = T + (size_t)DCP_T_MI * M, *II = T + (size_t)DCP_T_II * M;
+    double x[13];
+    for (int i = 0; i < 13; ++i)
+        x[i] = f(xtrans[i]);
+    for (size_t i = 0; i < 10 * (size_t)M; ++i)
+        bM[i] = 0.0; // (bI follows bM)
+    double bN[5], bJ[5], bC[5];
+    for (int h = 0; h < 5; ++h)
+        bN[h] = bJ[h] = bC[h] = 0.0;
+    // row L's part of the rule: ref = max(ET, CT), before anything reads the ring
+    int s = 0;
+    double ETL = x[DCP_X_ET], CTL = x[DCP_X_CT];
+    if (dcp_fws_finite(ETL) && dcp_fws_finite(CTL))
+        if (int const k = dcp_fws_rescale_by(dcp_fwd_max(ETL, CTL), band))
+        {
+            double const c = dcp_fws_pow2(-k);
+            ETL *= c, CTL *= c;
+            s = k;
+        }
+    static unsigned const code_off[5] = {0u, 4u, 20u, 84u, 340u};
+    bool bad = false;
+    double bB = 0.0, bPN = 0.0;
+    for (unsigned j = L;; --j)
+    {
+        unsigned code[5], slot[5], v = 0;
+        double fN[5], fI[5];
+        for (unsigned l = 1; l <= 5u; ++l)
+        {
+            v = (v << 2) | (j + l - 1u < L ? seq[j + l - 1u] : 0u);
+            code[l - 1] = code_off[l - 1] + v;
+            slot[l - 1] = (j + l) % 5u; // row j + l's slot; row j itself goes to j % 5, row j + 5's
+            fN[l - 1] = f(emis_null[code[l - 1]]);
+            fI[l - 1] = f(emis_insert[code[l - 1]]);
+        }
+        bPN = 0.0;
+        double bPJ = 0.0, bPC = 0.0;
+        for (int l = 0; l < 5; ++l)
+        {
+            bPN = dcp_fws_fma(bN[slot[l]], fN[l], bPN), bPJ = dcp_fws_fma(bJ[slot[l]], fN[l], bPJ);
+            bPC = dcp_fws_fma(bC[slot[l]], fN[l], bPC);
+        }
+        for (unsigned k = 0; k < M; ++k)
+        {
+            double p = 0.0, q = 0.0;
+            for (int l = 0; l < 5; ++l)
+            {
+                p = dcp_fws_fma(bM[(size_t)slot[l] * M + k], f(emis_match[(size_t)code[l] * ldk + k]), p);
+                q = dcp_fws_fma(bI[(size_t)slot[l] * M + k], fI[l], q);
+            }
+            bP[k] = p, bQ[k] = q;
+        }
+        bB = 0.0;
+        for (unsigned k = 0; k < M; ++k)
+            bB += ENT[k] * bP[k];
+        bool const last = j == L;
+        double bE = last ? ETL : 0.0;
+        bE = dcp_fws_fma(x[DCP_X_EB], bB, bE);
+        bE = dcp_fws_fma(x[DCP_X_EJ], bPJ, bE);
+        bE = dcp_fws_fma(x[DCP_X_EC], bPC, bE);
+        unsigned const r = j % 5u;
+        bN[r] = dcp_fws_fma(x[DCP_X_NN], bPN, x[DCP_X_NB] * bB);
+        bJ[r] = dcp_fws_fma(x[DCP_X_JJ], bPJ, x[DCP_X_JB] * bB);
+        bC[r] = dcp_fws_fma(x[DCP_X_CC], bPC, last ? CTL : 0.0);
+        double *const m = bM + (size_t)r * M, *const ins = bI + (size_t)r * M;
+        for (unsigned k = M; k-- > 0;)
+        {
+            bool const nx = k + 1u < M; // node k + 1 exists; else its factors are 0
+            double const dn = nx ? bD[k + 1] : 0.0, pn = nx ? bP[k + 1] : 0.0;
+            double const dd = nx ? DD[k + 1] : 0.0, dm = nx ? DM[k + 1] : 0.0, md = nx ? MD[k + 1] : 0.0,
+                         mm = nx ? MM[k + 1] : 0.0, im = nx ? IM[k + 1] : 0.0;
+            bD[k] = dcp_fws_fma(dd, dn, dcp_fws_fma(dm, pn, bE));
+            double mv = dcp_fws_fma(md, dn, bE);
+            mv = dcp_fws_fma(mm, pn, mv);
+            m[k] = dcp_fws_fma(MI[k], bQ[k], mv);
+            ins[k] = dcp_fws_fma(II[k], bQ[k], im * pn);
+            bad |= !dcp_fws_finite(m[k]) || !dcp_fws_finite(ins[k]);
+        }
+        bad |= !dcp_fws_finite(bB) || !dcp_fws_finite(bE) || !dcp_fws_finite(bN[r]) || !dcp_fws_finite(bJ[r]) ||
+               !dcp_fws_finite(bC[r]);
+        if (bad) break;
+        double *const o = br + (size_t)DCP_POST_REC * j;
+        o[0] = dcp_fws_score(bN[r], s), o[1] = dcp_fws_score(bJ[r], s), o[2] = dcp_fws_score(bC[r], s);
+        o[3] = dcp_fws_score(bB, s), o[4] = dcp_fws_score(bE, s);
+        if (dcp_bws_lossy(dcp_bws_rec_max(fr + (size_t)DCP_POST_REC * j), dcp_bws_rec_max(o), alt_fwd, band))
+        {
+            bad = true;
+            break;
+        }
+        double const ref = dcp_fwd_max(dcp_fwd_max(dcp_fwd_max(bN[r], bJ[r]), dcp_fwd_max(bC[r], bB)), bE);
+        if (int const k = dcp_fws_rescale_by(ref, band))
+        {
+            double const c = dcp_fws_pow2(-k);
+            for (size_t i = 0; i < 10 * (size_t)M; ++i)
+                bM[i] *= c;
+            for (int h = 0; h < 5; ++h)
+                bN[h] *= c, bJ[h] *= c, bC[h] *= c;
+            bB *= c, bPN *= c;
+            s += k;
+        }
+        if (j == 0) break;
+    }
+    double alt = 0.0;
+    if (!bad)
+    {
+        // row 0's bB and bPN with the larger of them in [1, 2): the product with SB, SN near e^-708 stays normal
+        int const k = dcp_fws_rescale_by(dcp_fwd_max(bB, bPN), 0);
+        double const c = dcp_fws_pow2(-k);
+        alt = dcp_fws_fma(x[DCP_X_SN], bPN * c, x[DCP_X_SB] * (bB * c));
+        s += k;
+        bad = !dcp_fws_finite(alt);
+    }
+    *out_of_range = bad ? 1 : 0;
+    if (!bad)
+    {
+        for (unsigned j = 0; j <= L; ++j)
+        {
+            unsigned win = 0; // bases j - 5 .. j + 3, first most significant; outside the sequence 0
+            for (unsigned i = 0; i < 9u; ++i)
+            {
+                long const t = (long)j - 5 + (long)i;
+                win = (win << 2) | (t >= 0 && t < (long)L ? seq[t] : 0u);
+            }
+            dcp_posterior_row<double>(fr, br, emis_null, win, j, L, alt_fwd, begin_out + j, end_out + j, core_out + j);
+        }
+        *alt_fwd_out = alt_fwd;
+        *alt_bwd_out = dcp_fws_score(alt, s);
+    }
+    std::free(mem);
+    return DCP_OK;
+}
+
+extern "C" int dcp_posterior_scaled_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                           double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                           unsigned char const *seq, unsigned L, int float_factors, double *begin_out,
+                                           double *end_out, double *core_out, double *alt_fwd_out, double *alt_bwd_out,
+                                           int *out_of_range)
+{
+    return dcp_posterior_scaled_tables_band(M, ldk, trans8, emis_match, emis_insert, emis_null, xtrans, seq, L, float_factors,
+                                            DCP_FWS_BAND, begin_out, end_out, core_out, alt_fwd_out, alt_bwd_out, out_of_range);
 }
 
 // Envelopes: the maximal runs of bases with core >= threshold that are at least min_len bases long, as half-open base

@@ -1095,6 +1095,42 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, ui
 float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *);
 
 /* ------------------------------------------------------------------------ */
+/* The scaled probability-space Backward sweep and posterior rows */
+/* ------------------------------------------------------------------------ */
+/* dcp_posterior_tables with both sweeps in the scaled representation of §24 (csrc/dcp_backward_scaled.h): values are
+ * probabilities beside a power-of-two exponent, a row's five record values are turned into logs once per row, and the
+ * rows are combined by the same rule.  float_factors as dcp_forward_scaled_tables.  Arguments and refusals are
+ * dcp_posterior_tables' (a null out_of_range is DCP_EINVAL too).  *out_of_range = 1, nothing else written: a value left
+ * the double range in either sweep, or a row's records may have lost a term of 2^-64 or more of a posterior to underflow
+ * (F + Bk - a > (958 - band) ln 2 for the largest record values F, Bk of the two sweeps at a row and the Forward alt
+ * score a); else 0 and every output.  alt_fwd_out has dcp_forward_scaled_tables' bits.  No device. */
+int dcp_posterior_scaled_tables(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                unsigned char const *seq, unsigned L, int float_factors, double *begin_out, double *end_out,
+                                double *core_out, double *alt_fwd_out, double *alt_bwd_out, int *out_of_range);
+/* The same with the band of the rescaling rule given (1 .. 500; dcp_posterior_scaled_tables: 64).  The scores and rows of
+ * a pair that is in range under both bands do not depend on it; which pairs the underflow check flags does. */
+int dcp_posterior_scaled_tables_band(unsigned M, unsigned ldk, double const *trans8, double const *emis_match,
+                                     double const *emis_insert, double const *emis_null, double const xtrans[13],
+                                     unsigned char const *seq, unsigned L, int float_factors, int band, double *begin_out,
+                                     double *end_out, double *core_out, double *alt_fwd_out, double *alt_bwd_out,
+                                     int *out_of_range);
+/* dcp_gpu_posterior_pairs by the scaled sweeps (csrc/dcp_forward_scaled.hip's row-storing variant and csrc/
+ * dcp_backward_scaled.hip): the same signature, checks, messages, rounds, outputs and synchronisation.  Pairs that either
+ * sweep flags are collected on the device and rerun, both sweeps, by dcp_gpu_posterior_pairs' kernels before the round's
+ * rows are combined: those come back with dcp_gpu_posterior_pairs' bits, and every returned row is valid.  alt_fwd_out
+ * of a pair that was not rerun has dcp_gpu_forward_pairs_scaled's bits. */
+int dcp_gpu_posterior_pairs_scaled(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
+                                   uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
+                                   double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out,
+                                   double *alt_bwd_out);
+/* How many pairs the context's last dcp_gpu_posterior_pairs_scaled reran in log space, over all its rounds. */
+unsigned dcp_gpu_posterior_scaled_redo_pairs(dcp_gpu_ctx *);
+/* Milliseconds, by HIP events, summed over the rounds' launches (the reruns included) of the context's last
+ * dcp_gpu_posterior_pairs_scaled that launched any; negative before. */
+float dcp_gpu_posterior_scaled_kernel_ms(dcp_gpu_ctx *);
+
+/* ------------------------------------------------------------------------ */
 /* Posterior-decoded (maximum expected accuracy) alignment for a list of pairs */
 /* ------------------------------------------------------------------------ */
 /* Every path above is a Viterbi path.  The posterior-decoded path is chosen by what all paths say about each step: with

@@ -113,6 +113,8 @@ ABI_SYMBOLS = [
     # the scaled Backward sweep and posterior rows of a pair list, and the host twin
     "dcp_posterior_scaled_tables", "dcp_posterior_scaled_tables_band", "dcp_gpu_posterior_pairs_scaled",
     "dcp_gpu_posterior_scaled_redo_pairs", "dcp_gpu_posterior_scaled_kernel_ms",
+    # posterior envelopes of a pair list found on the device, the host twin, envelopes as regions to cut
+    "dcp_posterior_envelope_records", "dcp_gpu_envelope_pairs", "dcp_gpu_envelope_kernel_ms", "dcp_envelopes_regions",
 ]
 
 
@@ -163,6 +165,10 @@ HIT64_DTYPE = np.dtype([("seq_idx", np.uint32), ("profile_idx", np.uint32),
 # struct dcp_domain: one B .. E stretch of an alt path (Scanner.path_domains)
 DOMAIN_DTYPE = np.dtype([(f, np.uint32) for f in ("path", "step_begin", "step_end", "seq_begin", "seq_end", "node_first",
                                                    "node_last", "n_match", "n_insert", "n_delete", "n_shift", "reserved")])
+# struct dcp_envelope (48 bytes): a posterior envelope of pair `pair` of a list, bases [begin, end) of its sequence
+ENVELOPE_DTYPE = np.dtype([("pair", np.uint32), ("begin", np.uint32), ("end", np.uint32), ("peak", np.uint32),
+                           ("core_max", np.float64), ("core_sum", np.float64), ("begin_sum", np.float64),
+                           ("end_sum", np.float64)])
 
 
 def _load(path=None, hooks=False):
@@ -309,6 +315,10 @@ def _load(path=None, hooks=False):
         "dcp_gpu_forward_kernel_ms": (F, [P]),
         "dcp_posterior_tables": (I, [U, U, P, P, P, P, P, P, U, P, P, P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "dcp_posterior_envelopes": (I, [P, U, C.c_double, U, P, P, U, C.POINTER(U)]),
+        "dcp_posterior_envelope_records": (I, [P, P, P, U, C.c_double, C.c_double, U, P, U, C.POINTER(U)]),
+        "dcp_gpu_envelope_pairs": (I, [P, I, I, I, P, P, U, C.c_double, C.c_double, U, P, C.c_uint64, P, P, P]),
+        "dcp_gpu_envelope_kernel_ms": (F, [P]),
+        "dcp_envelopes_regions": (I, [P, C.c_uint64, P, U, P, U, U, P, P, P, P]),
         "dcp_gpu_posterior_pairs": (I, [P, I, I, P, P, U, P, P, P, P, C.c_uint64, P, P]),
         "dcp_gpu_posterior_kernel_ms": (F, [P]),
         "dcp_mea_tables": (I, [U, U, P, P, P, P, P, P, U, P, U, C.POINTER(U), P, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -358,6 +368,8 @@ def _load(path=None, hooks=False):
         sig["dcp_gpu_test_set_forward_scale_band"] = (I, [P, U])
         sig["dcp_gpu_test_set_posterior_budget"] = (I, [P, C.c_ulonglong])
         sig["dcp_gpu_test_set_mea_budget"] = (I, [P, C.c_ulonglong])
+        sig["dcp_gpu_test_envelope_records_kernel_ms"] = (F, [P])
+        sig["dcp_gpu_test_envelopes_of_rows"] = (I, [P, P, P, P, P, U, C.c_double, C.c_double, U, P, C.c_uint64, P])
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
         fn.restype = res
@@ -850,6 +862,49 @@ def posterior_envelopes(core, threshold=0.5, min_len=1):
     if rc:
         raise DcpError(rc, "dcp_posterior_envelopes")
     return [(int(x), int(y)) for x, y in zip(b, e)]
+
+
+def posterior_envelope_records(begin, end, core, hi=0.5, lo=None, min_len=1):
+    """The envelopes of one pair's posterior rows as ENVELOPE_DTYPE records, in order (dcp_posterior_envelope_records,
+    the host twin of Scanner.envelope_pairs): the maximal runs of bases with core >= lo (lo=None: hi) that are at least
+    min_len bases long and reach hi somewhere; per run its interval, the first base where core is largest and that
+    value, and the sums of core, begin and end over it -- the expected numbers of core-emitted bases, domain starts and
+    domain ends.  begin, end, core are rows of posterior_tables / posterior_pairs (L + 1 values, base i at core[i + 1]);
+    pair is 0."""
+    begin, end, core = _f64(begin), _f64(end), _f64(core)
+    if not len(begin) == len(end) == len(core):
+        raise DcpError(RC_EINVAL, "rows of one length")
+    L = max(len(core) - 1, 0)
+    lo = hi if lo is None else lo
+    n = C.c_uint(0)
+    rc = lib.dcp_posterior_envelope_records(begin.ctypes.data, end.ctypes.data, core.ctypes.data, L, float(hi), float(lo),
+                                            int(min_len), None, 0, C.byref(n))
+    if rc != RC_OK:
+        raise DcpError(rc, "dcp_posterior_envelope_records")
+    out = np.zeros(n.value, ENVELOPE_DTYPE)
+    rc = lib.dcp_posterior_envelope_records(begin.ctypes.data, end.ctypes.data, core.ctypes.data, L, float(hi), float(lo),
+                                            int(min_len), out.ctypes.data, n.value, C.byref(n))
+    if rc != RC_OK:
+        raise DcpError(rc, "dcp_posterior_envelope_records")
+    return out
+
+
+def envelopes_regions(env, seq_idx, seq_len, flank=0):
+    """(src, begin, length, profile_pair) for Scanner.cut_regions from ENVELOPE_DTYPE records (dcp_envelopes_regions):
+    envelope k becomes the stretch [max(begin - flank, 0), min(end + flank, L)) of resident sequence
+    seq_idx[env[k].pair], L = seq_len[that sequence]; profile_pair[k] = env[k].pair names the list entry whose profile
+    the region is to be scored against.  seq_idx is the list envelope_pairs was given, seq_len the resident
+    sequences' lengths."""
+    env = np.ascontiguousarray(env, ENVELOPE_DTYPE)
+    sq = np.ascontiguousarray(np.atleast_1d(seq_idx), np.uint32)
+    sl = np.ascontiguousarray(np.atleast_1d(seq_len), np.uint32)
+    n = len(env)
+    src, begin, length, pair = (np.zeros(n, np.uint32) for _ in range(4))
+    rc = lib.dcp_envelopes_regions(env.ctypes.data, n, sq.ctypes.data, len(sq), sl.ctypes.data, len(sl), int(flank),
+                                   src.ctypes.data, begin.ctypes.data, length.ctypes.data, pair.ctypes.data)
+    if rc != RC_OK:
+        raise DcpError(rc, "dcp_envelopes_regions")
+    return src, begin, length, pair
 
 
 def lrt(null_loglik, alt_loglik):
@@ -1670,6 +1725,59 @@ class Scanner:
         """TEST-ONLY (test-hooks build): the device memory the following posterior_pairs calls give their row records
         (0: the default, 1 GiB)."""
         self._check(self._lib.dcp_gpu_test_set_posterior_budget(self._c, int(nbytes)))
+
+    def envelope_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False, hi=0.5, lo=None, min_len=1,
+                       scaled=True):
+        """(env_off, env, alt_fwd, alt_bwd) of the pairs (resident sequence seq_idx[i], resident profile profile_idx[i])
+        on a float or a double DB (dcp_gpu_envelope_pairs): the posterior envelopes of every pair, found on the device
+        from the rows posterior_pairs_scaled (scaled=True) or posterior_pairs (scaled=False) would return, without those
+        rows leaving it.  env is an ENVELOPE_DTYPE array, pair i's records env[env_off[i]:env_off[i + 1]] in order of
+        begin: the maximal runs of bases with core >= lo (lo=None: hi), at least min_len bases long, that reach hi
+        (posterior_envelope_records is the host twin).  alt_fwd / alt_bwd have the posterior call's bits.  The array
+        is sized by a first guess of four envelopes a pair; if the list has more, the call names the count
+        (DCP_ENOMEM's env_off) and runs once more.  Returns synchronised; the last scan's results stay what they were."""
+        sq, pr = _pair_list(seq_idx, profile_idx)
+        n = len(sq)
+        lo = hi if lo is None else lo
+        cap = 4 * n + 64
+        off = np.zeros(n + 1, np.uint64)
+        fwd, bwd = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        for _ in range(2):
+            env = np.zeros(cap, ENVELOPE_DTYPE)
+            rc = self._lib.dcp_gpu_envelope_pairs(self._c, int(multi_hits), int(hmmer3_compat), int(bool(scaled)),
+                                                  sq.ctypes.data, pr.ctypes.data, n, float(hi), float(lo), int(min_len),
+                                                  env.ctypes.data, cap, off.ctypes.data, fwd.ctypes.data, bwd.ctypes.data)
+            if rc != RC_ENOMEM or int(off[n]) <= cap:
+                break
+            cap = int(off[n])
+        self._check(rc)
+        return off, env[:int(off[n])].copy(), fwd, bwd
+
+    @property
+    def envelope_kernel_ms(self):
+        """Milliseconds of the last envelope_pairs call's launches -- sweeps, reruns, combining and envelope kernels, all
+        rounds -- by HIP events; negative before any."""
+        return self._lib.dcp_gpu_envelope_kernel_ms(self._c)
+
+    @property
+    def test_envelope_records_kernel_ms(self):
+        """TEST-ONLY (test-hooks build): the envelope kernels' own part of envelope_kernel_ms."""
+        return self._lib.dcp_gpu_test_envelope_records_kernel_ms(self._c)
+
+    def test_envelopes_of_rows(self, row_off, begin, end, core, hi=0.5, lo=None, min_len=1):
+        """TEST-ONLY (test-hooks build): (env_off, env) of caller-made rows by the envelope kernels alone
+        (dcp_gpu_test_envelopes_of_rows): pair i's rows are [row_off[i], row_off[i + 1]) of the three arrays."""
+        row_off = np.ascontiguousarray(row_off, np.uint64)
+        begin, end, core = _f64(begin), _f64(end), _f64(core)
+        n = len(row_off) - 1
+        lo = hi if lo is None else lo
+        off = np.zeros(n + 1, np.uint64)
+        cap = int(row_off[-1] - row_off[0])  # no more runs than rows
+        env = np.zeros(max(cap, 1), ENVELOPE_DTYPE)
+        self._check(self._lib.dcp_gpu_test_envelopes_of_rows(self._c, row_off.ctypes.data, begin.ctypes.data, end.ctypes.data,
+                                                             core.ctypes.data, n, float(hi), float(lo), int(min_len),
+                                                             env.ctypes.data, cap, off.ctypes.data))
+        return off, env[:int(off[n])].copy()
 
     def mea_pairs(self, seq_idx, profile_idx, multi_hits=True, hmmer3_compat=False):
         """(paths, posts, gain, alt_fwd) of the pairs (resident sequence seq_idx[i], resident profile profile_idx[i])

@@ -16,6 +16,7 @@
 #include "dcp_backward_scaled.h"
 #include "dcp_mea.h"
 #include "dcp_posterior.h"
+#include "dcp_envelopes.h"
 #include "dcp_test_hooks.h"
 
 #include <hip/hip_runtime.h>
@@ -438,8 +439,18 @@ struct dcp_gpu_ctx
     // band: the hooks build's band of the rescaling rule (0: DCP_FWS_BAND); scaled_ms, scaled_redo: the last scaled
     // pair-list call's launches, the last scaled call's rerun pairs; dense_scaled: which sweep filled d_dense.
     // post_scaled_ms, post_scaled_redo: the same of the last dcp_gpu_posterior_pairs_scaled, summed over its rounds.
+    // The envelope call (dcp_gpu_envelope_pairs; dcp_envelopes.hip) reads a round's d_rows on the device and adds:
+    //  d_env_count  a round's envelopes per pair, as its count pass leaves them
+    //  d_env_at     their exclusive scan, formed on the host;  d_env: the round's records
+    // ev_env: around each of the two envelope passes.  env_ms: the last call's launches, summed over its rounds;
+    // env_own_ms: the envelope kernels' own part of it.
     struct PairSweeps
     {
+        DevBuf<uint32_t> d_env_count;
+        DevBuf<uint64_t> d_env_at;
+        DevBuf<dcp_envelope> d_env;
+        hipEvent_t ev_env[2] = {nullptr, nullptr};
+        float env_ms = -1.0f, env_own_ms = -1.0f;
         DevBuf<dcp_fwd_pair> d_redo, d_redo_pairs;
         DevBuf<uint32_t> d_nredo;
         int band = 0;
@@ -828,6 +839,8 @@ void dcp_gpu_ctx_del(dcp_gpu_ctx *c)
     for (hipEvent_t e : c->ev_exp)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : c->sweeps.ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->sweeps.ev_env)
         if (e) (void)hipEventDestroy(e);
     for (int k = 0; k < kMaxLaunches; ++k)
         if (c->ev_class[k]) (void)hipEventDestroy(c->ev_class[k]);
@@ -3989,23 +4002,94 @@ static int run_scaled_posterior_sweeps(dcp_gpu_ctx *c, dcp_fwd_args &a, ForwardB
     return DCP_OK;
 }
 
+// What becomes of a round's rows: copied out into the caller's arrays (dcp_gpu_posterior_pairs), or turned into envelope
+// records on the device, of which the counts and the records alone are copied out (dcp_gpu_envelope_pairs).
+struct PosteriorSink
+{
+    uint64_t *row_off = nullptr;
+    double *begin_out = nullptr, *end_out = nullptr, *core_out = nullptr;
+    uint64_t cap_rows = 0;
+    bool envelopes = false;
+    double hi = 0.0, lo = 0.0;
+    unsigned min_len = 0;
+    dcp_envelope *env_out = nullptr;
+    uint64_t cap_env = 0;
+    uint64_t *env_off = nullptr;
+};
+
+// A round's envelopes from its rows on the device: the count pass, the counts copied out and scanned on the host, the
+// write pass, the records copied out behind those of the rounds before.  ea: the round's row offsets, list length, planes,
+// thresholds and first pair.  count_out [ea.nlist].  The wavefronts take dcp_gpu_test_set_forward_waves' cap.  *own_ms
+// grows by the two passes' time, by events of their own (ev_env).  Returns synchronised.
+static int envelope_round(dcp_gpu_ctx *c, dcp_env_args ea, uint32_t *count_out, std::vector<dcp_envelope> &recs, float *own_ms)
+{
+    auto &W = c->sweeps;
+    unsigned const n = ea.nlist;
+    for (hipEvent_t &e : W.ev_env)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    ea.nwaves = (unsigned)std::min<uint64_t>(n, 32ull * c->num_cus); // eight wavefronts per SIMD: the passes wait for memory
+    if (W.waves_cap) ea.nwaves = std::min(ea.nwaves, W.waves_cap);
+    HIP_TRY(c, W.d_env_count.reserve(n));
+    HIP_TRY(c, W.d_env_at.reserve((size_t)n + 1u));
+    ea.count = W.d_env_count.p, ea.env_at = W.d_env_at.p;
+    HIP_TRY(c, hipEventRecord(W.ev_env[0], c->stream));
+    if (dcp_envelopes_count_launch(&ea, c->stream)) return c->fail(DCP_EFAIL, "the envelope count pass refused a round of %u pairs", n);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(W.ev_env[1], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(count_out, W.d_env_count.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, W.ev_env[0], W.ev_env[1]));
+    *own_ms += ms;
+    std::vector<uint64_t> at((size_t)n + 1u, 0u);
+    for (unsigned i = 0; i < n; ++i)
+        at[i + 1u] = at[i] + count_out[i];
+    uint64_t const total = at[n];
+    if (total == 0u) return DCP_OK;
+    HIP_TRY(c, W.d_env.reserve(total));
+    ea.env = W.d_env.p;
+    HIP_TRY(c, hipMemcpyAsync(W.d_env_at.p, at.data(), at.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipEventRecord(W.ev_env[0], c->stream));
+    if (dcp_envelopes_write_launch(&ea, c->stream)) return c->fail(DCP_EFAIL, "the envelope write pass refused a round of %u pairs", n);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(W.ev_env[1], c->stream));
+    size_t const had = recs.size();
+    recs.resize(had + total);
+    HIP_TRY(c, hipMemcpyAsync(recs.data() + had, W.d_env.p, total * sizeof(dcp_envelope), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream)); // (and `at` is up)
+    HIP_TRY(c, hipEventElapsedTime(&ms, W.ev_env[0], W.ev_env[1]));
+    *own_ms += ms;
+    return DCP_OK;
+}
+
 static int posterior_pairs(dcp_gpu_ctx *c, bool scaled, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
-                           uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
-                           double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
+                           uint32_t const *profile_idx, unsigned npairs, PosteriorSink const &s, double *alt_fwd_out,
+                           double *alt_bwd_out)
 {
     if (!c) return DCP_EINVAL;
     if (int rc = forward_check_list(c, seq_idx, profile_idx, npairs, alt_fwd_out && alt_bwd_out)) return rc;
-    if (!row_off) return c->fail(DCP_EINVAL, "a pair list without its row offsets");
+    if (s.envelopes)
+    {
+        if (!s.env_off) return c->fail(DCP_EINVAL, "a pair list without its envelope offsets");
+        if (dcp_env_thresholds_refused(s.hi, s.lo))
+            return c->fail(DCP_EINVAL, "envelope thresholds hi %g, lo %g: neither may be NaN, and lo may not exceed hi", s.hi, s.lo);
+        if (npairs && s.cap_env && !s.env_out) return c->fail(DCP_EINVAL, "a pair list without its envelope array");
+    }
+    else if (!s.row_off) return c->fail(DCP_EINVAL, "a pair list without its row offsets");
     std::vector<uint64_t> off((size_t)npairs + 1u, 0u);
     for (unsigned i = 0; i < npairs; ++i)
         off[i + 1u] = off[i] + c->seq_len[seq_idx[i]] + 1u;
-    uint64_t const need = off[npairs];
-    if (need > cap_rows)
-        return c->fail(DCP_EINVAL, "the list needs %llu rows, the arrays hold %llu", (unsigned long long)need, (unsigned long long)cap_rows);
-    if (npairs && (!begin_out || !end_out || !core_out)) return c->fail(DCP_EINVAL, "a pair list without its row arrays");
+    if (!s.envelopes)
+    {
+        uint64_t const need = off[npairs];
+        if (need > s.cap_rows)
+            return c->fail(DCP_EINVAL, "the list needs %llu rows, the arrays hold %llu", (unsigned long long)need,
+                           (unsigned long long)s.cap_rows);
+        if (npairs && (!s.begin_out || !s.end_out || !s.core_out)) return c->fail(DCP_EINVAL, "a pair list without its row arrays");
+    }
     if (npairs == 0)
     {
-        row_off[0] = 0u;
+        (s.envelopes ? s.env_off : s.row_off)[0] = 0u;
         return DCP_OK;
     }
     auto &W = c->sweeps;
@@ -4032,7 +4116,9 @@ static int posterior_pairs(dcp_gpu_ctx *c, bool scaled, int multi_hits, int hmme
     pa.alt_fwd = d_fwd;
 
     std::vector<double> rows;
-    float ms_total = 0.0f;
+    std::vector<uint32_t> env_count(s.envelopes ? npairs : 0u, 0u); // the call's own copy of every pair's count and of the
+    std::vector<dcp_envelope> env;                                   // records: the caller's arrays wait for the total
+    float ms_total = 0.0f, env_own_ms = 0.0f;
     unsigned redone = 0;
     for (unsigned i0 = 0, i1; i0 < npairs; i0 = i1)
     {
@@ -4054,6 +4140,18 @@ static int posterior_pairs(dcp_gpu_ctx *c, bool scaled, int multi_hits, int hmme
             return c->fail(DCP_EFAIL, "no combining kernel for a round of %llu rows", (unsigned long long)nrows);
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipEventRecord(W.ev[1], c->stream));
+        if (s.envelopes)
+        {
+            // the rows stay where they are: the round's counts and records alone are copied out
+            dcp_env_args ea{};
+            ea.row_off = pa.row_off, ea.nlist = n, ea.begin = pa.begin, ea.end = pa.end, ea.core = pa.core;
+            ea.hi = s.hi, ea.lo = s.lo, ea.min_len = s.min_len, ea.pair_base = i0;
+            if (int rc = envelope_round(c, ea, env_count.data() + i0, env, &env_own_ms)) return rc;
+            float ms = 0.0f;
+            HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
+            ms_total += ms;
+            continue;
+        }
         // into a buffer of the call's own first: the caller's arrays stay untouched if this round's copy fails
         rows.resize(3u * (size_t)nrows);
         HIP_TRY(c, hipMemcpyAsync(rows.data(), W.d_rows.p, rows.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -4061,15 +4159,33 @@ static int posterior_pairs(dcp_gpu_ctx *c, bool scaled, int multi_hits, int hmme
         float ms = 0.0f;
         HIP_TRY(c, hipEventElapsedTime(&ms, W.ev[0], W.ev[1]));
         ms_total += ms;
-        std::memcpy(begin_out + off[i0], rows.data(), (size_t)nrows * sizeof(double));
-        std::memcpy(end_out + off[i0], rows.data() + nrows, (size_t)nrows * sizeof(double));
-        std::memcpy(core_out + off[i0], rows.data() + 2u * nrows, (size_t)nrows * sizeof(double));
+        std::memcpy(s.begin_out + off[i0], rows.data(), (size_t)nrows * sizeof(double));
+        std::memcpy(s.end_out + off[i0], rows.data() + nrows, (size_t)nrows * sizeof(double));
+        std::memcpy(s.core_out + off[i0], rows.data() + 2u * nrows, (size_t)nrows * sizeof(double));
     }
     std::vector<double> score(2u * (size_t)npairs);
     HIP_TRY(c, hipMemcpy(score.data(), d_fwd, score.size() * sizeof(double), hipMemcpyDeviceToHost));
+    if (s.envelopes)
+    {
+        W.env_ms = ms_total + env_own_ms, W.env_own_ms = env_own_ms; // the call ran all its rounds, whatever cap_env makes of it
+        if (scaled) W.post_scaled_redo = redone;
+        s.env_off[0] = 0u;
+        for (unsigned i = 0; i < npairs; ++i)
+            s.env_off[i + 1u] = s.env_off[i] + env_count[i];
+        uint64_t const total = s.env_off[npairs];
+        if (total != env.size()) return c->fail(DCP_EFAIL, "the rounds counted %llu envelopes and wrote %llu", (unsigned long long)total,
+                                                (unsigned long long)env.size());
+        if (total > s.cap_env)
+            return c->fail(DCP_ENOMEM, "the list has %llu envelopes, the array holds %llu", (unsigned long long)total,
+                           (unsigned long long)s.cap_env);
+        if (total) std::memcpy(s.env_out, env.data(), (size_t)total * sizeof(dcp_envelope));
+        std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
+        std::memcpy(alt_bwd_out, score.data() + npairs, (size_t)npairs * sizeof(double));
+        return DCP_OK;
+    }
     std::memcpy(alt_fwd_out, score.data(), (size_t)npairs * sizeof(double));
     std::memcpy(alt_bwd_out, score.data() + npairs, (size_t)npairs * sizeof(double));
-    std::memcpy(row_off, off.data(), off.size() * sizeof(uint64_t));
+    std::memcpy(s.row_off, off.data(), off.size() * sizeof(uint64_t));
     if (scaled) W.post_scaled_ms = ms_total, W.post_scaled_redo = redone;
     else W.post_ms = ms_total;
     return DCP_OK;
@@ -4079,21 +4195,39 @@ int dcp_gpu_posterior_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, u
                             uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
                             double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
 {
-    return posterior_pairs(c, false, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, row_off, begin_out, end_out, core_out,
-                           cap_rows, alt_fwd_out, alt_bwd_out);
+    PosteriorSink s;
+    s.row_off = row_off, s.begin_out = begin_out, s.end_out = end_out, s.core_out = core_out, s.cap_rows = cap_rows;
+    return posterior_pairs(c, false, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, s, alt_fwd_out, alt_bwd_out);
 }
 
 int dcp_gpu_posterior_pairs_scaled(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, uint32_t const *seq_idx,
                                    uint32_t const *profile_idx, unsigned npairs, uint64_t *row_off, double *begin_out,
                                    double *end_out, double *core_out, uint64_t cap_rows, double *alt_fwd_out, double *alt_bwd_out)
 {
-    return posterior_pairs(c, true, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, row_off, begin_out, end_out, core_out,
-                           cap_rows, alt_fwd_out, alt_bwd_out);
+    PosteriorSink s;
+    s.row_off = row_off, s.begin_out = begin_out, s.end_out = end_out, s.core_out = core_out, s.cap_rows = cap_rows;
+    return posterior_pairs(c, true, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, s, alt_fwd_out, alt_bwd_out);
 }
 
 float dcp_gpu_posterior_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.post_ms : -1.0f; }
 unsigned dcp_gpu_posterior_scaled_redo_pairs(dcp_gpu_ctx *c) { return c ? c->sweeps.post_scaled_redo : 0u; }
 float dcp_gpu_posterior_scaled_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.post_scaled_ms : -1.0f; }
+
+// ---- Posterior envelopes of a pair list (dcp_envelopes.hip) ----------------------------------------------
+// posterior_pairs with the other sink: everything up to a round's combining kernel is the posterior call's of the same
+// sweeps; the round's rows then stay in d_rows, where the two envelope passes read them (envelope_round).
+int dcp_gpu_envelope_pairs(dcp_gpu_ctx *c, int multi_hits, int hmmer3_compat, int scaled, uint32_t const *seq_idx,
+                           uint32_t const *profile_idx, unsigned npairs, double hi, double lo, unsigned min_len,
+                           struct dcp_envelope *env_out, uint64_t cap_env, uint64_t *env_off, double *alt_fwd_out,
+                           double *alt_bwd_out)
+{
+    PosteriorSink s;
+    s.envelopes = true, s.hi = hi, s.lo = lo, s.min_len = min_len;
+    s.env_out = env_out, s.cap_env = cap_env, s.env_off = env_off;
+    return posterior_pairs(c, scaled != 0, multi_hits, hmmer3_compat, seq_idx, profile_idx, npairs, s, alt_fwd_out, alt_bwd_out);
+}
+
+float dcp_gpu_envelope_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.env_ms : -1.0f; }
 
 // ---- The posterior-decoded alignment of a pair list (dcp_mea.hip) ---------------------------------------------------
 // The list runs in rounds of consecutive pairs whose matrices (P, Q, bM, bI: 32 bytes a cell), cell choices (2 bytes a
@@ -4390,6 +4524,52 @@ int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *c, unsigned long long bytes)
     c->sweeps.post_budget = bytes;
     return DCP_OK;
 }
+
+int dcp_gpu_test_envelopes_of_rows(dcp_gpu_ctx *c, uint64_t const *row_off, double const *begin, double const *end,
+                                   double const *core, unsigned npairs, double hi, double lo, unsigned min_len,
+                                   struct dcp_envelope *out, uint64_t cap, uint64_t *env_off)
+{
+    if (!c) return DCP_EINVAL;
+    if (!env_off || !row_off || (cap && !out) || (npairs && (!begin || !end || !core)) || dcp_env_thresholds_refused(hi, lo))
+        return c->fail(DCP_EINVAL, "rows without their arrays or thresholds");
+    for (unsigned i = 0; i < npairs; ++i)
+        if (row_off[i + 1u] <= row_off[i] || row_off[i + 1u] - row_off[i] > 0xffffffffull)
+            return c->fail(DCP_EINVAL, "pair %u has no row 0", i);
+    if (npairs == 0)
+    {
+        env_off[0] = 0u;
+        return DCP_OK;
+    }
+    uint64_t const nrows = row_off[npairs] - row_off[0];
+    HIP_TRY(c, hipSetDevice(c->device));
+    auto &W = c->sweeps;
+    HIP_TRY(c, W.d_rows.reserve(3u * nrows));
+    HIP_TRY(c, W.d_off.reserve((size_t)npairs + 1u));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpy(W.d_off.p, row_off, ((size_t)npairs + 1u) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(W.d_rows.p, begin + row_off[0], nrows * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(W.d_rows.p + nrows, end + row_off[0], nrows * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(W.d_rows.p + 2u * nrows, core + row_off[0], nrows * sizeof(double), hipMemcpyHostToDevice));
+    dcp_env_args ea{};
+    ea.row_off = W.d_off.p, ea.nlist = npairs;
+    ea.begin = W.d_rows.p, ea.end = ea.begin + nrows, ea.core = ea.end + nrows;
+    ea.hi = hi, ea.lo = lo, ea.min_len = min_len, ea.pair_base = 0u;
+    std::vector<uint32_t> count(npairs, 0u);
+    std::vector<dcp_envelope> env;
+    float ms = 0.0f;
+    if (int rc = envelope_round(c, ea, count.data(), env, &ms)) return rc;
+    env_off[0] = 0u; // (only now: an error above leaves every output as it was)
+    for (unsigned i = 0; i < npairs; ++i)
+        env_off[i + 1u] = env_off[i] + count[i];
+    if (env_off[npairs] != env.size()) return c->fail(DCP_EFAIL, "the passes counted %llu envelopes and wrote %llu",
+                                                      (unsigned long long)env_off[npairs], (unsigned long long)env.size());
+    if (env.size() > cap) return c->fail(DCP_ENOMEM, "the rows have %llu envelopes, the array holds %llu", (unsigned long long)env.size(),
+                                         (unsigned long long)cap);
+    if (!env.empty()) std::memcpy(out, env.data(), env.size() * sizeof(dcp_envelope));
+    return DCP_OK;
+}
+
+float dcp_gpu_test_envelope_records_kernel_ms(dcp_gpu_ctx *c) { return c ? c->sweeps.env_own_ms : -1.0f; }
 
 int dcp_gpu_test_set_mea_budget(dcp_gpu_ctx *c, unsigned long long bytes)
 {

@@ -2546,6 +2546,63 @@ extern "C" int dcp_posterior_envelopes(double const *core, unsigned L, double th
 }
 
 // ---------------------------------------------------------------------------
+// Envelope records on the host: the twin of dcp_envelopes.hip.  The rule is dcp_envelopes.h's; the bases of a run are
+// taken one by one, so the sums run in index order.  No device.
+// ---------------------------------------------------------------------------
+#include "dcp_envelopes.h"
+
+extern "C" int dcp_posterior_envelope_records(double const *begin, double const *end, double const *core, unsigned L,
+                                              double hi, double lo, unsigned min_len, struct dcp_envelope *out,
+                                              unsigned cap, unsigned *n_out)
+{
+    if (!n_out || (L && (!begin || !end || !core)) || (cap && !out) || dcp_env_thresholds_refused(hi, lo)) return DCP_EINVAL;
+    unsigned n = 0;
+    for (unsigned i = 0; i < L;)
+    {
+        if (!dcp_env_in(core[i + 1u], lo))
+        {
+            ++i;
+            continue;
+        }
+        dcp_env_run run{i, i, core[i + 1u], core[i + 1u], begin[i], end[i + 1u]};
+        unsigned e = i + 1u;
+        for (; e < L && dcp_env_in(core[e + 1u], lo); ++e)
+            dcp_env_run_add(run, e, core[e + 1u], core[e + 1u], begin[e], end[e + 1u]);
+        if (dcp_env_kept(run.begin, e, run.core_max, hi, min_len))
+        {
+            if (n < cap) out[n] = dcp_env_record(run, 0u, e);
+            ++n;
+        }
+        i = e;
+    }
+    *n_out = n;
+    return DCP_OK;
+}
+
+// Envelopes as dcp_gpu_seqs_cut_regions' (src, begin, length), widened by flank and clipped to their sequences.
+extern "C" int dcp_envelopes_regions(struct dcp_envelope const *env, uint64_t n, uint32_t const *seq_idx, unsigned npairs,
+                                     uint32_t const *seq_len, unsigned nseqs, unsigned flank, uint32_t *src_out,
+                                     uint32_t *begin_out, uint32_t *len_out, uint32_t *profile_pair_out)
+{
+    if (n && (!env || !seq_idx || !seq_len || !src_out || !begin_out || !len_out || !profile_pair_out)) return DCP_EINVAL;
+    for (uint64_t k = 0; k < n; ++k)
+    {
+        dcp_envelope const &v = env[k];
+        if (v.pair >= npairs || seq_idx[v.pair] >= nseqs) return DCP_EINVAL;
+        if (v.begin >= v.end || v.end > seq_len[seq_idx[v.pair]]) return DCP_EINVAL;
+    }
+    for (uint64_t k = 0; k < n; ++k)
+    {
+        dcp_envelope const &v = env[k];
+        uint32_t const src = seq_idx[v.pair], len = seq_len[src];
+        uint32_t const b = v.begin > flank ? v.begin - flank : 0u;
+        uint32_t const e = len - v.end > flank ? v.end + flank : len;
+        src_out[k] = src, begin_out[k] = b, len_out[k] = e - b, profile_pair_out[k] = v.pair;
+    }
+    return DCP_OK;
+}
+
+// ---------------------------------------------------------------------------
 // The posterior-decoded alignment on the host: the twin of dcp_mea.hip and the tests' yardstick.  The rule, the choice
 // codes and the walk are dcp_mea.h's; the two sweeps are the ones above, with their full matrices.  No device.
 // ---------------------------------------------------------------------------

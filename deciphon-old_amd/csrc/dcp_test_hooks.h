@@ -61,6 +61,18 @@ int dcp_gpu_test_set_posterior_budget(dcp_gpu_ctx *, unsigned long long bytes);
 // restores the default (8 GiB).  Results must not change with it.  (Its launches take dcp_gpu_test_set_forward_waves'
 // cap too.)
 int dcp_gpu_test_set_mea_budget(dcp_gpu_ctx *, unsigned long long bytes);
+// (dcp_gpu_envelope_pairs takes dcp_gpu_test_set_forward_waves' cap -- its envelope passes' launches too -- and
+// dcp_gpu_test_set_posterior_budget's bound.)
+// The envelope passes (dcp_envelopes.hip) alone, on rows of the caller's making: pair i's rows are
+// [row_off[i], row_off[i + 1]) of begin / end / core, at least one row each, uploaded as one round; the records come back
+// as dcp_gpu_envelope_pairs returns them, pair = i, env_off [npairs + 1] written in full.  DCP_ENOMEM past cap (env_off
+// is written; after any other error no output is touched), DCP_EINVAL for a null pointer, a pair without rows, NaN thresholds or lo > hi.  Needs no DB and no batch.
+int dcp_gpu_test_envelopes_of_rows(dcp_gpu_ctx *, uint64_t const *row_off, double const *begin, double const *end,
+                                   double const *core, unsigned npairs, double hi, double lo, unsigned min_len,
+                                   struct dcp_envelope *out, uint64_t cap, uint64_t *env_off);
+// The envelope kernels' own part of dcp_gpu_envelope_kernel_ms (the two passes of every round, by events of their own) of
+// the context's last dcp_gpu_envelope_pairs that ran all its rounds; negative before.  Changes nothing.
+float dcp_gpu_test_envelope_records_kernel_ms(dcp_gpu_ctx *);
 }
 #endif
 

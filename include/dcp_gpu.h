@@ -1184,6 +1184,58 @@ int dcp_gpu_mea_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, uint32_t
 float dcp_gpu_mea_kernel_ms(dcp_gpu_ctx *);
 
 /* ------------------------------------------------------------------------ */
+/* Posterior envelopes of a pair list, found on the device       */
+/* ------------------------------------------------------------------------ */
+/* An envelope of a pair is a maximal run [b, e) of bases with core[i + 1] >= lo (core: dcp_posterior_tables' row) that
+ * is at least min_len bases long and whose largest core value is >= hi: a run needs a peak and is extended down to the
+ * lower threshold.  With lo == hi the intervals are dcp_posterior_envelopes'.  The rule is csrc/dcp_envelopes.h, which
+ * the device kernels (csrc/dcp_envelopes.hip) and the host twin compile alike. */
+struct dcp_envelope
+{
+    uint32_t pair;       /* index into the call's list                                   */
+    uint32_t begin, end; /* half-open base interval in the resident sequence             */
+    uint32_t peak;       /* first base of the run at which core is largest               */
+    double core_max;     /* core[peak + 1]                                               */
+    double core_sum;     /* sum of core[i + 1], i in [b, e): expected core-emitted bases */
+    double begin_sum;    /* sum of begin[j], j in [b, e - 1]: expected domain starts     */
+    double end_sum;      /* sum of end[j],   j in [b + 1, e]: expected domain ends       */
+};
+/* The host twin, from one pair's three rows [L + 1]: the kept runs in order of begin, pair = 0, the sums in index order.
+ * *n_out receives the true count, of which the first cap are written.  DCP_EINVAL, nothing written: n_out null, a row
+ * null with L > 0, out null with cap > 0, hi or lo NaN, lo > hi.  No device. */
+int dcp_posterior_envelope_records(double const *begin, double const *end, double const *core, unsigned L, double hi,
+                                   double lo, unsigned min_len, struct dcp_envelope *out, unsigned cap, unsigned *n_out);
+/* The envelopes of the npairs pairs (resident sequence seq_idx[i], resident profile profile_idx[i]): the sweeps, rounds,
+ * budget (1 GiB of row records), redo of flagged pairs and combining kernel of dcp_gpu_posterior_pairs_scaled (scaled
+ * != 0) or dcp_gpu_posterior_pairs (scaled == 0), but a round's three rows stay in device memory: two kernels, one
+ * wavefront per pair, count the round's envelopes and write their records, and only counts and records are copied out.
+ * Pair i's records are [env_off[i], env_off[i + 1]) of env_out [cap_env], in order of begin; env_off [npairs + 1] is
+ * written by the call; alt_fwd_out / alt_bwd_out [npairs] have the bits of the posterior call of the same sweeps.
+ * pair, begin, end, peak and core_max equal the host twin's on the same rows bit for bit; the three sums are a run's
+ * own terms added in another order: within (end - begin) 2^-52 sum |term| of the twin's.  A pair listed twice is
+ * reported twice; a pair whose alt score is -inf has rows of 0; npairs == 0 is DCP_OK with env_off[0] = 0.
+ * Checks, messages, special transitions, batches, precisions, stream and what is left untouched: all as
+ * dcp_gpu_forward_pairs.  DCP_EINVAL, nothing written, also: env_off null, env_out null with cap_env > 0, hi or lo NaN,
+ * lo > hi.  DCP_ENOMEM if the list has more than cap_env envelopes: env_off is written in full (env_off[npairs] is
+ * the need) and every other output stays untouched. */
+int dcp_gpu_envelope_pairs(dcp_gpu_ctx *, int multi_hits, int hmmer3_compat, int scaled, uint32_t const *seq_idx,
+                           uint32_t const *profile_idx, unsigned npairs, double hi, double lo, unsigned min_len,
+                           struct dcp_envelope *env_out, uint64_t cap_env, uint64_t *env_off, double *alt_fwd_out,
+                           double *alt_bwd_out);
+/* Milliseconds, by HIP events, summed over the rounds' launches (sweeps, reruns, combining and envelope kernels) of
+ * the context's last dcp_gpu_envelope_pairs that ran all its rounds -- one that then returned DCP_ENOMEM for its
+ * cap_env included; negative before. */
+float dcp_gpu_envelope_kernel_ms(dcp_gpu_ctx *);
+/* Envelopes as regions for dcp_gpu_seqs_cut_regions: envelope k gives the stretch [max(begin - flank, 0),
+ * min(end + flank, L)) of resident sequence seq_idx[env[k].pair], L = seq_len[that sequence]: src_out[k], begin_out[k],
+ * len_out[k]; profile_pair_out[k] = env[k].pair, the list entry whose profile the region is to be scored against.
+ * DCP_EINVAL, nothing written: a pair >= npairs, a sequence index >= nseqs, end > L, begin >= end, a null pointer with
+ * n > 0.  No device. */
+int dcp_envelopes_regions(struct dcp_envelope const *env, uint64_t n, uint32_t const *seq_idx, unsigned npairs,
+                          uint32_t const *seq_len, unsigned nseqs, unsigned flank, uint32_t *src_out,
+                          uint32_t *begin_out, uint32_t *len_out, uint32_t *profile_pair_out);
+
+/* ------------------------------------------------------------------------ */
 /* One process per GPU: profile shards + the hit gather over RCCL */
 /* ------------------------------------------------------------------------ */
 /* Pairs (profile, query) are independent: every rank keeps a contiguous profile shard (balanced by sum
